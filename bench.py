@@ -22,11 +22,17 @@ The JSON line also carries
                  peak = 157.3 TFLOP/s fp32 MFMA (MI355X_MICROARCH.md).
   cpu_baseline : oracle/dreamer_oracle.py (torch CPU restatement pinned to the reference by goldens, kind "port") timed
                  on this box's host cores on a bounded sample of the same workload (rank 0, N=1 only).
+
+--steps K runs exactly K timed steps; `ms_per_step` is the time of one of them.  --dump-outputs DIR writes what the last
+timed step handed its caller (losses, recurrent state, metrics, tensors, gradient norms, the parameters after AdamW) as
+DIR/<name>.npy, so that two builds run with the same arguments - hence the same seeded inputs - can be compared output for
+output.
 """
 import argparse
 import ctypes
 import json
 import os
+import re
 import sys
 import time
 
@@ -198,6 +204,33 @@ def cpu_baseline(sample_batch=50, threads_cap=32, timeout_s=260):
                     sample=f'oracle sample of {sample_batch}/50 batch columns did not finish within {timeout_s} s ({type(e).__name__})')
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 21       # an output of more elements is dumped as a fixed, seeded sample of this many of its flat elements
+
+
+def dump_outputs(out_dir, outputs):
+    """Write every tensor of `outputs` (name -> tensor) as out_dir/<name>.npy: float64 and integer outputs as float64, the
+    rest as float32.  Returns {name: [shape, sampled]}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total, index = 0, {}
+    for name, t in outputs.items():
+        t = t.detach()
+        exact = t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)
+        a = t.to('cpu', torch.float64 if exact else torch.float32).numpy().reshape(-1)
+        sampled = a.size > DUMP_SAMPLE
+        if sampled:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        else:
+            a = a.reshape(tuple(t.shape))
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f'--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB at {name}')
+        np.save(os.path.join(out_dir, re.sub(r'[^\w.-]', '_', name) + '.npy'), a)
+        index[name] = [list(t.shape), sampled]
+    return index
+
+
 def csrc_sha():
     """Fingerprint of the kernel sources: PMC traffic files carry it, so a stale file is refused instead of silently reported."""
     import hashlib
@@ -221,8 +254,9 @@ def main():
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--ring', type=int, default=8)
-    ap.add_argument('--reps', type=int, default=3, help='the timed region of exactly --steps steps (barrier + synchronise on both sides) is repeated this '
-                    'many times back to back; `value` / `ms_per_step` are the MEDIAN region (max over ranks each), min / max are printed beside it')
+    ap.add_argument('--reps', type=int, default=1, help='the --steps timed steps run as this many back-to-back regions (barrier + synchronise on both '
+                    'sides, at most one region per step); `value` / `ms_per_step` are the MEDIAN region\'s (max over ranks each), min / max are printed beside it')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR', help='write the outputs of the last timed step to DIR/<name>.npy (rank 0)')
     ap.add_argument('--prof-steps', type=int, default=2)
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--pmc-json', default='',
@@ -247,6 +281,8 @@ def main():
     ap.add_argument('--h2d-steps', type=int, default=40)
     ap.add_argument('--shape-table', default='', help='write the per-shape GEMM table of the profiled pass to this file (diagnostic)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if not args.pmc_json:       # the committed counter summary of the same command (fp32 / bf16 step), if its fingerprint matches the tree
         import glob
         cands = sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r[0-9][0-9]_pmc_traffic' + ('_bf16' if args.dtype == 'bf16' else '') + '.json')))
@@ -330,10 +366,10 @@ def main():
             opt.zero_grad()
         for loss in losses:
             loss.backward()
-        model.grad_clip(conf.grad_clip, conf.grad_clip_ac)
+        norms = model.grad_clip(conf.grad_clip, conf.grad_clip_ac)
         for opt in opts:
             opt.step()
-        return metrics
+        return losses, new_state, metrics, tensors, norms
 
     main_prio = os.environ.get('DM_MAIN_PRIO')            # experiment switch: run the caller's stream at another priority
     if main_prio is not None:
@@ -343,23 +379,25 @@ def main():
         torch.cuda.set_stream(hip.cu_masked_stream([0xFFFFFFFF ^ ((1 << main_res) - 1)] * 8, dev))
     for i in range(args.warmup):
         step(i)
-    # the timed region: EXACTLY --steps steps between barrier + synchronise, max over ranks; repeated --reps times back to back
-    # (state, optimizer moments and replay ring carry on), the median region is the reported one
+    # the timed steps: EXACTLY --steps of them, split into --reps regions run back to back (state, optimizer moments and replay
+    # ring carry on), each between barrier + synchronise, max over ranks; the median region is the reported one
+    n_regions = min(max(1, args.reps), args.steps)
+    sizes = [args.steps // n_regions + (1 if r < args.steps % n_regions else 0) for r in range(n_regions)]
     regions, t_enq = [], []
     n_done = args.warmup
-    for rep in range(max(1, args.reps)):
+    for n_steps in sizes:
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for i in range(args.steps):
-            metrics = step(n_done + i)
+        for i in range(n_steps):
+            last = step(n_done + i)
         t_enq.append(time.perf_counter() - t0)          # host done enqueuing; the GPU may still be running
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         el = time.perf_counter() - t0
-        n_done += args.steps
+        n_done += n_steps
         per = [el]
         if world > 1:
             t = torch.tensor([el], device=dev, dtype=torch.float64)
@@ -367,13 +405,24 @@ def main():
             dist.all_gather(per_rank, t)
             per = [float(x.item()) for x in per_rank]
         regions.append(per)
-    order = sorted(range(len(regions)), key=lambda r: max(regions[r]))
-    mid = order[len(order) // 2]                        # the median region (by its max over ranks)
-    elapsed = max(regions[mid])
-    t_enqueued = t_enq[mid]
-    rank_ms = [1e3 * x / args.steps for x in regions[mid]]
-    region_ms = [1e3 * max(r) / args.steps for r in regions]
+    order = sorted(range(len(regions)), key=lambda r: max(regions[r]) / sizes[r])
+    mid = order[len(order) // 2]                        # the median region (by its max over ranks, per step)
+    ms_step = 1e3 * max(regions[mid]) / sizes[mid]
+    t_enqueued = t_enq[mid] / sizes[mid]              # per step
+    rank_ms = [1e3 * x / sizes[mid] for x in regions[mid]]
+    region_ms = [1e3 * max(r) / n for r, n in zip(regions, sizes)]
+    metrics = last[2]
     loss_model = float(metrics['loss_model'])
+    dumped = None
+    if args.dump_outputs and rank == 0:     # before any further step reuses the step's buffers
+        losses, new_state, _, tensors, norms = last
+        outs = dict(zip(('loss_model', 'loss_probe', 'loss_actor', 'loss_critic'), losses))
+        outs.update((f'state_{i}', s) for i, s in enumerate(new_state))
+        outs.update((f'metrics.{k}', torch.as_tensor(v)) for k, v in metrics.items() if torch.is_tensor(v) or isinstance(v, (int, float)))
+        outs.update((f'tensors.{k}', v) for k, v in dict.items(tensors) if torch.is_tensor(v))    # (thunks the step never ran stay out)
+        outs.update((f'grad_norms.{k}', torch.as_tensor(v)) for k, v in norms.items() if torch.is_tensor(v) or isinstance(v, (int, float)))
+        outs.update((f'params.{name}', o.flat_param) for name, o in zip(('wm', 'probe', 'actor', 'critic'), opts))
+        dumped = dict(dir=args.dump_outputs, outputs=dump_outputs(args.dump_outputs, outs))
     # What the host needs to ENQUEUE a step when nothing holds it back: three more steps right after the synchronise (empty
     # queues).  `host_enqueue_ms_per_step` above is taken over the timed region, where the runtime's queue back-pressure
     # makes the launching threads wait for the GPU once they are a few steps ahead - it tracks the GPU, not the host's cost.
@@ -385,7 +434,7 @@ def main():
     dist_info = None
     if world > 1 or args.force_dp:      # (--force-dp: the same record over a ONE-rank RCCL group)
         # per-rank numbers (before the MAX) and the stand-alone cost of the step's all-reduces on this fabric
-        mine = torch.tensor([1e3 * t_enqueued / args.steps], device=dev, dtype=torch.float64)
+        mine = torch.tensor([1e3 * t_enqueued], device=dev, dtype=torch.float64)
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         host_ms = [float(x.item()) for x in allr]
@@ -600,8 +649,8 @@ def main():
         cpu = cpu_baseline()
 
     if rank == 0:
-        ms = 1e3 * elapsed / args.steps
-        line = dict(metric=METRIC, value=args.steps / elapsed, unit='grad-steps/s', n_gpus=world, steps=args.steps,
+        ms = ms_step
+        line = dict(metric=METRIC, value=1e3 / ms, unit='grad-steps/s', n_gpus=world, steps=args.steps,
                     warmup=args.warmup, ms_per_step=ms, ms_per_step_min=min(region_ms), ms_per_step_median=ms,
                     ms_per_step_max=max(region_ms), timed_regions=len(region_ms), ms_per_step_regions=region_ms, higher_is_better=True, scaling='strong', vs_baseline=None,
                     dtype='f32' if args.dtype == 'f32' else 'bf16 (MFMA operands; fp32 accumulate, fp32 storage and non-GEMM math)', data='synthetic',
@@ -621,14 +670,14 @@ def main():
                     **({'INVALID_smoke_all_ranks_on_one_device': True} if one_device else {}),
                     loss_model_last=loss_model,
                     param_checksum=[float(o.flat_param.double().sum()) for o in opts] + [float(o.flat_param.double().abs().sum()) for o in opts],
-                    host_enqueue_ms_per_step=1e3 * t_enqueued / args.steps,
+                    host_enqueue_ms_per_step=1e3 * t_enqueued,
                     host_enqueue_unthrottled_ms_per_step=host_free_ms,
                     fp32_products='fp32 MFMA',
                     step_tflops=alg_tflop / (ms * 1e-3), step_frac_of_fp32_peak=alg_tflop / (ms * 1e-3) / 157.3,
                     h2d_included=h2d, distributed=dist_info, rccl_version=(dist_info or {}).get('rccl_version'),
                     **({} if args.workload == 'atari-literal' else {'INVALID_diagnostic_workload': args.workload}),
                     **({} if args.dtype == 'f32' else {'note_dtype': 'BASELINE configs[2] (mixed precision); the headline metric is the f32 line'}),
-                    roofline=roof, cpu_baseline=cpu)
+                    roofline=roof, cpu_baseline=cpu, **({'dumped_outputs': dumped} if dumped else {}))
         print(json.dumps(line))
     if world > 1 or args.force_dp:
         dist.destroy_process_group()

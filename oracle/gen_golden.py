@@ -393,6 +393,28 @@ def run_inference(name, sections, overrides):
     print('wrote', path, f'{os.path.getsize(path) / 1024:.0f} KiB', 'policy_value', float(metrics['policy_value']))
 
 
+def run_state_dict_table(name, sections, overrides):
+    """The reference's state_dict as a checkpoint reader sees it (tools.py:164-197): key order, shape and dtype of every
+    entry, and fp64 sums of the entries after the reference loaded oracle.make_params(seed=0) - the weights run_inference
+    computes its golden with.  Lets tests check checkpoint interop without the reference."""
+    sys.path.insert(0, REF)
+    from pydreamer.models import Dreamer
+    rconf = reference_conf(sections, overrides)
+    oconf = O.make_conf(**{k: getattr(rconf, k) for k in O.DEFAULTS})
+    model = Dreamer(rconf)
+    model.load_state_dict(O.make_params(oconf, seed=0), strict=True)
+    sd = model.state_dict()
+    nd = max(v.dim() for v in sd.values())
+    out = dict(conf_json=np.array(repr(sorted(vars(oconf).items()))), keys=np.array(list(sd.keys())),
+               shapes=np.array([list(v.shape) + [-1] * (nd - v.dim()) for v in sd.values()], dtype=np.int64),
+               dtypes=np.array([str(v.dtype) for v in sd.values()]),
+               sums=np.array([float(v.double().sum()) for v in sd.values()]),
+               abs_sums=np.array([float(v.double().abs().sum()) for v in sd.values()]))
+    path = os.path.join(ROOT, 'tests', 'golden', f'{name}.npz')
+    np.savez_compressed(path, **out)
+    print('wrote', path, f'{os.path.getsize(path) / 1024:.0f} KiB', len(sd), 'entries')
+
+
 SMALL_GRADS = ('wm.core.cell.a_mlp.weight', 'wm.core.cell.gru.layers.0.bias_hh', 'wm.core.cell.post_norm.weight',
                'wm.core.cell.prior_mlp.bias', 'wm.encoder.encoder_image.model.0.weight',
                'wm.decoder.image.model.8.weight', 'ac.actor.model.12.weight', 'ac.critic.model.1.weight')
@@ -540,6 +562,11 @@ if __name__ == '__main__':
         run_inference('tiny_inference', ['defaults', 'atari'],
                       dict(deter_dim=t.deter_dim, hidden_dim=t.hidden_dim, stoch_dim=t.stoch_dim, stoch_discrete=t.stoch_discrete,
                            cnn_depth=t.cnn_depth, action_dim=t.action_dim))
+    if 'state_dict' in which:
+        t = O.tiny_conf()
+        run_state_dict_table('reference_state_dict', ['defaults', 'atari'],
+                             dict(deter_dim=t.deter_dim, hidden_dim=t.hidden_dim, stoch_dim=t.stoch_dim,
+                                  stoch_discrete=t.stoch_discrete, cnn_depth=t.cnn_depth, action_dim=t.action_dim))
     if 'iwae' in which:
         # iwae_samples > 1 (rssm.py:35-41 batch expansion, dreamer.py:340-343 sampled KL,
         # functions.py:97-102 logavgexp), as a TRAINING step (gradients included), tiny dims, I = 3

@@ -184,45 +184,65 @@ def test_init_weights_tf2_matches_reference_rule():
     assert not any(p.requires_grad for p in m.ac.critic_target.parameters())
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/pydreamer'), reason='the reference exists in the build container only')
 def test_reference_loads_build_state_dict():
-    """Checkpoint interop, model side (tools.py:164-197, generator.py:109): the REAL reference Dreamer loads the state_dict
-    written by this package (strict: identical keys and shapes) and, with those weights, reproduces the inference golden;
-    and this package loads the reference's state_dict.  Runs only where /root/reference exists; nothing is read from it on
-    the GPU box."""
+    """Checkpoint interop, model side (tools.py:164-197, generator.py:109), against the reference's state_dict table at the
+    tiny configuration (tests/golden/reference_state_dict.npz, written from the real reference by oracle/gen_golden.py):
+    the reference's strict load of the state_dict this package writes needs the same keys in the same order with the same
+    shapes and dtypes; this package loads a checkpoint of the reference's layout and hands it back unchanged; and what it
+    writes after loading the inference golden's weights holds, entry for entry, the values the reference computed
+    tests/golden/tiny_inference.npz with."""
     import ast
-    import sys
     import numpy as np
-    import torch
-    import yaml
-    from argparse import Namespace
-    from oracle import dreamer_oracle as O
-    from oracle.gen_golden import MultinomialPatch, reference_conf
     from pydreamer_amd.models import Dreamer
-    g = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'tiny_inference.npz'))
-    oconf = O.make_conf(**dict(ast.literal_eval(str(g['conf_json']))))
+    gold = os.path.join(os.path.dirname(__file__), 'golden')
+    g = np.load(os.path.join(gold, 'tiny_inference.npz'))
+    r = np.load(os.path.join(gold, 'reference_state_dict.npz'))
+    gconf, rconf = (dict(ast.literal_eval(str(f['conf_json']))) for f in (g, r))
+    assert all(rconf[k] == v for k, v in gconf.items()), 'the table was written for another configuration'
+    keys = [str(k) for k in r['keys']]
+    shapes = [tuple(int(d) for d in s if d >= 0) for s in r['shapes']]
+    assert keys == [str(k) for k in g['state_dict_keys']]
+    oconf = O.make_conf(**gconf)
     conf = config.load_config('defaults', 'atari', **{k: getattr(oconf, k) for k in vars(oconf)})
     ours = Dreamer(conf)                                     # parameters on CPU: holding and exchanging them needs no GPU
+    sd = ours.state_dict()
+    assert list(sd.keys()) == keys
+    for k, s, dt in zip(keys, shapes, r['dtypes']):
+        assert tuple(sd[k].shape) == s and str(sd[k].dtype) == str(dt), (k, tuple(sd[k].shape), s, sd[k].dtype, dt)
+    gen = torch.Generator().manual_seed(5)
+    theirs = {k: torch.randn(s, generator=gen) for k, s in zip(keys, shapes)}
+    ours.load_state_dict(theirs, strict=True)                # a checkpoint in the reference's layout loads as is
+    back = ours.state_dict()
+    for k in keys:
+        assert torch.equal(back[k], theirs[k]), k
     ours.load_state_dict(O.make_params(oconf, seed=0), strict=True)
-    sys.path.insert(0, '/root/reference')
-    from pydreamer.models import Dreamer as RefDreamer
-    import torch.distributions as D
-    D.Distribution.set_default_validate_args(False)
-    t = O.tiny_conf()
-    rconf = reference_conf(['defaults', 'atari'], dict(deter_dim=t.deter_dim, hidden_dim=t.hidden_dim, stoch_dim=t.stoch_dim,
-                                                       stoch_discrete=t.stoch_discrete, cnn_depth=t.cnn_depth,
-                                                       action_dim=t.action_dim))
-    ref = RefDreamer(rconf)
-    ref.load_state_dict(ours.state_dict(), strict=True)      # the reference accepts the build's checkpoint as is
-    ours.load_state_dict(ref.state_dict(), strict=True)      # ... and the other way round
-    u8 = torch.from_numpy(g['in_image_u8'])
-    obs = dict(image=(u8.float() / 255.0 - 0.5).permute(0, 1, 4, 2, 3).contiguous(), action=torch.from_numpy(g['in_action']),
-               reset=torch.from_numpy(g['in_reset']), reward=torch.zeros(1, 3), terminal=torch.zeros(1, 3))
-    with MultinomialPatch() as mp, torch.no_grad():
-        mp.queue = [torch.from_numpy(g['in_u'])[0]]
-        dist, (h1, z1), metrics = ref.inference(obs, (torch.from_numpy(g['in_h']), torch.from_numpy(g['in_z'])))
-    np.testing.assert_allclose(dist.probs.numpy(), g['action_probs'], rtol=0, atol=1e-7)
-    np.testing.assert_allclose(h1.numpy(), g['out_h'], rtol=0, atol=1e-7)
+    for k, s, a in zip(keys, r['sums'], r['abs_sums']):
+        v = ours.state_dict()[k].double()
+        assert abs(float(v.sum()) - s) <= 1e-12 * a + 1e-30, (k, float(v.sum()), s)
+        assert abs(float(v.abs().sum()) - a) <= 1e-12 * a + 1e-30, (k, float(v.abs().sum()), a)
+
+
+def test_bench_dump_outputs_types_sample_and_budget(tmp_path):
+    """bench.py --dump-outputs: float64 / integer outputs are written as float64, every other dtype as float32, shapes kept;
+    an output above DUMP_SAMPLE elements becomes the same seeded sample on every call; more than 64 MB in all is refused."""
+    import numpy as np
+    import bench
+    big = torch.arange(bench.DUMP_SAMPLE + 5, dtype=torch.float32)
+    outs = {'a/b': torch.ones(2, 3, dtype=torch.bfloat16), 'idx': torch.tensor([3, 2 ** 40]), 'f64': torch.tensor(0.1, dtype=torch.float64),
+            'flag': torch.tensor([True, False]), 'big': big}
+    index = bench.dump_outputs(str(tmp_path / 'x'), outs)
+    assert index == {'a/b': [[2, 3], False], 'idx': [[2], False], 'f64': [[], False], 'flag': [[2], False], 'big': [[bench.DUMP_SAMPLE + 5], True]}
+    ld = lambda d, n: np.load(str(tmp_path / d / f'{n}.npy'))
+    assert ld('x', 'a_b').dtype == np.float32 and ld('x', 'a_b').shape == (2, 3) and (ld('x', 'a_b') == 1).all()
+    assert ld('x', 'idx').dtype == np.float64 and ld('x', 'idx').tolist() == [3, 2 ** 40]
+    assert ld('x', 'f64').dtype == np.float64 and ld('x', 'f64') == 0.1
+    assert ld('x', 'flag').dtype == np.float32 and ld('x', 'flag').tolist() == [1, 0]
+    s = ld('x', 'big')
+    assert s.shape == (bench.DUMP_SAMPLE,) and (np.diff(s) > 0).all() and s[-1] <= bench.DUMP_SAMPLE + 4
+    bench.dump_outputs(str(tmp_path / 'y'), {'big': big})
+    assert np.array_equal(ld('y', 'big'), s)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / 'z'), {f'p{i}': big for i in range(9)})
 
 
 def test_graft_entry_build_passes():
