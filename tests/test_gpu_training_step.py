@@ -598,8 +598,8 @@ def _run_pair(oconf, steps, forced=False, seed=0, mutate=None):
     ora.init_optimizers()
     model = _build(oconf, params)
     opts = model.init_optimizers(oconf.adam_lr, oconf.adam_lr_actor, oconf.adam_lr_critic, oconf.adam_eps)
-    st_o = ora.init_state(oconf.batch_size)
-    st_h = model.init_state(oconf.batch_size)
+    st_o = ora.init_state(oconf.batch_size * oconf.iwae_samples)       # IWAE: B*I state rows, row b*I + i (rssm.py:35-41)
+    st_h = model.init_state(oconf.batch_size * oconf.iwae_samples)
     out = []
     for s in range(steps):
         raw = O.synthetic_batch(oconf, seed=1234 + s, first=(s == 0))
@@ -609,7 +609,7 @@ def _run_pair(oconf, steps, forced=False, seed=0, mutate=None):
         obs = O.preprocess(raw, oconf)
         lo, st_o2, mo, to, xo = ora.training_step(obs, st_o, noise)
         gmo, go = ora.backward_clip_step(lo)
-        fidx = xo['post_idx'].reshape(oconf.batch_length, oconf.batch_size, -1).to(DEV) if forced else None
+        fidx = xo['post_idx'].reshape(oconf.batch_length, oconf.batch_size * oconf.iwae_samples, -1).to(DEV) if forced else None
         lh, st_h2, mh, th, _ = model.training_step(_to_dev(obs), st_h, noise=_to_dev(noise), forced_idx=fidx)
         for opt in opts:
             opt.zero_grad()
@@ -631,7 +631,7 @@ def _run_pair(oconf, steps, forced=False, seed=0, mutate=None):
 
 
 def _check_pair(r, oconf, free_running=True):
-    T, B, S = oconf.batch_length, oconf.batch_size, oconf.stoch_dim
+    T, B, S = oconf.batch_length, oconf.batch_size * oconf.iwae_samples, oconf.stoch_dim      # posterior rows: B*I under IWAE
     if free_running:
         pi_h = r['xh']['post_idx'].cpu().long().reshape(T, B, S)
         pi_o = r['xo']['post_idx'].reshape(T, B, S)
@@ -683,6 +683,38 @@ def test_training_step_at_dispatch_boundaries_vs_oracle(hip, B, T, Hh):
     sampled index, per-parameter gradient and post-AdamW parameter against the oracle."""
     oconf = O.tiny_conf(batch_size=B, batch_length=T, imag_horizon=Hh)
     for r in _run_pair(oconf, 2, seed=B + T):
+        _check_pair(r, oconf)
+
+
+NON_DEFAULT_BOUNDARY_CASES = [
+    # Gaussian latents: posterior rows 17 / 32 / 33 / 65, imagination rows T x B = 255 / 256 / 66 / 260
+    dict(stoch_discrete=0, batch_size=17, batch_length=15), dict(stoch_discrete=0, batch_size=32, batch_length=8),
+    dict(stoch_discrete=0, batch_size=33, batch_length=2), dict(stoch_discrete=0, batch_size=65, batch_length=4),
+    # continuous actors, action_dim 1 and 12, imagination rows 255 / 256 / 260
+    dict(actor_dist='tanh_normal', action_dim=1, batch_size=17, batch_length=15),
+    dict(actor_dist='tanh_normal', action_dim=12, batch_size=65, batch_length=4),
+    dict(actor_dist='normal_tanh', action_dim=12, batch_size=17, batch_length=15),
+    dict(actor_dist='normal_tanh', action_dim=1, batch_size=32, batch_length=8),
+]
+
+
+def _case_id(kw):
+    fam = 'actor' if 'actor_dist' in kw else 'gauss'
+    parts = [fam] + [f'{k}={v}' for k, v in kw.items() if k not in ('batch_size', 'batch_length')]
+    return '-'.join(parts) + f'-B{kw["batch_size"]}-T{kw["batch_length"]}'
+
+
+@pytest.mark.parametrize('kw', NON_DEFAULT_BOUNDARY_CASES, ids=[_case_id(k) for k in NON_DEFAULT_BOUNDARY_CASES])
+def test_non_default_configs_at_dispatch_boundaries_vs_oracle(hip, kw):
+    """The sibling of test_training_step_at_dispatch_boundaries_vs_oracle for the configurations off the default path:
+    Gaussian latents (stoch_discrete = 0) and the tanh_normal / normal_tanh actors with one and twelve action dimensions, each
+    at posterior-row counts around 16 / 32 / 64 and imagination row counts T x B of 255 / 256 / 260.  Two consecutive trainer
+    iterations, all of _check_pair's bars."""
+    kw = dict(kw)
+    if 'actor_dist' in kw:
+        kw.setdefault('entropy', 1.0e-4)
+    oconf = O.tiny_conf(imag_horizon=2, **kw)
+    for r in _run_pair(oconf, 2, seed=kw['batch_size'] + kw['batch_length']):
         _check_pair(r, oconf)
 
 
