@@ -70,7 +70,7 @@ typedef struct dm_shape {
 #define DM_FLAG_GRU_MASK (3 << DM_FLAG_GRU_SHIFT)
 
 /* ---------------------------------------------------------------- library ---------------------- */
-int dm_version(void);                 /* ABI version, currently 13 (v2: LayerNorm-GRU slots; v3: per-call precision; v4: GRUCellStack layer slots;
+int dm_version(void);                 /* ABI version, currently 14 (v2: LayerNorm-GRU slots; v3: per-call precision; v4: GRUCellStack layer slots;
                                          v5: dm_kl_sampled_gauss_*, dm_chain_graph_*, dm_fp32_mode - additions only;
                                          v6: LayerNorm slots of GRUCellStack layers 1..3, dm_rssm_params grows to 58;
                                          v7: dm_wgrad_side_arm / _join, dm_dream_rollout_marks, dm_mlp_head_fwd_rows - additions only;
@@ -82,12 +82,14 @@ int dm_version(void);                 /* ABI version, currently 13 (v2: LayerNor
                                          v11: dm_dec_l4_bwd_direct_enable added;
                                          v12: dm_rssm_lds_status_ack / dm_rssm_lds_gave_up; the native exchange step dm_rccl_* / dm_allreduce_grads;
                                               dm_rollout_fuse_act_enable;
-                                         v13: dm_wgrad_side_touch added */
+                                         v13: dm_wgrad_side_touch added;
+                                         v14: dm_conv_encoder_fwd_rows, dm_conv_decoder_mse_fwd_rows, dm_rssm_sequence_fwd_steps removed (the forward
+                                              time-chunk pipeline) */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
 size_t dm_workspace_bytes(const dm_shape* shp);   /* scratch needed by any call below for this shape */
-/* A stream confined to the CUs whose bit is set in mask[0..words) (32 CUs per word): the host mirror reserves CUs for the
- * posterior loop's latency chain with it (no reference counterpart: torch exposes no CU masks). */
+/* A stream confined to the CUs whose bit is set in mask[0..words) (32 CUs per word), for CU-reservation experiments (no
+ * reference counterpart: torch exposes no CU masks). */
 int dm_stream_create_cu_mask(const uint32_t* mask, int words, void** stream);
 int dm_stream_destroy(void* stream);
 /* Weight gradients off the critical chain.  In the world-model backward (train.py:189 loss_model.backward()) only the DATA
@@ -299,11 +301,6 @@ typedef struct dm_conv_grads { float* w[5]; float* b[5]; } dm_conv_grads;
 size_t dm_conv_encoder_acts_floats(const dm_shape* shp);
 int dm_conv_encoder_fwd(const dm_shape* shp, const float* image /* (N,ch,64,64) */, const dm_conv_params* p,
                         float* acts, float* embed /* (N,E) torch (c,y,x) order */, void* ws, size_t ws_bytes, void* stream);
-/* Frames [n0, n0+n) only (all buffers are the full-batch ones; every per-layer buffer is frame-major).  prepare != 0 also
- * builds what all ranges share (gather tables, repacked weights); n = 0 prepares only.  Lets the host pipeline time chunks
- * of encoder -> posterior loop -> decoder over three streams (the T-step loop is a latency chain that leaves most CUs idle). */
-int dm_conv_encoder_fwd_rows(const dm_shape* shp, int n0, int n, int prepare, const float* image, const dm_conv_params* p,
-                             float* acts, float* embed, void* ws, size_t ws_bytes, void* stream);
 int dm_conv_encoder_bwd(const dm_shape* shp, const float* image, const dm_conv_params* p, const float* acts,
                         const float* dembed, const dm_conv_grads* g, void* ws, size_t ws_bytes, void* stream);
 
@@ -316,10 +313,6 @@ size_t dm_conv_decoder_pred_offset(const dm_shape* shp);
 int dm_conv_decoder_mse_fwd(const dm_shape* shp, const float* feat, int ldf, const float* target,
                             const dm_conv_params* p, float* acts, float* loss_image, float* image_rec /* nullable, NCHW */,
                             void* ws, size_t ws_bytes, void* stream);
-/* Frame-range form, see dm_conv_encoder_fwd_rows; the workspace need scales with n. */
-int dm_conv_decoder_mse_fwd_rows(const dm_shape* shp, int n0, int n, int prepare, const float* feat, int ldf,
-                                 const float* target, const dm_conv_params* p, float* acts, float* loss_image,
-                                 float* image_rec, void* ws, size_t ws_bytes, void* stream);
 /* dfeat (N,F) accumulated (+=) ; scale = image_weight / (T*B).  _rows: an optional per-frame factor on top (IWAE weights). */
 int dm_conv_decoder_mse_bwd_rows(const dm_shape* shp, const float* feat, int ldf, const float* target,
                                  const dm_conv_params* p, const float* acts, float scale, const float* row_scale,
@@ -359,12 +352,6 @@ int dm_rssm_sequence_fwd(const dm_shape* shp, const float* embed, const float* a
                          const float* h0, const float* z0, const float* u, const int32_t* forced_idx,
                          const dm_rssm_params* p, float* acts, float* feat, float* post, float* prior, int32_t* idx,
                          void* ws, size_t ws_bytes, void* stream);
-/* Time steps [t0, t1) only: step t0 > 0 continues from the state step t0-1 left in `feat`; consecutive ranges issued in
- * order on one stream equal one full call (rssm.py:38-58 is a plain loop over t). */
-int dm_rssm_sequence_fwd_steps(const dm_shape* shp, int t0, int t1, const float* embed, const float* action,
-                               const uint8_t* reset, const float* h0, const float* z0, const float* u,
-                               const int32_t* forced_idx, const dm_rssm_params* p, float* acts, float* feat, float* post,
-                               float* prior, int32_t* idx, void* ws, size_t ws_bytes, void* stream);
 /* dfeat (N,F) from decoders/heads (consumed, overwritten as scratch), dpost/dprior (N,Z) from the KL term.
  * Produces parameter grads and dembed (N,E). */
 int dm_rssm_sequence_bwd(const dm_shape* shp, const float* embed, const float* action, const uint8_t* reset,

@@ -495,91 +495,69 @@ __global__ void __launch_bounds__(256) nhwc_to_chw_flat_kernel(size_t n, int hw,
   }
 }
 
-// Frames [n0, n0+n) of the batch; `acts` / `embed` / `image` are the FULL-batch buffers (every per-layer buffer is
-// frame-major, so a frame range is a contiguous slice of each).  prepare != 0 additionally builds what all ranges share
-// (gather tables, repacked weights) - callers that pipeline ranges over several streams prepare once, with n = 0, on
-// the stream every range stream waits on.
-extern "C" int dm_conv_encoder_fwd_rows(const dm_shape* shp, int n0, int n, int prepare, const float* image,
-                                        const dm_conv_params* p, float* acts, float* embed, void* ws, size_t ws_bytes,
-                                        void* stream) {
+extern "C" int dm_conv_encoder_fwd(const dm_shape* shp, const float* image, const dm_conv_params* p, float* acts,
+                                   float* embed, void* ws, size_t ws_bytes, void* stream) {
   DM_REQUIRE(shp && image && p && acts && embed && ws, DM_E_NULL, "conv_encoder_fwd: null pointer");
   DmPrecisionScope prec(shp->flags & DM_FLAG_BF16);
   EncGeom g(shp);
   DM_REQUIRE(g.valid(shp), DM_E_SHAPE, "conv_encoder: unsupported geometry (img=%d, E=%d, depth=%d)", shp->img, shp->E,
              shp->cnn_depth);
-  DM_REQUIRE(n0 >= 0 && n >= 0 && n0 + n <= g.N, DM_E_SHAPE, "conv_encoder_fwd: frame range [%d,%d) outside 0..%d", n0,
-             n0 + n, g.N);
   hipStream_t st = (hipStream_t)stream;
   EncActs a;
   enc_carve(g, acts, (size_t)1 << 60, &a);
   DM_REQUIRE(ws_bytes >= DM_SPLITK_FLOATS * sizeof(float), DM_E_WORKSPACE, "conv_encoder_fwd: workspace too small");
   DmTwinScope tw((shp->flags & DM_FLAG_BF16) != 0);
-  enc_register_twins(g, a, false, !prepare && dm_twin_arena_valid(acts));
+  enc_register_twins(g, a, false, false);
   dm_twin_arena_note(acts, dm_twins_on());
-  if (prepare) {
-    for (int l = 1; l < 4; ++l) {
-      DM_TRY(conv_tables_launch(g.N, g.hb[l], g.hb[l], g.cin[l], 4, a.rowoff[l], a.koff[l], st));
-      DM_TRY(dm_permute4_launch(p->w[l], a.wr[l], g.cout[l], g.cin[l], 4, 4, 0, 2, 3, 1, st));
-    }
-    if (dm_twins_on()) {
-      DmCvtSeg sg[3];
-      for (int l = 1; l < 4; ++l) { sg[l - 1] = DmCvtSeg{a.wr[l], a.wrh[l], (size_t)g.cout[l] * g.kdim[l]}; dm_twin_mark(a.wr[l]); }
-      DM_TRY(dm_to_bf16_multi_launch(sg, 3, st));
-    }
+  for (int l = 1; l < 4; ++l) {
+    DM_TRY(conv_tables_launch(g.N, g.hb[l], g.hb[l], g.cin[l], 4, a.rowoff[l], a.koff[l], st));
+    DM_TRY(dm_permute4_launch(p->w[l], a.wr[l], g.cout[l], g.cin[l], 4, 4, 0, 2, 3, 1, st));
   }
-  if (n == 0) return DM_OK;
+  if (dm_twins_on()) {
+    DmCvtSeg sg[3];
+    for (int l = 1; l < 4; ++l) { sg[l - 1] = DmCvtSeg{a.wr[l], a.wrh[l], (size_t)g.cout[l] * g.kdim[l]}; dm_twin_mark(a.wr[l]); }
+    DM_TRY(dm_to_bf16_multi_launch(sg, 3, st));
+  }
+  if (g.N == 0) return DM_OK;
   for (int l = 0; l < 4; ++l) {
-    const size_t r0 = (size_t)n0 * g.hs[l] * g.hs[l];          // first patch row of the range in layer l
     if (l == 0 && g.direct0) {      // 3 -> d channels: one direct kernel on the frame, no patch matrix (conv_direct.hip)
       DmArena ar(ws, ws_bytes);
       ar.take(DM_SPLITK_FLOATS);
       float* wt = ar.take((size_t)48 * g.d);
       DM_REQUIRE(ar.ok, DM_E_WORKSPACE, "conv_encoder_fwd: workspace too small for the layer-1 weights");
-      const size_t frame = (size_t)g.ch * g.hb[0] * g.hb[0];
-      const void* img = shape_u8(shp) ? (const void*)((const uint8_t*)image + (size_t)n0 * frame)
-                                      : (const void*)(image + (size_t)n0 * frame);
-      unsigned short* y0h = dm_twin_of(a.y[0] + r0 * g.cout[0], false);
-      DM_TRY(dm_enc_l1_fwd_launch(n, g.d, shape_u8(shp) ? 1 : 0, img, p->w[0], p->b[0], wt, a.y[0] + r0 * g.cout[0], y0h, st));
+      unsigned short* y0h = dm_twin_of(a.y[0], false);
+      DM_TRY(dm_enc_l1_fwd_launch(g.N, g.d, shape_u8(shp) ? 1 : 0, image, p->w[0], p->b[0], wt, a.y[0], y0h, st));
       if (y0h) dm_twin_mark(a.y[0]);
       continue;
     }
     if (l == 0) {
-      const size_t frame = (size_t)g.ch * g.hb[0] * g.hb[0];
       if (shape_u8(shp)) {
-        const size_t total = (size_t)n * g.hs[0] * g.hs[0] * g.kdim[0];
-        hipLaunchKernelGGL(im2col_s2_u8hwc_kernel, dim3(grid_for(total)), dim3(256), 0, st, n, g.hb[0], g.hb[0], g.cin[0], 4,
-                           g.hs[0], g.hs[0], (const uint8_t*)image + (size_t)n0 * frame, a.xcol[0] + r0 * g.kdim[0]);
+        const size_t total = (size_t)g.N * g.hs[0] * g.hs[0] * g.kdim[0];
+        hipLaunchKernelGGL(im2col_s2_u8hwc_kernel, dim3(grid_for(total)), dim3(256), 0, st, g.N, g.hb[0], g.hb[0], g.cin[0], 4,
+                           g.hs[0], g.hs[0], (const uint8_t*)image, a.xcol[0]);
         DM_LAUNCH_CHECK();
       } else {
-        DM_TRY(dm_im2col_s2_launch(n, g.hb[0], g.hb[0], g.cin[0], 4, image + (size_t)n0 * frame, 1,
-                                   a.xcol[0] + r0 * g.kdim[0], st));
+        DM_TRY(dm_im2col_s2_launch(g.N, g.hb[0], g.hb[0], g.cin[0], 4, image, 1, a.xcol[0], st));
       }
     }
     DmGemm q;
     q.a_layout = 0; q.b_layout = 0;
-    q.M = n * g.hs[l] * g.hs[l]; q.N = g.cout[l]; q.K = (int)g.kdim[l];
-    if (l == 0) { q.A = a.xcol[0] + r0 * g.kdim[0]; q.lda = q.K; }
+    q.M = g.N * g.hs[l] * g.hs[l]; q.N = g.cout[l]; q.K = (int)g.kdim[l];
+    if (l == 0) { q.A = a.xcol[0]; q.lda = q.K; }
     else {
-      q.A = a.y[l - 1]; q.a_maj = a.rowoff[l] + r0; q.a_min = a.koff[l];
+      q.A = a.y[l - 1]; q.a_maj = a.rowoff[l]; q.a_min = a.koff[l];
       q.a_tab_vec = (g.cin[l] & 3) == 0; q.a_tab_vec8 = (g.cin[l] & 7) == 0;
     }
     q.B = l == 0 ? p->w[0] : a.wr[l]; q.ldb = q.K;
-    q.C = a.y[l] + r0 * g.cout[l]; q.ldc = q.N;
+    q.C = a.y[l]; q.ldc = q.N;
     q.bias = p->b[l];
     q.flags = DM_GEMM_ELU;
     DM_TRY(dm_gemm_launch(q, ws, DM_SPLITK_FLOATS * sizeof(float), st));
   }
-  const size_t tot = (size_t)n * 4 * g.cout[3];
-  hipLaunchKernelGGL(nhwc_to_chw_flat_kernel, dim3(grid_for(tot)), dim3(256), 0, st, (size_t)n, 4, g.cout[3],
-                     a.y[3] + (size_t)n0 * 4 * g.cout[3], embed + (size_t)n0 * 4 * g.cout[3], 1);
+  const size_t tot = (size_t)g.N * 4 * g.cout[3];
+  hipLaunchKernelGGL(nhwc_to_chw_flat_kernel, dim3(grid_for(tot)), dim3(256), 0, st, (size_t)g.N, 4, g.cout[3], a.y[3], embed, 1);
   DM_LAUNCH_CHECK();
   return DM_OK;
-}
-extern "C" int dm_conv_encoder_fwd(const dm_shape* shp, const float* image, const dm_conv_params* p, float* acts,
-                                   float* embed, void* ws, size_t ws_bytes, void* stream) {
-  DM_REQUIRE(shp, DM_E_NULL, "conv_encoder_fwd: null shape");
-  return dm_conv_encoder_fwd_rows(shp, 0, shp->T * shp->B * (shp->I > 0 ? shp->I : 1), 1, image, p, acts, embed, ws,
-                                  ws_bytes, stream);
 }
 
 extern "C" int dm_conv_encoder_bwd(const dm_shape* shp, const float* image, const dm_conv_params* p, const float* acts,
@@ -792,32 +770,27 @@ extern "C" size_t dm_conv_decoder_pred_offset(const dm_shape* shp) {
   return off;
 }
 
-// Frames [n0, n0+n); buffers are the full-batch ones (see dm_conv_encoder_fwd_rows).  The patch-matrix workspace
-// scales with n, so a range stream needs only 1/chunks of the full-batch workspace.
-extern "C" int dm_conv_decoder_mse_fwd_rows(const dm_shape* shp, int n0, int n, int prepare, const float* feat, int ldf,
-                                            const float* target, const dm_conv_params* p, float* acts, float* loss_image,
-                                            float* image_rec, void* ws, size_t ws_bytes, void* stream) {
+extern "C" int dm_conv_decoder_mse_fwd(const dm_shape* shp, const float* feat, int ldf, const float* target,
+                                       const dm_conv_params* p, float* acts, float* loss_image, float* image_rec,
+                                       void* ws, size_t ws_bytes, void* stream) {
   DM_REQUIRE(shp && feat && target && p && acts && ws, DM_E_NULL, "conv_decoder_fwd: null pointer");
   DmPrecisionScope prec(shp->flags & DM_FLAG_BF16);
   DecGeom g(shp);
   DM_REQUIRE(g.valid(shp), DM_E_SHAPE, "conv_decoder: unsupported geometry (img=%d)", shp->img);
-  DM_REQUIRE(n0 >= 0 && n >= 0 && n0 + n <= g.N, DM_E_SHAPE, "conv_decoder_fwd: frame range [%d,%d) outside 0..%d", n0,
-             n0 + n, g.N);
+  const int n = g.N;
   hipStream_t st = (hipStream_t)stream;
   DecActs a;
   dec_carve(g, acts, (size_t)1 << 60, &a);
   DmTwinScope tw((shp->flags & DM_FLAG_BF16) != 0);
   const bool tw_on = dm_twins_on();
-  dec_register_twins(g, a, false, !prepare && dm_twin_arena_valid(acts));
+  dec_register_twins(g, a, false, false);
   dm_twin_arena_note(acts, tw_on);
-  if (prepare) {
-    for (int l = 1; l <= 4; ++l)
-      DM_TRY(dm_permute4_launch(p->w[l], a.wr[l], g.cin[l], g.cout[l], g.k[l], g.k[l], 0, 2, 3, 1, st));
-    if (tw_on) {
-      DmCvtSeg sg[4];
-      for (int l = 1; l <= 4; ++l) { sg[l - 1] = DmCvtSeg{a.wr[l], a.wrh[l], dec_w_elems(g, l)}; dm_twin_mark(a.wr[l]); }
-      DM_TRY(dm_to_bf16_multi_launch(sg, 4, st));
-    }
+  for (int l = 1; l <= 4; ++l)
+    DM_TRY(dm_permute4_launch(p->w[l], a.wr[l], g.cin[l], g.cout[l], g.k[l], g.k[l], 0, 2, 3, 1, st));
+  if (tw_on) {
+    DmCvtSeg sg[4];
+    for (int l = 1; l <= 4; ++l) { sg[l - 1] = DmCvtSeg{a.wr[l], a.wrh[l], dec_w_elems(g, l)}; dm_twin_mark(a.wr[l]); }
+    DM_TRY(dm_to_bf16_multi_launch(sg, 4, st));
   }
   if (n == 0) return DM_OK;
   DmArena ar(ws, ws_bytes);
@@ -851,18 +824,17 @@ extern "C" int dm_conv_decoder_mse_fwd_rows(const dm_shape* shp, int n0, int n, 
   {
     DmGemm q;   // x0 = feat W^T + b
     q.M = n; q.N = g.cin[1]; q.K = g.F;
-    q.A = feat + (size_t)n0 * ldf; q.lda = ldf;
+    q.A = feat; q.lda = ldf;
     q.B = p->w[0]; q.ldb = g.F;
-    q.C = a.x[0] + (size_t)n0 * g.cin[1]; q.ldc = q.N;
+    q.C = a.x[0]; q.ldc = q.N;
     q.bias = p->b[0];
     DM_TRY(dm_gemm_launch(q, splitk, skb, st));
   }
   for (int l = 1; l <= 4; ++l) {
     const int kk = g.k[l] * g.k[l];
-    const float* xin = l == 1 ? a.x[0] + (size_t)n0 * g.cin[1]
-                              : a.x[l - 1] + (size_t)n0 * g.hbg[l - 1] * g.hbg[l - 1] * g.cout[l - 1];
+    const float* xin = a.x[l - 1];
     if (l == 4 && direct4) {
-      DM_TRY(dm_dec_l4_fwd_launch(n, g.d, xin, p->w[4], p->b[4], w4, a.x[4] + (size_t)n0 * g.hbg[4] * g.hbg[4] * g.cout[4], st));
+      DM_TRY(dm_dec_l4_fwd_launch(n, g.d, xin, p->w[4], p->b[4], w4, a.x[4], st));
       continue;
     }
     if (convt_gather_ok(g.k[l], g.cin[l], g.cout[l], g.hsm[l], (size_t)n)) {
@@ -890,7 +862,7 @@ extern "C" int dm_conv_decoder_mse_fwd_rows(const dm_shape* shp, int n0, int n, 
       q.A = xpad; q.a_maj = t_rowoff; q.a_min = t_koff; q.a_tab_vec = 1; q.a_tab_vec8 = 1;
       if (hpath) { q.A = nullptr; q.A_h = (const unsigned short*)xpad; q.B_h = wcat_h; }
       q.B = wcat; q.ldb = kdim;
-      q.C = a.x[l] + (size_t)n0 * hb * hb * g.cout[l];
+      q.C = a.x[l];
       q.c_tab = t_ctab; q.sc_cout = g.cout[l]; q.sc_wpitch = hb * g.cout[l];
       q.bias = p->b[l];
       q.flags = l < 4 ? DM_GEMM_ELU : 0;
@@ -904,7 +876,7 @@ extern "C" int dm_conv_decoder_mse_fwd_rows(const dm_shape* shp, int n0, int n, 
     q.B = a.wr[l]; q.ldb = q.N;
     q.C = ycol; q.ldc = q.N;
     if (g.hsm[l] == 1) {     // a 1x1 input: no windows overlap, the column matrix IS the NHWC output - bias + ELU in the epilogue
-      q.C = a.x[l] + (size_t)n0 * g.hbg[l] * g.hbg[l] * g.cout[l];
+      q.C = a.x[l];
       q.bias = p->b[l]; q.bias_mod = g.cout[l];
       q.flags = l < 4 ? DM_GEMM_ELU : 0;
       DM_TRY(dm_gemm_launch(q, splitk, skb, st));
@@ -912,28 +884,16 @@ extern "C" int dm_conv_decoder_mse_fwd_rows(const dm_shape* shp, int n0, int n, 
     }
     DM_TRY(dm_gemm_launch(q, splitk, skb, st));
     DM_TRY(dm_col2im_s2_launch(n, g.hbg[l], g.hbg[l], g.cout[l], g.k[l], ycol, p->b[l], l < 4 ? DM_C2I_ELU : 0, nullptr,
-                               a.x[l] + (size_t)n0 * g.hbg[l] * g.hbg[l] * g.cout[l], st));
+                               a.x[l], st));
   }
   if (loss_image || image_rec) {
-    // targets are indexed by frame / I (I = iwae_samples, decoders.py:163-167), so the kernel gets the full target base
-    const size_t per = (size_t)g.hbg[4] * g.hbg[4] * g.ch;
+    // targets are indexed by frame / I (I = iwae_samples, decoders.py:163-167)
     const int I = shp->I > 0 ? shp->I : 1;
-    DM_REQUIRE(n0 % I == 0, DM_E_SHAPE, "conv_decoder_fwd: frame range must start on a multiple of iwae_samples");
-    const void* tbase = shape_u8(shp) ? (const void*)((const uint8_t*)target + (size_t)(n0 / I) * per)
-                                      : (const void*)(target + (size_t)(n0 / I) * per);
-    DM_TRY(mse_launch(shape_u8(shp), n, g.hbg[4] * g.hbg[4], g.ch, a.x[4] + n0 * per, tbase, I, 0.f, nullptr,
-                      loss_image ? loss_image + n0 : nullptr, nullptr, g.ch, image_rec ? image_rec + n0 * per : nullptr, st));
+    DM_TRY(mse_launch(shape_u8(shp), n, g.hbg[4] * g.hbg[4], g.ch, a.x[4], target, I, 0.f, nullptr, loss_image, nullptr, g.ch,
+                      image_rec, st));
   }
   return DM_OK;
 }
-extern "C" int dm_conv_decoder_mse_fwd(const dm_shape* shp, const float* feat, int ldf, const float* target,
-                                       const dm_conv_params* p, float* acts, float* loss_image, float* image_rec,
-                                       void* ws, size_t ws_bytes, void* stream) {
-  DM_REQUIRE(shp, DM_E_NULL, "conv_decoder_fwd: null shape");
-  return dm_conv_decoder_mse_fwd_rows(shp, 0, shp->T * shp->B * (shp->I > 0 ? shp->I : 1), 1, feat, ldf, target, p, acts,
-                                      loss_image, image_rec, ws, ws_bytes, stream);
-}
-
 static int conv_decoder_mse_bwd_impl(const dm_shape* shp, const float* feat, int ldf, const float* target,
                                      const dm_conv_params* p, const float* acts, float scale, const float* row_scale,
                                      const dm_conv_grads* gr, float* dfeat, int lddf, void* ws, size_t ws_bytes, void* stream);

@@ -3,7 +3,6 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
-#include <stdlib.h>
 #include <mutex>
 
 static thread_local char g_err[512] = "";
@@ -16,7 +15,7 @@ int dm_fail(int code, const char* fmt, ...) {
   return code;
 }
 
-extern "C" int dm_version(void) { return 13; }
+extern "C" int dm_version(void) { return 14; }
 extern "C" const char* dm_last_error(void) { return g_err; }
 
 extern "C" int dm_device_check(void) {
@@ -30,8 +29,7 @@ extern "C" int dm_device_check(void) {
 }
 
 // A HIP stream restricted to a subset of the compute units (hipExtStreamCreateWithCUMask): `mask` has one bit per CU, 32
-// per word.  Used by WorldModel's time-chunk pipeline to RESERVE a few CUs of every XCD for the posterior loop's latency
-// chain, so its small kernels never queue behind the convolution GEMMs of the neighbouring streams.
+// per word.  bench.py's DM_MAIN_RESERVE_CUS experiment runs the caller's stream on one.
 extern "C" int dm_stream_create_cu_mask(const uint32_t* mask, int words, void** stream) {
   DM_REQUIRE(mask && stream && words >= 1, DM_E_NULL, "stream_create_cu_mask: null argument");
   hipStream_t s = nullptr;
@@ -65,20 +63,8 @@ static int side_init_locked() {
   if (g_side_stream) return dm_fail(DM_E_DEVICE, "wgrad_side: created on device %d, called on device %d", g_side_dev, dev);
   int least = 0, greatest = 0;
   (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-  const char* pe = getenv("DM_WGRAD_SIDE_PRIO");
-  const int prio = pe ? atoi(pe) : least;               // lowest priority: the chains' small kernels dispatch first
-  // DM_WGRAD_SIDE_RESERVE_CUS=k (experiment): the side stream without the first k CUs of every 32 (hipExtStreamCreateWithCUMask),
-  // so the deferred weight-gradient products never occupy the CUs the BPTT chain's small kernels are dispatched to
-  const char* re = getenv("DM_WGRAD_SIDE_RESERVE_CUS");
-  const int res = re ? atoi(re) : 0;
-  hipError_t e;
-  if (res > 0 && res < 32) {
-    uint32_t mask[8];
-    for (int i = 0; i < 8; ++i) mask[i] = 0xFFFFFFFFu ^ ((1u << res) - 1u);
-    e = hipExtStreamCreateWithCUMask(&g_side_stream, 8, mask);
-  } else {
-    e = hipStreamCreateWithPriority(&g_side_stream, hipStreamNonBlocking, prio);
-  }
+  // lowest priority: the chains' small kernels dispatch first
+  hipError_t e = hipStreamCreateWithPriority(&g_side_stream, hipStreamNonBlocking, least);
   for (int i = 0; i < 8 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&g_side_fork_ev[i], hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&g_side_done_ev, hipEventDisableTiming);
   if (e != hipSuccess) return dm_fail(DM_E_HIP, "wgrad_side: %s", hipGetErrorString(e));

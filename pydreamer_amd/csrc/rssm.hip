@@ -17,7 +17,7 @@ struct RssmActs {
   float *ea, *ee, *hin, *zin, *x1, *st1, *za, *gi, *gh, *x2, *st2, *pin, *x3, *st3, *prin;
   float *gs, *gst;      // LayerNorm GRU cells: pre-LayerNorm gate sums (N,3D) and their statistics (N,6 per stack layer)
 };
-// A/B switch (DM_FWD_LN_Z=0): the posterior launch chain's gather kernel normalises its rows itself (see ln_z in dm_rssm_sequence_fwd_steps)
+// A/B switch (DM_FWD_LN_Z=0): the posterior launch chain's gather kernel normalises its rows itself (see ln_z in dm_rssm_sequence_fwd)
 static const int g_fwd_ln_z = getenv("DM_FWD_LN_Z") ? atoi(getenv("DM_FWD_LN_Z")) : 1;
 static inline int rssm_gru_kind(const dm_shape* s) { return (s->flags & DM_FLAG_GRU_MASK) >> DM_FLAG_GRU_SHIFT; }
 static inline int rssm_gru_layers(const dm_shape* s) {
@@ -188,21 +188,15 @@ static int gru_stack_fwd(hipStream_t st, void* sk, size_t skb, const GruStack& k
   return DM_OK;
 }
 
-// Time steps [t0, t1) of the sequence; all buffers are the full (T*B)-row ones.  Step t0 > 0 continues from the state
-// that step t0-1 left in `feat`, so consecutive ranges issued in order on one stream equal one full call; the encoder
-// range that feeds them and the decoder range that consumes them can then run on other streams (see WorldModel._forward).
-extern "C" int dm_rssm_sequence_fwd_steps(const dm_shape* s, int t0, int t1, const float* embed, const float* action,
-                                          const uint8_t* reset, const float* h0, const float* z0, const float* u,
-                                          const int32_t* forced_idx, const dm_rssm_params* P, float* acts, float* feat,
-                                          float* post, float* prior, int32_t* idx, void* ws, size_t ws_bytes,
-                                          void* stream) {
+extern "C" int dm_rssm_sequence_fwd(const dm_shape* s, const float* embed, const float* action, const uint8_t* reset,
+                                    const float* h0, const float* z0, const float* u, const int32_t* forced_idx,
+                                    const dm_rssm_params* P, float* acts, float* feat, float* post, float* prior,
+                                    int32_t* idx, void* ws, size_t ws_bytes, void* stream) {
   DM_REQUIRE(s && embed && action && reset && h0 && z0 && P && acts && feat && post && prior && ws, DM_E_NULL,
              "rssm_sequence_fwd: null pointer");
   DM_REQUIRE(u || forced_idx, DM_E_NULL, "rssm_sequence_fwd: need uniforms or forced indices");
   DmPrecisionScope prec(s->flags & DM_FLAG_BF16);
   DM_TRY(rssm_check(s));
-  DM_REQUIRE(t0 >= 0 && t0 <= t1 && t1 <= s->T, DM_E_SHAPE, "rssm_sequence_fwd: step range [%d,%d) outside 0..%d", t0, t1, s->T);
-  if (t0 == t1) return DM_OK;
   DM_REQUIRE(ws_bytes >= DM_SPLITK_FLOATS * sizeof(float), DM_E_WORKSPACE, "rssm_sequence_fwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   // Z: width of z (S one-hot groups of C, or S Gaussian dimensions when C = 0); ZP: width of the posterior / prior
@@ -210,23 +204,20 @@ extern "C" int dm_rssm_sequence_fwd_steps(const dm_shape* s, int t0, int t1, con
   const int T = s->T, B = s->B, D = s->D, Hd = s->Hd, S = s->S, C = s->C, Z = S * (C ? C : 1), ZP = S * (C ? C : 2);
   const int F = D + Z, E = s->E, A = s->A;
   const bool gauss = C == 0;
-  (void)T;
-  const int N = (t1 - t0) * B;                        // rows of this range
-  const size_t q0 = (size_t)t0 * B;                   // its first row
+  const int N = T * B;
   const size_t skb = DM_SPLITK_FLOATS * sizeof(float);
   RssmActs a;
   rssm_carve(s, acts, &a);
   const float* const* p = P->p;
 
-
-  DM_TRY(linear(st, ws, skb, N, Hd, A, action + q0 * A, A, p[DM_RSSM_A_W], nullptr, nullptr, 0, a.ea + q0 * Hd, Hd));
-  DM_TRY(linear(st, ws, skb, N, Hd, E, embed + q0 * E, E, p[DM_RSSM_POST_E_W], nullptr, nullptr, 0, a.ee + q0 * Hd, Hd));
+  DM_TRY(linear(st, ws, skb, N, Hd, A, action, A, p[DM_RSSM_A_W], nullptr, nullptr, 0, a.ea, Hd));
+  DM_TRY(linear(st, ws, skb, N, Hd, E, embed, E, p[DM_RSSM_POST_E_W], nullptr, nullptr, 0, a.ee, Hd));
 
   // Fused schedule (5 launches per step instead of 8) when the <= 64-row products qualify: the two LayerNorm+ELU stages
   // ride in the PROLOGUE of the product that consumes them (each workgroup recomputes the row statistics of its <= 64
   // rows from L2) and the straight-through sampler rides in the EPILOGUE of the posterior-logits product (one 32-logit
   // group per workgroup).  The post-LayerNorm activations `za` / `pin` that only the backward pass needs (weight
-  // gradients, ELU') are then produced for ALL rows of the range by two batched launches after the loop.
+  // gradients, ELU') are then produced for ALL rows by two batched launches after the loop.
   const int kind = rssm_gru_kind(s);
   const float* lng[3] = {p[DM_RSSM_GRU_LN_G0], p[DM_RSSM_GRU_LN_G1], p[DM_RSSM_GRU_LN_G2]};
   const float* lnb[3] = {p[DM_RSSM_GRU_LN_B0], p[DM_RSSM_GRU_LN_B1], p[DM_RSSM_GRU_LN_B2]};
@@ -251,11 +242,11 @@ extern "C" int dm_rssm_sequence_fwd_steps(const dm_shape* s, int t0, int t1, con
   DmArena ar(ws, ws_bytes);
   ar.take(DM_SPLITK_FLOATS);
   // z_mlp of the sampled (one-hot) latent as a gather-sum over rows of z_mlp^T (dm_z_embed_launch): every step after the
-  // first of a range takes its z from the sampler, whose indices are at hand; the first step's z comes from the caller as
-  // a dense vector and keeps the product.
+  // first takes its z from the sampler, whose indices are at hand; the first step's z comes from the caller as a dense
+  // vector and keeps the product.
   static const int no_embed = getenv("DM_RSSM_NO_Z_EMBED") ? 1 : 0;        // A/B switch
   float* wzt = nullptr;
-  if (!no_embed && !gauss && idx && t1 - t0 > 1 && dm_z_embed_ok(Hd)) {
+  if (!no_embed && !gauss && idx && T > 1 && dm_z_embed_ok(Hd)) {
     const size_t mark = ar.off;
     float* w = ar.take((size_t)Z * Hd);
     if (ar.ok) {
@@ -270,47 +261,44 @@ extern "C" int dm_rssm_sequence_fwd_steps(const dm_shape* s, int t0, int t1, con
     float* f3 = ar.take(dm_frag_floats(D)); float* f4 = ar.take(dm_frag_floats(Hd));
     if (ar.ok) { zinf = f0; x1f = f1; hinf = f2; hf = f3; x2f = f4; }
   }
-  // The fused schedule's steps after the first of a range as ONE persistent kernel with the cell's weights stationary in
+  // The fused schedule's steps after the first as ONE persistent kernel with the cell's weights stationary in
   // LDS (rssm_lds.hip): the first step runs as launches (its z is a dense vector from the caller) and leaves h, the masked
   // inputs and the indices the kernel's first step continues from.
   float* psync = nullptr;
   size_t psync_floats = 0;
-  if (normed && !stacked && !gauss && kind == 0 && wzt && idx && (F & 3) == 0 && t1 - t0 >= 3 && dm_rssm_lds_ok(B, D, Hd, S, C)) {
-    psync_floats = dm_rssm_lds_ws_floats(B, D, Hd, S, C, t1 - t0 - 1);
+  if (normed && !stacked && !gauss && kind == 0 && wzt && idx && (F & 3) == 0 && T >= 3 && dm_rssm_lds_ok(B, D, Hd, S, C)) {
+    psync_floats = dm_rssm_lds_ws_floats(B, D, Hd, S, C, T - 1);
     float* sy = ar.take(psync_floats);
     if (ar.ok) psync = sy;
     else ar.ok = true;
   }
-  const int t_launch_end = psync ? t0 + 1 : t1;
+  const int t_launch_end = psync ? 1 : T;
   // 8 launches per step otherwise: the reset masks of step t+1 are applied by the kernels that produce h_t and z_t (only
-  // the first step of a range needs the stand-alone mask kernel), and the GRU's two gate products share one launch.
-  for (int t = t0; t < t_launch_end; ++t) {
+  // the first step needs the stand-alone mask kernel), and the GRU's two gate products share one launch.
+  for (int t = 0; t < t_launch_end; ++t) {
     const size_t r0 = (size_t)t * B;
     float* hin = a.hin + r0 * D;
     float* zin = a.zin + r0 * Z;
-    if (t == t0) {
-      const float* ph = t == 0 ? h0 : feat + (r0 - B) * F;
-      const float* pz = t == 0 ? z0 : feat + (r0 - B) * F + D;
-      const int ldp_h = t == 0 ? D : F, ldp_z = t == 0 ? Z : F;
-      DM_TRY(dm_mask_rows2_launch(B, D, ph, ldp_h, hin, D, Z, pz, ldp_z, zin, Z, reset + r0, st));
+    if (t == 0) {
+      DM_TRY(dm_mask_rows2_launch(B, D, h0, D, hin, D, Z, z0, Z, zin, Z, reset, st));
       if (zinf) {
         DM_TRY(dm_frag_pack_launch(B, D, hin, D, hinf, st));
         DM_TRY(dm_frag_pack_launch(B, Z, zin, Z, zinf, st));
       }
     }
-    const bool more = t + 1 < t1;
+    const bool more = t + 1 < T;
     float* hin_next = more ? a.hin + (r0 + B) * D : nullptr;
     float* zin_next = more ? a.zin + (r0 + B) * Z : nullptr;
     const uint8_t* reset_next = more ? reset + r0 + B : nullptr;
     // x = z_mlp(z) + a_mlp(a) ; za = ELU(in_norm(x))                                   rssm.py:138-140
     // (ln_z: the gather kernel owns complete rows, so it also normalises them and the gate product below runs plain - the
     //  prologue form makes each of that product's 226 workgroups redo the LayerNorm + ELU of the whole operand)
-    const bool ln_z = fuse_ln && g_fwd_ln_z && wzt && t > t0 && x1f && !stacked && S <= 32;     // the row-per-workgroup form holds <= 32 groups (stoch_dim 64 / 96 take the branch below)
+    const bool ln_z = fuse_ln && g_fwd_ln_z && wzt && t > 0 && x1f && !stacked && S <= 32;     // the row-per-workgroup form holds <= 32 groups (stoch_dim 64 / 96 take the branch below)
     if (ln_z) {
       DM_TRY(dm_z_embed_launch(B, Hd, S, C, idx + (r0 - B) * S, reset + r0, wzt, p[DM_RSSM_Z_B], a.ea + r0 * Hd, Hd,
                                nullptr, nullptr, a.x1 + r0 * Hd, Hd, nullptr, p[DM_RSSM_IN_G], p[DM_RSSM_IN_B], 1e-3f,
                                a.za + r0 * Hd, Hd, st, x1f, a.st1 + r0 * 2));
-    } else if (wzt && t > t0) {
+    } else if (wzt && t > 0) {
       DM_TRY(dm_z_embed_launch(B, Hd, S, C, idx + (r0 - B) * S, reset + r0, wzt, p[DM_RSSM_Z_B], a.ea + r0 * Hd, Hd,
                                nullptr, nullptr, a.x1 + r0 * Hd, Hd, x1f, nullptr, nullptr, 0.f, nullptr, 0, st));
     } else {
@@ -386,7 +374,7 @@ extern "C" int dm_rssm_sequence_fwd_steps(const dm_shape* s, int t0, int t1, con
   }
   if (psync) {
     DmRssmLds pq;
-    pq.B = B; pq.D = D; pq.Hd = Hd; pq.S = S; pq.C = C; pq.F = F; pq.t_begin = t0 + 1; pq.t_end = t1;
+    pq.B = B; pq.D = D; pq.Hd = Hd; pq.S = S; pq.C = C; pq.F = F; pq.t_begin = 1; pq.t_end = T;
     pq.wzt = wzt; pq.zb = p[DM_RSSM_Z_B];
     pq.wih = p[DM_RSSM_GRU_WIH]; pq.bih = p[DM_RSSM_GRU_BIH]; pq.whh = p[DM_RSSM_GRU_WHH]; pq.bhh = p[DM_RSSM_GRU_BHH];
     pq.wph = p[DM_RSSM_POST_H_W]; pq.bph = p[DM_RSSM_POST_H_B]; pq.wpo = p[DM_RSSM_POST_W]; pq.bpo = p[DM_RSSM_POST_OB];
@@ -396,28 +384,15 @@ extern "C" int dm_rssm_sequence_fwd_steps(const dm_shape* s, int t0, int t1, con
     pq.idx = idx; pq.ws = psync; pq.ws_floats = psync_floats;
     DM_TRY(dm_rssm_lds_launch(pq, st));
   }
-  if (fuse_ln || psync) {     // what only the backward pass reads: post-LayerNorm activations + statistics of every row of the range
-    DM_TRY(norm_elu_fwd(N, Hd, a.x1 + q0 * Hd, Hd, p[DM_RSSM_IN_G], p[DM_RSSM_IN_B], 1e-3f, a.za + q0 * Hd, Hd,
-                                a.st1 + q0 * 2, st));
-    DM_TRY(norm_elu_fwd(N, Hd, a.x2 + q0 * Hd, Hd, p[DM_RSSM_POST_G], p[DM_RSSM_POST_B], 1e-3f, a.pin + q0 * Hd, Hd,
-                                a.st2 + q0 * 2, st));
+  if (fuse_ln || psync) {     // what only the backward pass reads: post-LayerNorm activations + statistics of every row
+    DM_TRY(norm_elu_fwd(N, Hd, a.x1, Hd, p[DM_RSSM_IN_G], p[DM_RSSM_IN_B], 1e-3f, a.za, Hd, a.st1, st));
+    DM_TRY(norm_elu_fwd(N, Hd, a.x2, Hd, p[DM_RSSM_POST_G], p[DM_RSSM_POST_B], 1e-3f, a.pin, Hd, a.st2, st));
   }
   // batch_prior over all (T*B) rows                                                    rssm.py:61,186-193
-  DM_TRY(linear(st, ws, skb, N, Hd, D, feat + q0 * F, F, p[DM_RSSM_PRIOR_H_W], p[DM_RSSM_PRIOR_H_B], nullptr, 0,
-                a.x3 + q0 * Hd, Hd));
-  DM_TRY(norm_elu_fwd(N, Hd, a.x3 + q0 * Hd, Hd, p[DM_RSSM_PRIOR_G], p[DM_RSSM_PRIOR_B], 1e-3f, a.prin + q0 * Hd,
-                              Hd, a.st3 + q0 * 2, st));
-  DM_TRY(linear(st, ws, skb, N, ZP, Hd, a.prin + q0 * Hd, Hd, p[DM_RSSM_PRIOR_W], p[DM_RSSM_PRIOR_OB], nullptr, 0,
-                prior + q0 * ZP, ZP));
+  DM_TRY(linear(st, ws, skb, N, Hd, D, feat, F, p[DM_RSSM_PRIOR_H_W], p[DM_RSSM_PRIOR_H_B], nullptr, 0, a.x3, Hd));
+  DM_TRY(norm_elu_fwd(N, Hd, a.x3, Hd, p[DM_RSSM_PRIOR_G], p[DM_RSSM_PRIOR_B], 1e-3f, a.prin, Hd, a.st3, st));
+  DM_TRY(linear(st, ws, skb, N, ZP, Hd, a.prin, Hd, p[DM_RSSM_PRIOR_W], p[DM_RSSM_PRIOR_OB], nullptr, 0, prior, ZP));
   return DM_OK;
-}
-extern "C" int dm_rssm_sequence_fwd(const dm_shape* s, const float* embed, const float* action, const uint8_t* reset,
-                                    const float* h0, const float* z0, const float* u, const int32_t* forced_idx,
-                                    const dm_rssm_params* P, float* acts, float* feat, float* post, float* prior,
-                                    int32_t* idx, void* ws, size_t ws_bytes, void* stream) {
-  DM_REQUIRE(s, DM_E_NULL, "rssm_sequence_fwd: null shape");
-  return dm_rssm_sequence_fwd_steps(s, 0, s->T, embed, action, reset, h0, z0, u, forced_idx, P, acts, feat, post, prior,
-                                    idx, ws, ws_bytes, stream);
 }
 
 // A/B switch of the BPTT launch schedule's folded LayerNorm backward (include/dreamer_hip.h dm_bptt_fold_enable; DM_BPTT_FOLD=0 in the environment)
@@ -815,7 +790,7 @@ extern "C" int dm_dream_rollout(const dm_shape* s, int M, const float* start, co
   DM_TRY(rssm_check(s));
   DM_REQUIRE(M >= 1 && s->H >= 1, DM_E_SHAPE, "dream_rollout: M=%d H=%d", M, s->H);
   hipStream_t st = (hipStream_t)stream;
-  const int H = s->H, D = s->D, Hd = s->Hd, S = s->S, C = s->C, Z = S * (C ? C : 1), ZP = S * (C ? C : 2);   // see fwd_steps
+  const int H = s->H, D = s->D, Hd = s->Hd, S = s->S, C = s->C, Z = S * (C ? C : 1), ZP = S * (C ? C : 2);   // see dm_rssm_sequence_fwd
   const int F = D + Z, A = s->A;
   const int Hm = s->mlp_hidden, L = s->mlp_layers;
   const int adist = s->flags & 3;                 // 0 onehot, 1 tanh_normal, 2 normal_tanh

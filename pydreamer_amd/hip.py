@@ -21,7 +21,6 @@ DM_C2I_ELU = 1
 DM_FLAG_IMAGE_U8 = 16
 DM_FLAG_BF16 = 128            # dm_shape.flags: this call runs its contractions on bf16 operands (conf.amp)
 DM_GEMM_BF16 = 256            # dm_gemm_f32 flags: the same for a single product
-DM_SPLITK_FLOATS = 16 * 1024 * 1024    # split-K partial region carved at the front of every operator workspace
 
 RSSM_PARAM_ORDER = [
     'z_mlp.weight', 'z_mlp.bias', 'a_mlp.weight', 'in_norm.weight', 'in_norm.bias',
@@ -149,16 +148,12 @@ _SIGNATURES = {
     'dm_preprocess_image_u8': (c_int, [c_int64, c_int, c_int, _P, _P, _P]),
     'dm_conv_encoder_acts_floats': (c_size_t, [POINTER(dm_shape)]),
     'dm_conv_encoder_fwd': (c_int, [POINTER(dm_shape), _P, POINTER(dm_conv_params), _P, _P, _P, c_size_t, _P]),
-    'dm_conv_encoder_fwd_rows': (c_int, [POINTER(dm_shape), c_int, c_int, c_int, _P, POINTER(dm_conv_params), _P, _P, _P,
-                                         c_size_t, _P]),
     'dm_conv_encoder_bwd': (c_int, [POINTER(dm_shape), _P, POINTER(dm_conv_params), _P, _P, POINTER(dm_conv_grads), _P,
                                     c_size_t, _P]),
     'dm_conv_decoder_acts_floats': (c_size_t, [POINTER(dm_shape)]),
     'dm_conv_decoder_pred_offset': (c_size_t, [POINTER(dm_shape)]),
     'dm_conv_decoder_mse_fwd': (c_int, [POINTER(dm_shape), _P, c_int, _P, POINTER(dm_conv_params), _P, _P, _P, _P,
                                         c_size_t, _P]),
-    'dm_conv_decoder_mse_fwd_rows': (c_int, [POINTER(dm_shape), c_int, c_int, c_int, _P, c_int, _P, POINTER(dm_conv_params),
-                                             _P, _P, _P, _P, c_size_t, _P]),
     'dm_conv_decoder_mse_bwd': (c_int, [POINTER(dm_shape), _P, c_int, _P, POINTER(dm_conv_params), _P, c_float,
                                         POINTER(dm_conv_grads), _P, c_int, _P, c_size_t, _P]),
     'dm_conv_decoder_mse_bwd_rows': (c_int, [POINTER(dm_shape), _P, c_int, _P, POINTER(dm_conv_params), _P, c_float, _P,
@@ -166,8 +161,6 @@ _SIGNATURES = {
     'dm_rssm_acts_floats': (c_size_t, [POINTER(dm_shape)]),
     'dm_rssm_sequence_fwd': (c_int, [POINTER(dm_shape), _P, _P, _P, _P, _P, _P, _P, POINTER(dm_rssm_params), _P, _P, _P,
                                      _P, _P, _P, c_size_t, _P]),
-    'dm_rssm_sequence_fwd_steps': (c_int, [POINTER(dm_shape), c_int, c_int, _P, _P, _P, _P, _P, _P, _P,
-                                           POINTER(dm_rssm_params), _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     'dm_rssm_sequence_bwd': (c_int, [POINTER(dm_shape), _P, _P, _P, POINTER(dm_rssm_params), _P, _P, _P, _P, _P, _P,
                                      POINTER(dm_rssm_grads), _P, _P, c_size_t, _P]),
     'dm_dream_rollout': (c_int, [POINTER(dm_shape), c_int, _P, POINTER(dm_rssm_params), POINTER(dm_mlp_params), _P, _P,
@@ -207,7 +200,7 @@ _SIGNATURES = {
 }
 
 _lib = None
-DM_ABI_VERSION = 13     # include/dreamer_hip.h dm_version(): the struct layouts above (dm_rssm_params: 58 slots) belong to this one
+DM_ABI_VERSION = 14     # include/dreamer_hip.h dm_version(): the struct layouts above (dm_rssm_params: 58 slots) belong to this one
 
 
 def lib():

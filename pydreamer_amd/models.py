@@ -493,15 +493,8 @@ class _Overlap:
     def __init__(self, device):
         # the latency-bound chain gets the high-priority queue: its 40-110-workgroup kernels must be dispatched ahead of
         # the thousands of queued GEMM workgroups of the concurrent work, or the chain just slows down
-        self.s_wm = torch.cuda.Stream(device, priority=int(os.environ.get('DM_WM_PRIO', '-1')))
-        # DM_AC_RESERVE_CUS=k (experiment): the actor-critic stream is created through
-        # hipExtStreamCreateWithCUMask WITHOUT the first k CUs of every 32, so the world-model stream's latency chain always finds
-        # k CUs per XCD free of this stream's full-chip products - no additional stream, s_wm stays unmasked
-        res = int(os.environ.get('DM_AC_RESERVE_CUS', '0'))
-        if res > 0:
-            self.s_ac = H.cu_masked_stream([0xFFFFFFFF ^ ((1 << res) - 1)] * 8, device)
-        else:
-            self.s_ac = torch.cuda.Stream(device, priority=int(os.environ.get('DM_AC_PRIO', '0')))
+        self.s_wm = torch.cuda.Stream(device, priority=-1)
+        self.s_ac = torch.cuda.Stream(device)
         self.ev_wm_fwd = torch.cuda.Event()
         self.ev_fwd = torch.cuda.Event()
         self.ev_fork, self.ev_tail = torch.cuda.Event(), torch.cuda.Event()      # the world-model forward's tail on s_wm (WorldModel._forward)
@@ -630,25 +623,6 @@ class _Done:
         return self.value
 
 
-class _StepArena:
-    """Allocator of everything the library's launch chains read or write in one step (dm_rssm_sequence_fwd / _bwd,
-    dm_dream_rollout).  Rounds 3-4 kept these buffers persistent per geometry for the hipGraph replay of the chains
-    (csrc/chain_graph.hip), which removed host time only and was deleted in round 5 (the chains are GPU-latency-bound); what is
-    left is `get` = torch.empty - nothing is shared between steps, a backward() on an older step's losses is always valid -
-    behind the same interface, so the call sites did not move."""
-
-    on = False
-
-    def begin_step(self, geometry):
-        return None
-
-    def current(self, stamp):
-        return True
-
-    def get(self, name, shape, dtype=torch.float32, device=None):
-        return torch.empty(tuple(int(x) for x in shape), dtype=dtype, device=device)
-
-
 def _require_cuda(t, what):
     if not t.is_cuda:
         raise H.DreamerHipError(f'{what} is on {t.device}: pydreamer_amd has no CPU path (the HIP library is the product)')
@@ -718,15 +692,8 @@ class WorldModel(_Params):
         for m in self.modules():
             init_weights_tf2(m)
         self._ws = None
-        self._pipe = None
-        self._arena = _StepArena()
         self._ws_dec = None                # own workspaces of the decoder / encoder backward while weight gradients are deferred
         self._ws_enc = None
-        # Forward time-chunk pipeline over 3 streams (encoder chunk i+1 | posterior steps of chunk i | decoder chunk i-1).
-        # OFF by default: measured on MI355X / ROCm 7.2 it LOSES (61.9 vs 47.7 ms per step at B=50, 33.1 vs 16.5 ms at
-        # B=7): the loop's 1024-thread workgroups starve behind the conv GEMMs of the other streams and every cross-stream
-        # dependency costs a cache writeback/invalidate between queues.  Kept because it is exact (tested) and cheap to flip.
-        self.pipeline_chunks = int(os.environ.get('DM_PIPELINE_CHUNKS', '1'))
 
     def init_state(self, batch_size):
         return self.core.init_state(batch_size)
@@ -747,39 +714,12 @@ class WorldModel(_Params):
             self._ws = torch.empty(need, dtype=torch.uint8, device=device)
         return self._ws
 
-    def _pipeline(self, shp, T, B, chunks, device):
-        """Streams, events and per-stream workspaces of the forward time-chunk pipeline (cached per geometry)."""
-        key = (T, B, chunks, str(device))
-        pp = self._pipe
-        if pp is None or pp['key'] != key:
-            step = -(-T // chunks)
-            ranges = [(t, min(t + step, T)) for t in range(0, T, step)]
-            sub = H.dm_shape.from_buffer_copy(shp)
-            sub.T = step                                   # per-range decoder workspace: patch matrices scale with rows
-            # DM_PIPE_RESERVE_CUS=r (0..31): the chain stream owns r CUs of every 32 and the convolution streams the other
-            # 32-r (hipExtStreamCreateWithCUMask), so the chain's small kernels never wait for a CU to drain
-            r = int(os.environ.get('DM_PIPE_RESERVE_CUS', '0'))
-            if 0 < r < 32:
-                lo, n_words = (1 << r) - 1, 8
-                s_chain = H.cu_masked_stream([lo] * n_words, device)
-                s_dec = H.cu_masked_stream([0xFFFFFFFF ^ lo] * n_words, device)
-                s_enc = H.cu_masked_stream([0xFFFFFFFF ^ lo] * n_words, device)
-            else:
-                s_chain, s_dec, s_enc = torch.cuda.Stream(device, priority=-1), torch.cuda.Stream(device), None
-            pp = dict(key=key, ranges=ranges, s_chain=s_chain, s_dec=s_dec, s_enc=s_enc,
-                      ev_prep=torch.cuda.Event(), ev_enc=[torch.cuda.Event() for _ in ranges],
-                      ev_chain=[torch.cuda.Event() for _ in ranges],
-                      ws_chain=torch.empty((int(H.DM_SPLITK_FLOATS) + 4096) * 4, dtype=torch.uint8, device=device),
-                      ws_dec=torch.empty(H.workspace_bytes(sub), dtype=torch.uint8, device=device))
-            self._pipe = pp
-        return pp
-
     def forward(self, obs, in_state, u_post=None):
         """dreamer.py:289-295: features and out_state only (used by Dreamer.inference)."""
         with torch.no_grad():
             pk = self._forward(obs, in_state, u_post, None, forward_only=True)
         T, B = obs['action'].shape[:2]
-        return (pk['feat'].clone() if self._arena.on else pk['feat']).view(T, B, 1, -1), pk['out_state']
+        return pk['feat'].view(T, B, 1, -1), pk['out_state']
 
     # ---- forward through the C-ABI
     def _forward(self, obs, in_state, u_post, forced_idx, forward_only=False, imag_horizon=1, open_loop=False, mbuf=None,
@@ -833,24 +773,10 @@ class WorldModel(_Params):
         bad = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
         if bad:
             raise ValueError('training_step input shapes (got, expected): ' + ', '.join(f'{k}: {v[0]} != {v[1]}' for k, v in bad.items()))
-        # Everything the posterior chain touches lives in the step arena (stable addresses -> the chain's hipGraph is replayed)
-        ar = self._arena
-        gen = ar.begin_step((T, B, I))
-        if ar.on:
-            u_buf = None
-            if forced_idx is None or u_post is not None:
-                # uniforms for the categorical inverse-CDF rule; standard-normal eps of Normal.rsample for Gaussian latents
-                u_buf = ar.get('u_post', (T, BI, c.stoch_dim), device=dev)
-                if u_post is not None:
-                    u_buf.copy_(u_post.reshape(T, BI, c.stoch_dim))
-                elif gauss:
-                    u_buf.normal_()
-                else:
-                    u_buf.uniform_()
-            u_post = u_buf
-            h0 = ar.get('h0', (BI, D_), device=dev).copy_(h0)
-            z0 = ar.get('z0', (BI, Z), device=dev).copy_(z0)
-        elif u_post is not None:
+        # Every buffer of the step is its own allocation: nothing is shared between steps, so a backward() on an older
+        # step's losses is always valid.  Uniforms for the categorical inverse-CDF rule; standard-normal eps of
+        # Normal.rsample for Gaussian latents.
+        if u_post is not None:
             u_post = u_post.reshape(T, BI, c.stoch_dim).float().contiguous()
         elif forced_idx is None:
             u_post = (torch.randn if gauss else torch.rand)(T, BI, c.stoch_dim, device=dev)
@@ -865,7 +791,7 @@ class WorldModel(_Params):
         enc = self.encoder.encoder_image
         enc_p = H.conv_struct([m.weight for m in enc.convs()], [m.bias for m in enc.convs()])
         enc_acts = torch.empty(int(lib.dm_conv_encoder_acts_floats(ctypes.byref(shp_e))), device=dev)
-        embed = ar.get('embed', (NE, E), device=dev)
+        embed = torch.empty(NE, E, device=dev)
         cell = self.core.cell
         rssm_p = H.rssm_struct(cell.ordered())
         if open_loop:
@@ -879,15 +805,12 @@ class WorldModel(_Params):
                              ('post_mlp.weight', 'prior_mlp.weight'), ('post_mlp.bias', 'prior_mlp.bias')):
                 po[ix[dst]] = po[ix[src]]
             rssm_p = H.rssm_struct(po)
-        rssm_acts = ar.get('rssm_acts', (int(lib.dm_rssm_acts_floats(ctypes.byref(shp_r))),), device=dev)
-        feat = ar.get('feat', (N, F_), device=dev)
-        post = ar.get('post', (N, ZP), device=dev)
-        prior = ar.get('prior', (N, ZP), device=dev)
-        idx = ar.get('idx', (N, c.stoch_dim), torch.int32, device=dev)
-        fidx = None
-        if forced_idx is not None:
-            fidx = (ar.get('forced_idx', (T, BI, c.stoch_dim), torch.int32, device=dev).copy_(forced_idx) if ar.on
-                    else forced_idx.to(torch.int32).contiguous())
+        rssm_acts = torch.empty(int(lib.dm_rssm_acts_floats(ctypes.byref(shp_r))), device=dev)
+        feat = torch.empty(N, F_, device=dev)
+        post = torch.empty(N, ZP, device=dev)
+        prior = torch.empty(N, ZP, device=dev)
+        idx = torch.empty(N, c.stoch_dim, dtype=torch.int32, device=dev)
+        fidx = forced_idx.to(torch.int32).contiguous() if forced_idx is not None else None
         u_ptr = H.fptr(u_post) if u_post is not None else None
         dec = self.decoder
         dl = dec.image.layers()
@@ -897,69 +820,30 @@ class WorldModel(_Params):
             loss_image = torch.empty(N, device=dev)
             image_rec = None          # materialised lazily from the decoder's saved prediction (see LazyTensors)
 
-        chunks = min(self.pipeline_chunks, T) if (T >= 4 and not forward_only and not open_loop and I == 1) else 1
-        # rssm.py:35-41: (T,B,X) -> (T,B*I,X), pure data movement - into the arena (I = 1: a plain copy of the caller's tensors)
+        # rssm.py:35-41: (T,B,X) -> (T,B*I,X), pure data movement (I = 1: the caller's tensors as they are)
         A_ = c.action_dim
-        if ar.on or I > 1:
-            action_x = ar.get('action_x', (T, BI, A_), device=dev)
+        if I > 1:
+            action_x = torch.empty(T, BI, A_, device=dev)
             action_x.view(T, B, I, A_).copy_(action.view(T, B, 1, A_).expand(T, B, I, A_))
-            reset_x = ar.get('reset_x', (T, BI), torch.uint8, device=dev)
+            reset_x = torch.empty(T, BI, dtype=torch.uint8, device=dev)
             reset_x.view(T, B, I).copy_(reset.view(T, B, 1).expand(T, B, I))
         else:
             action_x, reset_x = action, reset
+        H.call('dm_conv_encoder_fwd', ctypes.byref(shp_e), H.ptr(image), ctypes.byref(enc_p), H.fptr(enc_acts),
+               H.fptr(embed), H.ptr(ws), ws.numel(), H.stream())
         embed_x = embed
-        if chunks <= 1:
-            H.call('dm_conv_encoder_fwd', ctypes.byref(shp_e), H.ptr(image), ctypes.byref(enc_p), H.fptr(enc_acts),
-                   H.fptr(embed), H.ptr(ws), ws.numel(), H.stream())
-            if I > 1:
-                embed_x = ar.get('embed_x', (N, E), device=dev)
-                embed_x.view(T, B, I, E).copy_(embed.view(T, B, 1, E).expand(T, B, I, E))
-            embed_rssm = ar.get('embed_zero', tuple(embed_x.shape), device=dev).zero_() if open_loop else embed_x
-            H.call('dm_rssm_sequence_fwd', ctypes.byref(shp_r), H.fptr(embed_rssm), H.fptr(action_x), H.ptr(reset_x), H.fptr(h0),
-                   H.fptr(z0), u_ptr, H.ptr(fidx), ctypes.byref(rssm_p), H.fptr(rssm_acts), H.fptr(feat), H.fptr(post),
-                   H.fptr(prior), H.ptr(idx), H.ptr(ws), ws.numel(), H.stream())
-        else:
-            # Time-chunk pipeline over three streams: the posterior loop is a latency chain of T x ~10 small kernels
-            # (rssm.py:38-58) that leaves most CUs idle, so the encoder of chunk i+1 and the decoder of chunk i-1 run
-            # beside the loop steps of chunk i.  Same kernels on the same rows as the single-stream path.
-            pp = self._pipeline(shp, T, B, chunks, dev)
-            main = torch.cuda.current_stream()
-            H.call('dm_conv_encoder_fwd_rows', ctypes.byref(shp), 0, 0, 1, H.ptr(image), ctypes.byref(enc_p),
-                   H.fptr(enc_acts), H.fptr(embed), H.ptr(ws), ws.numel(), H.stream())
-            H.call('dm_conv_decoder_mse_fwd_rows', ctypes.byref(shp), 0, 0, 1, H.fptr(feat), F_, H.ptr(image),
-                   ctypes.byref(dec_p), H.fptr(dec_acts), H.fptr(loss_image), None, H.ptr(ws), ws.numel(),
-                   H.stream())
-            pp['ev_prep'].record(main)
-            pp['s_chain'].wait_event(pp['ev_prep'])
-            pp['s_dec'].wait_event(pp['ev_prep'])
-            s_enc = pp['s_enc'] or main
-            s_enc.wait_event(pp['ev_prep'])
-            for i, (t0, t1) in enumerate(pp['ranges']):
-                with torch.cuda.stream(s_enc):
-                    H.call('dm_conv_encoder_fwd_rows', ctypes.byref(shp), t0 * B, (t1 - t0) * B, 0, H.ptr(image),
-                           ctypes.byref(enc_p), H.fptr(enc_acts), H.fptr(embed), H.ptr(ws), ws.numel(), H.stream())
-                    pp['ev_enc'][i].record(s_enc)
-                pp['s_chain'].wait_event(pp['ev_enc'][i])
-                with torch.cuda.stream(pp['s_chain']):
-                    H.call('dm_rssm_sequence_fwd_steps', ctypes.byref(shp), t0, t1, H.fptr(embed), H.fptr(action_x),
-                           H.ptr(reset_x), H.fptr(h0), H.fptr(z0), u_ptr, H.ptr(fidx), ctypes.byref(rssm_p),
-                           H.fptr(rssm_acts), H.fptr(feat), H.fptr(post), H.fptr(prior), H.ptr(idx), H.ptr(pp['ws_chain']),
-                           pp['ws_chain'].numel(), H.stream())
-                    pp['ev_chain'][i].record(pp['s_chain'])
-                pp['s_dec'].wait_event(pp['ev_chain'][i])
-                with torch.cuda.stream(pp['s_dec']):
-                    H.call('dm_conv_decoder_mse_fwd_rows', ctypes.byref(shp), t0 * B, (t1 - t0) * B, 0, H.fptr(feat), F_,
-                           H.ptr(image), ctypes.byref(dec_p), H.fptr(dec_acts), H.fptr(loss_image), None,
-                           H.ptr(pp['ws_dec']), pp['ws_dec'].numel(), H.stream())
-            main.wait_stream(pp['s_chain'])
-            main.wait_stream(pp['s_dec'])
-            if pp['s_enc'] is not None:
-                main.wait_stream(pp['s_enc'])
+        if I > 1:
+            embed_x = torch.empty(N, E, device=dev)
+            embed_x.view(T, B, I, E).copy_(embed.view(T, B, 1, E).expand(T, B, I, E))
+        embed_rssm = torch.zeros_like(embed_x) if open_loop else embed_x
+        H.call('dm_rssm_sequence_fwd', ctypes.byref(shp_r), H.fptr(embed_rssm), H.fptr(action_x), H.ptr(reset_x), H.fptr(h0),
+               H.fptr(z0), u_ptr, H.ptr(fidx), ctypes.byref(rssm_p), H.fptr(rssm_acts), H.fptr(feat), H.fptr(post),
+               H.fptr(prior), H.ptr(idx), H.ptr(ws), ws.numel(), H.stream())
 
         last = feat[(T - 1) * BI:]
         out_state = (last[:, :D_].clone(), last[:, D_:].clone())                  # detached by construction (rssm.py:77)
         pk = dict(shp=shp, shp_e=shp_e, shp_r=shp_r, T=T, B=B, I=I, feat=feat, post=post, prior=prior, idx=idx,
-                  out_state=out_state, embed=embed, embed_x=embed_x, action_x=action_x, reset_x=reset_x, gen=gen)
+                  out_state=out_state, embed=embed, embed_x=embed_x, action_x=action_x, reset_x=reset_x)
         if forward_only:
             return pk
         # The tail of the world-model forward - decoder + MSE, reward / terminal heads, KL, the loss sums (dreamer.py:311-365) -
@@ -968,7 +852,7 @@ class WorldModel(_Params):
         # the world-model stream, in front of the pre-launched backward, with that stream's workspace, and the caller's stream
         # goes from the posterior loop straight to the rollout.  Same kernels on the same operands: bit-identical
         # (test_world_model_tail_on_side_stream_is_bit_identical).
-        use_tail = tail is not None and chunks <= 1
+        use_tail = tail is not None
         if use_tail:
             need = ws.numel()
             if tail.ws_wm is None or tail.ws_wm.numel() < need:
@@ -978,20 +862,18 @@ class WorldModel(_Params):
             tail.s_wm.wait_event(tail.ev_fork)
             pk['tail'] = tail
         with (torch.cuda.stream(tail.s_wm) if use_tail else contextlib.nullcontext()):
-            return self._forward_tail(pk, obs, c, dec, dec_p, dec_acts, loss_image, ws, mbuf, chunks, image, action, reset,
-                                      enc_acts, rssm_acts)
+            return self._forward_tail(pk, obs, c, dec, dec_p, dec_acts, loss_image, ws, mbuf, image, action, reset, enc_acts,
+                                      rssm_acts)
 
-    def _forward_tail(self, pk, obs, c, dec, dec_p, dec_acts, loss_image, ws, mbuf, chunks, image, action, reset, enc_acts,
-                      rssm_acts):
+    def _forward_tail(self, pk, obs, c, dec, dec_p, dec_acts, loss_image, ws, mbuf, image, action, reset, enc_acts, rssm_acts):
         shp, T, B, I, feat, post, prior, idx = (pk[k] for k in ('shp', 'T', 'B', 'I', 'feat', 'post', 'prior', 'idx'))
         lib = H.lib()
         N, NE, dev = T * B * I, T * B, feat.device
         D_, F_ = c.deter_dim, self.features_dim
         gauss = not c.stoch_discrete
         Z = c.stoch_dim * (c.stoch_discrete or 1)
-        if chunks <= 1:
-            H.call('dm_conv_decoder_mse_fwd', ctypes.byref(shp), H.fptr(feat), F_, H.ptr(image), ctypes.byref(dec_p),
-                   H.fptr(dec_acts), H.fptr(loss_image), None, H.ptr(ws), ws.numel(), H.stream())
+        H.call('dm_conv_decoder_mse_fwd', ctypes.byref(shp), H.fptr(feat), F_, H.ptr(image), ctypes.byref(dec_p),
+               H.fptr(dec_acts), H.fptr(loss_image), None, H.ptr(ws), ws.numel(), H.stream())
 
         reward_t = obs['reward'].float().contiguous()
         terminal_t = obs['terminal'].float().contiguous()
@@ -1117,18 +999,13 @@ class WorldModel(_Params):
         iw = pk.get('iw')          # IWAE importance weights (N,) or None: every per-sample gradient of loss_model carries them
         feat, dev = pk['feat'], pk['feat'].device
         F_, Z, E = self.features_dim, c.stoch_dim * (c.stoch_discrete or 2), self.encoder.out_dim   # Z: parameter width here
-        if not self._arena.current(pk.get('gen')):
-            raise RuntimeError('the activations saved by this training_step() were overwritten by a later training_step() '
-                               '(they live in per-model buffers with stable addresses); call backward() after each '
-                               'training_step()')
-        ar = self._arena
         plist = self._param_order()
         flat, views, direct = _flat_views(plist, dev, getattr(self, '_fused', None), scratch)
         gof = {id(p): v for p, v in zip(plist, views)}
         dec = self.decoder
 
         gw = float(getattr(self, 'grad_weight', 1.0))          # data-parallel shard weight B_r/B (dist.attach)
-        dfeat = ar.get('dfeat', (N, F_), device=dev).zero_()
+        dfeat = torch.zeros(N, F_, device=dev)
         # dense heads (decoders.py:73-83)
         if iw is not None and not pk.get('iw_applied'):
             for dout in (pk['dmu'], pk['dtl']):
@@ -1168,8 +1045,8 @@ class WorldModel(_Params):
                    H.fptr(pk['dec_acts']), gw * dec.image_weight / NE, H.fptr(iw), ctypes.byref(dec_g), H.fptr(dfeat), F_,
                    H.ptr(ws_dec), ws_dec.numel(), H.stream())
             # KL (dreamer.py:334-343)
-            dpost = ar.get('dpost', (N, Z), device=dev)
-            dprior = ar.get('dprior', (N, Z), device=dev)
+            dpost = torch.empty(N, Z, device=dev)
+            dprior = torch.empty(N, Z, device=dev)
             if iw is not None and not c.stoch_discrete:      # sampled Normal KL: explicit parameter gradients + the path through z
                 D_ = c.deter_dim
                 H.call('dm_kl_sampled_gauss_bwd', N, c.stoch_dim, H.fptr(pk['post']), H.fptr(pk['prior']),
@@ -1189,7 +1066,7 @@ class WorldModel(_Params):
             cell = self.core.cell
             rssm_p = H.rssm_struct(cell.ordered())
             rssm_g = H.rssm_struct([None if p is None else gof[id(p)] for p in cell.ordered()], cls=H.dm_rssm_grads)
-            dembed = ar.get('dembed', (N, E), device=dev)
+            dembed = torch.empty(N, E, device=dev)
             H.call('dm_rssm_sequence_bwd', ctypes.byref(pk['shp_r']), H.fptr(pk['embed_x']), H.fptr(pk['action_x']),
                    H.ptr(pk['reset_x']), ctypes.byref(rssm_p), H.fptr(pk['rssm_acts']), H.fptr(feat), H.fptr(pk['post']),
                    H.fptr(dfeat), H.fptr(dpost), H.fptr(dprior), ctypes.byref(rssm_g), H.fptr(dembed), H.ptr(ws), ws.numel(),
@@ -1275,7 +1152,7 @@ class WorldModel(_Params):
         return metrics, tensors, idx
 
     def training_step(self, obs, in_state, iwae_samples=1, do_open_loop=False, do_image_pred=False, forward_only=False,
-                      u_post=None, forced_idx=None, imag_horizon=1, u_pred=None, mbuf=None, _internal=False, _tail=None):
+                      u_post=None, forced_idx=None, imag_horizon=1, u_pred=None, mbuf=None, _tail=None):
         """dreamer.py:297-396. Returns (loss, features (T,B,1,F), states, out_state, metrics, tensors)."""
         I = int(iwae_samples)
         if do_open_loop and torch.is_grad_enabled():
@@ -1291,9 +1168,7 @@ class WorldModel(_Params):
         if pk.get('tail') is not None:        # everything the forward's tail produced is final once the caller's stream has
             pk['tail'].ev_tail.record(pk['tail'].s_wm)      # waited for this event (Dreamer.training_step does, before returning)
         D_ = self.deter_dim
-        # the feature matrix lives in the step arena (overwritten by the next step): callers get their own copy, except
-        # Dreamer.training_step, which consumes it before returning (_internal)
-        feat = pk['feat'] if (_internal or not self._arena.on) else pk['feat'].clone()
+        feat = pk['feat']
         features = feat.view(T, B, I, -1)
         states = (feat[:, :D_].view(T, B, I, -1), feat[:, D_:].view(T, B, I, -1))
         self._last_pack = pk
@@ -1569,7 +1444,7 @@ class Dreamer(nn.Module):
         if o is None:
             return
         on = bool(self.pipeline_ac_optimizer) and ov is not None and all(o[k].dp is None for k in ('actor', 'critic')) \
-            and not torch.cuda.is_current_stream_capturing() and not self.wm._arena.on      # (the step arena re-uses buffers)
+            and not torch.cuda.is_current_stream_capturing()
         for k in ('actor', 'critic'):
             if o[k].home is not None and not on:
                 o[k].join()
@@ -1663,7 +1538,7 @@ class Dreamer(nn.Module):
         start = torch.cat((h, z), -1).contiguous()           # to_feature (rssm.py:83-84)
         return self._dream_from_features(start, Hh, u_act, u_prior, _pack)
 
-    def _dream_from_features(self, start, Hh, u_act=None, u_prior=None, _pack=None, _start_in_arena=False, early=None):
+    def _dream_from_features(self, start, Hh, u_act=None, u_prior=None, _pack=None, early=None):
         """start: (M,F) rows [h|z] (the world model's feature matrix is passed as is, no concat copy)."""
         c = self.conf
         M, dev = start.shape[0], start.device
@@ -1671,46 +1546,25 @@ class Dreamer(nn.Module):
         shp = self.wm.shape(1, M, Hh)                        # T*B = M rows for workspace sizing
         ws = self.wm.workspace(shp, dev)
         kind = self.ac.dist_kind
-        # the rollout chain's buffers live in the world model's step arena (stable addresses -> its hipGraph is replayed);
         # uniforms for the one-hot actor / the categorical latents, standard-normal noise for continuous actors / Gaussian latents
-        ar = self.wm._arena
         ua_shape = (Hh, M) if kind == 0 else (Hh, M, A)
         if u_act is not None and tuple(u_act.shape) != ua_shape:
             raise ValueError(f'actor noise has shape {tuple(u_act.shape)}, expected {ua_shape}')
-        if ar.on:
-            ua = ar.get('u_act', ua_shape, device=dev)
-            up = ar.get('u_prior', (Hh, M, S), device=dev)
-            if u_act is not None:
-                ua.copy_(u_act)
-            elif kind == 0:
-                ua.uniform_()
-            else:
-                ua.normal_()
-            if u_prior is not None:
-                up.copy_(u_prior.reshape(Hh, M, S))
-            elif c.stoch_discrete:
-                up.uniform_()
-            else:
-                up.normal_()
-            u_act, u_prior = ua, up
-        else:
-            if u_act is None:
-                u_act = torch.rand(ua_shape, device=dev) if kind == 0 else torch.randn(ua_shape, device=dev)
-            if u_prior is None:
-                u_prior = (torch.rand if c.stoch_discrete else torch.randn)(Hh, M, S, device=dev)
-            u_act, u_prior = u_act.float().contiguous(), u_prior.reshape(Hh, M, S).float().contiguous()
-        if ar.on and not _start_in_arena:
-            start = ar.get('dream_start', tuple(start.shape), device=dev).copy_(start)
+        if u_act is None:
+            u_act = torch.rand(ua_shape, device=dev) if kind == 0 else torch.randn(ua_shape, device=dev)
+        if u_prior is None:
+            u_prior = (torch.rand if c.stoch_discrete else torch.randn)(Hh, M, S, device=dev)
+        u_act, u_prior = u_act.float().contiguous(), u_prior.reshape(Hh, M, S).float().contiguous()
         start = start.contiguous()
-        feats = ar.get('dream_feats', (Hh + 1, M, F_), device=dev)
-        actions = ar.get('dream_actions', (Hh, M, A), device=dev)
-        act_idx = ar.get('dream_act_idx', (Hh, M), torch.int32, device=dev)
+        feats = torch.empty(Hh + 1, M, F_, device=dev)
+        actions = torch.empty(Hh, M, A, device=dev)
+        act_idx = torch.empty(Hh, M, dtype=torch.int32, device=dev)
         cell_p = H.rssm_struct(self.wm.core.cell.ordered())
         actor_p = self.ac.actor.struct()
         a_acts = a_logits = None
         if _pack is not None:          # training: keep the actor activations of all H steps for the policy-gradient backward
-            a_acts = ar.get('dream_actor_acts', (self.ac.actor.acts_floats(Hh * M),), device=dev)
-            a_logits = ar.get('dream_actor_logits', (Hh * M, self.ac.actor.out_dim), device=dev)
+            a_acts = torch.empty(int(self.ac.actor.acts_floats(Hh * M)), device=dev)
+            a_logits = torch.empty(Hh * M, self.ac.actor.out_dim, device=dev)
         # The heads over the imagined states (reward, terminal: dreamer.py:212-213; critic_target, critic: a2c.py:85,113) are
         # per-row work on 40 000 rows, 4 ms behind a rollout whose last steps leave the chip half idle (profiles/r03_queues_*):
         # they run as two row windows - steps [0, split) and [split, H] - and with `early` (the training step's side streams)
@@ -1720,7 +1574,7 @@ class Dreamer(nn.Module):
         r_split = self.ac.split_steps(Hh + 1) * M
         # (not under conf.amp: there the world-model backward chain on the other side stream is the step's critical path and the
         #  early window only takes CUs from it - measured 23.5 vs 23.2 ms; fp32: 37.1 vs 37.3 ms, 7-column shard 11.36 vs 11.50)
-        use_early = (early is not None and _pack is not None and not ar.on and r_split < rows and _HEADS_EARLY
+        use_early = (early is not None and _pack is not None and r_split < rows and _HEADS_EARLY
                      and not getattr(c, 'amp', False))
         if use_early:
             H.call('dm_dream_rollout_marks', 1, (ctypes.c_int * 1)(r_split // M - 2),
@@ -1773,7 +1627,7 @@ class Dreamer(nn.Module):
             u_post = u_post.reshape(T, B * I, -1)
 
         if self._overlap is not None:
-            # pre-launched backward passes of a step whose losses were never backpropagated may still be reading the arena -
+            # pre-launched backward passes of a step whose losses were never backpropagated may still be using the side streams' workspaces -
             # and their launcher jobs may still be ENQUEUING: a stream wait only orders what is already in the stream, so the
             # jobs are awaited first (their exceptions belong to the backward() that owns them, not to this step)
             stale = [getattr(self.wm, '_last_pack', None)] + list(getattr(self.ac, '_last_packs', None) or ())
@@ -1801,7 +1655,7 @@ class Dreamer(nn.Module):
         loss_model, features, states, out_state, metrics, tensors = \
             self.wm.training_step(obs, in_state, iwae_samples=iwae_samples, do_open_loop=do_open_loop,
                                   do_image_pred=do_image_pred, u_post=u_post, forced_idx=forced_idx,
-                                  imag_horizon=imag_horizon, u_pred=noise.get('u_pred'), mbuf=mbuf, _internal=True, _tail=tail)
+                                  imag_horizon=imag_horizon, u_pred=noise.get('u_pred'), mbuf=mbuf, _tail=tail)
         pk = self.wm._last_pack
         ov = None
         if not (self.overlap_backward and torch.is_grad_enabled()):
@@ -1841,7 +1695,7 @@ class Dreamer(nn.Module):
         features_dream, actions_dream, rewards_dream, terminals_dream = \
             self._dream_from_features(pk['feat'], imag_horizon,
                                       noise.get('u_act') if self.ac.dist_kind == 0 else noise.get('eps_act'),
-                                      noise.get('u_prior'), _pack=dpk, _start_in_arena=True, early=ov)
+                                      noise.get('u_prior'), _pack=dpk, early=ov)
         (loss_actor, loss_critic), metrics_ac, tensors_ac = \
             self.ac.training_step(features_dream, actions_dream, rewards_dream.mean, terminals_dream.mean,
                                   act_idx=dpk['act_idx'], ws=dpk['ws'], actor_acts=dpk['actor_acts'],
@@ -1859,7 +1713,7 @@ class Dreamer(nn.Module):
             H.call('dm_reduce_i', T * B, I, 1, H.fptr(tensors_ac['value'][0].contiguous()), 0, H.fptr(pv), None, H.stream())
             tensors.update(policy_value=pv)
         # Diagnostics for tests / debugging (not part of the reference API).  The index tensors are copies; `actions`,
-        # `dream_features`, `post` and `prior` are views of the step arena: valid until the next training_step().
+        # `dream_features`, `post` and `prior` are the step's own buffers.
         self.last_extras = dict(post_idx=pk['idx'].view(T, B * I, -1).clone(), act_idx=dpk['act_idx'].clone(),
                                 actions=actions_dream, dream_features=features_dream, actor_logits=dpk.get('actor_logits'),
                                 ac_tensors=tensors_ac, post=pk['post'], prior=pk['prior'], pred_idx=pk.get('pred_idx'))
