@@ -70,7 +70,7 @@ typedef struct dm_shape {
 #define DM_FLAG_GRU_MASK (3 << DM_FLAG_GRU_SHIFT)
 
 /* ---------------------------------------------------------------- library ---------------------- */
-int dm_version(void);                 /* ABI version, currently 14 (v2: LayerNorm-GRU slots; v3: per-call precision; v4: GRUCellStack layer slots;
+int dm_version(void);                 /* ABI version, currently 15 (v2: LayerNorm-GRU slots; v3: per-call precision; v4: GRUCellStack layer slots;
                                          v5: dm_kl_sampled_gauss_*, dm_chain_graph_*, dm_fp32_mode - additions only;
                                          v6: LayerNorm slots of GRUCellStack layers 1..3, dm_rssm_params grows to 58;
                                          v7: dm_wgrad_side_arm / _join, dm_dream_rollout_marks, dm_mlp_head_fwd_rows - additions only;
@@ -84,7 +84,9 @@ int dm_version(void);                 /* ABI version, currently 14 (v2: LayerNor
                                               dm_rollout_fuse_act_enable;
                                          v13: dm_wgrad_side_touch added;
                                          v14: dm_conv_encoder_fwd_rows, dm_conv_decoder_mse_fwd_rows, dm_rssm_sequence_fwd_steps removed (the forward
-                                              time-chunk pipeline) */
+                                              time-chunk pipeline);
+                                         v15: the native exchange step dm_rccl_available / _version / _unique_id / _comm_init / _comm_destroy
+                                              and dm_allreduce_grads removed */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
 size_t dm_workspace_bytes(const dm_shape* shp);   /* scratch needed by any call below for this shape */
@@ -441,25 +443,6 @@ int dm_prof_end(double* out, int nkinds);
 int dm_prof_rows(double* rows, int max_rows);
 /* y = a*x + b*y */
 int dm_axpby(int64_t n, float a, const float* x, float b, float* y, void* stream);
-
-/* ---- the data-parallel exchange step, native (csrc/comm.hip; SURVEY 8(b) dm_allreduce_grads, 8(e)) ------------------------
- * The reference is single-process (no counterpart); pydreamer_amd/dist.py shards the batch axis and SUM-all-reduces each
- * optimizer group's flat fp32 gradient buffer before grad_clip (dreamer.py:73-87 then sees the global-batch gradient).
- * RCCL is bound with dlopen at first use (no link-time dependency; the instance torch already holds is preferred).
- *   dm_rccl_available()                1 when librccl could be bound, else 0 (never fails)
- *   dm_rccl_version()                  ncclGetVersion's code, 0 when unavailable
- *   dm_rccl_unique_id(id128)           rank 0: the 128-byte id of a new communicator (the host carries it to the other ranks)
- *   dm_rccl_comm_init(&comm, n, id, r) collective over the n ranks; the communicator is bound to the CURRENT device
- *   dm_allreduce_grads(buf, n, comm, stream)   buf[0..n) <- sum over ranks, in place, fp32, enqueued on `stream`; never
- *                                      synchronises.  One communicator per optimizer group: a group's collective is ordered by
- *                                      its stream alone (right behind the backward pass that filled the buffer).
- *   dm_rccl_comm_destroy(comm) */
-int dm_rccl_available(void);
-int dm_rccl_version(void);
-int dm_rccl_unique_id(void* id128);
-int dm_rccl_comm_init(void** comm, int nranks, const void* id128, int rank);
-int dm_rccl_comm_destroy(void* comm);
-int dm_allreduce_grads(void* buf, size_t n, void* comm, void* stream);
 
 #ifdef __cplusplus
 }

@@ -447,17 +447,6 @@ def _finish_backward(owner, grads, flat, direct, grad_loss):
     return tuple(None for _ in grads) if direct else tuple(grads)
 
 
-def _prelaunched(owner, fn):
-    """Runs a pre-launched backward pass (on its side stream, from the launcher thread) and, under data parallelism,
-    starts the all-reduce of its gradient buffer right behind it on the same stream."""
-    out = fn()
-    fused = getattr(owner, '_fused', None)
-    if fused is not None and fused.dp is not None and out[1] is fused.scratch:
-        from . import dist as D
-        D.allreduce_scratch_async(fused)
-    return out
-
-
 _HEADS_EARLY = os.environ.get('DM_HEADS_EARLY', '1') != '0'    # A/B switch: 0 runs the heads over the imagined states behind the rollout only
 _WGRAD_SIDE_DP = os.environ.get('DM_WGRAD_SIDE_DP', '1') != '0'    # A/B switch: 0 = no side stream under data parallelism (rounds 3-5)
 _WGRAD_SIDE = os.environ.get('DM_WGRAD_SIDE', '1') != '0'      # A/B switch: 0 keeps every weight gradient on the caller's stream
@@ -505,7 +494,7 @@ class _Overlap:
             self.ev_heads.record()
         # Every stream of the step gets one command NOW (round 6): a HIP stream takes its hardware queue when it first gets work, and
         # which streams later SHARE a queue depends on that order - a communicator created before these streams had run anything
-        # cost the step +13 ms, an early all-reduce whose communicator appeared mid-step +6 ms (profiles/r06_force_dp.txt).
+        # cost the step +13 ms, a communicator that appeared mid-step +6 ms (profiles/r06_force_dp.txt).
         if os.environ.get('DM_STREAM_PREBIND', '1') != '0':
             with torch.cuda.device(device):
                 for st in (self.s_wm, self.s_ac):
@@ -541,10 +530,7 @@ class _Overlap:
                 stream.wait_event(wait_event)
                 with torch.cuda.stream(stream):
                     return fn()
-        fut = self.pool.submit(job)
-        from . import dist as D
-        D.track(fut)              # a main-thread collective must not overtake the collectives this job may issue
-        return fut
+        return self.pool.submit(job)
 
 
 def pack_metrics(*dicts):
@@ -1029,7 +1015,7 @@ class WorldModel(_Params):
         # dm_wgrad_side_arm).  The encoder backward is not deferred (it is the tail: there is nothing left to hide behind).
         # (measured: no gain on a 7-column shard, -1.1 ms at 25 columns.  Rounds 3-5 switched it off under data parallelism, unmeasured;
         #  round 6 measured it over a one-rank RCCL group: off costs +0.9 ... +1.2 ms at 25 / 50 columns, on costs nothing beside the
-        #  late all-reduce or the library's own - profiles/r06_force_dp.txt run K.  DM_WGRAD_SIDE_DP=0 restores the old behaviour.)
+        #  all-reduce - profiles/r06_force_dp.txt run K.  DM_WGRAD_SIDE_DP=0 restores the old behaviour.)
         dp_on = getattr(getattr(self, '_fused', None), 'dp', None) is not None and not _WGRAD_SIDE_DP
         side = defer_wgrad and _WGRAD_SIDE and B * I >= 16 and not dp_on and not torch.cuda.is_current_stream_capturing()
         ws_dec = ws_enc = ws
@@ -1677,8 +1663,8 @@ class Dreamer(nn.Module):
                 ov.ws_wm = torch.empty(need, dtype=torch.uint8, device=dev)
             # (with the forward's tail already on s_wm the backward simply follows it in stream order)
             ov.ev_wm_fwd.record(ov.s_wm if pk.get('tail') is not None else torch.cuda.current_stream())
-            pk['pre'] = ov.submit(ov.s_wm, ov.ev_wm_fwd, lambda: _prelaunched(self.wm, lambda: self.wm._backward(
-                pk, ov.ws_wm, scratch=gens.get(id(self.wm), True), defer_wgrad=True)))
+            pk['pre'] = ov.submit(ov.s_wm, ov.ev_wm_fwd, lambda: self.wm._backward(
+                pk, ov.ws_wm, scratch=gens.get(id(self.wm), True), defer_wgrad=True))
         metrics, tensors = dict(metrics), tensors.copy()          # LazyTensors.copy(): image_rec stays a thunk
         loss_probe, metrics_probe, tensors_probe = self.probe_model.training_step(features.detach(), obs)
         metrics.update(**metrics_probe)
@@ -1703,8 +1689,8 @@ class Dreamer(nn.Module):
         if ov is not None:
             ov.ev_fwd.record(torch.cuda.current_stream())
             for mlp, hp in zip((self.ac.actor, self.ac.critic), self.ac._last_packs):
-                hp['pre'] = ov.submit(ov.s_ac, ov.ev_fwd, lambda mlp=mlp, hp=hp: _prelaunched(mlp, lambda: mlp.bwd(
-                    hp['x'], hp['ldx'], hp['rows'], hp['acts'], hp['dout'], ov.ws_ac, scratch=gens.get(id(mlp), True))))
+                hp['pre'] = ov.submit(ov.s_ac, ov.ev_fwd, lambda mlp=mlp, hp=hp: mlp.bwd(
+                    hp['x'], hp['ldx'], hp['rows'], hp['acts'], hp['dout'], ov.ws_ac, scratch=gens.get(id(mlp), True)))
         metrics.update(**metrics_ac)
         if I == 1:
             tensors.update(policy_value=tensors_ac['value'][0].view(T, B))

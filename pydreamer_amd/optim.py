@@ -5,7 +5,7 @@ Each optimizer group (wm / probe / actor / critic) owns ONE contiguous fp32 para
 two moment buffers; the nn.Parameters become views into the parameter buffer and their `.grad`s views into the gradient
 buffer, so that
   * the norm, the in-place clip and the AdamW update are three streaming kernels per group instead of ~100 small ones;
-  * data-parallel training all-reduces one buffer per group over RCCL (see pydreamer_amd/dist.py).
+  * data-parallel training all-reduces one buffer per group over RCCL through torch.distributed (see pydreamer_amd/dist.py).
 """
 import contextlib
 import ctypes
@@ -50,8 +50,6 @@ class FusedAdamW(torch.optim.Optimizer):
         self.scratch = None                               # the OTHER gradient buffer: pre-launched backward passes write here
         self.scratch_gen = 0                              # bumped every time the scratch buffer is handed out
         self._pending = False                             # a pre-launched backward result sits in `scratch`, not yet handed over
-        self.early_reduce = None                          # (work handle) all-reduce of `scratch` already in flight (dist.py)
-        self._reduced = False                             # flat_grad already holds the all-reduced gradient of this step
         # Pipelined mode (models.Dreamer.pipeline_ac_optimizer): the stream this group's backward pass ran on.  The gradient
         # hand-over, the clip and the AdamW step of the group are then enqueued THERE instead of on the caller's stream, so the
         # caller's stream does not wait for that backward pass before the next step's forward; `done` is recorded behind
@@ -160,7 +158,6 @@ class FusedAdamW(torch.optim.Optimizer):
                 self.flat_grad.zero_()
             self._lazy_zero = False
         self.fresh = True
-        self._reduced = False
 
     def claim_scratch(self):
         """Called by training_step() on the CALLER's thread before the backward pass is handed to the launcher thread:
@@ -180,7 +177,6 @@ class FusedAdamW(torch.optim.Optimizer):
         if bump:
             self.scratch_gen += 1
         self._pending = True
-        self.early_reduce = None
         by_id = {id(p): v for p, v in zip(self._plist, self._views_of(self.scratch))}
         return [by_id[id(p)] for p in plist]
 
@@ -194,24 +190,16 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def _adopt_scratch(self, gl):
         self._pending = False
-        work, self.early_reduce = self.early_reduce, None
-        if work is not None:
-            work.wait()                                   # the all-reduce of `scratch` issued right after its backward
         if self.fresh and not torch.cuda.is_current_stream_capturing():
             self.flat_grad, self.scratch = self.scratch, self.flat_grad
             self._point_grads(self.flat_grad)
             self._lazy_zero = False
             H.call('dm_scale_inplace', H.fptr(self.flat_grad), self.numel, H.fptr(gl), H.stream())
-            self._reduced = work is not None
         elif self.fresh:                                  # inside a graph capture: fixed addresses, so copy
             self._ensure_zeroed()
             torch.mul(self.scratch, gl, out=self.flat_grad)
         else:                                             # accumulation onto gradients that are already there
             self._ensure_zeroed()
-            if work is not None and self.dp is not None and not self._reduced:
-                from . import dist as D
-                D.allreduce_grads(self)                   # what is there has not been reduced yet; the addend has
-                self._reduced = True
             self.flat_grad.addcmul_(self.scratch, gl.expand_as(self.scratch))
         self.fresh = False
 
@@ -236,10 +224,9 @@ class FusedAdamW(torch.optim.Optimizer):
         if not self._grads_are_views():
             self._regather()
         self._ensure_zeroed()
-        if self.dp is not None and not self._reduced:
+        if self.dp is not None:
             from . import dist as D
             D.allreduce_grads(self)
-        self._reduced = False
         nb = self.norm_buf if out is None else out
         H.call('dm_multi_tensor_norm_clip', H.fptr(self.flat_grad), self.numel, float(max_norm), H.fptr(nb),
                H.fptr(self._ws), self._ws.numel() * 4, H.stream())

@@ -1,9 +1,9 @@
 """-m gpu: the data-parallel step through the REAL optimizer path (FusedAdamW + pydreamer_amd.dist), two ranks.
 
 With >= 2 visible GPUs the ranks run one per GPU over RCCL ("nccl"); on a 1-GPU box both ranks share cuda:0 and talk
-over gloo (which all-reduces CUDA tensors through host staging) - the same FusedAdamW.clip_grad_norm / (late or early)
-all-reduce code runs either way.  Bars: posterior indices of every shard bit-identical to the matching
-columns of the 1-rank run (uniforms are sliced from the global layout); parameters after clip + AdamW within 1e-5."""
+over gloo (which all-reduces CUDA tensors through host staging) - the same FusedAdamW.clip_grad_norm all-reduce code runs
+either way.  Bars: posterior indices of every shard bit-identical to the matching columns of the 1-rank run
+(uniforms are sliced from the global layout); parameters after clip + AdamW within 1e-5."""
 import os
 import socket
 
@@ -44,7 +44,7 @@ def _one_step(model, conf, opts, obs, noise, steps=2):
     return out
 
 
-def _worker(rank, world, port, overlap, fold, out, early=False):
+def _worker(rank, world, port, overlap, fold, out):
     import torch.distributed as dist
     from oracle import dreamer_oracle as O
     from pydreamer_amd import config
@@ -71,7 +71,6 @@ def _worker(rank, world, port, overlap, fold, out, early=False):
         model = model.to(dev)
         model.overlap_backward = overlap
         opts = model.init_optimizers(conf.adam_lr, conf.adam_lr_actor, conf.adam_lr_critic, conf.adam_eps)
-        DP._EARLY = early       # the all-reduce behind each pre-launched backward (overlapped) instead of inside grad_clip (round 6: the default is late)
         DP.attach(opts, hi - lo, B, model=model if fold else None)    # fold: B_r/B inside the backward kernels' scales
         assert opts[0].dp is not None and opts[0].dp_folded == fold and not opts[1].dp_folded
         shard, _ = DP.shard_obs(obs, world, rank)
@@ -83,8 +82,10 @@ def _worker(rank, world, port, overlap, fold, out, early=False):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize('overlap,fold,early', [(True, True, False), (False, True, False), (True, False, False), (True, True, True)])
-def test_two_rank_step_equals_one_rank(hip, overlap, fold, early):
+# (the ids are those these cases had while a third parameter selected an early all-reduce, since removed: they stay stable)
+@pytest.mark.parametrize('overlap,fold', [(True, True), (False, True), (True, False)],
+                         ids=['True-True-False', 'False-True-False', 'True-False-False'])
+def test_two_rank_step_equals_one_rank(hip, overlap, fold):
     import torch.multiprocessing as mp
     from oracle import dreamer_oracle as O
     from pydreamer_amd import config
@@ -92,7 +93,7 @@ def test_two_rank_step_equals_one_rank(hip, overlap, fold, early):
     world = 2
     mgr = mp.Manager()
     out = mgr.dict()
-    mp.spawn(_worker, args=(world, _free_port(), overlap, fold, out, early), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, _free_port(), overlap, fold, out), nprocs=world, join=True)
     res = dict(out)
     assert set(res) == {0, 1}
     # the single-process run of the whole batch
@@ -220,8 +221,8 @@ def test_bench_steps_and_dump_outputs(hip, tmp_path):
 
 @pytest.mark.parametrize('world', [2, 4, 8])
 def test_default_deployment_over_rccl_on_real_gpus(hip, world):
-    """The deployment every real shard runs - one process per GPU over RCCL ("nccl"), data-parallel FusedAdamW with the (round 6: late, inside grad_clip; DM_DP_EARLY=1: early)
-    all-reduce and the B_r/B weight folded into the backward kernels, the pipelined actor / critic optimizer, AND the persistent
+    """The deployment every real shard runs - one process per GPU over RCCL ("nccl"), data-parallel FusedAdamW with the all-reduce inside grad_clip
+    and the B_r/B weight folded into the backward kernels, the pipelined actor / critic optimizer, AND the persistent
     posterior kernel ON (its default for <= 32-column shards: 25/25, 13/13/12/12, 7/7/6/6/6/6/6/6 of the 50 columns) - at the
     full Atari-literal size, through bench.py as the driver launches it.  Needs `world` GPUs: two trainers cannot share one
     device with the persistent kernel on (each needs every CU at once), which is why the one-device smoke mode of the tests
@@ -269,46 +270,6 @@ def test_default_deployment_over_rccl_on_real_gpus(hip, world):
         assert abs(c8[i] - c1[i]) <= 2e-5 * c1[4 + i] + 1e-6, (i, c8, c1)
 
 
-def test_native_rccl_entry_points_one_rank():
-    """The native exchange step (include/dreamer_hip.h dm_rccl_* / dm_allreduce_grads, csrc/comm.hip) on real hardware as far as a
-    1-GPU box can take it: RCCL is bound with dlopen, a ONE-rank communicator is created on the current device, and the in-place
-    SUM all-reduce of two flat fp32 buffers - enqueued on two different non-default streams, one communicator each, as
-    dist.attach(native=True) lays them out per optimizer group - leaves the data unchanged (the sum over one rank) and ordered
-    behind the kernel that wrote the buffer on that stream.  N > 1 needs N GPUs (RCCL refuses two ranks on one device)."""
-    import ctypes
-    from pydreamer_amd import hip as H
-    lib = H.lib()
-    if not lib.dm_rccl_available():
-        pytest.skip('librccl is not loadable on this box')
-    assert lib.dm_rccl_version() > 20000
-    dev = torch.device('cuda', 0)
-    torch.cuda.set_device(dev)
-    comms, streams, bufs, refs = [], [], [], []
-    for i in range(2):
-        idb = (ctypes.c_char * 128)()
-        H.call('dm_rccl_unique_id', idb)
-        comm = ctypes.c_void_p()
-        H.call('dm_rccl_comm_init', ctypes.byref(comm), 1, ctypes.c_char_p(bytes(idb)), 0)
-        assert comm.value
-        comms.append(comm)
-        streams.append(torch.cuda.Stream(dev))
-    for i, (comm, st) in enumerate(zip(comms, streams)):
-        with torch.cuda.stream(st):
-            x = torch.randn(1_000_003 + i, device=dev)
-            y = x * 3.0 + 1.0                      # the producer on this stream; the collective must see its result
-            H.call('dm_allreduce_grads', H.fptr(y), y.numel(), comm, H.stream())
-            z = y * 0.5                             # ... and the consumer the collective's
-            bufs.append(z)
-            refs.append((x * 3.0 + 1.0) * 0.5)
-    torch.cuda.synchronize()
-    for z, r in zip(bufs, refs):
-        assert torch.equal(z, r)
-    with pytest.raises(H.DreamerHipError):
-        H.call('dm_allreduce_grads', None, 4, comms[0], None)
-    for comm in comms:
-        H.call('dm_rccl_comm_destroy', comm)
-
-
 def test_default_shard_deployment_over_one_rank_rccl(hip):
     """What a 1-GPU box can run of the real deployment (round 6): `bench.py --force-dp --emulate-world 8 --pipeline` - rank 0's
     7-column shard of an 8-way split at the FULL Atari-literal size, the data-parallel code path switched on over a ONE-rank RCCL
@@ -333,29 +294,6 @@ def test_default_shard_deployment_over_one_rank_rccl(hip):
     assert di['persistent_posterior_kernel_ran'] == [True] and di['rssm_lds_status'] == [0]
     assert di['replicas_identical'] and np.isfinite(d['loss_model_last']) and d['loss_model_last'] > 0
     assert all(v['ms'] >= 0 for v in di['allreduce_standalone'].values())
-
-
-def test_native_overlapped_allreduce_equals_late_torch_one_rank(hip):
-    """The library's own exchange step in its OVERLAPPED form (DM_DP_NATIVE=1 DM_DP_EARLY=1: dm_allreduce_grads enqueued right
-    behind each pre-launched backward on that backward's stream, one communicator per optimizer group, created at the first
-    all-reduce) against the product default (torch.distributed, inside grad_clip) on the 7-column shard over a ONE-rank RCCL
-    group: a sum over one rank is the identity, so after the same steps the parameter checksums must be EQUAL to the bit."""
-    import json
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lines = {}
-    for name, extra in (('late', {}), ('native_early', dict(DM_DP_NATIVE='1', DM_DP_EARLY='1'))):
-        env = dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT=str(_free_port()), **extra)
-        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--force-dp', '--emulate-world', '8', '--reps', '1',
-               '--steps', '3', '--warmup', '1', '--prof-steps', '0', '--no-cpu-baseline', '--no-h2d-leg', '--ring', '2']
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
-        assert r.returncode == 0, r.stderr[-2000:]
-        lines[name] = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
-    assert lines['native_early']['INVALID_diagnostic_forced_one_rank_dp'] == 'native dm_allreduce_grads'
-    a, b = (lines[k]['distributed']['param_checksum_rank0'] for k in ('late', 'native_early'))
-    assert a == b, (a, b)
-    assert lines['late']['loss_model_last'] == lines['native_early']['loss_model_last']
 
 
 _ORDER_SCRIPT = r'''

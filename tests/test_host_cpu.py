@@ -14,11 +14,11 @@ from pydreamer_amd import config, dist as DP, hip
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_library_abi_v14_exports_every_declared_symbol():
+def test_library_abi_v15_exports_every_declared_symbol():
     hdr = open(os.path.join(ROOT, 'include', 'dreamer_hip.h')).read()
     declared = sorted(set(re.findall(r'\b(dm_[a-z0-9_]+)\s*\(', hdr)))
     lib = hip.lib()
-    assert lib.dm_version() == hip.DM_ABI_VERSION == 14
+    assert lib.dm_version() == hip.DM_ABI_VERSION == 15
     missing = [n for n in declared if not hasattr(lib, n)]
     assert not missing, missing
     assert sorted(hip.exported_symbols()) == declared, set(declared) ^ set(hip.exported_symbols())
@@ -260,9 +260,6 @@ def test_runtime_switch_defaults():
         assert lib.dm_rssm_lds_enable(-1) == 1
         assert lib.dm_bptt_fold_enable(-1) == 1 or os.environ.get('DM_BPTT_FOLD')
     assert lib.dm_rssm_lds_status() == 0 and lib.dm_rssm_lds_status_ack() == 0 and lib.dm_rssm_lds_gave_up() == 0
-    assert lib.dm_rccl_available() in (0, 1)          # the native exchange step binds RCCL with dlopen: no link-time dependency
-    if lib.dm_rccl_available():
-        assert lib.dm_rccl_version() > 20000
     assert lib.dm_bf16_twins_enable(0) == 0 and lib.dm_bf16_twins_enable(1) == 1
     if not os.environ.get('DM_ROLLOUT_NO_FUSE_ACT'):      # round 6: the rollout's action draw rides in the actor kernel by default
         assert lib.dm_rollout_fuse_act_enable(-1) == 1 and lib.dm_rollout_fuse_act_enable(0) == 0 and lib.dm_rollout_fuse_act_enable(1) == 1
