@@ -13,15 +13,20 @@ the batch axis (7,7,6,6,6,6,6,6 at N=8) with one RCCL all-reduce per optimizer g
 Other workloads (diagnostic lines, marked as such): --workload atari-native = pydreamer's own `defaults+atari` (B=32, T=48,
 deter 1024: what the reference's README measured), --workload dmc = BASELINE configs[4] at one GPU (defaults+dmc, B=T=50).
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line; `h2d_included`, `roofline`,
+`cpu_baseline` and `host_enqueue_unthrottled_ms_per_step` are null in it.  --full adds the legs that fill them, each after
+the timed region (--no-h2d-leg, --prof-steps 0 and --no-cpu-baseline drop one of them again):
+  host_enqueue_unthrottled_ms_per_step : three more steps right after the timed region, host time to enqueue one.
   h2d_included : the same step fed from HOST memory through pydreamer_amd.replay.DeviceRing (pinned uint8 frames, copies
                  prefetched behind the forward) - SURVEY 8(d) asks for it next to `value`, which keeps the replay resident in HBM.
   roofline     : the GEMM kernel family (every dense contraction of the step runs on it), algorithmic 2MNK flops per
                  launch / HIP-event launch durations recorded on the launch stream in a profiled pass of the same steps
                  that directly follows the timed region (events are kept out of the timed region so `value` is unperturbed);
-                 peak = 157.3 TFLOP/s fp32 MFMA (MI355X_MICROARCH.md).
+                 peak = 157.3 TFLOP/s fp32 MFMA (MI355X_MICROARCH.md).  An explicit --prof-steps N > 0 runs this pass
+                 without --full as well (--shape-table needs it).
   cpu_baseline : oracle/dreamer_oracle.py (torch CPU restatement pinned to the reference by goldens, kind "port") timed
                  on this box's host cores on a bounded sample of the same workload (rank 0, N=1 only).
+A run with N > 1 ranks (or --force-dp) always carries its `distributed` record: per-rank times, replica and loss checks.
 
 --steps K runs exactly K timed steps; `ms_per_step` is the time of one of them.  --dump-outputs DIR writes what the last
 timed step handed its caller (losses, recurrent state, metrics, tensors, gradient norms, the parameters after AdamW) as
@@ -257,7 +262,9 @@ def main():
     ap.add_argument('--reps', type=int, default=1, help='the --steps timed steps run as this many back-to-back regions (barrier + synchronise on both '
                     'sides, at most one region per step); `value` / `ms_per_step` are the MEDIAN region\'s (max over ranks each), min / max are printed beside it')
     ap.add_argument('--dump-outputs', default='', metavar='DIR', help='write the outputs of the last timed step to DIR/<name>.npy (rank 0)')
-    ap.add_argument('--prof-steps', type=int, default=2)
+    ap.add_argument('--full', action='store_true', help='after the timed region, also run the legs beyond the headline: unthrottled host '
+                    'enqueue cost, the H2D-included leg, the profiled roofline pass and the CPU baseline')
+    ap.add_argument('--prof-steps', type=int, default=None, help='steps of the profiled roofline pass (default 2 with --full, else 0)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--pmc-json', default='',
                     help='per-kernel HBM traffic from two rocprofv3 PMC passes of THIS command (scripts/pmc_traffic.py); it carries a '
@@ -283,6 +290,10 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    if args.prof_steps is None:
+        args.prof_steps = 2 if args.full else 0
+    if args.shape_table and args.prof_steps < 1:
+        ap.error('--shape-table needs the profiled pass: add --full or --prof-steps N')
     if not args.pmc_json:       # the committed counter summary of the same command (fp32 / bf16 step), if its fingerprint matches the tree
         import glob
         cands = sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r[0-9][0-9]_pmc_traffic' + ('_bf16' if args.dtype == 'bf16' else '') + '.json')))
@@ -426,11 +437,13 @@ def main():
     # What the host needs to ENQUEUE a step when nothing holds it back: three more steps right after the synchronise (empty
     # queues).  `host_enqueue_ms_per_step` above is taken over the timed region, where the runtime's queue back-pressure
     # makes the launching threads wait for the GPU once they are a few steps ahead - it tracks the GPU, not the host's cost.
-    th = time.perf_counter()
-    for i in range(3):
-        step(n_done + i)
-    host_free_ms = 1e3 * (time.perf_counter() - th) / 3
-    torch.cuda.synchronize()
+    host_free_ms = None
+    if args.full:
+        th = time.perf_counter()
+        for i in range(3):
+            step(n_done + i)
+        host_free_ms = 1e3 * (time.perf_counter() - th) / 3
+        torch.cuda.synchronize()
     dist_info = None
     if world > 1 or args.force_dp:      # (--force-dp: the same record over a ONE-rank RCCL group)
         # per-rank numbers (before the MAX) and the stand-alone cost of the step's all-reduces on this fabric
@@ -482,7 +495,7 @@ def main():
 
     # H2D-included leg: the same step fed from host memory through the DeviceRing (pinned uint8 frames, copies prefetched behind the forward)
     h2d = None
-    if world == 1 and not args.no_h2d_leg and args.emulate_world <= 1:
+    if args.full and world == 1 and not args.no_h2d_leg and args.emulate_world <= 1:
         from pydreamer_amd.replay import DeviceRing
         import itertools
         host_ring = make_host_ring(conf, hi - lo, 4, 4321)
@@ -645,13 +658,13 @@ def main():
                     kinds=kinds, note='HIP events on the launch stream around every GEMM launch, eager (un-graphed) pass of the same steps right after the timed region')
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == 'atari-literal':
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == 'atari-literal':
         cpu = cpu_baseline()
 
     if rank == 0:
         ms = ms_step
         line = dict(metric=METRIC, value=1e3 / ms, unit='grad-steps/s', n_gpus=world, steps=args.steps,
-                    warmup=args.warmup, ms_per_step=ms, ms_per_step_min=min(region_ms), ms_per_step_median=ms,
+                    warmup=args.warmup, full=args.full, ms_per_step=ms, ms_per_step_min=min(region_ms), ms_per_step_median=ms,
                     ms_per_step_max=max(region_ms), timed_regions=len(region_ms), ms_per_step_regions=region_ms, higher_is_better=True, scaling='strong', vs_baseline=None,
                     dtype='f32' if args.dtype == 'f32' else 'bf16 (MFMA operands; fp32 accumulate, fp32 storage and non-GEMM math)', data='synthetic',
                     config=dict(workload={'atari-literal': 'atari-literal: defaults+atari, batch_size 50, batch_length 50, imag_horizon 15, '

@@ -15,7 +15,7 @@ done
 python $REPO/scripts/pmc_traffic.py $(find /tmp/profh_FETCH_SIZE -name "*counter_collection.csv" | head -1) $(find /tmp/profh_WRITE_SIZE -name "*counter_collection.csv" | head -1) 3 $SHA > $OUT/${TAG}_pmc_traffic_bf16.json
 cd $REPO
 cp $OUT/${TAG}_pmc_traffic_bf16.json profiles/${TAG}_pmc_traffic_bf16.json
-python bench.py --dtype bf16 --no-cpu-baseline --shape-table $OUT/${TAG}_gemm_shapes_bf16.txt > $OUT/${TAG}_bench_bf16.json 2>/dev/null
+python bench.py --full --dtype bf16 --no-cpu-baseline --shape-table $OUT/${TAG}_gemm_shapes_bf16.txt > $OUT/${TAG}_bench_bf16.json 2>/dev/null
 python - << PY
 import json
 p = json.load(open('$OUT/${TAG}_pmc_traffic_bf16.json'))

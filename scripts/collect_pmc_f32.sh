@@ -10,5 +10,5 @@ done
 python $REPO/scripts/pmc_traffic.py $(find /tmp/prof_FETCH_SIZE -name "*counter_collection.csv" | head -1) $(find /tmp/prof_WRITE_SIZE -name "*counter_collection.csv" | head -1) 3 $SHA > $OUT/${TAG}_pmc_traffic.json
 cd $REPO
 cp $OUT/${TAG}_pmc_traffic.json profiles/${TAG}_pmc_traffic.json
-timeout 300 python bench.py > $OUT/${TAG}_bench.json 2> $OUT/bench.err
+timeout 300 python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/bench.err
 tail -c 300 $OUT/${TAG}_bench.json

@@ -32,5 +32,5 @@ for v in 256 1024; do
 done
 } > $OUT/chain_rows.txt 2>&1
 cat $OUT/chain_rows.txt
-python bench.py --no-cpu-baseline --no-h2d-leg > $OUT/bench_base.json 2> $OUT/bench_base.err
+python bench.py --full --no-cpu-baseline --no-h2d-leg > $OUT/bench_base.json 2> $OUT/bench_base.err
 python -c "import json; d=json.load(open('$OUT/bench_base.json')); print('bench', d['ms_per_step'], d['ms_per_step_regions'], d['roofline']['frac'], d['roofline']['all_gemm'])"

@@ -219,6 +219,23 @@ def test_bench_steps_and_dump_outputs(hip, tmp_path):
     assert arrays['state_0'].shape == (50, 600)
 
 
+def test_bench_plain_run_is_the_headline_and_full_adds_the_legs(hip):
+    """A plain bench.py run reports the headline and nothing that needs runs of its own: no roofline pass, H2D leg, CPU
+    baseline or unthrottled-enqueue steps.  --full runs those legs after the timed region (the CPU baseline left out here:
+    it takes half a minute of host time) without changing what the timed steps computed."""
+    plain = _run_bench(1, {}, '--steps', '2', '--warmup', '1', '--ring', '2')
+    assert plain['full'] is False and plain['steps'] == 2 and plain['value'] > 0
+    assert abs(plain['ms_per_step'] * plain['value'] - 1e3) < 1e-6 * 1e3
+    assert plain['roofline'] is None and plain['h2d_included'] is None and plain['cpu_baseline'] is None
+    assert plain['host_enqueue_unthrottled_ms_per_step'] is None
+    full = _run_bench(1, {}, '--steps', '2', '--warmup', '1', '--ring', '2', '--full', '--no-cpu-baseline', '--h2d-steps', '2', '--prof-steps', '1')
+    assert full['full'] is True and full['cpu_baseline'] is None
+    assert full['roofline'] is not None and full['roofline']['frac'] > 0
+    assert full['h2d_included'] is not None and full['h2d_included']['steps'] == 2 and full['h2d_included']['value'] > 0
+    assert full['host_enqueue_unthrottled_ms_per_step'] > 0
+    assert full['loss_model_last'] == plain['loss_model_last']
+
+
 @pytest.mark.parametrize('world', [2, 4, 8])
 def test_default_deployment_over_rccl_on_real_gpus(hip, world):
     """The deployment every real shard runs - one process per GPU over RCCL ("nccl"), data-parallel FusedAdamW with the all-reduce inside grad_clip

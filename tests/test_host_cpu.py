@@ -245,6 +245,15 @@ def test_bench_dump_outputs_types_sample_and_budget(tmp_path):
         bench.dump_outputs(str(tmp_path / 'z'), {f'p{i}': big for i in range(9)})
 
 
+def test_bench_shape_table_needs_the_profiled_pass():
+    """A plain bench.py run has no profiled pass, so --shape-table alone is refused before anything touches a device."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--shape-table', os.devnull], capture_output=True, text=True,
+                       timeout=120, cwd=ROOT)
+    assert r.returncode == 2 and '--shape-table needs the profiled pass' in r.stderr, r.stderr[-1000:]
+
+
 def test_graft_entry_build_passes():
     """The driver's build check (make is a no-op on an up-to-date tree; the ABI assertion and symbol walk are what is tested)."""
     import __graft_entry__ as g
