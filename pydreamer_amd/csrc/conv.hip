@@ -1020,6 +1020,15 @@ static int conv_decoder_mse_bwd_impl(const dm_shape* shp, const float* feat, int
       d.a_tab_vec8 = (co & 7) == 0 || (co == 4 && (g.k[l] & 1) == 0);
       d.B = padded ? wpad : a.wr[l]; d.ldb = ncol;
       d.C = Gn; d.ldc = g.cin[l];
+      if (l - 1 >= 1 && co4[l - 1] != g.cin[l]) {
+        // the layer below gathers its output gradient with co4[l-1] channels per pixel (cnn_depth 6: 6 -> 8): write the rows
+        // at that pitch, over zeroed pad channels
+        hipError_t e = hipMemsetAsync(Gn, 0, gsz[l - 1] * sizeof(float), st);
+        if (e == hipSuccess && dm_twin_of(Gn, false))
+          e = hipMemsetAsync(dm_twin_of(Gn, false), 0, gsz[l - 1] * sizeof(unsigned short), st);
+        if (e != hipSuccess) return dm_fail(DM_E_HIP, "conv_decoder_bwd: %s", hipGetErrorString(e));
+        d.ldc = co4[l - 1];
+      }
       if (l - 1 >= 1) { d.mulref = a.x[l - 1]; d.ldmul = g.cin[l]; }
       DM_TRY(dm_gemm_launch(d, splitk, skb, st));
     }

@@ -12,6 +12,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from oracle import conv_reference as CR
 from oracle import dreamer_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -299,6 +300,14 @@ def test_conv_encoder_fwd_bwd(hip, depth, T, B):
     for i in range(4):
         assert _rel_l2(grads[0][i], p[f'wm.encoder.encoder_image.model.{2 * i}.weight'].grad) < 2e-4, f'conv{i} dW'
         assert _rel_l2(grads[1][i], p[f'wm.encoder.encoder_image.model.{2 * i}.bias'].grad) < 2e-4, f'conv{i} db'
+    # ... and element by element: max |got - ref64| / rms(ref64) within 10x what the oracle's own fp32 arithmetic misses fp64 by
+    # (oracle/conv_reference.py; tests/test_gpu_conv_stack.py does the same at production frame counts)
+    frames, dcpu = image.cpu().reshape(N, 3, 64, 64), dembed.cpu()
+    r64, r32 = (CR.encoder_reference(params, frames, dcpu, dtype=dt) for dt in (torch.float64, torch.float32))
+    CR.check_tensor('encoder embed', embed.cpu(), r64['embed'], r32['embed'], ('frame', 'feature(c,y,x)'))
+    for i in range(4):
+        CR.check_tensor(f'encoder dW{i}', grads[0][i].cpu(), r64[f'dW{i}'], r32[f'dW{i}'], ('out', 'in', 'ky', 'kx'))
+        CR.check_tensor(f'encoder db{i}', grads[1][i].cpu(), r64[f'db{i}'], r32[f'db{i}'], ('out',))
 
 
 @pytest.mark.parametrize('depth,l4_direct', [(8, 1), (8, 0), (16, 1), (48, 1), (48, 0), (64, 1)])
@@ -354,6 +363,16 @@ def _conv_decoder_mse_fwd_bwd(depth):
     for i, idx in enumerate((0, 2, 4, 6, 8)):
         assert _rel_l2(gw[i], p[f'wm.decoder.image.model.{idx}.weight'].grad) < 2e-4, f'dec layer {i} dW'
         assert _rel_l2(gb[i], p[f'wm.decoder.image.model.{idx}.bias'].grad) < 2e-4, f'dec layer {i} db'
+    # ... and element by element (see test_conv_encoder_fwd_bwd).  dfeat was accumulated onto ones: the reference is 1 + gradient,
+    # summed in fp64 and - for the bar - in fp32, so the rounding of that sum is part of both
+    r64, r32 = (CR.decoder_reference(params, feat.cpu(), target.cpu(), scale, dtype=dt) for dt in (torch.float64, torch.float32))
+    CR.check_tensor('decoder image_rec', rec.cpu(), r64['image_rec'], r32['image_rec'], ('frame', 'channel', 'y', 'x'))
+    CR.check_tensor('decoder loss_image', loss.cpu(), r64['loss_image'], r32['loss_image'], ('frame',))
+    CR.check_tensor('decoder dfeat + 1', dfeat.cpu(), 1.0 + r64['dfeat'], 1.0 + r32['dfeat'], ('frame', 'feature'))
+    for i in range(5):
+        axes = ('out', 'in') if i == 0 else ('in', 'out', 'ky', 'kx')
+        CR.check_tensor(f'decoder dW{i}', gw[i].cpu(), r64[f'dW{i}'], r32[f'dW{i}'], axes)
+        CR.check_tensor(f'decoder db{i}', gb[i].cpu(), r64[f'db{i}'], r32[f'db{i}'], ('out',))
 
 
 def _conv_stack_bf16(model, T, B, twins, seed=5, flip_before_backward=False):
@@ -411,7 +430,7 @@ def _conv_stack_bf16(model, T, B, twins, seed=5, flip_before_backward=False):
         H.lib().dm_bf16_twins_enable(1)
 
 
-@pytest.mark.parametrize('depth,T,B', [(8, 2, 3), (48, 2, 2), (16, 3, 5)])
+@pytest.mark.parametrize('depth,T,B', [(8, 2, 3), (48, 2, 2), (16, 3, 5), (48, 1, 513), (48, 50, 50)])
 def test_conv_bf16_storage_twins_match_fp32_storage(hip, depth, T, B):
     """conf.amp convolution stack with operands STORED as bf16 (twins written by the producing kernels, gemm_h_kernel) against
     the same bf16 products fed from fp32 storage (rounded on the way into LDS): the operand values are identical (RNE of
