@@ -137,13 +137,13 @@ int dm_bf16_twins_enable(int on);
  * ring, counted vmcnt across a raw s_barrier, inline-asm fragment reads (csrc/gemm.hip).  Same tiles, k order and epilogue as the
  * register-staged gemm_f32_kernel: bit-identical results, so the library picks per call: the LDS-DMA loop from 14 k-tiles per
  * work item up, the register-staged loop (higher residency) below.  1 / 0 switches it on / off, 2 = on for every k extent (the
- * bit-identity test), -1 queries; returns the state (default 1; DM_GEMM_DMA=0 / 2 in the environment). */
+ * bit-identity test), -1 queries; returns the state (default 1). */
 int dm_gemm_dma_enable(int on);
 /* The image layer of the decoder (ConvTranspose2d(d -> 3, k6, s2), decoders.py:154-155) runs its backward - data gradient with
  * the ELU' of the layer below folded in, weight gradient - as two direct MFMA kernels that read the 3-channel output gradient
  * of a frame from LDS (csrc/conv_direct.hip) instead of as gather-form products through the generic tile (3 -> 4 channel pad, 48
  * columns in a 64-wide tile).  Same sums in another order (fp32 rounding only).  1 / 0 switches it on / off, -1 queries; returns
- * the state (default 1; DM_DEC_L4_BWD_GEMM=1 in the environment = off). */
+ * the state (default 1). */
 int dm_dec_l4_bwd_direct_enable(int on);
 /* The posterior T loop (rssm.py:38-58, cell rssm.py:125-153, nn.GRUCell rnn.py:40-67) runs, when the shape qualifies (plain
  * single-layer GRU, LayerNorm, categorical latents, B <= 64, the layer slices fit one CU's LDS), as ONE persistent kernel with
@@ -151,10 +151,10 @@ int dm_dec_l4_bwd_direct_enable(int on);
  * the small activation rows through poison-filled per-step buffers (csrc/rssm_lds.hip) - instead of five
  * dependent launches per step that re-stream the weights.  Same arithmetic up to fp32 summation order, same sampler rule.
  * dm_rssm_lds_enable: 1 / 0 switches it on / off, 2 = on also for small models (slices under half a CU's LDS: tests), -1 queries;
- * returns the state (default 1; DM_RSSM_LDS=0 / 2 in the environment).
+ * returns the state (default 1).
  * Co-residency is checked with the occupancy API before the first launch of a variant (>= 1 workgroup per CU at its LDS size; the grid
- * never exceeds the CU count) and the spin loops are bounded; DM_RSSM_LDS_COOP=1 launches cooperatively instead (measured slower: it drains
- * the other streams around the kernel).
+ * never exceeds the CU count) and the spin loops are bounded (a cooperative launch was measured slower - it drains the other streams
+ * around the kernel - and is not built).
  * dm_rssm_lds_status: non-zero once such a kernel has given up in a spin loop (that step's outputs are invalid; every later call
  * takes the launch chain).  dm_rssm_lds_status_ack: the same word, read AND cleared - the give-up is reported once
  * (Dreamer.check_device_status() / packed_metrics_host() raise on it) while the kernel stays switched off for the life of the
@@ -163,7 +163,7 @@ int dm_dec_l4_bwd_direct_enable(int on);
 int dm_rssm_lds_enable(int on);
 int dm_bptt_fold_enable(int on);        /* launch schedule of the BPTT loop: the two LayerNorm+ELU backward stages of a step folded into the products
                                             that consume them, dx W = rstd (g W - mean(g) colsum(W) - mean(g xhat) xhat W), so those products start
-                                            with their operand loads instead of a row reduction.  ON by default (DM_BPTT_FOLD=0); -1 queries. */
+                                            with their operand loads instead of a row reduction.  ON by default; -1 queries. */
 int dm_rssm_lds_status(void);
 int dm_rssm_lds_status_ack(void);
 int dm_rssm_lds_gave_up(void);

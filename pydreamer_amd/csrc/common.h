@@ -9,12 +9,6 @@ int dm_fail(int code, const char* fmt, ...);
 
 #define DM_MAX_DEVICES 16      // per-device once-flags (function attributes are per device)
 
-// Wave priority of the latency-chain kernels (experiment, round 6): s_setprio raises a wave's instruction-issue priority on its SIMD
-// over the co-resident waves of other streams' throughput kernels.  0 = leave the hardware default (compile-time: -DDM_CHAIN_SETPRIO=n).
-#ifndef DM_CHAIN_SETPRIO
-#define DM_CHAIN_SETPRIO 0
-#endif
-#define DM_CHAIN_PRIO() do { if (DM_CHAIN_SETPRIO > 0) __builtin_amdgcn_s_setprio(DM_CHAIN_SETPRIO); } while (0)
 #define DM_LAUNCH_CHECK()                                                                      \
   do {                                                                                         \
     hipError_t e__ = hipGetLastError();                                                        \
@@ -80,7 +74,7 @@ struct DmPrecisionScope {
 // Other producers (direct convolutions, pad / col2im / loss kernels) write their twin themselves and call dm_twin_mark.
 // The map is thread-local and dies with the scope: nothing is remembered between calls (a backward entry point re-registers
 // the arena twins its forward wrote as valid - acts must come from a forward call with the same dm_shape.flags).
-// DM_BF16_NO_TWINS=1 (A/B switch) makes every scope inactive: the fp32-storage bf16 products of rounds 1-2.
+// dm_bf16_twins_enable(0) (A/B switch) makes every scope inactive: the fp32-storage bf16 products of rounds 1-2.
 struct DmTwinScope {
   bool active, opened;
   explicit DmTwinScope(bool bf16_mode);

@@ -8,7 +8,6 @@
 // The backward passes are the same two gathers with the roles swapped (convT backward-data is a conv).
 // All kernels here are HBM-streaming; the contractions run in gemm.hip on the matrix cores.
 #include "common.h"
-#include <stdlib.h>
 
 // ---------------------------------------------------------------- patch gather ------------------
 // col[(i,ys,xs)][(ky,kx,cc)] = big[i, 2ys+ky, 2xs+kx, cc]      (NHWC, VEC floats of c per thread)
@@ -296,13 +295,12 @@ __global__ void __launch_bounds__(256) convt_repack_kernel(int cin, int cout, in
     wcat[e] = w[(((size_t)ci * cout + o) * k + (py + 2 * a)) * k + (px + 2 * b)];
   }
 }
-static const int g_convt_gather_off = getenv("DM_CONVT_COLUMN") ? 1 : 0;       // A/B switch: keep the column-matrix form
 // layers this form is used for: even kernel, 16-byte gathers, and enough output channels that N = 4*cout fills MFMA tiles
 // (and an input large enough that the multiplied zero border stays under 40 % extra MACs: (Hc/hs)^2 <= 1.4, i.e. hs >= 6 for
 // k = 4 and hs >= 11 for k = 6)
 static bool convt_gather_ok(int k, int cin, int cout, int hs, size_t n) {
   const int Hc = hs + k / 2 - 1;
-  return !g_convt_gather_off && (k & 1) == 0 && (cin & 3) == 0 && cout >= 16 && 10 * Hc * Hc <= 14 * hs * hs &&
+  return (k & 1) == 0 && (cin & 3) == 0 && cout >= 16 && 10 * Hc * Hc <= 14 * hs * hs &&
          n * (size_t)(2 * (hs - 1) + k + 1) * (2 * (hs - 1) + k + 1) * cout < ((size_t)1 << 31);
 }
 

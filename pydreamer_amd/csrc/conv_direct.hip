@@ -19,14 +19,9 @@
 //                        (scalar loads), the input pixel vectors are 16-byte loads
 // fp32 VALU arithmetic (v_fmac with an SGPR operand); bound: VALU issue (13 / 5.5 GFMA-lanes) and the output write.
 #include "common.h"
-#include <stdlib.h>
 
 static inline int grid_for_px(size_t total, int per_block) { return (int)((total + per_block - 1) / per_block); }
 
-bool dm_conv_direct_enabled() {
-  static const int off = getenv("DM_CONV_NO_DIRECT") ? 1 : 0;      // A/B switch: the explicit patch / column matrices
-  return !off;
-}
 
 // ---------------------------------------------------------------- encoder layer 1, forward --------
 // wt: (48 taps, CO) with tap = c*16 + ky*4 + kx (the torch weight (CO,3,4,4) transposed once per call)
@@ -80,7 +75,7 @@ __global__ void __launch_bounds__(256) enc_l1_wt_kernel(int co, const float* __r
 }
 
 bool dm_enc_l1_direct_ok(int ch, int d, int img) {
-  return dm_conv_direct_enabled() && ch == 3 && img == 64 && (d == 8 || d == 16 || d == 32 || d == 48 || d == 64);
+  return ch == 3 && img == 64 && (d == 8 || d == 16 || d == 32 || d == 48 || d == 64);
 }
 // y (frames*961, d) NHWC post-ELU; wt: scratch of 48*d floats (the transposed weights, written here)
 int dm_enc_l1_fwd_launch(int frames, int d, int u8, const void* image, const float* w, const float* bias, float* wt,
@@ -275,7 +270,7 @@ __global__ void __launch_bounds__(256) dec_l4_fwd_kernel(int frames, const float
 }
 
 bool dm_dec_l4_direct_ok(int ch, int d, int hs, int k) {
-  return dm_conv_direct_enabled() && ch == 3 && hs == 30 && k == 6 && (d == 8 || d == 16 || d == 32 || d == 48 || d == 64);
+  return ch == 3 && hs == 30 && k == 6 && (d == 8 || d == 16 || d == 32 || d == 48 || d == 64);
 }
 size_t dm_dec_l4_w4_floats(int d) { return (size_t)4 * 9 * d * 4; }
 int dm_dec_l4_fwd_launch(int frames, int d, const float* x, const float* w, const float* bias, float* w4, float* out,
@@ -317,7 +312,7 @@ int dm_dec_l4_fwd_launch(int frames, int d, const float* x, const float* w, cons
 //                         global memory (each 64-byte segment is read once), IB x 7 accumulator tiles per wave over ALL its
 //                         frames; per-wave partials in the torch (d, 3, 6, 6) order, summed in fixed order by
 //                         dm_colsum_launch (deterministic)
-static int g_l4_bwd_direct = getenv("DM_DEC_L4_BWD_GEMM") ? 0 : 1;
+static int g_l4_bwd_direct = 1;
 extern "C" int dm_dec_l4_bwd_direct_enable(int on) {
   if (on >= 0) g_l4_bwd_direct = on ? 1 : 0;
   return g_l4_bwd_direct;

@@ -1007,8 +1007,7 @@ int dm_z_embed_launch(int rows, int n, int S, int C, const int32_t* idx, const u
   DM_REQUIRE((ldx & 3) == 0 && (ldy & 3) == 0 && (ldadd & 3) == 0, DM_E_SHAPE, "z_embed: leading dims must be multiples of 4");
   DM_REQUIRE(!x_frag || rows <= 64, DM_E_SHAPE, "z_embed: the fragment-major copy needs rows <= 64");
   DM_REQUIRE(!y || (gamma != nullptr) == (beta != nullptr), DM_E_NULL, "z_embed: LayerNorm gain without its bias");
-  static const int no_wide = getenv("DM_Z_EMBED_NO_WIDE") ? 1 : 0;      // A/B switch
-  if (!y && x && rows <= 64 && S <= 32 && !no_wide) {      // the chain's steps: latency only, one workgroup per row
+  if (!y && x && rows <= 64 && S <= 32) {      // the chain's steps: latency only, one workgroup per row
     hipLaunchKernelGGL(z_embed_wide_kernel, dim3(rows), dim3(256), 0, st, n, S, C, idx, row_zero, Wt, bias, add, ldadd, idx2, Wt2, x,
                        ldx, x_frag);
     DM_LAUNCH_CHECK();

@@ -889,7 +889,7 @@ struct HOperand {
       }
     }
   }
-  __device__ __forceinline__ void load(dm_u32x4 (&r)[NCH], int k0, int kend, bool nt = false) const {
+  __device__ __forceinline__ void load(dm_u32x4 (&r)[NCH], int k0, int kend) const {
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
       const bool ok = k0 + kin[i] < kend;
@@ -898,8 +898,7 @@ struct HOperand {
       else at = GATHER ? (size_t)off[i] + (size_t)tvar[ok ? k0 + kin[i] : 0] : (size_t)k0 * ld + (size_t)off[i];
       typedef const __attribute__((address_space(1))) dm_u32x4* gptr4;
       const uintptr_t src = ok ? (uintptr_t)(P + at) : (uintptr_t)dm_zero_page;
-      if (nt) r[i] = __builtin_nontemporal_load(reinterpret_cast<gptr4>(src));
-      else r[i] = *reinterpret_cast<gptr4>(src);
+      r[i] = *reinterpret_cast<gptr4>(src);
     }
   }
   __device__ __forceinline__ void stash(const dm_u32x4 (&r)[NCH], unsigned short* S, int tid) const {
@@ -970,14 +969,13 @@ __global__ void __launch_bounds__(256, 2) gemm_h_kernel(const GemmKArgs g) {
     sa.init(reinterpret_cast<const unsigned short*>(g.A), g.lda, cur.m0, g.M, g.a_maj, g.a_min, tid);
     sb.init(reinterpret_cast<const unsigned short*>(g.B), g.ldb, cur.n0, g.N, g.b_maj, g.b_min, tid);
     dm_u32x4 ra[OA::NCH], rb[OB::NCH];
-    const bool nt = (g.flags & (1 << 20)) != 0;        // experiment switch DM_GEMM_H_NT: non-temporal operand loads
-    sa.load(ra, cur.kbeg, cur.kend, nt);
-    sb.load(rb, cur.kbeg, cur.kend, nt);
+    sa.load(ra, cur.kbeg, cur.kend);
+    sb.load(rb, cur.kbeg, cur.kend);
     sa.stash(ra, smem, tid);
     sb.stash(rb, smem + BM * LDH, tid);
     if (nkt > 1) {
-      sa.load(ra, cur.kbeg + BK, cur.kend, nt);
-      sb.load(rb, cur.kbeg + BK, cur.kend, nt);
+      sa.load(ra, cur.kbeg + BK, cur.kend);
+      sb.load(rb, cur.kbeg + BK, cur.kend);
     }
     __syncthreads();
     for (int kt = 0; kt < nkt; ++kt) {
@@ -1008,8 +1006,8 @@ __global__ void __launch_bounds__(256, 2) gemm_h_kernel(const GemmKArgs g) {
             sb.stash(rb, Bw, tid);
           }
           if (kt + 2 < nkt) {
-            sa.load(ra, cur.kbeg + (kt + 2) * BK, cur.kend, nt);
-            sb.load(rb, cur.kbeg + (kt + 2) * BK, cur.kend, nt);
+            sa.load(ra, cur.kbeg + (kt + 2) * BK, cur.kend);
+            sb.load(rb, cur.kbeg + (kt + 2) * BK, cur.kend);
           }
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -1185,7 +1183,7 @@ static int gemm_h_tiles(int tc, const GemmKArgs& a, int al, int bl, int gather, 
 }
 
 // ---- gemm_dma_kernel launch: dynamic LDS (NS stages of (BM + BN) x 128 B), attribute set once per instantiation
-static int g_dma_enabled = getenv("DM_GEMM_DMA") ? atoi(getenv("DM_GEMM_DMA")) : 1;
+static int g_dma_enabled = 1;
 // 1 / 0: the direct-to-LDS main loop for fp32 16-byte-load products on / off (A/B and the bit-identity test), -1: query.
 extern "C" int dm_gemm_dma_enable(int on) {
   if (on >= 0) g_dma_enabled = on > 2 ? 2 : on;      // 2: also for products of a few k-tiles (the bit-identity test)
@@ -1259,7 +1257,7 @@ struct TwinRange { const float* base; size_t n; unsigned short* twin; bool valid
 static thread_local TwinRange tl_twins[48];
 static thread_local int tl_ntwins = 0;
 static thread_local bool tl_twins_on = false;
-static int g_twins_enabled = getenv("DM_BF16_NO_TWINS") ? 0 : 1;
+static int g_twins_enabled = 1;
 // 1 / 0: switch the bf16-storage operand path of bf16-mode calls on / off (A/B and parity tests), -1: query.  Returns the state.
 extern "C" int dm_bf16_twins_enable(int on) {
   if (on >= 0) g_twins_enabled = on ? 1 : 0;
@@ -1385,11 +1383,7 @@ int dm_gemm_launch(const DmGemm& q, void* ws, size_t ws_bytes, hipStream_t strea
   a.c_tab = q.c_tab; a.sc_cout = q.sc_cout; a.sc_wpitch = q.sc_wpitch; a.bias_mod = q.bias_mod;
   DM_REQUIRE(!q.c_tab || (q.sc_cout > 0 && q.N % q.sc_cout == 0 && q.N / q.sc_cout == 4 && !q.add && !(q.flags & DM_GEMM_ACCUM)),
              DM_E_SHAPE, "gemm: scatter epilogue needs N = 4 * sc_cout, no addend, no accumulate");
-  if (hstore) {
-    a.A = reinterpret_cast<const float*>(Ah); a.B = reinterpret_cast<const float*>(Bh);
-    static const int h_nt = getenv("DM_GEMM_H_NT") ? 1 : 0;
-    if (h_nt) a.flags |= 1 << 20;
-  }
+  if (hstore) { a.A = reinterpret_cast<const float*>(Ah); a.B = reinterpret_cast<const float*>(Bh); }
   // 16-byte load path: aligned base, rows a multiple of 4 floats apart, and the vectorised (minor) extent a multiple
   // of 4 so that no group of 4 straddles the edge.  Minor extent: K for layout 0, M (resp. N) for layout 1.
   a.a_vec = hstore ? 1 : (((uintptr_t)q.A & 15) == 0 && (q.a_maj ? q.a_tab_vec != 0 : (q.lda & 3) == 0) &&
@@ -1434,13 +1428,7 @@ int dm_gemm_launch(const DmGemm& q, void* ws, size_t ws_bytes, hipStream_t strea
   const int kt1 = ktiles > 0 ? ktiles : 1;
   const bool dma_shape_pre = !hstore && !q.bf16 && a.a_vec && a.b_vec;
   for (int c = 0; c < 5; ++c) {
-    static const int sc_tile = getenv("DM_SC_TILE") ? atoi(getenv("DM_SC_TILE")) : 0;      // tuning override: scatter-epilogue products only
     if (force_tile && c != force_tile - 1) continue;
-    if (sc_tile && q.c_tab && c != sc_tile - 1) continue;
-    static const int plain_tile = getenv("DM_PLAIN_TILE") ? atoi(getenv("DM_PLAIN_TILE")) : 0;   // tuning override: products without gather / scatter
-    if (plain_tile && !q.c_tab && !q.a_maj && !q.b_maj && c != plain_tile - 1) continue;
-    static const int ga_tile = getenv("DM_GA_TILE") ? atoi(getenv("DM_GA_TILE")) : 0;      // tuning override: gathered-operand products
-    if (ga_tile && !q.c_tab && (q.a_maj || q.b_maj) && c != ga_tile - 1) continue;
     if (!(a.a_vec && a.b_vec) && c != 2) continue;        // the scalar-load variant exists for the 64x64 tile only
     const int bm = cand[c][0], bn = cand[c][1];
     const int64_t t = (int64_t)dm_cdiv(q.M, bm) * dm_cdiv(q.N, bn);
@@ -1453,18 +1441,16 @@ int dm_gemm_launch(const DmGemm& q, void* ws, size_t ws_bytes, hipStream_t strea
     if (sp_fill < 1) sp_fill = 1;
     // grids of a few tiles also try 1.5x and 2x the fill split: a long reduction on few tiles is latency /
     // bandwidth bound per workgroup (per_kt = lat_macs below), so more, shorter workgroups per CU finish sooner
-    // (decoder layer-4 weight gradient 48 x 144 x 2.25 M: 1096 -> 700 us); DM_GEMM_NO_WIDE_SPLIT=1 restores {1, fill}
-    static const int no_wide = getenv("DM_GEMM_NO_WIDE_SPLIT") ? 1 : 0;
-    const bool wide = t < 16 && !no_wide;          // (at 16+ tiles the extra partial traffic loses: 400 x 400 x 40 000 196 -> 225 us)
+    // (decoder layer-4 weight gradient 48 x 144 x 2.25 M: 1096 -> 700 us)
+    const bool wide = t < 16;          // (at 16+ tiles the extra partial traffic loses: 400 x 400 x 40 000 196 -> 225 us)
     const int sp15 = wide ? sp_fill + sp_fill / 2 : sp_fill, sp20 = wide ? 2 * sp_fill : sp_fill;
     // ... and the BALANCED splits floor(256 k / tiles), k = 2..5: just under k workgroups on EVERY CU.  When all workgroups
     // of a launch are resident at once it ends with its fullest CU, so the load model below takes ceil(workgroups per CU)
     // there: 52 tiles x 10 splits = 520 workgroups leave 8 CUs with 3 and run 1.5x longer than 52 x 19 = 988 (3.86 per CU).
     // Measured: 400 x 1624 x 40 000 820 -> 602 us, 96 x 1728 x 422 500 1889 -> 1301 us, 96 x 768 x 490 000 928 -> 702 us,
-    // no shape slower, step -0.46 ms.  DM_GEMM_NO_BALANCED_SPLIT=1 restores the previous candidate set and fractional load.
-    static const int balanced = getenv("DM_GEMM_NO_BALANCED_SPLIT") ? 0 : 1;
+    // no shape slower, step -0.46 ms.
     int sps[10] = {1, sp_fill, t >= 256 ? 2 : sp_fill, t >= 256 ? 4 : sp_fill, sp15, sp20, sp_fill, sp_fill, sp_fill, sp_fill};
-    if (balanced && t < 256)
+    if (t < 256)
       for (int k = 2; k <= 5; ++k) sps[4 + k] = (int)((256 * k) / t) > 0 ? (int)((256 * k) / t) : 1;
     for (int pass = 0; pass < 10; ++pass) {
       int sp = force_split > 0 ? force_split : sps[pass];
@@ -1474,7 +1460,7 @@ int dm_gemm_launch(const DmGemm& q, void* ws, size_t ws_bytes, hipStream_t strea
       const double avg = (double)(t * sp) / 256.0;
       const double R = resid[c];
       const double waves = avg > R ? ceil(avg / R) : 1.0;
-      const double conc = avg > R ? avg / waves : (avg > 1.0 ? (balanced ? ceil(avg - 1e-9) : avg) : 1.0);
+      const double conc = avg > R ? avg / waves : (avg > 1.0 ? ceil(avg - 1e-9) : 1.0);
       const double nkt = (double)dm_cdiv(kt1, sp);
       const double tm = (double)bm * bn * 32.0 / rate[c];
       const double per_kt = conc * tm > lat_macs ? conc * tm : lat_macs;
@@ -1482,9 +1468,9 @@ int dm_gemm_launch(const DmGemm& q, void* ws, size_t ws_bytes, hipStream_t strea
       if (sp > 1) cost += 0.4 * sp * out_elems + 1.2e6;
       // scatter-epilogue products (gather-form transposed convolution): the epilogue (table look-ups, 4 parity classes) is
       // dearer per tile than the model's, which was fitted to plain stores.  Measured on the step's three such products
-      // (DM_SC_TILE sweep): 562500x192x384 1176 -> 1051 us and 122500x384x768 981 -> 837 us on 64x64, 562500x192x864
+      // (sweep with the scatter-epilogue products forced onto each tile): 562500x192x384 1176 -> 1051 us and 122500x384x768 981 -> 837 us on 64x64, 562500x192x864
       // 2214 -> 2087 us on 128x96
-      if (q.a_maj && !q.c_tab && q.N <= 64 && c == 2) cost *= 0.8;      // gathered patches x <= 64 channels (DM_GA_TILE sweep): 2250000x48x144 742 -> 597 us
+      if (q.a_maj && !q.c_tab && q.N <= 64 && c == 2) cost *= 0.8;      // gathered patches x <= 64 channels (sweep with the gathered products forced onto each tile): 2250000x48x144 742 -> 597 us
       if (q.c_tab) {
         if (c == 2 && q.K <= 800) cost *= 0.8;
         if (c == 3 && q.N % 96 == 0 && q.K > 800) cost *= 0.8;
@@ -1504,7 +1490,7 @@ int dm_gemm_launch(const DmGemm& q, void* ws, size_t ws_bytes, hipStream_t strea
   // tile's prologue and epilogue better (profiles/r05_gemm_shapes_dma.txt vs _regstaged.txt with the switch at 2: K = 144 /
   // 192 / 384 products lose 8-15 %); both loops give the same bits, so the choice is free per call.  Layout 0 clamps edge
   // rows to the last row, layout 1 to the last full group of 4: >= 1 / >= 4 rows.
-  static const int dma_min_kt = getenv("DM_GEMM_DMA_MIN_KT") ? atoi(getenv("DM_GEMM_DMA_MIN_KT")) : 14;
+  constexpr int dma_min_kt = 14;
   const bool dma_shape = !hstore && !q.bf16 && a.a_vec && a.b_vec && (q.a_layout == 0 ? q.M >= 1 : q.M >= 4) && (q.b_layout == 0 ? q.N >= 1 : q.N >= 4);
   auto dma_for = [&](int sp) { return g_dma_enabled && dma_shape && (dm_cdiv(kt1, sp) >= dma_min_kt || g_dma_enabled >= 2); };
   // (A one-round 128 x 160 tile for the rollout's 2 500 x 1 800 gate products - 240 workgroups, one per CU, instead of 1 160
@@ -1525,14 +1511,12 @@ int dm_gemm_launch(const DmGemm& q, void* ws, size_t ws_bytes, hipStream_t strea
   a.n_fast = tiles_n <= tiles_m ? 1 : 0;
   a.n_items = (int)(tiles * nsplit);
   {      // column groups of the fast dimension (gemm_decode): the grouping that minimises the operand rows one XCD's chunk touches
-    static const int grp_env = getenv("DM_GEMM_XCD_GROUPS") ? atoi(getenv("DM_GEMM_XCD_GROUPS")) : 0;      // 0 auto, 1 off, 2 / 4 forced
     const int F = a.n_fast ? tiles_n : tiles_m, S = a.n_fast ? tiles_m : tiles_n;
     const int bf = a.n_fast ? BN : BM, bs = a.n_fast ? BM : BN;
     int best_g = 1;
     if (nsplit == 1 && tiles >= 64 && !q.c_tab) {
       double best = -1.0;
       for (int G = 1; G <= 4; G *= 2) {
-        if (grp_env > 1 && G != grp_env) continue;
         if (F / G < 2) break;
         const double width = (double)F / G;
         double srows = ((double)tiles / 8.0) / width;
@@ -1542,7 +1526,7 @@ int dm_gemm_launch(const DmGemm& q, void* ws, size_t ws_bytes, hipStream_t strea
         if (best < 0 || cost < best * 0.95) { best = cost; best_g = G; }      // (a new grouping has to win by 5 %)
       }
     }
-    a.n_groups = grp_env == 1 ? 1 : best_g;
+    a.n_groups = best_g;
   }
   const int tc = (BM == 128 && BN == 128) ? 0 : (BM == 128 && BN == 64) ? 1 : (BM == 64 ? 2 : (BN == 96 ? 3 : 4));
   dim3 grid((unsigned)a.n_items);
@@ -1561,9 +1545,8 @@ int dm_gemm_launch(const DmGemm& q, void* ws, size_t ws_bytes, hipStream_t strea
   }
   int rc;
   const bool vec = a.a_vec && a.b_vec;
-  static const int no_pipe = getenv("DM_GEMM_NO_PIPE") ? 1 : 0;      // A/B switch: the single-stage loop for the bf16-pipe modes
   // the pipelined kernel clamps edge rows instead of masking them: it needs >= 1 full row (layout 0) / >= 4 (layout 1 groups)
-  const bool pipe_ok = vec && !no_pipe && (q.a_layout == 0 ? q.M >= 1 : q.M >= 4) && (q.b_layout == 0 ? q.N >= 1 : q.N >= 4);
+  const bool pipe_ok = vec && (q.a_layout == 0 ? q.M >= 1 : q.M >= 4) && (q.b_layout == 0 ? q.N >= 1 : q.N >= 4);
   if (hstore) rc = gemm_h_tiles(tc, a, q.a_layout, q.b_layout, gather, grid, stream);
   else if (pipe_ok && q.bf16) rc = gemm_pipe_tiles(tc, a, q.a_layout, q.b_layout, gather, grid, stream);
   else if (vec && q.bf16) {

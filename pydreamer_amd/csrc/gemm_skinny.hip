@@ -14,7 +14,6 @@
 // fp32-input MFMA is an exact fmaf chain, so numerics match the tiled kernel up to summation order.
 // skinny_gemm_pair_kernel runs two independent products in one launch (the loops are bound by the launch count).
 #include "common.h"
-#include <stdlib.h>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -452,16 +451,10 @@ __device__ __forceinline__ void skinny_strip(const SkinnyArgs& g, int strip, int
   }
 }
 
-// DM_SKINNY_LDS_PAD (floats, compile-time experiment of round 6): LDS claimed beyond what the strip needs, so that no workgroup of
-// the LDS-DMA tile kernels (48 KB each) fits on a CU beside a strip - does a chain kernel run faster with the CU to itself?
-#ifndef DM_SKINNY_LDS_PAD
-#define DM_SKINNY_LDS_PAD 0
-#endif
 template <int BL, int NRB, int MODE, int EPI = 0>
 __global__ void __launch_bounds__(SK_WAVES * 64) skinny_gemm_kernel(const SkinnyArgs g) {
-  __shared__ float part[SK_WAVES * 64 * 16 + DM_SKINNY_LDS_PAD];
+  __shared__ float part[SK_WAVES * 64 * 16];
   __shared__ SkinnyShared sh;
-  DM_CHAIN_PRIO();
   skinny_strip<BL, NRB, 1, MODE, EPI, MODE == 2 ? 2 : 4>(g, blockIdx.x, blockIdx.y * (16 * NRB), part, &sh, nullptr);   // grid.y = (16 NRB)-row chunks of M
 }
 // Posterior / prior head with the sampler in the epilogue: LayerNorm+ELU prologue, 32-wide strips (one categorical group
@@ -471,7 +464,6 @@ __global__ void __launch_bounds__(SK_WAVES * 64) skinny_gemm_sample_kernel(const
   __shared__ float part[SK_WAVES * 64 * 32];
   __shared__ SkinnyShared sh;
   __shared__ float tile[64 * 33];
-  DM_CHAIN_PRIO();
   skinny_strip<0, NRB, 2, 1, 1, 2>(g, blockIdx.x, blockIdx.y * (16 * NRB), part, &sh, tile);      // grid.y = (16 NRB)-row chunks of M
 }
 // Two independent products in ONE launch (the loops are bound by the number of launches, ~5 us of GPU time and ~6 us of
@@ -483,18 +475,17 @@ struct SkinnyPairArgs { SkinnyArgs g[2]; int nb0, nb; };      // nb = strips of 
 // NCB1 = 2: the second product in 32-wide strips (softmax-backward epilogue: a strip is one categorical group)
 template <int NRB, int MODE0, int MODE1, int NCB1 = 1>
 __global__ void __launch_bounds__(SK_WAVES * 64) skinny_gemm_pair_kernel(const SkinnyPairArgs a) {
-  __shared__ float part[SK_WAVES * 64 * 16 * NCB1 + (NCB1 == 1 ? DM_SKINNY_LDS_PAD : 0)];
+  __shared__ float part[SK_WAVES * 64 * 16 * NCB1];
   __shared__ SkinnyShared sh;
-  DM_CHAIN_PRIO();
   const int b = blockIdx.x % a.nb, m0 = (blockIdx.x / a.nb) * (16 * NRB);
   if (b < a.nb0) skinny_strip<0, NRB, 1, MODE0, 0, MODE0 == 2 ? 2 : 4>(a.g[0], b, m0, part, &sh, nullptr);
   else skinny_strip<0, NRB, NCB1, MODE1, 0, (MODE1 == 2 || NCB1 == 2) ? 2 : 4>(a.g[1], b - a.nb0, m0, part, &sh, nullptr);
 }
 
 // max_m: 64 for the pair kernel (one chunk); the single-product kernel walks M in 64-row chunks (grid.y) up to
-// g_skinny_max_m rows, where it still beats the tiled kernel's <= ~100 workgroups (imagination products of a
+// SK_MAX_M rows, where it still beats the tiled kernel's <= ~100 workgroups (imagination products of a
 // data-parallel shard: M = T*B/8 = 350)
-static const int g_skinny_max_m = getenv("DM_SKINNY_MAX_M") ? atoi(getenv("DM_SKINNY_MAX_M")) : 512;
+constexpr int SK_MAX_M = 512;
 static bool skinny_ok(const DmGemm& q, int max_m) {
   if (q.M > max_m || q.M < 1 || q.N < 1 || q.K < 16) return false;
   if (q.a_layout != 0 || q.a_maj || q.b_maj || q.mulref || q.c_tab || q.bias_mod) return false;
@@ -523,14 +514,11 @@ static void skinny_fill(const DmGemm& q, SkinnyArgs& a) {
   const bool one_chunk = q.M <= 64;       // the fragment-major layout holds ONE 64-row chunk
   a.Af = one_chunk ? q.A_frag : nullptr; a.Cf = one_chunk ? q.C_frag : nullptr; a.znf = nullptr;
 }
-static const int g_skinny_disabled = getenv("DM_GEMM_NO_SKINNY") ? 1 : 0;      // A/B switch for scripts/gemm_bench.py
-static const int g_skinny_nofuse = getenv("DM_SKINNY_NO_FUSE") ? 1 : 0;        // A/B switch: keep LayerNorm / sampler launches
-static const int g_skinny_msplit = getenv("DM_SKINNY_MSPLIT") ? atoi(getenv("DM_SKINNY_MSPLIT")) : 2;      // A/B switch: 0 one workgroup per strip, 1 32-row halves, 2 also 16-row quarters
 
 // Can a <= 64-row product with reduction length K take the LayerNorm+ELU prologue (and, for N % 32 == 0, the sampler
 // epilogue)?  Shape-only test: rssm.hip picks the fused or the unfused schedule of the T loop with it.
 bool dm_skinny_ln_ok(int M, int N, int K) {
-  return !g_skinny_disabled && !g_skinny_nofuse && M >= 1 && M <= 64 && K >= 16 && K <= SK_LN_MAXK && (K & 3) == 0 &&
+  return M >= 1 && M <= 64 && K >= 16 && K <= SK_LN_MAXK && (K & 3) == 0 &&
          (int64_t)N * K >= (int64_t)64 * 1024;
 }
 
@@ -539,14 +527,14 @@ int dm_gemm_skinny_try(const DmGemm& q, hipStream_t stream) {
   if (q.sm_logits) return dm_fail(DM_E_SHAPE, "skinny gemm: the softmax-backward epilogue exists in the pair launch only");
   const bool folded = q.eg_x || q.lnf_ps;      // folded LayerNorm backward (producer / consumer side): skinny-only epilogues
   if (folded) {
-    if (g_skinny_disabled || !skinny_ok(q, 64) || q.b_layout != 0 || q.ln_g || q.lnb_x)
+    if (!skinny_ok(q, 64) || q.b_layout != 0 || q.ln_g || q.lnb_x)
       return dm_fail(DM_E_SHAPE, "skinny gemm: the folded LayerNorm backward is built for plain <= 64-row skinny products (M=%d N=%d K=%d)", q.M, q.N, q.K);
     if (q.eg_x && (!q.eg_stats || !q.eg_gamma || !q.eg_beta || !q.eg_ps || (!q.eg_G && !q.eg_Gf)))
       return dm_fail(DM_E_SHAPE, "skinny gemm: folded LayerNorm backward, producer side: statistics, gamma, beta, an output for g and the strip sums are required");
     if (q.lnf_ps && (!q.lnf_stats || !q.lnf_xw || !q.lnf_cs || q.lnf_nps < 1))
       return dm_fail(DM_E_SHAPE, "skinny gemm: folded LayerNorm backward, consumer side: statistics, x B^T and the weights' k-sums are required");
   }
-  if (g_skinny_disabled || !skinny_ok(q, g_skinny_max_m)) return 0;
+  if (!skinny_ok(q, SK_MAX_M)) return 0;
   if (q.C_frag && q.M > 64) return 0;      // the tiled path reports the misuse
   // beyond one chunk it pays only for short reductions over small weight matrices (measured at M = 350: 1000x1024
   // 31.9 -> 24.8 us, 400x400 15.1 -> 8.7 us; 1800x1000 equal; 400x1624 18.2 -> 19.9 us)
@@ -560,8 +548,8 @@ int dm_gemm_skinny_try(const DmGemm& q, hipStream_t stream) {
   // 33..64 rows: two 32-row workgroups per strip instead of one 64-row one (half the matrix-pipe and operand work per
   // workgroup on the chain's critical path; the strip's weights are read twice, from L2) while both fit the chip
   const int nst = dm_cdiv(q.N, 16);
-  const bool quarters = g_skinny_msplit >= 2 && q.M > 16 && q.M <= 64 && dm_cdiv(q.M, 16) * nst <= 256;
-  const bool halves = !quarters && g_skinny_msplit && q.M > 32 && q.M <= 64 && 2 * nst <= 256;
+  const bool quarters = q.M > 16 && q.M <= 64 && dm_cdiv(q.M, 16) * nst <= 256;
+  const bool halves = !quarters && q.M > 32 && q.M <= 64 && 2 * nst <= 256;
   const dim3 grid((unsigned)nst, (unsigned)(quarters ? dm_cdiv(q.M, 16) : halves ? 2 : dm_cdiv(q.M, 64)));
   const dim3 blk(SK_WAVES * 64);
 #define SK_LAUNCH(BL_, MODE_, EPI_)                                                                                     \
@@ -591,7 +579,7 @@ int dm_gemm_pair_launch(const DmGemm& q0, const DmGemm& q1, void* ws, size_t ws_
   DM_REQUIRE(!q0.lnb_x && !(q1.ln_g && !q1.lnb_x) && !q0.gates && !q1.gates, DM_E_SHAPE,
              "gemm pair: built for a forward LayerNorm prologue on the first product or a backward one on the second");
   const bool fused = ln0 || lnb1;
-  if (!g_skinny_disabled && skinny_ok(q0, 64) && skinny_ok(q1, 64) && q0.b_layout == 0 && q1.b_layout == 0 &&
+  if (skinny_ok(q0, 64) && skinny_ok(q1, 64) && q0.b_layout == 0 && q1.b_layout == 0 &&
       (!ln0 || (q0.K <= SK_LN_MAXK && q0.ln_b)) &&
       (!lnb1 || (q1.K <= SK_LN_MAXK && q1.ln_g && q1.ln_b && q1.lnb_stats && (q1.lnb_ldx & 3) == 0 && ((uintptr_t)q1.lnb_x & 15) == 0))) {
     SkinnyPairArgs a;
@@ -603,8 +591,8 @@ int dm_gemm_pair_launch(const DmGemm& q0, const DmGemm& q1, void* ws, size_t ws_
     a.nb0 = dm_cdiv(q0.N, 16);
     a.nb = a.nb0 + dm_cdiv(q1.N, sm1 ? 32 : 16);
     const int mmax = q0.M > q1.M ? q0.M : q1.M;
-    const bool quarters = g_skinny_msplit >= 2 && mmax > 16 && dm_cdiv(mmax, 16) * a.nb <= 256;
-    const bool halves = !quarters && g_skinny_msplit && mmax > 32 && 2 * a.nb <= 256;
+    const bool quarters = mmax > 16 && dm_cdiv(mmax, 16) * a.nb <= 256;
+    const bool halves = !quarters && mmax > 32 && 2 * a.nb <= 256;
     const dim3 grid((unsigned)(quarters ? dm_cdiv(mmax, 16) * a.nb : halves ? 2 * a.nb : a.nb)), blk(SK_WAVES * 64);
 #define SKP_LAUNCH(M0_, M1_)                                                                                            \
   do {                                                                                                                  \
@@ -645,8 +633,8 @@ int dm_gemm_sample_launch(const DmGemm& q, const DmSample& sm, hipStream_t strea
   // row-split strips as in dm_gemm_skinny_try: every workgroup redoes the LayerNorm + ELU of ITS rows only, so quarters also
   // quarter that prologue (27 -> 1x us at 64 rows)
   const int nst = q.N / 32;
-  const bool quarters = g_skinny_msplit >= 2 && q.M > 16 && dm_cdiv(q.M, 16) * nst <= 256;
-  const bool halves = !quarters && g_skinny_msplit && q.M > 32 && 2 * nst <= 256;
+  const bool quarters = q.M > 16 && dm_cdiv(q.M, 16) * nst <= 256;
+  const bool halves = !quarters && q.M > 32 && 2 * nst <= 256;
   const dim3 grid((unsigned)nst, (unsigned)(quarters ? dm_cdiv(q.M, 16) : halves ? 2 : 1)), blk(SK_WAVES * 64);
   if (q.M <= 16 || quarters) hipLaunchKernelGGL((skinny_gemm_sample_kernel<1>), grid, blk, 0, stream, a);
   else if (q.M <= 32 || halves) hipLaunchKernelGGL((skinny_gemm_sample_kernel<2>), grid, blk, 0, stream, a);

@@ -2,7 +2,6 @@
 // Used by the reward / terminal decoders (decoders.py:257-319) and actor / critic / critic_target (a2c.py:37-39).
 // Contractions run on gemm.hip (MFMA); LayerNorm+ELU and the bias / gamma / beta column sums are row kernels.
 #include "common.h"
-#include <stdlib.h>
 
 struct MlpActs {
   float* xpre[DM_MAX_MLP_LAYERS];
@@ -141,13 +140,11 @@ int dm_mlp_fwd_launch(int rows, int in_dim, int hidden, int layers, int out_dim,
     // others contribute the sum of the weight rows their non-zeros name (x W^T = x_dense W_d^T + sum_e x_e W^T[e]);
     // for the DreamerV2 feature (600 dense + 32 of 1024) that is 63 % of the layer's flops replaced by a 32-row gather
     // (40 000 rows: 764 us -> 290 us + 135 us).  fp32 only: with bf16 operands the product is cheaper than the gather
-    // (measured: step +0.4 ms), DM_MLP_SPARSE_BF16=1 forces it there for tests.
-    static const int no_sparse = getenv("DM_MLP_NO_SPARSE") ? 1 : 0;         // A/B switch
-    static const int sparse_bf16 = getenv("DM_MLP_SPARSE_BF16") ? 1 : 0;
+    // (measured: step +0.4 ms).
     const float* addm = nullptr;
     int k0 = in_dim;
     const int dense = in_dim - sparse_cols;
-    if (ar.ok && sparse_cols > 0 && !no_sparse && (!dm_cur_precision() || sparse_bf16) && in_dim <= 4096 && (dense & 7) == 0 && dense >= 32 && (ldx & 3) == 0) {
+    if (ar.ok && sparse_cols > 0 && !dm_cur_precision() && in_dim <= 4096 && (dense & 7) == 0 && dense >= 32 && (ldx & 3) == 0) {
       float* g = ar.take((size_t)rows * hidden);
       float* w0t = ar.take((size_t)in_dim * hidden);
       if (ar.ok) {

@@ -29,7 +29,6 @@
 // the tiling (the 7-block wave: 102 + 3*25 groups x 28 MFMAs x 32 clk = 158 k cycles = 66 us in fp32).  Measured per
 // 2500-row call: 130 us fp32, 65 us bf16 (per-layer launches: 167 / 136).
 #include "common.h"
-#include <stdlib.h>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -449,20 +448,14 @@ __device__ __forceinline__ void chain_body(const ChainArgs& g, float* ybuf, floa
 // round-5 kernel's 465 registers had kept every other wave off its SIMDs.  The EXCL build claims the accumulator file up to
 // a255 (one dead write), so a wave owns its SIMD again; the multi-round launches (the 938-block head windows) take the shared
 // build, where a second block's MFMAs cover the first one's epilogue.
-// (DM_CHAIN_EXCL_AGPR, compile-time: the highest accumulator register the exclusive build claims.  255 = the whole file, nobody fits
-//  beside the wave; 127 / 191 leave room for one 128- / 96-register wave of another kernel - measured, profiles/r06_chain_exclusivity.txt)
-#ifndef DM_CHAIN_EXCL_AGPR
-#define DM_CHAIN_EXCL_AGPR 255
-#endif
-#define DM_STR2(x) #x
-#define DM_STR(x) DM_STR2(x)
+// (a255 = the whole file, nobody fits beside the wave; a127 / a191 leave room for one 128- / 96-register wave of another kernel -
+//  measured, profiles/r06_chain_exclusivity.txt)
 template <bool BF, int PACKED, bool EXCL>
 __global__ void __launch_bounds__(256, (PACKED && !EXCL) ? 2 : 1) mlp_chain_fwd_kernel(const ChainArgs g) {      // (the row-major A/B form keeps one block per CU)
   __shared__ __attribute__((aligned(16))) float ybuf[16 * CH_LD];      // the next layer's input block
   __shared__ float red[2][4][16];                                      // per-wave row partials: [0] sums, [1] centred squares
   __shared__ float outp[4][16][32];                                    // per-wave output-layer partials
-  if constexpr (EXCL) asm volatile("v_accvgpr_write_b32 a" DM_STR(DM_CHAIN_EXCL_AGPR) ", 0" ::: "a" DM_STR(DM_CHAIN_EXCL_AGPR));
-  DM_CHAIN_PRIO();
+  if constexpr (EXCL) asm volatile("v_accvgpr_write_b32 a255, 0" ::: "a255");
   chain_body<BF, PACKED>(g, ybuf, red, outp);
 }
 
@@ -521,14 +514,13 @@ __global__ void __launch_bounds__(256) mlp_chain_pack_kernel(const ChainPackArgs
 }
 
 // ---------------------------------------------------------------- host side ---------------------
-static const int g_chain_off = getenv("DM_MLP_NO_CHAIN") ? 1 : 0;       // A/B switch: keep the per-layer launches
 // A row block takes ~135 us however many there are (one CU walks all 1.13 M MACs per row: 66 us of MFMA issue plus the
 // weight stream's latency).  Alone, the per-layer form's ~13 launches win below ~1000 rows (350 rows: 95 us of kernels,
 // spread over all CUs by split-K); INSIDE the step their 12 dependent-launch gaps cost more than that: measured in round 5
 // at the 350 / 650 rows of the 8- / 4-way shards, one launch beats the 13 by 0.1 ms per step; round 6 measured the 300 rows
 // of a 6-column shard (ranks 2-7 of an 8-way split; `bench.py --emulate-world 8 --emulate-rank 7`, profiles/r06_chain_rows.txt).
-// The default sits just below that smallest measured size.  DM_CHAIN_MIN_ROWS / dm_mlp_chain_min_rows override.
-static int g_chain_min_rows = getenv("DM_CHAIN_MIN_ROWS") ? atoi(getenv("DM_CHAIN_MIN_ROWS")) : 256;
+// The default sits just below that smallest measured size.  dm_mlp_chain_min_rows overrides.
+static int g_chain_min_rows = 256;
 extern "C" int dm_mlp_chain_min_rows(int rows) {       // rows >= 1: set; returns the previous value
   const int prev = g_chain_min_rows;
   if (rows >= 1) g_chain_min_rows = rows;
@@ -536,11 +528,10 @@ extern "C" int dm_mlp_chain_min_rows(int rows) {       // rows >= 1: set; return
 }
 
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-static const int g_chain_nopack = getenv("DM_CHAIN_NO_PACK") ? 1 : 0;      // A/B switch
 
 bool dm_mlp_chain_ok(int rows, int in_dim, int hidden, int layers, int out_dim, const float* x, int ldx,
                      const dm_mlp_params* p) {
-  if (g_chain_off || hidden != CH_N || rows < 1 || rows < g_chain_min_rows || layers < 1 || layers > DM_MAX_MLP_LAYERS || out_dim < 1 || out_dim > 32)
+  if (hidden != CH_N || rows < 1 || rows < g_chain_min_rows || layers < 1 || layers > DM_MAX_MLP_LAYERS || out_dim < 1 || out_dim > 32)
     return false;
   if ((in_dim & 3) != 0 || in_dim < 4 || (ldx & 3) != 0 || !al16(x)) return false;
   for (int l = 0; l < layers; ++l)
@@ -551,9 +542,8 @@ bool dm_mlp_chain_ok(int rows, int in_dim, int hidden, int layers, int out_dim, 
 // fp32 calls only (with bf16 operands the product is cheaper than the gather, as measured for the row panels); the dense
 // part keeps the 16-byte operand loads
 bool dm_mlp_chain_sparse_ok(int in_dim, int sparse_cols) {
-  static const int no_sparse = getenv("DM_MLP_NO_SPARSE") ? 1 : 0;         // A/B switch (shared with the row-panel path)
   const int dense = in_dim - sparse_cols;
-  return !no_sparse && !g_chain_nopack && !dm_cur_precision() && sparse_cols > 0 && sparse_cols < in_dim && in_dim <= 4096 &&
+  return !dm_cur_precision() && sparse_cols > 0 && sparse_cols < in_dim && in_dim <= 4096 &&
          (dense & 7) == 0 && dense >= 32;
 }
 static size_t chain_pack_layer_floats(int K) { return (size_t)CH_NBLK * ((K + 31) / 32) * 512; }
@@ -599,9 +589,9 @@ int dm_mlp_chain_fwd_launch(int rows, int in_dim, int layers, int out_dim, const
     a.samp_u = sample->u; a.samp_onehot = sample->onehot; a.samp_ld = sample->ldo; a.samp_idx = sample->idx;
   }
   if (k0 == 0) k0 = in_dim;
-  DM_REQUIRE(k0 == in_dim || (add0 && wpack && !g_chain_nopack && k0 >= 4 && k0 < in_dim && (k0 & 3) == 0), DM_E_SHAPE,
+  DM_REQUIRE(k0 == in_dim || (add0 && wpack && k0 >= 4 && k0 < in_dim && (k0 & 3) == 0), DM_E_SHAPE,
              "mlp_chain: a sparse-tail layer 0 (k0=%d of %d) needs its addend and weights packed for k0", k0, in_dim);
-  if (wpack && !g_chain_nopack) {
+  if (wpack) {
     size_t off = 0;
     for (int l = 0; l < layers; ++l) {
       a.wp[l] = wpack + off;
@@ -625,8 +615,7 @@ int dm_mlp_chain_fwd_launch(int rows, int in_dim, int layers, int out_dim, const
   // packed copies are bf16 when the kernel multiplies in bf16 (dm_mlp_chain_pack_launch); all layers or none are packed
   const dim3 grid((unsigned)dm_cdiv(rows, 16)), blk(256);
   const bool packed = a.wp[0] != nullptr;
-  static const int excl_env = getenv("DM_CHAIN_EXCL") ? atoi(getenv("DM_CHAIN_EXCL")) : 1;      // A/B switch: 0 = the shared build everywhere
-  const bool excl = excl_env && grid.x <= 256;
+  const bool excl = grid.x <= 256;
 #define DM_CHAIN_LAUNCH(BF_, PK_)                                                                        \
   do {                                                                                                   \
     if (excl) hipLaunchKernelGGL((mlp_chain_fwd_kernel<BF_, PK_, true>), grid, blk, 0, st, a);          \

@@ -18,7 +18,6 @@
 // The k -> (mfma step, lane group) map is the skinny kernel's: step j of a 16-k group feeds k = 16g + 4q + j from lane
 // group q, for A and B alike.  fp32-input MFMA = exact fmaf chain, so results are fp32-class like gemm.hip's.
 #include "common.h"
-#include <stdlib.h>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -545,10 +544,10 @@ __global__ void __launch_bounds__(1024) panel_colsum_final_kernel(const PanelFin
 //  The 64-row panels below are 625 workgroups on 512 resident slots.  What bounds these kernels is that quantisation
 //  (DESIGN 7), not the fragment traffic.)
 // ---------------------------------------------------------------- host side ---------------------
-static const int g_panel_min_rows = getenv("DM_PANEL_MIN_ROWS") ? atoi(getenv("DM_PANEL_MIN_ROWS")) : 16384;
+constexpr int PANEL_MIN_ROWS = 16384;
 
 // The panel path serves hidden = 400 (the only width pydreamer's heads use: a2c.py:16, decoders.py:259,289).
-bool dm_panel_ok(int rows, int hidden) { return hidden == 400 && rows >= g_panel_min_rows; }
+bool dm_panel_ok(int rows, int hidden) { return hidden == 400 && rows >= PANEL_MIN_ROWS; }
 int dm_panel_count(int rows) { return dm_cdiv(rows, PANEL_BM); }
 
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }

@@ -11,14 +11,11 @@
 //  * reset masks (rssm.py:41,134-135) are applied forward by a tiny row-scale kernel (the masked states are saved
 //    for backward) and backward through the GEMM / GRU epilogues' row_zero option.
 #include "common.h"
-#include <stdlib.h>
 
 struct RssmActs {
   float *ea, *ee, *hin, *zin, *x1, *st1, *za, *gi, *gh, *x2, *st2, *pin, *x3, *st3, *prin;
   float *gs, *gst;      // LayerNorm GRU cells: pre-LayerNorm gate sums (N,3D) and their statistics (N,6 per stack layer)
 };
-// A/B switch (DM_FWD_LN_Z=0): the posterior launch chain's gather kernel normalises its rows itself (see ln_z in dm_rssm_sequence_fwd)
-static const int g_fwd_ln_z = getenv("DM_FWD_LN_Z") ? atoi(getenv("DM_FWD_LN_Z")) : 1;
 static inline int rssm_gru_kind(const dm_shape* s) { return (s->flags & DM_FLAG_GRU_MASK) >> DM_FLAG_GRU_SHIFT; }
 static inline int rssm_gru_layers(const dm_shape* s) {
   return 1 + ((s->flags & DM_FLAG_GRU_LAYERS_MASK) >> DM_FLAG_GRU_LAYERS_SHIFT);
@@ -231,22 +228,19 @@ extern "C" int dm_rssm_sequence_fwd(const dm_shape* s, const float* embed, const
              "rssm: the cell's three norms must be all LayerNorm or all NoNorm");
   const bool fuse_ln = normed && !stacked && !gauss && dm_skinny_ln_ok(B, 3 * D, Hd) && dm_skinny_ln_ok(B, ZP, Hd) &&
                        (ZP >= 64 * 1024 / Hd);
-  static const int no_fuse_sample = getenv("DM_RSSM_NO_FUSE_SAMPLE") ? 1 : 0;      // A/B switch
-  const bool fuse_sample = !no_fuse_sample && fuse_ln && C == 32 && (Z & 31) == 0 && (F & 3) == 0 && (D & 3) == 0 &&
+  const bool fuse_sample = fuse_ln && C == 32 && (Z & 31) == 0 && (F & 3) == 0 && (D & 3) == 0 &&
                            (((uintptr_t)feat | (uintptr_t)a.zin) & 15) == 0;
   // Fragment-major copies of the chain's <= 64-row operands (common.h dm_frag_off), written by the kernel that produces
   // each operand next to its ordinary copy and read by the product that consumes it: z_in -> x1 -> (gi | gh from h_in)
   // -> h -> x2 -> z.  One buffer per operand is enough (producer and consumer alternate in stream order).
-  static const int no_frag = getenv("DM_SKINNY_NO_FRAG") ? 1 : 0;          // A/B switch
   float *zinf = nullptr, *x1f = nullptr, *hinf = nullptr, *hf = nullptr, *x2f = nullptr;
   DmArena ar(ws, ws_bytes);
   ar.take(DM_SPLITK_FLOATS);
   // z_mlp of the sampled (one-hot) latent as a gather-sum over rows of z_mlp^T (dm_z_embed_launch): every step after the
   // first takes its z from the sampler, whose indices are at hand; the first step's z comes from the caller as a dense
   // vector and keeps the product.
-  static const int no_embed = getenv("DM_RSSM_NO_Z_EMBED") ? 1 : 0;        // A/B switch
   float* wzt = nullptr;
-  if (!no_embed && !gauss && idx && T > 1 && dm_z_embed_ok(Hd)) {
+  if (!gauss && idx && T > 1 && dm_z_embed_ok(Hd)) {
     const size_t mark = ar.off;
     float* w = ar.take((size_t)Z * Hd);
     if (ar.ok) {
@@ -256,7 +250,7 @@ extern "C" int dm_rssm_sequence_fwd(const dm_shape* s, const float* embed, const
       ar.off = mark; ar.ok = true;
     }
   }
-  if (!no_frag && fuse_sample && kind == 0 && B <= 64) {
+  if (fuse_sample && kind == 0 && B <= 64) {
     float* f0 = ar.take(dm_frag_floats(Z)); float* f1 = ar.take(dm_frag_floats(Hd)); float* f2 = ar.take(dm_frag_floats(D));
     float* f3 = ar.take(dm_frag_floats(D)); float* f4 = ar.take(dm_frag_floats(Hd));
     if (ar.ok) { zinf = f0; x1f = f1; hinf = f2; hf = f3; x2f = f4; }
@@ -293,7 +287,7 @@ extern "C" int dm_rssm_sequence_fwd(const dm_shape* s, const float* embed, const
     // x = z_mlp(z) + a_mlp(a) ; za = ELU(in_norm(x))                                   rssm.py:138-140
     // (ln_z: the gather kernel owns complete rows, so it also normalises them and the gate product below runs plain - the
     //  prologue form makes each of that product's 226 workgroups redo the LayerNorm + ELU of the whole operand)
-    const bool ln_z = fuse_ln && g_fwd_ln_z && wzt && t > 0 && x1f && !stacked && S <= 32;     // the row-per-workgroup form holds <= 32 groups (stoch_dim 64 / 96 take the branch below)
+    const bool ln_z = fuse_ln && wzt && t > 0 && x1f && !stacked && S <= 32;     // the row-per-workgroup form holds <= 32 groups (stoch_dim 64 / 96 take the branch below)
     if (ln_z) {
       DM_TRY(dm_z_embed_launch(B, Hd, S, C, idx + (r0 - B) * S, reset + r0, wzt, p[DM_RSSM_Z_B], a.ea + r0 * Hd, Hd,
                                nullptr, nullptr, a.x1 + r0 * Hd, Hd, nullptr, p[DM_RSSM_IN_G], p[DM_RSSM_IN_B], 1e-3f,
@@ -395,8 +389,8 @@ extern "C" int dm_rssm_sequence_fwd(const dm_shape* s, const float* embed, const
   return DM_OK;
 }
 
-// A/B switch of the BPTT launch schedule's folded LayerNorm backward (include/dreamer_hip.h dm_bptt_fold_enable; DM_BPTT_FOLD=0 in the environment)
-static int g_bptt_fold = getenv("DM_BPTT_FOLD") ? (atoi(getenv("DM_BPTT_FOLD")) ? 1 : 0) : 1;
+// A/B switch of the BPTT launch schedule's folded LayerNorm backward (include/dreamer_hip.h dm_bptt_fold_enable)
+static int g_bptt_fold = 1;
 extern "C" int dm_bptt_fold_enable(int on) {
   const int was = g_bptt_fold;
   if (on >= 0) g_bptt_fold = on ? 1 : 0;
@@ -509,8 +503,7 @@ extern "C" int dm_rssm_sequence_bwd(const dm_shape* s, const float* embed, const
     eps1 = ar.take((size_t)nstrip * 128);
     if (!ar.ok) { ar.off = mark; ar.ok = true; fold = false; }       // a small caller workspace keeps the prologue form
   }
-  static const int no_fold_sm = getenv("DM_BPTT_NO_FOLD_SM") ? 1 : 0;      // A/B switch
-  const bool fold_sm = fold && !gauss && C == 32 && Z == ZP && !no_fold_sm;
+  const bool fold_sm = fold && !gauss && C == 32 && Z == ZP;
   if (fold) {
     DM_TRY(dgrad(st, sk, skb, N, Hd, D, a.x2, Hd, p[DM_RSSM_POST_H_W], xw2, D, 0, nullptr));      // x2 W_post_h
     DM_TRY(dgrad(st, sk, skb, N, Hd, Z, a.x1, Hd, p[DM_RSSM_Z_W], xwz, Z, 0, nullptr));           // x1 W_z
@@ -519,8 +512,7 @@ extern "C" int dm_rssm_sequence_bwd(const dm_shape* s, const float* embed, const
   }
   // fragment-major copies (common.h dm_frag_off) of the two K = 3D operands of a step, dgi and dgh: written by the gates
   // backward epilogue, read by the two products that follow it
-  static const int no_frag = getenv("DM_SKINNY_NO_FRAG") ? 1 : 0;
-  float* dgif = (fuse_b && !no_frag && B <= 64) ? ar.take(dm_frag_floats(3 * D)) : nullptr;
+  float* dgif = (fuse_b && B <= 64) ? ar.take(dm_frag_floats(3 * D)) : nullptr;
   float* dghf = dgif ? ar.take(dm_frag_floats(3 * D)) : nullptr;
   float* dpinf = dgif ? ar.take(dm_frag_floats(Hd)) : nullptr;      // ... and of dpin, dza (written by the epilogue of the
   float* dzaf = dgif ? ar.take(dm_frag_floats(Hd)) : nullptr;       // product that makes them)
@@ -773,7 +765,7 @@ struct DmRolloutMarks {
   }
 };
 
-static int g_rollout_fuse_act = getenv("DM_ROLLOUT_NO_FUSE_ACT") ? 0 : 1;
+static int g_rollout_fuse_act = 1;
 // 1 / 0: the rollout's one-hot action draw in the output stage of the whole-MLP actor kernel / as its own launch; -1 queries.
 extern "C" int dm_rollout_fuse_act_enable(int on) {
   if (on >= 0) g_rollout_fuse_act = on ? 1 : 0;
@@ -845,10 +837,9 @@ extern "C" int dm_dream_rollout(const dm_shape* s, int M, const float* start, co
   }
   // steps 1.. of the rollout read the z the prior sampler of the step before drew: z_mlp + in_norm + ELU become one
   // gather-sum launch over z_mlp^T (dm_z_embed_launch) instead of a (M x Hd x Z) product and a LayerNorm launch
-  static const int no_embed = getenv("DM_RSSM_NO_Z_EMBED") ? 1 : 0;        // A/B switch
   float *wzt = nullptr, *wat = nullptr;
   int32_t *pidx = nullptr, *aidx = nullptr;
-  if (!no_embed && C != 0 && H > 1 && dm_z_embed_ok(Hd)) {
+  if (C != 0 && H > 1 && dm_z_embed_ok(Hd)) {
     const size_t mark = ar.off;
     float* w = ar.take((size_t)Z * Hd);
     float* w2 = ar.take((size_t)A * Hd);
@@ -906,7 +897,7 @@ extern "C" int dm_dream_rollout(const dm_shape* s, int M, const float* start, co
     }
     const int asp = actor_add0 ? Z : 0;
     int32_t* ai = act_idx ? act_idx + (size_t)i * M : aidx;       // the sampled action's index (scratch if the caller wants none)
-    // one-hot actors on the whole-MLP kernel: the action draw rides in that kernel's output stage (round 6; DM_ROLLOUT_NO_FUSE_ACT=1
+    // one-hot actors on the whole-MLP kernel: the action draw rides in that kernel's output stage (round 6; dm_rollout_fuse_act_enable(0)
     // keeps the stand-alone sampler launch - same rule, same operation order, bit-identical draws)
     const bool fuse_act = adist == 0 && actor_wpack && g_rollout_fuse_act;
     const DmChainSample samp = {u_act + (size_t)i * M, act, A, ai};

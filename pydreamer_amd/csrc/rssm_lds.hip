@@ -758,7 +758,7 @@ struct RlPlan {
   int wz_global;
 };
 
-int g_rssm_lds = getenv("DM_RSSM_LDS") ? atoi(getenv("DM_RSSM_LDS")) : 1;
+int g_rssm_lds = 1;
 int g_cus = -1, g_lds_max = -1;
 unsigned* g_host_err = nullptr;      // mapped pinned word
 unsigned* g_host_err_dev = nullptr;
@@ -846,15 +846,9 @@ int rl_launch_exclusive(const void* fn, unsigned grid, void** args, size_t lds_b
   // Co-residency of the whole grid is CHECKED, not assumed: rl_raise_lds() asks the occupancy API for >= 1 workgroup of this
   // variant per CU at the LDS size it is launched with, and the grid never exceeds the CU count (rl_device_ok); the spin loops
   // are bounded.  A cooperative launch (hipLaunchCooperativeKernel: the runtime validates the same bound) was measured and is
-  // NOT the default: it drains the other streams' queues around the kernel - the 25-column shard goes from 19.2 to 25.2 ms
-  // per step, 13 / 7 columns +0.15 ms (profiles/r05_lds_coop.txt).  DM_RSSM_LDS_COOP=1 selects it.
-  static const int coop = getenv("DM_RSSM_LDS_COOP") ? atoi(getenv("DM_RSSM_LDS_COOP")) : 0;
-  bool launched = false;
-  if (coop && !capturing) {
-    if (hipLaunchCooperativeKernel(fn, dim3(grid), dim3(RL_THREADS), args, (unsigned)lds_bytes, st) == hipSuccess) launched = true;
-    else (void)hipGetLastError();
-  }
-  if (!launched && hipLaunchKernel(fn, dim3(grid), dim3(RL_THREADS), args, lds_bytes, st) != hipSuccess)
+  // not built: it drains the other streams' queues around the kernel - the 25-column shard goes from 19.2 to 25.2 ms
+  // per step, 13 / 7 columns +0.15 ms (profiles/r05_lds_coop.txt).
+  if (hipLaunchKernel(fn, dim3(grid), dim3(RL_THREADS), args, lds_bytes, st) != hipSuccess)
     return dm_fail(DM_E_HIP, "rssm_lds: launch failed: %s", hipGetErrorString(hipGetLastError()));
   if (!capturing && hipEventRecord(g_chip_lease, st) != hipSuccess) (void)hipGetLastError();
   return DM_OK;
@@ -917,11 +911,11 @@ extern "C" int dm_rssm_lds_gave_up(void) { return g_gave_up; }
 // per consuming workgroup (rssm.hip ln_z, gemm_skinny.hip row-split strips): T = 50, B = 50 2.15 vs 2.8-2.9 ms alone, the
 // step 34.26 vs 34.64 ms (bf16 19.71 vs 20.21); at 25 / 13 / 7 rows the persistent kernel wins inside the step (19.69 vs 20.30,
 // 13.53 vs 14.41, 9.84 vs 10.84 ms; profiles/r04_bench_fwdchain.txt).  Switch level 2 (tests, microbenchmarks) lifts the cap.
-static const int g_rssm_lds_max_b = getenv("DM_RSSM_LDS_MAX_B") ? atoi(getenv("DM_RSSM_LDS_MAX_B")) : 32;
+constexpr int RL_MAX_B = 32;
 bool dm_rssm_lds_ok(int B, int D, int Hd, int S, int C) {
   RlPlan p;
   // (once a persistent kernel has given up - dm_rssm_lds_status - every later call takes the launch chain instead of failing)
-  return g_rssm_lds && dm_rssm_lds_status() == 0 && g_gave_up == 0 && (B <= g_rssm_lds_max_b || g_rssm_lds >= 2) && rl_plan(B, D, Hd, S, C, &p) &&
+  return g_rssm_lds && dm_rssm_lds_status() == 0 && g_gave_up == 0 && (B <= RL_MAX_B || g_rssm_lds >= 2) && rl_plan(B, D, Hd, S, C, &p) &&
          rl_device_ok(p.G, p.lds_bytes) && rl_fwd_ready(p.rl);
 }
 size_t dm_rssm_lds_ws_floats(int B, int D, int Hd, int S, int C, int steps) {

@@ -14,7 +14,6 @@ probe_model='none', no vecobs / reward_input.
 """
 import contextlib
 import ctypes
-import os
 import math
 
 import torch
@@ -447,9 +446,8 @@ def _finish_backward(owner, grads, flat, direct, grad_loss):
     return tuple(None for _ in grads) if direct else tuple(grads)
 
 
-_HEADS_EARLY = os.environ.get('DM_HEADS_EARLY', '1') != '0'    # A/B switch: 0 runs the heads over the imagined states behind the rollout only
-_WGRAD_SIDE_DP = os.environ.get('DM_WGRAD_SIDE_DP', '1') != '0'    # A/B switch: 0 = no side stream under data parallelism (rounds 3-5)
-_WGRAD_SIDE = os.environ.get('DM_WGRAD_SIDE', '1') != '0'      # A/B switch: 0 keeps every weight gradient on the caller's stream
+_HEADS_EARLY = True     # A/B switch: False runs the heads over the imagined states behind the rollout only
+_WGRAD_SIDE = True      # A/B switch: False keeps every weight gradient on the caller's stream
 
 
 def _warn_if_communicator_exists():
@@ -495,17 +493,16 @@ class _Overlap:
         # Every stream of the step gets one command NOW (round 6): a HIP stream takes its hardware queue when it first gets work, and
         # which streams later SHARE a queue depends on that order - a communicator created before these streams had run anything
         # cost the step +13 ms, a communicator that appeared mid-step +6 ms (profiles/r06_force_dp.txt).
-        if os.environ.get('DM_STREAM_PREBIND', '1') != '0':
-            with torch.cuda.device(device):
-                for st in (self.s_wm, self.s_ac):
-                    with torch.cuda.stream(st):
-                        torch.zeros(64, device=device)
-                if _WGRAD_SIDE:
-                    try:
-                        H.call('dm_wgrad_side_touch')
-                    except H.DreamerHipError:       # an optimisation only (the library owns ONE side stream, on the device that used it first)
-                        pass
-                torch.cuda.synchronize(device)
+        with torch.cuda.device(device):
+            for st in (self.s_wm, self.s_ac):
+                with torch.cuda.stream(st):
+                    torch.zeros(64, device=device)
+            if _WGRAD_SIDE:
+                try:
+                    H.call('dm_wgrad_side_touch')
+                except H.DreamerHipError:       # an optimisation only (the library owns ONE side stream, on the device that used it first)
+                    pass
+            torch.cuda.synchronize(device)
         self.ws_wm = None
         self.ws_ac = None
         # The HIP runtime needs ~6 us of host time per kernel launch and a step is ~1800 launches; at small per-GPU
@@ -1015,9 +1012,8 @@ class WorldModel(_Params):
         # dm_wgrad_side_arm).  The encoder backward is not deferred (it is the tail: there is nothing left to hide behind).
         # (measured: no gain on a 7-column shard, -1.1 ms at 25 columns.  Rounds 3-5 switched it off under data parallelism, unmeasured;
         #  round 6 measured it over a one-rank RCCL group: off costs +0.9 ... +1.2 ms at 25 / 50 columns, on costs nothing beside the
-        #  all-reduce - profiles/r06_force_dp.txt run K.  DM_WGRAD_SIDE_DP=0 restores the old behaviour.)
-        dp_on = getattr(getattr(self, '_fused', None), 'dp', None) is not None and not _WGRAD_SIDE_DP
-        side = defer_wgrad and _WGRAD_SIDE and B * I >= 16 and not dp_on and not torch.cuda.is_current_stream_capturing()
+        #  all-reduce - profiles/r06_force_dp.txt run K: it stays on there.)
+        side = defer_wgrad and _WGRAD_SIDE and B * I >= 16 and not torch.cuda.is_current_stream_capturing()
         ws_dec = ws_enc = ws
         if side:
             need = H.workspace_bytes(shp)
@@ -1353,8 +1349,8 @@ class Dreamer(nn.Module):
                 m.precision = int(self.amp)
         self._overlap = None
         self.overlap_backward = True      # pre-launch the three backward passes on side streams (see _Overlap)
-        # the world-model forward's tail (decoder, heads, losses) on the world-model stream: WorldModel._forward (A/B: DM_WM_TAIL=0)
-        self.wm_tail_on_side = os.environ.get('DM_WM_TAIL', '1') != '0'
+        # the world-model forward's tail (decoder, heads, losses) on the world-model stream: WorldModel._forward (A/B: set False)
+        self.wm_tail_on_side = True
 
     # ---- optimizers (dreamer.py:60-87)
     def param_groups(self):

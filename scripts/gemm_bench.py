@@ -48,7 +48,9 @@ def main():
     ap.add_argument('--only', default='')       # comma-separated indices into SHAPES
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--bf16', action='store_true')       # bf16 operands / fp32 accumulate (conf.amp)
+    ap.add_argument('--dma', type=int, default=-1)       # dm_gemm_dma_enable level (0 off, 1 default, 2 also short reductions)
     args = ap.parse_args()
+    hip.lib().dm_gemm_dma_enable(args.dma)
     gflags = hip.DM_GEMM_BF16 if args.bf16 else 0
     shapes = [SHAPES[int(i)] for i in args.only.split(',')] if args.only else SHAPES
     ws = torch.empty(256 << 20, dtype=torch.uint8, device='cuda')

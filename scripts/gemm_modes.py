@@ -1,5 +1,5 @@
 """GPU microbenchmark (not a test): dm_gemm_f32 on the step's shapes - time AND error against an fp64 product, for the
-arithmetic mode the process runs in (default: fp32 MFMA; --bf16: bf16 operands; DM_GEMM_NO_PIPE=1: the single-stage loop instead of the software-pipelined kernel).  One JSON line per shape; profiles/r03_gemm_modes.txt keeps the
+arithmetic mode the process runs in (default: fp32 MFMA; --bf16: bf16 operands).  One JSON line per shape; profiles/r03_gemm_modes.txt keeps the
 round-3 table (which also has the split-bf16 mode, removed in round 4)."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

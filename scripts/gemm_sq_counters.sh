@@ -9,9 +9,9 @@ export TMPDIR=/tmp
 REPO=$PWD
 cd /tmp
 for D in 1 0; do
-  DM_GEMM_DMA=$D rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES \
-    --kernel-trace --output-format csv -d /tmp/prof_sq_$D -o p -- python $REPO/scripts/gemm_bench.py --only 0,9 --reps 4 > $OUT/sq_$D.log 2>&1
-  DM_GEMM_DMA=$D rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d /tmp/prof_grbm_$D -o p -- python $REPO/scripts/gemm_bench.py --only 0,9 --reps 4 > $OUT/grbm_$D.log 2>&1
+  rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES \
+    --kernel-trace --output-format csv -d /tmp/prof_sq_$D -o p -- python $REPO/scripts/gemm_bench.py --only 0,9 --reps 4 --dma $D > $OUT/sq_$D.log 2>&1
+  rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d /tmp/prof_grbm_$D -o p -- python $REPO/scripts/gemm_bench.py --only 0,9 --reps 4 --dma $D > $OUT/grbm_$D.log 2>&1
 done
 python - <<PY > $OUT/${TAG}_gemm_sq_counters.txt
 import csv, glob, collections
@@ -31,7 +31,7 @@ for d in (1, 0):
             if 'gemm_' not in k or 'splitk' in k: continue
             dur = float(r['End_Timestamp']) - float(r['Start_Timestamp'])
             c = clk.setdefault(k, [0.0, 0.0, 0]); c[0] += float(r['Counter_Value']); c[1] += dur; c[2] += 1
-    print(f'--- DM_GEMM_DMA={d}')
+    print(f'--- dm_gemm_dma_enable({d})')
     for k, v in agg.items():
         w = v.get('SQ_WAVE_CYCLES', 0) or 1
         n = cnt[(k, 'SQ_WAVE_CYCLES')]

@@ -205,7 +205,7 @@ def test_mlp_head_chain_fwd_bwd(hip, rows, in_dim, out_dim, layers):
     (csrc/mlp_chain.hip: 16-row blocks, activations in LDS between layers, K split over the 4 waves).  Ragged last block,
     a K that is not a multiple of 16 (1624 = 101.5 groups), 1..4 layers, a single row.  The saved activations must be
     what the per-layer backward expects (gradients checked through dm_mlp_head_bwd); the acts-free call gives identical
-    outputs; DM_MLP_NO_CHAIN=1 is the A/B switch back to GEMM + LayerNorm launches."""
+    outputs; dm_mlp_chain_min_rows is the A/B switch back to GEMM + LayerNorm launches."""
     from pydreamer_amd.models import MLP
     prev = hip.lib().dm_mlp_chain_min_rows(1)            # the production threshold is 256 rows
     try:
@@ -1340,7 +1340,7 @@ def test_early_head_window_is_bit_identical(hip):
     """The heads over the imagined states run as two row windows (ActorCritic.split_steps); in the training step the first
     one is issued on the actor-critic stream behind a progress mark of the rollout (dm_dream_rollout_marks) while the
     rollout finishes.  Same windows and kernels on another stream: losses, gradients and updated parameters are
-    bit-identical to issuing both windows behind the rollout (DM_HEADS_EARLY=0) and to the plain single-stream order
+    bit-identical to issuing both windows behind the rollout (models._HEADS_EARLY = False) and to the plain single-stream order
     (overlap_backward=False).  imag_horizon = 9: 10 imagined steps, windows [0, 6) and [6, 10)."""
     from pydreamer_amd import models as M
     oconf = O.tiny_conf(imag_horizon=9)

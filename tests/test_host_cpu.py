@@ -262,18 +262,32 @@ def test_graft_entry_build_passes():
 
 def test_runtime_switch_defaults():
     """Library-wide switches that change WHICH kernels run (never what they compute): the bf16-storage operand path is on, the
-    LDS-weight-stationary persistent posterior chain is on (where the shape qualifies) unless the environment says otherwise."""
+    LDS-weight-stationary persistent posterior chain is on (where the shape qualifies); the environment has no say in it."""
     lib = hip.lib()
-    if not any(os.environ.get(k) for k in ('DM_BF16_NO_TWINS', 'DM_RSSM_LDS')):
-        assert lib.dm_bf16_twins_enable(-1) == 1
-        assert lib.dm_rssm_lds_enable(-1) == 1
-        assert lib.dm_bptt_fold_enable(-1) == 1 or os.environ.get('DM_BPTT_FOLD')
+    assert lib.dm_bf16_twins_enable(-1) == 1
+    assert lib.dm_rssm_lds_enable(-1) == 1
+    assert lib.dm_bptt_fold_enable(-1) == 1
     assert lib.dm_rssm_lds_status() == 0 and lib.dm_rssm_lds_status_ack() == 0 and lib.dm_rssm_lds_gave_up() == 0
     assert lib.dm_bf16_twins_enable(0) == 0 and lib.dm_bf16_twins_enable(1) == 1
-    if not os.environ.get('DM_ROLLOUT_NO_FUSE_ACT'):      # round 6: the rollout's action draw rides in the actor kernel by default
-        assert lib.dm_rollout_fuse_act_enable(-1) == 1 and lib.dm_rollout_fuse_act_enable(0) == 0 and lib.dm_rollout_fuse_act_enable(1) == 1
+    # round 6: the rollout's action draw rides in the actor kernel by default
+    assert lib.dm_rollout_fuse_act_enable(-1) == 1 and lib.dm_rollout_fuse_act_enable(0) == 0 and lib.dm_rollout_fuse_act_enable(1) == 1
     assert lib.dm_gemm_dma_enable(-1) == 1 and lib.dm_gemm_dma_enable(0) == 0 and lib.dm_gemm_dma_enable(1) == 1
     assert lib.dm_dec_l4_bwd_direct_enable(-1) == 1 and lib.dm_dec_l4_bwd_direct_enable(0) == 0 and lib.dm_dec_l4_bwd_direct_enable(1) == 1
+
+
+def test_environment_inputs_are_the_three_kept():
+    """Dispatch depends on the shape alone: the package reads DM_LIB_PATH (which build to load) and DM_GEMM_TILE / DM_GEMM_SPLIT (the
+    tile-sweep tools' forced candidate), and no other DM_* variable."""
+    names = set()
+    for top in ('pydreamer_amd', 'include'):
+        for d, _, files in os.walk(os.path.join(ROOT, top)):
+            for f in files:
+                if f.endswith(('.py', '.hip', '.h')):
+                    src = open(os.path.join(d, f)).read()
+                    assert not re.search(r'getenv\s*\(\s*[^"\s]', src), f      # a computed name would escape the pattern below
+                    names |= set(re.findall(r'(?:getenv\s*\(|environ(?:\.get\s*\(|\.setdefault\s*\(|\s*\[))\s*[\'"](DM_\w+)', src))
+                    assert 'DM_CHAIN_SETPRIO' not in src and 'DM_SKINNY_LDS_PAD' not in src, f
+    assert names == {'DM_LIB_PATH', 'DM_GEMM_TILE', 'DM_GEMM_SPLIT'}, names
 
 
 def test_scheduling_switches_and_windows():
@@ -282,8 +296,7 @@ def test_scheduling_switches_and_windows():
     joining / disarming the side stream with nothing deferred is a no-op that needs no device; rollout marks are validated."""
     import ctypes
     from pydreamer_amd import models as M
-    if not any(os.environ.get(k) for k in ('DM_WGRAD_SIDE', 'DM_HEADS_EARLY')):
-        assert M._WGRAD_SIDE and M._HEADS_EARLY
+    assert M._WGRAD_SIDE is True and M._HEADS_EARLY is True
     S = M.ActorCritic.split_steps
     assert [S(j) for j in (2, 6, 8, 9, 10, 16, 50)] == [2, 6, 8, 5, 6, 10, 31]      # J < 9: one window; else 5/8 of the steps first
     assert all(0 < S(j) <= j for j in range(1, 200))
