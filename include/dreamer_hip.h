@@ -293,6 +293,11 @@ int dm_mlp_head_bwd(int rows, int in_dim, int hidden, int layers, int out_dim,
 int dm_head_loss(int kind, int rows, const float* out, const float* target, float scale, float loss_const,
                  float* loss, float* dout, float* mean_out, void* stream);
 
+/* the same for a DenseNormalDecoder with out_dim = V > 1 (decoders.py:295-304, Independent(Normal, 1): the vecobs decoder):
+ * out / target / dout / mean_out are (rows,V); loss[r] = 0.5 * sum_v (mu-y)^2 + V * loss_const; dout = scale * (mu-y). */
+int dm_head_loss_normal_nd(int rows, int V, const float* out, const float* target, float scale, float loss_const,
+                           float* loss, float* dout, float* mean_out, void* stream);
+
 /* uint8 ingest (preprocessing.py:21-29 to_image): src (n, h*w, c) uint8 HWC -> dst (n, c, h*w) float32,
  * x/255 - 0.5.  Lets the trainer hand the replay's native uint8 frames to training_step(). */
 int dm_preprocess_image_u8(int64_t n, int hw, int c, const uint8_t* src, float* dst, void* stream);
@@ -305,6 +310,22 @@ int dm_conv_encoder_fwd(const dm_shape* shp, const float* image /* (N,ch,64,64) 
                         float* acts, float* embed /* (N,E) torch (c,y,x) order */, void* ws, size_t ws_bytes, void* stream);
 int dm_conv_encoder_bwd(const dm_shape* shp, const float* image, const dm_conv_params* p, const float* acts,
                         const float* dembed, const dm_conv_grads* g, void* ws, size_t ws_bytes, void* stream);
+/* The encoder with a leading dimension on embed / dembed (encoders.py:64-68: the vecobs encoder's output sits behind the image
+ * embedding in the same buffer), and with reward_input when reward and terminal are both non-null (both null: the plain
+ * 3-channel first layer).
+ * reward_input (encoders.py:52-59): the reward and the terminal flag, reward / terminal (N,), enter the encoder as two more
+ * input planes, each constant over its frame; w[0] is (d,5,4,4).  The first Conv2d has no padding, so a plane adds
+ * r_n * sum_taps W[o,3] + t_n * sum_taps W[o,4] to every output pixel of frame n: the 5-channel image is never written, the
+ * direct layer-1 kernels keep reading the 3-channel frame (float or uint8) and start from a per-frame bias table; the planes'
+ * weight gradient, the same for all 16 taps, and the bias gradient come from one frame-weighted column sum over the layer's
+ * output gradient.  cnn_depth in {8,16,32,48,64}, img_ch = 3.  ld_embed / ld_dembed >= 32 * cnn_depth: leading dimension
+ * of embed / dembed (encoders.py:64-68 concatenates other encoders' outputs behind the image embedding); shp->E is not read. */
+int dm_conv_encoder_fwd_planes(const dm_shape* shp, const float* image, const dm_conv_params* p, const float* reward,
+                               const float* terminal, float* acts, float* embed, int ld_embed, void* ws, size_t ws_bytes,
+                               void* stream);
+int dm_conv_encoder_bwd_planes(const dm_shape* shp, const float* image, const dm_conv_params* p, const float* reward,
+                               const float* terminal, const float* acts, const float* dembed, int ld_dembed,
+                               const dm_conv_grads* g, void* ws, size_t ws_bytes, void* stream);
 
 /* ConvDecoder + MSE (decoders.py:111-180): Linear F->32d, 4 x ConvTranspose2d (k 5,5,6,6; s2), ELU x3.
  * w[0],b[0] = Linear; w[1..4]: (Cin,Cout,k,k) torch layout.  loss_image[n] = 0.5*sum (pred-target)^2. */

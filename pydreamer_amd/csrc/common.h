@@ -277,6 +277,13 @@ int dm_enc_l1_fwd_launch(int frames, int d, int u8, const void* image, const flo
 size_t dm_enc_l1_wgrad_part_floats(int frames, int d);
 int dm_enc_l1_wgrad_launch(int frames, int d, int u8, const void* image, const float* G, float* part, float* dW, void* ws,
                            size_t ws_bytes, hipStream_t st);
+// reward_input (two frame-constant planes folded into layer 1, conv_direct.hip): w5 is the (d, 5, 4, 4) weight
+int dm_enc_l1_fwd_planes_launch(int frames, int d, int u8, const void* image, const float* w5, const float* bias,
+                                const float* reward, const float* terminal, float* wt, float* fb, float* y,
+                                unsigned short* y_h, hipStream_t st);
+size_t dm_enc_l1_planes_part_floats(int frames, int d);
+int dm_enc_l1_planes_bwd_launch(int frames, int d, const float* G, const float* reward, const float* terminal,
+                                const float* dw3, float* part, float* db, float* dW5, hipStream_t st);
 bool dm_dec_l4_direct_ok(int ch, int d, int hs, int k);
 size_t dm_dec_l4_w4_floats(int d);
 int dm_dec_l4_fwd_launch(int frames, int d, const float* x, const float* w, const float* bias, float* w4, float* out,

@@ -493,13 +493,34 @@ __global__ void __launch_bounds__(256) nhwc_to_chw_flat_kernel(size_t n, int hw,
   }
 }
 
-extern "C" int dm_conv_encoder_fwd(const dm_shape* shp, const float* image, const dm_conv_params* p, float* acts,
-                                   float* embed, void* ws, size_t ws_bytes, void* stream) {
-  DM_REQUIRE(shp && image && p && acts && embed && ws, DM_E_NULL, "conv_encoder_fwd: null pointer");
+// the same with a leading dimension on the torch side: row i of it starts at i * ld (ld >= hw * c)
+__global__ void __launch_bounds__(256) nhwc_to_chw_flat_ld_kernel(size_t n, int hw, int c, const float* __restrict__ src,
+                                                                  float* __restrict__ dst, int ld, int to_chw) {
+  const size_t total = n * hw * c;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+    const size_t i = e / ((size_t)hw * c);
+    const int rem = (int)(e % ((size_t)hw * c));
+    const int pix = rem / c, cc = rem % c;        // e indexes the NHWC side
+    if (to_chw) dst[i * ld + (size_t)cc * hw + pix] = src[e];
+    else dst[e] = src[i * ld + (size_t)cc * hw + pix];
+  }
+}
+
+// reward / terminal (N,): non-null = reward_input, p->w[0] is (d, 5, 4, 4) and the two planes are folded into layer 1
+// (conv_direct.hip); ld: leading dimension of `embed` (the caller may keep other encoders' outputs behind the image embedding)
+static int conv_encoder_fwd_impl(const dm_shape* shp, const float* image, const dm_conv_params* p, float* acts, float* embed,
+                                 int ld, const float* reward, const float* terminal, void* ws, size_t ws_bytes, void* stream) {
   DmPrecisionScope prec(shp->flags & DM_FLAG_BF16);
   EncGeom g(shp);
-  DM_REQUIRE(g.valid(shp), DM_E_SHAPE, "conv_encoder: unsupported geometry (img=%d, E=%d, depth=%d)", shp->img, shp->E,
-             shp->cnn_depth);
+  const bool planes = reward != nullptr;
+  if (planes) {
+    DM_REQUIRE(shp->img == 64 && g.hs[3] == 2 && g.direct0 && ld >= 32 * g.d, DM_E_SHAPE,
+               "conv_encoder planes: built for 3 x 64 x 64 frames and cnn_depth in {8,16,32,48,64} (img=%d, ch=%d, depth=%d, ld=%d)",
+               shp->img, shp->img_ch, shp->cnn_depth, ld);
+  } else {
+    DM_REQUIRE(g.valid(shp) && ld >= 32 * g.d, DM_E_SHAPE, "conv_encoder: unsupported geometry (img=%d, E=%d, depth=%d, ld=%d)",
+               shp->img, shp->E, shp->cnn_depth, ld);
+  }
   hipStream_t st = (hipStream_t)stream;
   EncActs a;
   enc_carve(g, acts, (size_t)1 << 60, &a);
@@ -522,9 +543,14 @@ extern "C" int dm_conv_encoder_fwd(const dm_shape* shp, const float* image, cons
       DmArena ar(ws, ws_bytes);
       ar.take(DM_SPLITK_FLOATS);
       float* wt = ar.take((size_t)48 * g.d);
+      float* fb = ar.take(planes ? (size_t)g.N * g.d : 0);
       DM_REQUIRE(ar.ok, DM_E_WORKSPACE, "conv_encoder_fwd: workspace too small for the layer-1 weights");
       unsigned short* y0h = dm_twin_of(a.y[0], false);
-      DM_TRY(dm_enc_l1_fwd_launch(g.N, g.d, shape_u8(shp) ? 1 : 0, image, p->w[0], p->b[0], wt, a.y[0], y0h, st));
+      if (planes)
+        DM_TRY(dm_enc_l1_fwd_planes_launch(g.N, g.d, shape_u8(shp) ? 1 : 0, image, p->w[0], p->b[0], reward, terminal, wt, fb,
+                                           a.y[0], y0h, st));
+      else
+        DM_TRY(dm_enc_l1_fwd_launch(g.N, g.d, shape_u8(shp) ? 1 : 0, image, p->w[0], p->b[0], wt, a.y[0], y0h, st));
       if (y0h) dm_twin_mark(a.y[0]);
       continue;
     }
@@ -553,17 +579,39 @@ extern "C" int dm_conv_encoder_fwd(const dm_shape* shp, const float* image, cons
     DM_TRY(dm_gemm_launch(q, ws, DM_SPLITK_FLOATS * sizeof(float), st));
   }
   const size_t tot = (size_t)g.N * 4 * g.cout[3];
-  hipLaunchKernelGGL(nhwc_to_chw_flat_kernel, dim3(grid_for(tot)), dim3(256), 0, st, (size_t)g.N, 4, g.cout[3], a.y[3], embed, 1);
+  if (ld == 4 * g.cout[3])
+    hipLaunchKernelGGL(nhwc_to_chw_flat_kernel, dim3(grid_for(tot)), dim3(256), 0, st, (size_t)g.N, 4, g.cout[3], a.y[3], embed, 1);
+  else
+    hipLaunchKernelGGL(nhwc_to_chw_flat_ld_kernel, dim3(grid_for(tot)), dim3(256), 0, st, (size_t)g.N, 4, g.cout[3], a.y[3], embed,
+                       ld, 1);
   DM_LAUNCH_CHECK();
   return DM_OK;
 }
+extern "C" int dm_conv_encoder_fwd(const dm_shape* shp, const float* image, const dm_conv_params* p, float* acts,
+                                   float* embed, void* ws, size_t ws_bytes, void* stream) {
+  DM_REQUIRE(shp && image && p && acts && embed && ws, DM_E_NULL, "conv_encoder_fwd: null pointer");
+  return conv_encoder_fwd_impl(shp, image, p, acts, embed, 32 * shp->cnn_depth, nullptr, nullptr, ws, ws_bytes, stream);
+}
+extern "C" int dm_conv_encoder_fwd_planes(const dm_shape* shp, const float* image, const dm_conv_params* p,
+                                          const float* reward, const float* terminal, float* acts, float* embed, int ld_embed,
+                                          void* ws, size_t ws_bytes, void* stream) {
+  DM_REQUIRE(shp && image && p && acts && embed && ws && !reward == !terminal, DM_E_NULL, "conv_encoder_fwd_planes: null pointer");
+  return conv_encoder_fwd_impl(shp, image, p, acts, embed, ld_embed, reward, terminal, ws, ws_bytes, stream);
+}
 
-extern "C" int dm_conv_encoder_bwd(const dm_shape* shp, const float* image, const dm_conv_params* p, const float* acts,
-                                   const float* dembed, const dm_conv_grads* gr, void* ws, size_t ws_bytes, void* stream) {
-  DM_REQUIRE(shp && p && acts && dembed && gr && ws, DM_E_NULL, "conv_encoder_bwd: null pointer");
+static int conv_encoder_bwd_impl(const dm_shape* shp, const float* image, const dm_conv_params* p, const float* acts,
+                                 const float* dembed, int ld, const float* reward, const float* terminal, const dm_conv_grads* gr,
+                                 void* ws, size_t ws_bytes, void* stream) {
   DmPrecisionScope prec(shp->flags & DM_FLAG_BF16);
   EncGeom g(shp);
-  DM_REQUIRE(g.valid(shp), DM_E_SHAPE, "conv_encoder: unsupported geometry");
+  const bool planes = reward != nullptr;
+  if (planes) {
+    DM_REQUIRE(shp->img == 64 && g.hs[3] == 2 && g.direct0 && ld >= 32 * g.d, DM_E_SHAPE,
+               "conv_encoder planes: built for 3 x 64 x 64 frames and cnn_depth in {8,16,32,48,64} (img=%d, ch=%d, depth=%d, ld=%d)",
+               shp->img, shp->img_ch, shp->cnn_depth, ld);
+  } else {
+    DM_REQUIRE(g.valid(shp) && ld >= 32 * g.d, DM_E_SHAPE, "conv_encoder: unsupported geometry");
+  }
   hipStream_t st = (hipStream_t)stream;
   EncActs a;
   enc_carve(g, const_cast<float*>(acts), (size_t)1 << 60, &a);
@@ -607,8 +655,12 @@ extern "C" int dm_conv_encoder_bwd(const dm_shape* shp, const float* image, cons
   // dY3 (NHWC) = permute(dembed) ; G = dY3 * ELU'(Y3)
   float* G = gb;      // layer-3 grads are small; ping-pong between ga / gb going down
   const size_t tot3 = (size_t)g.N * 4 * g.cout[3];
-  hipLaunchKernelGGL(nhwc_to_chw_flat_kernel, dim3(grid_for(tot3)), dim3(256), 0, st, (size_t)g.N, 4, g.cout[3], dembed, G,
-                     0);
+  if (ld == 4 * g.cout[3])
+    hipLaunchKernelGGL(nhwc_to_chw_flat_kernel, dim3(grid_for(tot3)), dim3(256), 0, st, (size_t)g.N, 4, g.cout[3], dembed, G,
+                       0);
+  else
+    hipLaunchKernelGGL(nhwc_to_chw_flat_ld_kernel, dim3(grid_for(tot3)), dim3(256), 0, st, (size_t)g.N, 4, g.cout[3], dembed, G,
+                       ld, 0);
   DM_LAUNCH_CHECK();
   DM_TRY(dm_mul_elu_grad_launch(tot3, G, a.y[3], G, st));
   if (tw_on) {
@@ -618,6 +670,16 @@ extern "C" int dm_conv_encoder_bwd(const dm_shape* shp, const float* image, cons
   }
   for (int l = 3; l >= 0; --l) {
     const int rows = (int)g.rows[l], co = g.cout[l], kd = (int)g.kdim[l];
+    if (l == 0 && planes) {
+      // reward_input: the image channels' weight gradient as ever (into `dwr`, free by now), then ONE frame-weighted column sum
+      // over G gives the bias gradient and the two plane gradients, and the (d, 5, 4, 4) gradient is assembled (conv_direct.hip)
+      DM_REQUIRE(image, DM_E_NULL, "conv_encoder_bwd: the direct layer-1 weight gradient reads the image");
+      DM_REQUIRE(dm_enc_l1_wgrad_part_floats(g.N, g.d) <= xcmax && dm_enc_l1_planes_part_floats(g.N, g.d) <= xcmax,
+                 DM_E_WORKSPACE, "conv_encoder_bwd: partial buffer too small");
+      DM_TRY(dm_enc_l1_wgrad_launch(g.N, g.d, shape_u8(shp) ? 1 : 0, image, G, dxcol, dwr, splitk, skb, st));
+      DM_TRY(dm_enc_l1_planes_bwd_launch(g.N, g.d, G, reward, terminal, dwr, dxcol, gr->b[0], gr->w[0], st));
+      continue;
+    }
     DM_TRY(dm_colsum_launch(rows, co, G, co, gr->b[l], splitk, skb, st));
     if (l == 0 && g.direct0) {      // patches re-gathered from the frame inside the weight-gradient kernel (conv_direct.hip)
       DM_REQUIRE(image, DM_E_NULL, "conv_encoder_bwd: the direct layer-1 weight gradient reads the image");
@@ -693,6 +755,18 @@ extern "C" int dm_conv_encoder_bwd(const dm_shape* shp, const float* image, cons
     }
   }
   return DM_OK;
+}
+extern "C" int dm_conv_encoder_bwd(const dm_shape* shp, const float* image, const dm_conv_params* p, const float* acts,
+                                   const float* dembed, const dm_conv_grads* gr, void* ws, size_t ws_bytes, void* stream) {
+  DM_REQUIRE(shp && p && acts && dembed && gr && ws, DM_E_NULL, "conv_encoder_bwd: null pointer");
+  return conv_encoder_bwd_impl(shp, image, p, acts, dembed, 32 * shp->cnn_depth, nullptr, nullptr, gr, ws, ws_bytes, stream);
+}
+extern "C" int dm_conv_encoder_bwd_planes(const dm_shape* shp, const float* image, const dm_conv_params* p,
+                                          const float* reward, const float* terminal, const float* acts, const float* dembed,
+                                          int ld_dembed, const dm_conv_grads* gr, void* ws, size_t ws_bytes, void* stream) {
+  DM_REQUIRE(shp && p && acts && dembed && gr && ws && !reward == !terminal && (image || !reward), DM_E_NULL,
+             "conv_encoder_bwd_planes: null pointer");
+  return conv_encoder_bwd_impl(shp, image, p, acts, dembed, ld_dembed, reward, terminal, gr, ws, ws_bytes, stream);
 }
 
 // 4-channel trick for the image layer's backward (cout = 3): the output gradient is written with 4 channels per pixel (the

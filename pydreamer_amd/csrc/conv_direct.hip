@@ -18,6 +18,13 @@
 //                        is, per class, a 3x3 convolution over the input; the class's 9 x d x 3 weights are wave-uniform
 //                        (scalar loads), the input pixel vectors are 16-byte loads
 // fp32 VALU arithmetic (v_fmac with an SGPR operand); bound: VALU issue (13 / 5.5 GFMA-lanes) and the output write.
+//
+// reward_input (encoders.py:52-59): the encoder's first Conv2d sees two more input planes, the frame's reward and its terminal
+// flag, each constant over the frame.  The convolution has no padding, so every 4x4 window lies inside the frame and a plane
+// adds the same value to every output pixel of its frame: y[n,o,.,.] += r_n * sum_taps W[o,3] + t_n * sum_taps W[o,4].  The
+// 5-channel image is never written: enc_l1_fb_kernel builds the per-frame bias table fb[n][o], enc_l1_fwd_kernel<.., FB = true>
+// starts its accumulators from fb[n] instead of the bias, and the backward gets the plane gradients - the same for all 16 taps
+// - from ONE frame-weighted column sum over G (enc_l1_planes_colsum_kernel), which also yields the bias gradient.
 #include "common.h"
 
 static inline int grid_for_px(size_t total, int per_block) { return (int)((total + per_block - 1) / per_block); }
@@ -25,7 +32,8 @@ static inline int grid_for_px(size_t total, int per_block) { return (int)((total
 
 // ---------------------------------------------------------------- encoder layer 1, forward --------
 // wt: (48 taps, CO) with tap = c*16 + ky*4 + kx (the torch weight (CO,3,4,4) transposed once per call)
-template <int CO, bool U8>
+// FB: `bias` is the per-frame table fb (frames, CO) of enc_l1_fb_kernel (a wave of 64 pixels can straddle two frames: per-lane loads)
+template <int CO, bool U8, bool FB = false>
 __global__ void __launch_bounds__(256) enc_l1_fwd_kernel(int npix, const void* __restrict__ image_,
                                                          const float* __restrict__ wt, const float* __restrict__ bias,
                                                          float* __restrict__ y, unsigned short* __restrict__ y_h) {
@@ -34,8 +42,17 @@ __global__ void __launch_bounds__(256) enc_l1_fwd_kernel(int npix, const void* _
   const int pc = ok ? p : npix - 1;
   const int n = pc / 961, r = pc - n * 961, py = r / 31, px = r - py * 31;
   float acc[CO];
+  if (FB) {
+    const float4* fb = reinterpret_cast<const float4*>(bias + (size_t)n * CO);      // CO % 4 == 0: 16-byte aligned rows
 #pragma unroll
-  for (int o = 0; o < CO; ++o) acc[o] = bias[o];
+    for (int o = 0; o < CO; o += 4) {
+      const float4 b4 = fb[o >> 2];
+      acc[o] = b4.x; acc[o + 1] = b4.y; acc[o + 2] = b4.z; acc[o + 3] = b4.w;
+    }
+  } else {
+#pragma unroll
+    for (int o = 0; o < CO; ++o) acc[o] = bias[o];
+  }
 #pragma unroll 1
   for (int cy = 0; cy < 12; ++cy) {               // (c, ky) pairs; the 4 kx taps of a pair are 4 consecutive pixels of one row
     const int c = cy >> 2, ky = cy & 3;
@@ -69,9 +86,25 @@ __global__ void __launch_bounds__(256) enc_l1_fwd_kernel(int npix, const void* _
   }
 }
 
+// WROW: floats per output channel of `w`: 48 for the (CO,3,4,4) weight, 80 for the (CO,5,4,4) weight of reward_input (the
+// image taps are its first 48)
+template <int WROW = 48>
 __global__ void __launch_bounds__(256) enc_l1_wt_kernel(int co, const float* __restrict__ w, float* __restrict__ wt) {
   const int e = blockIdx.x * 256 + threadIdx.x;                // wt[t][o] = w[o][t], t = c*16 + ky*4 + kx
-  if (e < co * 48) wt[e] = w[(size_t)(e % co) * 48 + e / co];
+  if (e < co * 48) wt[e] = w[(size_t)(e % co) * WROW + e / co];
+}
+// fb[n][o] = b[o] + r_n * sum_taps W[o][3] + t_n * sum_taps W[o][4]      (W: the (CO,5,4,4) weight; taps summed in index order)
+__global__ void __launch_bounds__(256) enc_l1_fb_kernel(int frames, int co, const float* __restrict__ w5,
+                                                        const float* __restrict__ bias, const float* __restrict__ reward,
+                                                        const float* __restrict__ terminal, float* __restrict__ fb) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= frames * co) return;
+  const int n = e / co, o = e - n * co;
+  const float* w = w5 + (size_t)o * 80 + 48;
+  float s3 = 0.f, s4 = 0.f;
+#pragma unroll
+  for (int t = 0; t < 16; ++t) { s3 += w[t]; s4 += w[16 + t]; }
+  fb[e] = fmaf(terminal[n], s4, fmaf(reward[n], s3, bias[o]));
 }
 
 bool dm_enc_l1_direct_ok(int ch, int d, int img) {
@@ -81,7 +114,7 @@ bool dm_enc_l1_direct_ok(int ch, int d, int img) {
 int dm_enc_l1_fwd_launch(int frames, int d, int u8, const void* image, const float* w, const float* bias, float* wt,
                          float* y, unsigned short* y_h, hipStream_t st) {
   if (frames <= 0) return DM_OK;
-  hipLaunchKernelGGL(enc_l1_wt_kernel, dim3(grid_for_px((size_t)d * 48, 256)), dim3(256), 0, st, d, w, wt);
+  hipLaunchKernelGGL(enc_l1_wt_kernel<48>, dim3(grid_for_px((size_t)d * 48, 256)), dim3(256), 0, st, d, w, wt);
   DM_LAUNCH_CHECK();
   const int npix = frames * 961;
   const dim3 grid(grid_for_px((size_t)npix, 256)), blk(256);
@@ -92,6 +125,29 @@ int dm_enc_l1_fwd_launch(int frames, int d, int u8, const void* image, const flo
   }
   DM_ENC_L1(8) DM_ENC_L1(16) DM_ENC_L1(32) DM_ENC_L1(48) DM_ENC_L1(64)
 #undef DM_ENC_L1
+  DM_LAUNCH_CHECK();
+  return DM_OK;
+}
+
+// reward_input: w5 (d, 5, 4, 4); reward, terminal (frames,); fb: scratch of frames*d floats (the bias table, written here)
+int dm_enc_l1_fwd_planes_launch(int frames, int d, int u8, const void* image, const float* w5, const float* bias,
+                                const float* reward, const float* terminal, float* wt, float* fb, float* y,
+                                unsigned short* y_h, hipStream_t st) {
+  if (frames <= 0) return DM_OK;
+  hipLaunchKernelGGL(enc_l1_wt_kernel<80>, dim3(grid_for_px((size_t)d * 48, 256)), dim3(256), 0, st, d, w5, wt);
+  DM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(enc_l1_fb_kernel, dim3(grid_for_px((size_t)frames * d, 256)), dim3(256), 0, st, frames, d, w5, bias, reward,
+                     terminal, fb);
+  DM_LAUNCH_CHECK();
+  const int npix = frames * 961;
+  const dim3 grid(grid_for_px((size_t)npix, 256)), blk(256);
+#define DM_ENC_L1P(CO_)                                                                                             \
+  if (d == CO_) {                                                                                                   \
+    if (u8) hipLaunchKernelGGL((enc_l1_fwd_kernel<CO_, true, true>), grid, blk, 0, st, npix, image, wt, fb, y, y_h);  \
+    else hipLaunchKernelGGL((enc_l1_fwd_kernel<CO_, false, true>), grid, blk, 0, st, npix, image, wt, fb, y, y_h);    \
+  }
+  DM_ENC_L1P(8) DM_ENC_L1P(16) DM_ENC_L1P(32) DM_ENC_L1P(48) DM_ENC_L1P(64)
+#undef DM_ENC_L1P
   DM_LAUNCH_CHECK();
   return DM_OK;
 }
@@ -194,6 +250,95 @@ int dm_enc_l1_wgrad_launch(int frames, int d, int u8, const void* image, const f
 #undef DM_ENC_WG
   DM_LAUNCH_CHECK();
   return dm_colsum_launch(blocks * 4, d * 48, part, d * 48, dW, ws, ws_bytes, st);
+}
+
+// ---------------------------------------------------------------- encoder layer 1, reward_input backward
+// One pass over G (frames*961, d): part[(chunk*3 + q)*d + o] = sum over the chunk's frames of c_q(n) * sum_pixels G[n][pixel][o]
+// with c = (1, r_n, t_n).  A workgroup owns whole frames and walks a frame as a flat array in slabs of W = 256 - 256 % d floats,
+// so a thread stays on one column (as colsum_flat_kernel); the frame's sum is formed first and weighted once.  Fixed order.
+__global__ void __launch_bounds__(256) enc_l1_planes_colsum_kernel(int frames, int d, int W, int frames_per_chunk,
+                                                                   const float* __restrict__ G, const float* __restrict__ reward,
+                                                                   const float* __restrict__ terminal, float* __restrict__ part) {
+  __shared__ float sh[3][256];
+  const int tid = threadIdx.x;
+  const int n0 = blockIdx.x * frames_per_chunk, n1 = min(frames, n0 + frames_per_chunk);
+  const int fl = 961 * d;
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+  if (tid < W)
+    for (int n = n0; n < n1; ++n) {
+      const float* x = G + (size_t)n * fl;
+      float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
+      int i = tid;
+      for (; i + 3 * W < fl; i += 4 * W) {
+        b0 += x[i];
+        b1 += x[i + W];
+        b2 += x[i + 2 * W];
+        b3 += x[i + 3 * W];
+      }
+      for (; i < fl; i += W) b0 += x[i];
+      const float s = (b0 + b1) + (b2 + b3);
+      a0 += s;
+      a1 = fmaf(reward[n], s, a1);
+      a2 = fmaf(terminal[n], s, a2);
+    }
+  sh[0][tid] = a0; sh[1][tid] = a1; sh[2][tid] = a2;
+  __syncthreads();
+  if (tid < 3 * d) {
+    const int q = tid / d, o = tid - q * d;
+    float s = 0.f;
+    for (int t = o; t < W; t += d) s += sh[q][t];               // threads t == o (mod d) hold column o
+    part[((size_t)blockIdx.x * 3 + q) * d + o] = s;
+  }
+}
+// One workgroup: the chunk partials summed in fixed order, then db[o] = sum G, and the 5-channel dW (d, 5, 4, 4) assembled from
+// the image channels' dw3 (d, 3, 4, 4) and the two plane sums, each written to all 16 taps of its channel.
+__global__ void __launch_bounds__(256) enc_l1_planes_final_kernel(int d, int chunks, const float* __restrict__ part,
+                                                                  const float* __restrict__ dw3, float* __restrict__ db,
+                                                                  float* __restrict__ dW5) {
+  __shared__ float sums[3 * 64];
+  const int tid = threadIdx.x;
+  if (tid < 3 * d) {
+    const float* p = part + tid;
+    const size_t st = (size_t)3 * d;
+    float s = 0.f;
+    int c = 0;
+    for (; c + 3 < chunks; c += 4) {
+      const float v0 = p[(size_t)c * st], v1 = p[(size_t)(c + 1) * st], v2 = p[(size_t)(c + 2) * st], v3 = p[(size_t)(c + 3) * st];
+      s += v0; s += v1; s += v2; s += v3;
+    }
+    for (; c < chunks; ++c) s += p[(size_t)c * st];
+    sums[tid] = s;
+  }
+  __syncthreads();
+  if (tid < d) db[tid] = sums[tid];
+  for (int e = tid; e < d * 80; e += 256) {
+    const int o = e / 80, r = e - o * 80, c = r >> 4;
+    dW5[e] = c < 3 ? dw3[o * 48 + r] : sums[(c - 2) * d + o];
+  }
+}
+static int enc_l1_planes_chunks(int frames, int* frames_per_chunk) {
+  int chunks = frames > 2048 ? 2048 : frames;
+  *frames_per_chunk = (frames + chunks - 1) / chunks;
+  return (frames + *frames_per_chunk - 1) / *frames_per_chunk;
+}
+size_t dm_enc_l1_planes_part_floats(int frames, int d) {
+  int fpc;
+  return frames > 0 ? (size_t)enc_l1_planes_chunks(frames, &fpc) * 3 * d : 0;
+}
+// db (d,) and dW5 (d, 5, 4, 4) of the reward_input layer; dw3 (d, 3, 4, 4): the image channels' gradient (dm_enc_l1_wgrad_launch);
+// part: dm_enc_l1_planes_part_floats(frames, d) of scratch
+int dm_enc_l1_planes_bwd_launch(int frames, int d, const float* G, const float* reward, const float* terminal,
+                                const float* dw3, float* part, float* db, float* dW5, hipStream_t st) {
+  DM_REQUIRE(d >= 1 && d <= 64, DM_E_SHAPE, "enc_l1_planes_bwd: cnn_depth %d", d);
+  if (frames <= 0) return DM_OK;
+  int fpc;
+  const int chunks = enc_l1_planes_chunks(frames, &fpc);
+  hipLaunchKernelGGL(enc_l1_planes_colsum_kernel, dim3(chunks), dim3(256), 0, st, frames, d, 256 - 256 % d, fpc, G, reward,
+                     terminal, part);
+  DM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(enc_l1_planes_final_kernel, dim3(1), dim3(256), 0, st, d, chunks, part, dw3, db, dW5);
+  DM_LAUNCH_CHECK();
+  return DM_OK;
 }
 
 // ---------------------------------------------------------------- decoder layer 4, forward --------

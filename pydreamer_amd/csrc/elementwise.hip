@@ -1801,6 +1801,43 @@ extern "C" int dm_head_loss(int kind, int rows, const float* out, const float* t
   return DM_OK;
 }
 
+// Independent Normal over V > 1 outputs with a fixed std (DenseNormalDecoder with out_dim > 1, decoders.py:295-304: the vecobs
+// decoder): loss[r] = 0.5 * sum_v (mu - y)^2 + V * loss_const, dout[r][v] = scale * (mu - y), mean_out = mu.  A row reduction:
+// 8 lanes per row, lane l takes columns l, l + 8, ...; the row sum is an xor-shuffle tree inside the 8 lanes (fixed order).
+__global__ void __launch_bounds__(256) head_loss_nd_kernel(int rows, int V, const float* __restrict__ out,
+                                                           const float* __restrict__ target, float scale, float row_const,
+                                                           float* __restrict__ loss, float* __restrict__ dout,
+                                                           float* __restrict__ mean_out) {
+  const int sub = threadIdx.x & 7;
+  for (int r = blockIdx.x * 32 + (threadIdx.x >> 3); r < rows; r += gridDim.x * 32) {      // the 8 lanes of a row leave together
+    const size_t base = (size_t)r * V;
+    float s = 0.f;
+    for (int v = sub; v < V; v += 8) {
+      const float o = out[base + v];
+      const float d = o - (target ? target[base + v] : 0.f);
+      s = fmaf(d, d, s);
+      if (dout) dout[base + v] = scale * d;
+      if (mean_out) mean_out[base + v] = o;
+    }
+    s += __shfl_xor(s, 1, 8);
+    s += __shfl_xor(s, 2, 8);
+    s += __shfl_xor(s, 4, 8);
+    if (sub == 0 && loss) loss[r] = 0.5f * s + row_const;
+  }
+}
+extern "C" int dm_head_loss_normal_nd(int rows, int V, const float* out, const float* target, float scale, float loss_const,
+                                      float* loss, float* dout, float* mean_out, void* stream) {
+  DM_REQUIRE(out, DM_E_NULL, "head_loss_normal_nd: null pointer");
+  DM_REQUIRE(V >= 1, DM_E_SHAPE, "head_loss_normal_nd: V %d", V);
+  if (rows <= 0) return DM_OK;
+  int blocks = dm_cdiv(rows, 32);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(head_loss_nd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rows, V, out, target, scale,
+                     (float)V * loss_const, loss, dout, mean_out);
+  DM_LAUNCH_CHECK();
+  return DM_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // GAE reverse scan + reality weight, one thread per dream column (a2c.py:81-108)
 // ------------------------------------------------------------------------------------------------

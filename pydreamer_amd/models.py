@@ -10,7 +10,9 @@ reference (train.py:184-187).  There is no CPU path: tensors must live on a gfx9
 Supported configuration (everything else raises NotImplementedError): iwae_samples>=1 (also with the logging flags), gru_type in {gru, gru_layernorm,
 gru_layernorm_dv2}, gru_layers 1..4, stoch_discrete>0 or 0 (Gaussian latents, also with iwae_samples>1), layer_norm True or False,
 aux_critic, image_encoder/decoder='cnn' at 64x64, actor_dist in {onehot, tanh_normal, normal_tanh}, actor_grad='reinforce',
-probe_model='none', no vecobs / reward_input.
+probe_model='none', reward_input (cnn_depth in {8, 16, 32, 48, 64}: the reward and terminal planes are folded into the first
+convolution), vecobs_size > 0 beside the image (an MLP encoder whose output sits behind the image embedding, a
+DenseNormalDecoder with out_dim = vecobs_size).
 """
 import contextlib
 import ctypes
@@ -194,15 +196,26 @@ class ConvEncoder(_Params):
         return [self.model[i] for i in (0, 2, 4, 6)]
 
 
+VECOBS_EMBED = 256        # encoders.py:34
+REWARD_INPUT_DEPTHS = (8, 16, 32, 48, 64)     # the depths of the direct layer-1 kernels (csrc/conv_direct.hip dm_enc_l1_direct_ok)
+
+
 class MultiEncoder(_Params):
-    """encoders.py:10-69 (image encoder only)."""
+    """encoders.py:10-69 (image encoder, with or without the reward / terminal planes of reward_input)."""
 
     def __init__(self, conf):
         super().__init__()
-        if conf.reward_input or conf.vecobs_size or conf.image_encoder != 'cnn':
-            raise NotImplementedError('only image_encoder=cnn without reward_input/vecobs is built in the HIP path')
-        self.encoder_image = ConvEncoder(in_channels=conf.image_channels, cnn_depth=conf.cnn_depth)
-        self.out_dim = self.encoder_image.out_dim
+        if conf.image_encoder != 'cnn':
+            raise NotImplementedError('only image_encoder=cnn (with or without vecobs beside it) is built in the HIP path')
+        self.reward_input = bool(conf.reward_input)
+        if self.reward_input and (conf.cnn_depth not in REWARD_INPUT_DEPTHS or conf.image_channels != 3):
+            raise NotImplementedError(f'reward_input is built for 3-channel frames and cnn_depth in {REWARD_INPUT_DEPTHS} '
+                                      f'(got image_channels={conf.image_channels}, cnn_depth={conf.cnn_depth})')
+        # encoders.py:15-18: + reward, terminal.  The two planes exist in the weight only: the kernels read the 3-channel frame
+        self.encoder_image = ConvEncoder(in_channels=conf.image_channels + (2 if self.reward_input else 0), cnn_depth=conf.cnn_depth)
+        # encoders.py:33-36,64-68: the vecobs embedding is concatenated behind the image embedding
+        self.encoder_vecobs = MLP(conf.vecobs_size, VECOBS_EMBED, MLP_HIDDEN, 2, conf.layer_norm) if conf.vecobs_size else None
+        self.out_dim = self.encoder_image.out_dim + (VECOBS_EMBED if conf.vecobs_size else 0)
 
 
 class ConvDecoder(_Params):
@@ -226,9 +239,9 @@ class ConvDecoder(_Params):
 class DenseNormalDecoder(_Params):
     """decoders.py:287-319."""
 
-    def __init__(self, in_dim, hidden_layers, layer_norm=True):
+    def __init__(self, in_dim, hidden_layers, layer_norm=True, out_dim=1):
         super().__init__()
-        self.model = MLP(in_dim, 1, MLP_HIDDEN, hidden_layers, layer_norm)
+        self.model = MLP(in_dim, out_dim, MLP_HIDDEN, hidden_layers, layer_norm)
         self.std = REWARD_STD
 
 
@@ -245,12 +258,17 @@ class MultiDecoder(_Params):
 
     def __init__(self, features_dim, conf):
         super().__init__()
-        if conf.image_decoder != 'cnn' or conf.reward_decoder_categorical or conf.vecobs_size:
+        if conf.image_decoder != 'cnn' or conf.reward_decoder_categorical:
             raise NotImplementedError('only image_decoder=cnn with Normal reward decoder is built in the HIP path')
         self.image_weight, self.reward_weight, self.terminal_weight = conf.image_weight, conf.reward_weight, conf.terminal_weight
         self.image = ConvDecoder(in_dim=features_dim, out_channels=conf.image_channels, cnn_depth=conf.cnn_depth)
         self.reward = DenseNormalDecoder(features_dim, conf.reward_decoder_layers, conf.layer_norm)
         self.terminal = DenseBernoulliDecoder(features_dim, conf.terminal_decoder_layers, conf.layer_norm)
+        self.vecobs_weight = conf.vecobs_weight
+        if conf.vecobs_size:      # decoders.py:45-48
+            self.vecobs = DenseNormalDecoder(features_dim, 4, conf.layer_norm, out_dim=conf.vecobs_size)
+        else:
+            self.vecobs = None
 
 
 class NormGRUCellP(_Params):
@@ -423,7 +441,7 @@ def _multi_sum(items, device, out=None):
 METRIC_SLOTS = dict(loss_kl=0, loss_image=1, loss_reward=2, loss_terminal=3, entropy_prior=4, entropy_post=5, loss_model=6,
                     loss_critic=8, loss_actor=9, policy_entropy=10, policy_value=11, policy_value_im=12, policy_reward=13,
                     policy_reward_std=14, grad_norm=16, grad_norm_probe=18, grad_norm_actor=20, grad_norm_critic=22,
-                    loss_critic_aux=24, policy_value_aux=25)      # slot 7: loss_model + aux_critic_weight * loss_critic_aux
+                    loss_critic_aux=24, policy_value_aux=25, loss_vecobs=15)      # slot 7: loss_model + aux_critic_weight * loss_critic_aux
 METRIC_BUF_FLOATS = 28
 
 
@@ -637,7 +655,7 @@ class _WMStep(torch.autograd.Function):
             torch.cuda.current_stream().wait_stream(ov.s_wm)
         else:
             grads, flat, direct = wm._backward(pk, pk['ws'])
-        for k in ('enc_acts', 'rssm_acts', 'dec_acts', 'r_acts', 't_acts', 'aux'):
+        for k in ('enc_acts', 'rssm_acts', 'dec_acts', 'r_acts', 't_acts', 'aux', 'v_acts', 'ev_acts'):
             pk.pop(k, None)                               # only now: the side stream may have been reading them
         pk['consumed'] = True
         return (None, None) + _finish_backward(wm, grads, flat, direct, grad_loss)
@@ -743,10 +761,18 @@ class WorldModel(_Params):
         want = dict(image=(T, B, c.image_size, c.image_size, c.image_channels) if u8 else
                     (T, B, c.image_channels, c.image_size, c.image_size), action=(T, B, c.action_dim), reset=(T, B))
         got = dict(image=tuple(image.shape), action=tuple(action.shape), reset=tuple(reset.shape))
+        planes = self.encoder.reward_input
         for k in ('reward', 'terminal'):
+            if planes and k not in obs:
+                raise ValueError(f"reward_input: obs['{k}'] is an input of the encoder (encoders.py:52-59)")
             if not forward_only or k in obs:
                 if k in obs:
                     want[k], got[k] = (T, B), tuple(obs[k].shape)
+        V = c.vecobs_size
+        if V:
+            if 'vecobs' not in obs:
+                raise ValueError(f"vecobs_size={V}: obs['vecobs'] is an input of the encoder (encoders.py:64-66)")
+            want['vecobs'], got['vecobs'] = (T, B, V), tuple(obs['vecobs'].shape)
         want['in_state[0]'], got['in_state[0]'] = (BI, D_), tuple(h0.shape)
         want['in_state[1]'], got['in_state[1]'] = (BI, Z), tuple(z0.shape)
         if u_post is not None:
@@ -812,8 +838,24 @@ class WorldModel(_Params):
             reset_x.view(T, B, I).copy_(reset.view(T, B, 1).expand(T, B, I))
         else:
             action_x, reset_x = action, reset
-        H.call('dm_conv_encoder_fwd', ctypes.byref(shp_e), H.ptr(image), ctypes.byref(enc_p), H.fptr(enc_acts),
-               H.fptr(embed), H.ptr(ws), ws.numel(), H.stream())
+        plane_r = plane_t = vecobs = ev_acts = None
+        if planes:      # encoders.py:52-59: per-frame constants, (T,B) -> (N,); never expanded to image planes
+            plane_r = obs['reward'].float().contiguous().view(NE)
+            plane_t = obs['terminal'].float().contiguous().view(NE)
+        if planes or V:
+            # the image embedding is written as the leading E - 256 columns of the (NE, E) buffer (leading dimension E), the
+            # vecobs embedding behind it: one buffer for the RSSM, no copy pass over the image embedding
+            shp_c = H.dm_shape.from_buffer_copy(shp_e)
+            shp_c.E = enc.out_dim                   # the convolution stack's own width
+            H.call('dm_conv_encoder_fwd_planes', ctypes.byref(shp_c), H.ptr(image), ctypes.byref(enc_p), H.fptr(plane_r),
+                   H.fptr(plane_t), H.fptr(enc_acts), H.fptr(embed), E, H.ptr(ws), ws.numel(), H.stream())
+            if V:
+                vecobs = obs['vecobs'].float().contiguous().view(NE, V)
+                ev, ev_acts = self.encoder.encoder_vecobs.fwd(vecobs, V, NE, ws, save_acts=not forward_only)
+                embed[:, enc.out_dim:].copy_(ev)
+        else:
+            H.call('dm_conv_encoder_fwd', ctypes.byref(shp_e), H.ptr(image), ctypes.byref(enc_p), H.fptr(enc_acts),
+                   H.fptr(embed), H.ptr(ws), ws.numel(), H.stream())
         embed_x = embed
         if I > 1:
             embed_x = torch.empty(N, E, device=dev)
@@ -826,7 +868,8 @@ class WorldModel(_Params):
         last = feat[(T - 1) * BI:]
         out_state = (last[:, :D_].clone(), last[:, D_:].clone())                  # detached by construction (rssm.py:77)
         pk = dict(shp=shp, shp_e=shp_e, shp_r=shp_r, T=T, B=B, I=I, feat=feat, post=post, prior=prior, idx=idx,
-                  out_state=out_state, embed=embed, embed_x=embed_x, action_x=action_x, reset_x=reset_x)
+                  out_state=out_state, embed=embed, embed_x=embed_x, action_x=action_x, reset_x=reset_x,
+                  plane_r=plane_r, plane_t=plane_t, vecobs=vecobs, ev_acts=ev_acts)
         if forward_only:
             return pk
         # The tail of the world-model forward - decoder + MSE, reward / terminal heads, KL, the loss sums (dreamer.py:311-365) -
@@ -877,6 +920,18 @@ class WorldModel(_Params):
         H.call('dm_head_loss', 1, N, H.fptr(tl), H.fptr(terminal_t), gw * dec.terminal_weight / NE, 0.0, H.fptr(loss_terminal),
                H.fptr(dtl), H.fptr(terminal_rec), H.stream())
 
+        V = c.vecobs_size
+        loss_vecobs = dmu_v = vecobs_rec = v_acts = None
+        if V:      # decoders.py:66-71: Independent Normal over the V outputs, the reward head's std and constant per output
+            vec_t = pk['vecobs']
+            if I > 1:
+                vec_t = vec_t.repeat_interleave(I, dim=0).contiguous()
+            mu_v, v_acts = dec.vecobs.model.fwd(feat, F_, N, ws, sparse_cols=sp)
+            loss_vecobs = torch.empty(N, device=dev)
+            dmu_v, vecobs_rec = torch.empty(N, V, device=dev), torch.empty(N, V, device=dev)
+            H.call('dm_head_loss_normal_nd', N, V, H.fptr(mu_v), H.fptr(vec_t), gw * dec.vecobs_weight / NE, loss_const,
+                   H.fptr(loss_vecobs), H.fptr(dmu_v), H.fptr(vecobs_rec), H.stream())
+
         # KL + entropies (dreamer.py:326-343,369-379)
         kl, ent_post, ent_prior = (torch.empty(N, device=dev) for _ in range(3))
         H.call('dm_kl_balance_fwd', N, c.stoch_dim, c.stoch_discrete, H.fptr(post), H.fptr(prior), H.fptr(kl),
@@ -913,17 +968,25 @@ class WorldModel(_Params):
         if I == 1:
             means = _multi_sum([(kl, 1.0 / N), (loss_image, 1.0 / N), (loss_reward, 1.0 / N), (loss_terminal, 1.0 / N),
                                 (ent_prior, 1.0 / N), (ent_post, 1.0 / N)], dev, out=mbuf[0:6])
-            H.call('dm_combine', 4, H.fptr(means), w, ctypes.c_void_p(mbuf.data_ptr() + 24), H.stream())   # dreamer.py:362-365
+            terms = [(kl, 1.0 / N), (loss_image, 1.0 / N), (loss_reward, 1.0 / N), (loss_terminal, 1.0 / N)]
+            wts = [self.kl_weight, dec.image_weight, dec.reward_weight, dec.terminal_weight]
+            if V:      # loss_reconstr += vecobs_weight * loss_vecobs (decoders.py:68): a fifth term of loss_model
+                _multi_sum([(loss_vecobs, 1.0 / N)], dev, out=mbuf[15:16])
+                terms, wts = terms + [(loss_vecobs, 1.0 / N)], wts + [dec.vecobs_weight]
+                H.call('dm_combine', 5, H.fptr(_multi_sum(terms, dev)), (ctypes.c_float * 5)(*wts),
+                       ctypes.c_void_p(mbuf.data_ptr() + 24), H.stream())
+            else:
+                H.call('dm_combine', 4, H.fptr(means), w, ctypes.c_void_p(mbuf.data_ptr() + 24), H.stream())   # dreamer.py:362-365
             if aux is not None:       # loss = loss_model.mean() + aux_critic_weight * loss_critic_aux (dreamer.py:365) -> slot 7
-                t5 = _multi_sum([(kl, 1.0 / N), (loss_image, 1.0 / N), (loss_reward, 1.0 / N), (loss_terminal, 1.0 / N),
-                                 (aux['lc'], 1.0 / aux['rows'])], dev)
-                w5 = (ctypes.c_float * 5)(self.kl_weight, dec.image_weight, dec.reward_weight, dec.terminal_weight,
-                                          self.aux_critic_weight)
-                H.call('dm_combine', 5, H.fptr(t5), w5, ctypes.c_void_p(mbuf.data_ptr() + 28), H.stream())
+                terms, wts = terms + [(aux['lc'], 1.0 / aux['rows'])], wts + [self.aux_critic_weight]
+                H.call('dm_combine', len(wts), H.fptr(_multi_sum(terms, dev)), (ctypes.c_float * len(wts))(*wts),
+                       ctypes.c_void_p(mbuf.data_ptr() + 28), H.stream())
                 loss = mbuf[7]
             tb = lambda x: x.view(T, B)
             t_kl, t_ep, t_eq, t_li, t_lr, t_lt, t_rr, t_tr = (tb(x) for x in (kl, ent_prior, ent_post, loss_image, loss_reward,
                                                                               loss_terminal, reward_rec, terminal_rec))
+            if V:
+                t_lv, t_vr = tb(loss_vecobs), vecobs_rec.view(T, B, V)
         else:
             # IWAE: sampled KL (dreamer.py:340-343); loss_model = mean_tb -logavgexp_i(-loss_tbi) (dreamer.py:362-365);
             # the logged tensors are -logavgexp_i(-x) of the per-sample losses (decoders.py:170,277,312), means over I for the
@@ -936,8 +999,11 @@ class WorldModel(_Params):
                 H.call('dm_kl_sampled_fwd', N, c.stoch_dim, c.stoch_discrete, H.fptr(post), H.fptr(prior), H.ptr(idx), H.fptr(kl_s),
                        H.stream())
             l_tbi = torch.empty(N, device=dev)
-            ptrs = (ctypes.c_void_p * 4)(kl_s.data_ptr(), loss_image.data_ptr(), loss_reward.data_ptr(), loss_terminal.data_ptr())
-            H.call('dm_combine_rows', 4, N, ptrs, w, H.fptr(l_tbi), H.stream())
+            rows_l, rows_w = [kl_s, loss_image, loss_reward, loss_terminal], list(w)
+            if V:
+                rows_l, rows_w = rows_l + [loss_vecobs], rows_w + [dec.vecobs_weight]
+            ptrs = (ctypes.c_void_p * len(rows_l))(*[x.data_ptr() for x in rows_l])
+            H.call('dm_combine_rows', len(rows_l), N, ptrs, (ctypes.c_float * len(rows_w))(*rows_w), H.fptr(l_tbi), H.stream())
             iw = torch.empty(N, device=dev)                   # importance weights softmax_i(-loss_tbi) = d loss_tb / d loss_tbi
             red = torch.empty(9, NE, device=dev)
             H.call('dm_reduce_i', NE, I, 1, H.fptr(l_tbi), 1, H.fptr(red[0]), H.fptr(iw), H.stream())
@@ -949,9 +1015,15 @@ class WorldModel(_Params):
             means = mbuf[0:6]
             tb = lambda x: x.view(T, B)
             t_kl, t_li, t_lr, t_lt, t_ep, t_eq, t_rr, t_tr = (tb(red[j]) for j in range(1, 9))
+            if V:      # -logavgexp over I for the loss, the mean over I for the reconstruction (decoders.py:312-313)
+                t_lv, t_vr = torch.empty(T, B, device=dev), torch.empty(T, B, V, device=dev)
+                H.call('dm_reduce_i', NE, I, 1, H.fptr(loss_vecobs), 1, H.fptr(t_lv), None, H.stream())
+                H.call('dm_reduce_i', NE, I, V, H.fptr(vecobs_rec), 0, H.fptr(t_vr), None, H.stream())
+                _multi_sum([(t_lv, 1.0 / NE)], dev, out=mbuf[15:16])
 
         pk.update(loss=loss, image=image, action=action, reset=reset, enc_acts=enc_acts, rssm_acts=rssm_acts,
-                  dec_acts=dec_acts, r_acts=r_acts, t_acts=t_acts, dmu=dmu, dtl=dtl, ws=ws, mbuf=mbuf, iw=iw, aux=aux)
+                  dec_acts=dec_acts, r_acts=r_acts, t_acts=t_acts, dmu=dmu, dtl=dtl, ws=ws, mbuf=mbuf, iw=iw, aux=aux,
+                  v_acts=v_acts, dmu_v=dmu_v)
         pk['tensors'] = LazyTensors(loss_kl=t_kl, entropy_prior=t_ep, entropy_post=t_eq,
                                     loss_image=t_li, image_rec=None,
                                     loss_reward=t_lr, reward_rec=t_rr,
@@ -967,6 +1039,9 @@ class WorldModel(_Params):
         pk['tensors'].lazy('image_rec', image_rec_thunk)
         pk['metrics'] = dict(loss_model=mbuf[6], loss_kl=means[0], entropy_prior=means[4], entropy_post=means[5],
                              loss_image=means[1], loss_reward=means[2], loss_terminal=means[3])
+        if V:
+            pk['metrics'].update(loss_vecobs=mbuf[15])
+            pk['tensors'].update(loss_vecobs=t_lv, vecobs_rec=t_vr)
         if aux is not None:
             pk['metrics'].update(loss_critic_aux=mbuf[24], policy_value_aux=mbuf[25])
             pk['tensors']['policy_value_aux'] = aux['value'].view(T, B)
@@ -993,13 +1068,17 @@ class WorldModel(_Params):
         if iw is not None and not pk.get('iw_applied'):
             for dout in (pk['dmu'], pk['dtl']):
                 H.call('dm_scale_rows', N, 1, H.fptr(dout), 1, H.fptr(iw), 1.0, H.stream())
+            if pk.get('dmu_v') is not None:
+                H.call('dm_scale_rows', N, c.vecobs_size, H.fptr(pk['dmu_v']), c.vecobs_size, H.fptr(iw), 1.0, H.stream())
             pk['iw_applied'] = True
         heads = [(dec.reward.model, pk['r_acts'], pk['dmu']), (dec.terminal.model, pk['t_acts'], pk['dtl'])]
+        if pk.get('dmu_v') is not None:
+            heads.append((dec.vecobs.model, pk['v_acts'], pk['dmu_v']))
         if pk.get('aux') is not None:          # the auxiliary critic trains on the world model's own features (not detached)
             heads.append((self.ac_aux.critic, pk['aux']['acts'], pk['aux']['dvalue']))
         for head, acts, dout in heads:
             st, gs = head.struct(), head.grad_struct(gof)
-            H.call('dm_mlp_head_bwd', N, F_, head.hidden_dim, head.hidden_layers, 1, H.fptr(feat), F_, ctypes.byref(st),
+            H.call('dm_mlp_head_bwd', N, F_, head.hidden_dim, head.hidden_layers, head.out_dim, H.fptr(feat), F_, ctypes.byref(st),
                    H.fptr(acts), H.fptr(dout), ctypes.byref(gs), H.fptr(dfeat), F_, 1, H.ptr(ws), ws.numel(), H.stream())
         # image decoder
         dl = dec.image.layers()
@@ -1062,8 +1141,22 @@ class WorldModel(_Params):
             enc_p = H.conv_struct([m.weight for m in enc.convs()], [m.bias for m in enc.convs()])
             enc_g = H.conv_struct([gof[id(m.weight)] for m in enc.convs()], [gof[id(m.bias)] for m in enc.convs()],
                                   cls=H.dm_conv_grads)
-            H.call('dm_conv_encoder_bwd', ctypes.byref(pk['shp_e']), H.ptr(pk['image']), ctypes.byref(enc_p),
-                   H.fptr(pk['enc_acts']), H.fptr(dembed), ctypes.byref(enc_g), H.ptr(ws_enc), ws_enc.numel(), H.stream())
+            if pk.get('vecobs') is not None:      # the vecobs encoder: its output gradient is the trailing 256 columns of dembed
+                ev = self.encoder.encoder_vecobs
+                d_ev = dembed[:, enc.out_dim:].contiguous()
+                st, gs = ev.struct(), ev.grad_struct(gof)
+                H.call('dm_mlp_head_bwd', NE, ev.in_dim, ev.hidden_dim, ev.hidden_layers, ev.out_dim, H.fptr(pk['vecobs']), ev.in_dim,
+                       ctypes.byref(st), H.fptr(pk['ev_acts']), H.fptr(d_ev), ctypes.byref(gs), None, 0, 0, H.ptr(ws_enc),
+                       ws_enc.numel(), H.stream())
+            if pk.get('plane_r') is not None or pk.get('vecobs') is not None:
+                shp_c = H.dm_shape.from_buffer_copy(pk['shp_e'])
+                shp_c.E = enc.out_dim
+                H.call('dm_conv_encoder_bwd_planes', ctypes.byref(shp_c), H.ptr(pk['image']), ctypes.byref(enc_p),
+                       H.fptr(pk['plane_r']), H.fptr(pk['plane_t']), H.fptr(pk['enc_acts']), H.fptr(dembed), E, ctypes.byref(enc_g),
+                       H.ptr(ws_enc), ws_enc.numel(), H.stream())
+            else:
+                H.call('dm_conv_encoder_bwd', ctypes.byref(pk['shp_e']), H.ptr(pk['image']), ctypes.byref(enc_p),
+                       H.fptr(pk['enc_acts']), H.fptr(dembed), ctypes.byref(enc_g), H.ptr(ws_enc), ws_enc.numel(), H.stream())
         except BaseException:
             if side:
                 H.lib().dm_wgrad_side_join(H.stream())      # disarm this thread; the error propagates
@@ -1104,6 +1197,18 @@ class WorldModel(_Params):
             tl, _ = dec.terminal.model.fwd(fp, F_, N, ws, save_acts=False)
             lr, lt, rp, tp, scratch = (torch.empty(N, device=dev) for _ in range(5))
             loss_const = REWARD_STD ** 2 * (math.log(REWARD_STD) + math.log(math.sqrt(2 * math.pi)))
+            V = c.vecobs_size
+            if V:
+                vec_t = pk['vecobs'].repeat_interleave(I, dim=0).contiguous() if I > 1 else pk['vecobs']
+                mu_v, _ = dec.vecobs.model.fwd(fp, F_, N, ws, save_acts=False)
+                lv, vp = torch.empty(N, device=dev), torch.empty(N, V, device=dev)
+                H.call('dm_head_loss_normal_nd', N, V, H.fptr(mu_v), H.fptr(vec_t), 0.0, loss_const, H.fptr(lv), None, H.fptr(vp),
+                       H.stream())
+                if I > 1:
+                    lv_i, vp_i = lv, vp
+                    lv, vp = torch.empty(NE, device=dev), torch.empty(NE, V, device=dev)
+                    H.call('dm_reduce_i', NE, I, 1, H.fptr(lv_i), 1, H.fptr(lv), None, H.stream())
+                    H.call('dm_reduce_i', NE, I, V, H.fptr(vp_i), 0, H.fptr(vp), None, H.stream())
             reward_t, terminal_t = obs['reward'].float().contiguous(), obs['terminal'].float().contiguous()
             if I > 1:                              # targets expanded over I (decoders.py:270,305: insert_dim)
                 reward_t = reward_t.repeat_interleave(I, dim=1).contiguous()
@@ -1124,6 +1229,9 @@ class WorldModel(_Params):
             tensors = dict(logprob_image=tb(li), logprob_reward=tb(lr), logprob_terminal=tb(lt),
                            image_pred=image_pred, reward_pred=tb(rp), terminal_pred=tb(tp))
             metrics = dict(logprob_image=li.mean(), logprob_reward=lr.mean(), logprob_terminal=lt.mean())
+            if V:
+                tensors.update(logprob_vecobs=tb(lv), vecobs_pred=vp.view(T, B, V))
+                metrics.update(logprob_vecobs=lv.mean())
             nan = torch.full((), float('nan'), device=dev)
             nanmean = lambda x: torch.nansum(x) / (~torch.isnan(x)).sum()     # functions.py:149-150
             for sig in (-1, 1):

@@ -297,6 +297,8 @@ def preprocess_batch(batch, action_dim, clip_rewards=None, image_key='image'):
         raise ValueError(clip_rewards)
     out['reward'] = r
     out['reset'] = batch.get('reset', np.zeros((T, B), bool)).astype(bool)
+    if 'vecobs' in batch:                                    # preprocessing.py:162-163
+        out['vecobs'] = batch['vecobs'].astype(np.float32)
     return out
 
 
@@ -317,7 +319,7 @@ class ReplayFeed:
         # `terminal` always has a column: an episode without the field contributes zeros (SequentialReplay._copy), so a
         # repository that mixes files with and without it still yields the flags of those that carry them
         self._small = {k: np.empty((T, B) + probe[k].shape[1:], probe[k].dtype)
-                       for k in ('action', 'action_next', 'reward') if k in probe}
+                       for k in ('action', 'action_next', 'reward', 'vecobs') if k in probe}
         self._small['terminal'] = np.empty((T, B), probe['terminal'].dtype if 'terminal' in probe else np.float32)
         img = probe[image_key]
         if img.dtype != np.uint8 or img.ndim != 4:
@@ -325,6 +327,8 @@ class ReplayFeed:
         self._spec = {'image': ((T, B) + img.shape[1:], np.uint8), 'action': ((T, B, self.action_dim), np.float32),
                       'action_next': ((T, B, self.action_dim), np.float32), 'terminal': ((T, B), np.float32),
                       'reward': ((T, B), np.float32), 'reset': ((T, B), np.bool_)}
+        if 'vecobs' in probe:
+            self._spec['vecobs'] = ((T, B) + probe['vecobs'].shape[1:], np.float32)
 
     def spec(self):
         """{field: (shape, dtype)} of a slot."""
@@ -351,6 +355,8 @@ class ReplayFeed:
         elif self.clip_rewards == 'log1p':
             r = np.log1p(r)
         slot['reward'][...] = r
+        if 'vecobs' in raw:
+            slot['vecobs'][...] = raw['vecobs']
         return slot
 
 
