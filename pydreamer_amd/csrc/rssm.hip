@@ -2,26 +2,46 @@
 // Reference: RSSMCore.forward (rssm.py:21-78), RSSMCell.forward / forward_prior / batch_prior (rssm.py:125-193),
 // nn.GRUCell via GRUCellStack (rnn.py:40-67), Dreamer.dream (dreamer.py:188-216), ActorCritic.forward_actor (a2c.py:43-55).
 //
-// Design notes
-//  * a_mlp(action) and post_mlp_e(embed) are loop-invariant and hoisted out of the T loop as two (T*B)-row GEMMs.
-//  * h and z of every step are written straight into the (T*B, D+Z) feature matrix (h at column 0, z at column D),
-//    so to_feature()'s concat (rssm.py:83-84) never materialises; consumers read sub-matrices through leading dims.
-//  * Only the data-path GEMMs (d? @ W) are inside the sequential BPTT loop; every weight gradient is one
-//    (T*B)-row split-K GEMM after the loop, every bias / LayerNorm-parameter gradient one column-sum.
-//  * reset masks (rssm.py:41,134-135) are applied forward by a tiny row-scale kernel (the masked states are saved
-//    for backward) and backward through the GEMM / GRU epilogues' row_zero option.
+// Host code only: this file decides which launches a step makes.  Each entry point reads validate -> dimensions -> carve ->
+// plan (a context struct: the buffers, the optional buffers it obtained, the schedule) -> a loop that calls one step
+// function per iteration -> tail.
+//  * Loop-invariant projections (a_mlp(action), post_mlp_e(embed), the batched prior) are hoisted out of the T loop as
+//    (T*B)-row GEMMs.  h and z of every step are written straight into the (T*B, D+Z) feature matrix (h at column 0, z at
+//    column D), so to_feature()'s concat (rssm.py:83-84) never materialises; consumers read sub-matrices through leading dims.
+//  * T loop: post_step_fused (LayerNorm+ELU in the consuming product's prologue or in the z_embed gather, the sampler in the
+//    logits product's epilogue) or post_step_plain; <= 32-row batches hand steps 1.. over to ONE persistent kernel (rssm_lds.hip).
+//  * BPTT loop: bptt_step_fused (LayerNorm backward in prologues, or FOLDED over the producing product's epilogue and a plain
+//    consumer; gates backward in an epilogue), bptt_step_single, bptt_step_stacked.  Only data-path products are in the loop:
+//    the weight gradients are one ordered list, launched on the side stream in time chunks beside the loop (single-layer
+//    cells) or in the tail (stacks); every bias / LayerNorm-parameter gradient is one column pass in the tail.
+//  * Rollout: rollout_actor (actor + action draw), rollout_cell (prior cell, prior head, latent draw) per horizon step.
+//  * Reset masks (rssm.py:41,134-135) are applied forward by the kernels that produce the next step's h and z (step 0: a
+//    stand-alone mask kernel; the masked states are saved for backward) and backward through the products' row_zero option.
 #include "common.h"
+
+static inline int rssm_gru_kind(const dm_shape* s) { return (s->flags & DM_FLAG_GRU_MASK) >> DM_FLAG_GRU_SHIFT; }
+static inline int rssm_gru_layers(const dm_shape* s) {
+  return 1 + ((s->flags & DM_FLAG_GRU_LAYERS_MASK) >> DM_FLAG_GRU_LAYERS_SHIFT);
+}
+// Z: width of z (S one-hot groups of C, or S Gaussian dimensions when C = 0); ZP: width of the posterior / prior parameters
+// (logits, or mean | raw std - rssm.py:112,117); F: width of a feature row [h | z]; N = T*B; kind: 0 nn.GRUCell, 1 / 2 the
+// LayerNorm cells
+struct RssmDims {
+  int T, B, N, D, Hd, S, C, Z, ZP, F, E, A, kind, layers;
+  bool gauss;
+};
+static void rssm_dims(const dm_shape* s, RssmDims* d) {
+  d->T = s->T; d->B = s->B; d->N = s->T * s->B; d->D = s->D; d->Hd = s->Hd; d->S = s->S; d->C = s->C;
+  d->Z = s->S * (s->C ? s->C : 1); d->ZP = s->S * (s->C ? s->C : 2); d->F = d->D + d->Z; d->E = s->E; d->A = s->A;
+  d->gauss = s->C == 0; d->kind = rssm_gru_kind(s); d->layers = rssm_gru_layers(s);
+}
 
 struct RssmActs {
   float *ea, *ee, *hin, *zin, *x1, *st1, *za, *gi, *gh, *x2, *st2, *pin, *x3, *st3, *prin;
   float *gs, *gst;      // LayerNorm GRU cells: pre-LayerNorm gate sums (N,3D) and their statistics (N,6 per stack layer)
 };
-static inline int rssm_gru_kind(const dm_shape* s) { return (s->flags & DM_FLAG_GRU_MASK) >> DM_FLAG_GRU_SHIFT; }
-static inline int rssm_gru_layers(const dm_shape* s) {
-  return 1 + ((s->flags & DM_FLAG_GRU_LAYERS_MASK) >> DM_FLAG_GRU_LAYERS_SHIFT);
-}
-static size_t rssm_carve(const dm_shape* s, float* base, RssmActs* a) {
-  const size_t N = (size_t)s->T * s->B, Hd = s->Hd, D = s->D, Z = (size_t)s->S * (s->C ? s->C : 1);   // width of z
+static size_t rssm_carve(const RssmDims& d, float* base, RssmActs* a) {
+  const size_t N = (size_t)d.T * d.B, Hd = d.Hd, D = d.D, Z = d.Z;
   DmArena ar(base, (size_t)1 << 62);
   RssmActs t;
   t.ea = ar.take(N * Hd); t.ee = ar.take(N * Hd);
@@ -30,14 +50,15 @@ static size_t rssm_carve(const dm_shape* s, float* base, RssmActs* a) {
   t.gi = ar.take(N * 3 * D); t.gh = ar.take(N * 3 * D);
   t.x2 = ar.take(N * Hd); t.st2 = ar.take(N * 2); t.pin = ar.take(N * Hd);
   t.x3 = ar.take(N * Hd); t.st3 = ar.take(N * 2); t.prin = ar.take(N * Hd);
-  const bool lncell = rssm_gru_kind(s) != 0;
-  t.gs = ar.take(lncell ? N * 3 * D : 0); t.gst = ar.take(lncell ? N * 6 * rssm_gru_layers(s) : 0);
+  t.gs = ar.take(d.kind ? N * 3 * D : 0); t.gst = ar.take(d.kind ? N * 6 * d.layers : 0);
   if (a) *a = t;
   return ar.off;
 }
 extern "C" size_t dm_rssm_acts_floats(const dm_shape* shp) {
   if (!shp) return 0;
-  return rssm_carve(shp, nullptr, nullptr);
+  RssmDims d;
+  rssm_dims(shp, &d);
+  return rssm_carve(d, nullptr, nullptr);
 }
 
 static int rssm_check(const dm_shape* s) {
@@ -110,16 +131,20 @@ static int norm_elu_bwd_params(int rows, int n, const float* x, int ldx, const f
   return dm_ln_elu_bwd_params_launch(rows, n, x, ldx, y, ldy, stats, dy, lddy, dgamma, dbeta, ws, ws_bytes, st);
 }
 
-// y = x @ W^T (+ bias) (+ add)
-static int linear(hipStream_t st, void* sk, size_t skb, int rows, int nout, int kin, const float* x, int ldx,
-                  const float* W, const float* bias, const float* add, int ldadd, float* y, int ldy) {
+// y = x @ W^T (+ bias) (+ add): the descriptor (the chain steps add prologues, epilogues and fragment copies), and the launch
+static DmGemm linear_q(int rows, int nout, int kin, const float* x, int ldx, const float* W, const float* bias,
+                       const float* add, int ldadd, float* y, int ldy) {
   DmGemm q;
   q.M = rows; q.N = nout; q.K = kin;
   q.A = x; q.lda = ldx;
   q.B = W; q.ldb = kin;
   q.C = y; q.ldc = ldy;
   q.bias = bias; q.add = add; q.ldadd = ldadd;
-  return dm_gemm_launch(q, sk, skb, st);
+  return q;
+}
+static int linear(hipStream_t st, void* sk, size_t skb, int rows, int nout, int kin, const float* x, int ldx,
+                  const float* W, const float* bias, const float* add, int ldadd, float* y, int ldy) {
+  return dm_gemm_launch(linear_q(rows, nout, kin, x, ldx, W, bias, add, ldadd, y, ldy), sk, skb, st);
 }
 // dW[o][i] = sum_r dy[r][o] x[r][i]
 static int wgrad(hipStream_t st, void* sk, size_t skb, int rows, int nout, int kin, const float* dy, int lddy,
@@ -149,8 +174,8 @@ static int dgrad(hipStream_t st, void* sk, size_t skb, int rows, int nout, int k
 
 // dx[r][i] (+)= mask_r * sum_o dy[r][o] Wt[i][o]   (Wt = W^T materialised once per backward pass: the B-row chain
 // products of the BPTT loop then read their weights k-contiguous, the layout the skinny kernel streams fastest)
-static int dgrad_t(hipStream_t st, void* sk, size_t skb, int rows, int nout, int kin, const float* dy, int lddy,
-                   const float* Wt, float* dx, int lddx, int accum, const uint8_t* row_zero) {
+static DmGemm dgrad_t_q(int rows, int nout, int kin, const float* dy, int lddy, const float* Wt, float* dx, int lddx,
+                        int accum, const uint8_t* row_zero) {
   DmGemm q;
   q.M = rows; q.N = kin; q.K = nout;
   q.A = dy; q.lda = lddy;
@@ -158,7 +183,11 @@ static int dgrad_t(hipStream_t st, void* sk, size_t skb, int rows, int nout, int
   q.C = dx; q.ldc = lddx;
   q.flags = accum ? DM_GEMM_ACCUM : 0;
   q.row_zero = row_zero;
-  return dm_gemm_launch(q, sk, skb, st);
+  return q;
+}
+static int dgrad_t(hipStream_t st, void* sk, size_t skb, int rows, int nout, int kin, const float* dy, int lddy,
+                   const float* Wt, float* dx, int lddx, int accum, const uint8_t* row_zero) {
+  return dm_gemm_launch(dgrad_t_q(rows, nout, kin, dy, lddy, Wt, dx, lddx, accum, row_zero), sk, skb, st);
 }
 static int transpose(hipStream_t st, const float* W, float* Wt, int rows, int cols) {
   return dm_permute4_launch(W, Wt, 1, 1, rows, cols, 0, 1, 3, 2, st);
@@ -185,6 +214,159 @@ static int gru_stack_fwd(hipStream_t st, void* sk, size_t skb, const GruStack& k
   return DM_OK;
 }
 
+// ---------------------------------------------------------------- posterior T loop --------------
+struct PostCtx : RssmDims {
+  RssmActs a; GruStack gk;
+  const float* const* p; hipStream_t st; void* ws; size_t skb;      // ws: the split-K scratch at the head of the workspace
+  const uint8_t* reset; const float* u; const int32_t* forced; float *feat, *post; int32_t* idx;
+  // Fused schedule (5 launches per step instead of 8) when the <= 64-row products qualify: the two LayerNorm+ELU stages
+  // ride in the PROLOGUE of the product that consumes them (each workgroup recomputes the row statistics of its <= 64
+  // rows from L2) and the straight-through sampler rides in the EPILOGUE of the posterior-logits product (one 32-logit
+  // group per workgroup).  The post-LayerNorm activations `za` / `pin` that only the backward pass needs (weight
+  // gradients, ELU') are then produced for ALL rows by two batched launches after the loop.
+  bool fuse_ln, fuse_sample;
+  // z_mlp of the sampled (one-hot) latent as a gather-sum over rows of z_mlp^T (dm_z_embed_launch): every step after the
+  // first takes its z from the sampler, whose indices are at hand; the first step's z comes from the caller as a dense
+  // vector and keeps the product.
+  float* wzt;
+  // Fragment-major copies of the chain's <= 64-row operands (common.h dm_frag_off), written by the kernel that produces
+  // each operand next to its ordinary copy and read by the product that consumes it: z_in -> x1 -> (gi | gh from h_in)
+  // -> h -> x2 -> z.  One buffer per operand is enough (producer and consumer alternate in stream order).
+  float *zinf, *x1f, *hinf, *hf, *x2f;
+  // The fused schedule's steps after the first as ONE persistent kernel with the cell's weights stationary in
+  // LDS (rssm_lds.hip): the first step runs as launches (its z is a dense vector from the caller) and leaves h, the masked
+  // inputs and the indices the kernel's first step continues from.
+  float* psync; size_t psync_floats;
+
+  // Decides the schedule and takes the optional buffers (a small workspace keeps the schedule without them); no launches.
+  int plan(size_t ws_bytes) {
+    const bool stacked = gk.L > 1;      // GRUCellStack with several layers: the unfused schedule, 3 launches per layer
+    const bool normed = p[DM_RSSM_IN_G] != nullptr;      // layer_norm=False: all three norms are NoNorm (null parameters)
+    DM_REQUIRE((p[DM_RSSM_POST_G] != nullptr) == normed && (p[DM_RSSM_PRIOR_G] != nullptr) == normed, DM_E_NULL,
+               "rssm: the cell's three norms must be all LayerNorm or all NoNorm");
+    fuse_ln = normed && !stacked && !gauss && dm_skinny_ln_ok(B, 3 * D, Hd) && dm_skinny_ln_ok(B, ZP, Hd) &&
+              (ZP >= 64 * 1024 / Hd);
+    fuse_sample = fuse_ln && C == 32 && (Z & 31) == 0 && (F & 3) == 0 && (D & 3) == 0 &&
+                  (((uintptr_t)feat | (uintptr_t)a.zin) & 15) == 0;
+    DmArena ar(ws, ws_bytes);
+    ar.take(DM_SPLITK_FLOATS);
+    if (!gauss && idx && T > 1 && dm_z_embed_ok(Hd)) {
+      const size_t mark = ar.off;
+      float* w = ar.take((size_t)Z * Hd);
+      if (ar.ok) wzt = w;
+      else { ar.off = mark; ar.ok = true; }
+    }
+    if (fuse_sample && kind == 0 && B <= 64) {
+      float* f0 = ar.take(dm_frag_floats(Z)); float* f1 = ar.take(dm_frag_floats(Hd)); float* f2 = ar.take(dm_frag_floats(D));
+      float* f3 = ar.take(dm_frag_floats(D)); float* f4 = ar.take(dm_frag_floats(Hd));
+      if (ar.ok) { zinf = f0; x1f = f1; hinf = f2; hf = f3; x2f = f4; }
+    }
+    if (normed && !stacked && !gauss && kind == 0 && wzt && idx && (F & 3) == 0 && T >= 3 && dm_rssm_lds_ok(B, D, Hd, S, C)) {
+      psync_floats = dm_rssm_lds_ws_floats(B, D, Hd, S, C, T - 1);
+      float* sy = ar.take(psync_floats);
+      if (ar.ok) psync = sy;
+      else ar.ok = true;
+    }
+    return DM_OK;
+  }
+
+  // step t+1's masked inputs and reset flags: written / read by the kernels that produce h_t and z_t (null at the last step)
+  float* hin_next(int t) const { return t + 1 < T ? a.hin + (size_t)(t + 1) * B * D : nullptr; }
+  float* zin_next(int t) const { return t + 1 < T ? a.zin + (size_t)(t + 1) * B * Z : nullptr; }
+  const uint8_t* reset_next(int t) const { return t + 1 < T ? reset + (size_t)(t + 1) * B : nullptr; }
+
+  // x1 = z_mlp(z) + a_mlp(a) (rssm.py:138-139): the gather-sum from the indices step t-1 drew, else the product.
+  // ln_z: the gather kernel owns complete rows, so it also writes za = ELU(in_norm(x1)) (rssm.py:140) and the statistics.
+  int post_x1(int t, bool ln_z) const {
+    const size_t r0 = (size_t)t * B;
+    if (ln_z)
+      return dm_z_embed_launch(B, Hd, S, C, idx + (r0 - B) * S, reset + r0, wzt, p[DM_RSSM_Z_B], a.ea + r0 * Hd, Hd, nullptr,
+                               nullptr, a.x1 + r0 * Hd, Hd, nullptr, p[DM_RSSM_IN_G], p[DM_RSSM_IN_B], 1e-3f, a.za + r0 * Hd, Hd,
+                               st, x1f, a.st1 + r0 * 2);
+    if (wzt && t > 0)
+      return dm_z_embed_launch(B, Hd, S, C, idx + (r0 - B) * S, reset + r0, wzt, p[DM_RSSM_Z_B], a.ea + r0 * Hd, Hd, nullptr,
+                               nullptr, a.x1 + r0 * Hd, Hd, x1f, nullptr, nullptr, 0.f, nullptr, 0, st);
+    DmGemm q = linear_q(B, Hd, Z, a.zin + r0 * Z, Z, p[DM_RSSM_Z_W], p[DM_RSSM_Z_B], a.ea + r0 * Hd, Hd, a.x1 + r0 * Hd, Hd);
+    q.A_frag = zinf; q.C_frag = x1f;
+    return dm_gemm_launch(q, ws, skb, st);
+  }
+  // h = GRUCell(za, h_in) (rssm.py:141), single layer: the two gate products in one launch, then the gates.
+  // prologue: the first product reads x1 and applies in_norm + ELU itself (else za holds ELU(in_norm(x1)) already).
+  int post_cell(int t, bool prologue) const {
+    const size_t r0 = (size_t)t * B;
+    const float* hin = a.hin + r0 * D;
+    DmGemm gi_q = linear_q(B, 3 * D, Hd, (prologue ? a.x1 : a.za) + r0 * Hd, Hd, p[DM_RSSM_GRU_WIH], p[DM_RSSM_GRU_BIH], nullptr, 0,
+                           a.gi + r0 * 3 * D, 3 * D);
+    if (prologue) { gi_q.ln_g = p[DM_RSSM_IN_G]; gi_q.ln_b = p[DM_RSSM_IN_B]; gi_q.ln_eps = 1e-3f; }
+    gi_q.A_frag = x1f;      // (fused schedule: the copy of whichever operand this form reads)
+    DmGemm gh_q = linear_q(B, 3 * D, D, hin, D, p[DM_RSSM_GRU_WHH], p[DM_RSSM_GRU_BHH], nullptr, 0, a.gh + r0 * 3 * D, 3 * D);
+    gh_q.A_frag = hinf;
+    DM_TRY(dm_gemm_pair_launch(gi_q, gh_q, ws, skb, st));
+    if (kind == 0)
+      return dm_gru_gates_fwd_launch(B, D, a.gi + r0 * 3 * D, a.gh + r0 * 3 * D, hin, D, feat + r0 * F, F, hin_next(t),
+                                     reset_next(t), hf, t + 1 < T ? hinf : nullptr, st);
+    return dm_gru_norm_fwd_launch(kind, B, D, a.gi + r0 * 3 * D, a.gh + r0 * 3 * D, hin, D, gk.lng[0], gk.lnb[0], feat + r0 * F, F,
+                                  a.gs + r0 * 3 * D, a.gst + r0 * 6, hin_next(t), reset_next(t), st);
+  }
+  // x2 = post_mlp_h(h) + post_mlp_e(embed)                                              rssm.py:143-144
+  int post_x2(int t) const {
+    const size_t r0 = (size_t)t * B;
+    DmGemm q = linear_q(B, Hd, D, feat + r0 * F, F, p[DM_RSSM_POST_H_W], p[DM_RSSM_POST_H_B], a.ee + r0 * Hd, Hd, a.x2 + r0 * Hd, Hd);
+    q.A_frag = hf; q.C_frag = x2f;
+    return dm_gemm_launch(q, ws, skb, st);
+  }
+  // z ~ OneHotCategoricalStraightThrough(post) as its own launch                        rssm.py:147-148
+  int post_sample(int t) const {
+    const size_t r0 = (size_t)t * B;
+    return dm_sample_onehot_launch(B, S, C, post + r0 * ZP, ZP, u ? u + r0 * S : nullptr, forced ? forced + r0 * S : nullptr,
+                                   feat + r0 * F + D, F, idx ? idx + r0 * S : nullptr, zin_next(t), reset_next(t), st);
+  }
+
+  // 5 launches (one plain or LayerNorm cell, categorical latents, the three norms LayerNorm).
+  int post_step_fused(int t) const {
+    const size_t r0 = (size_t)t * B;
+    // in_norm + ELU in the gather (the prologue form makes each of the gate product's 226 workgroups redo the LayerNorm + ELU
+    // of the whole operand); the row-per-workgroup form holds <= 32 groups (stoch_dim 64 / 96 take the prologue)
+    const bool ln_z = wzt && t > 0 && x1f && S <= 32;
+    DM_TRY(post_x1(t, ln_z));
+    DM_TRY(post_cell(t, !ln_z));
+    DM_TRY(post_x2(t));
+    // post = post_mlp(ELU(post_norm(x2))), LayerNorm in the prologue                             rssm.py:145-146
+    DmGemm pq = linear_q(B, ZP, Hd, a.x2 + r0 * Hd, Hd, p[DM_RSSM_POST_W], p[DM_RSSM_POST_OB], nullptr, 0, post + r0 * ZP, ZP);
+    pq.ln_g = p[DM_RSSM_POST_G]; pq.ln_b = p[DM_RSSM_POST_B]; pq.ln_eps = 1e-3f;
+    pq.A_frag = x2f;
+    if (!fuse_sample) {
+      DM_TRY(dm_gemm_launch(pq, ws, skb, st));
+      return post_sample(t);
+    }
+    DmSample sm;      // ... and z ~ OneHotCategoricalStraightThrough(post) in the epilogue        rssm.py:147-148
+    sm.u = u ? u + r0 * S : nullptr; sm.forced = forced ? forced + r0 * S : nullptr;
+    sm.onehot = feat + r0 * F + D; sm.ldo = F; sm.idx = idx ? idx + r0 * S : nullptr;
+    sm.z_next = zin_next(t); sm.next_reset = reset_next(t); sm.z_next_frag = zinf;
+    return dm_gemm_sample_launch(pq, sm, st);
+  }
+  // 8 launches (3 per layer for a cell stack): the reset masks of step t+1 are applied by the kernels that produce h_t and
+  // z_t, and a single cell's two gate products share one launch.
+  int post_step_plain(int t) const {
+    const size_t r0 = (size_t)t * B;
+    DM_TRY(post_x1(t, false));
+    DM_TRY(norm_elu_fwd(B, Hd, a.x1 + r0 * Hd, Hd, p[DM_RSSM_IN_G], p[DM_RSSM_IN_B], 1e-3f, a.za + r0 * Hd, Hd, a.st1 + r0 * 2, st));
+    if (gk.L > 1)
+      DM_TRY(gru_stack_fwd(st, ws, skb, gk, B, Hd, D, a.za + r0 * Hd, a.hin + r0 * D, D, a.gi + r0 * 3 * D, a.gh + r0 * 3 * D,
+                           feat + r0 * F, F, hin_next(t), reset_next(t), kind ? a.gs + r0 * 3 * D : nullptr,
+                           kind ? a.gst + r0 * 6 * gk.L : nullptr));
+    else
+      DM_TRY(post_cell(t, false));
+    DM_TRY(post_x2(t));
+    // post = post_mlp(ELU(post_norm(x2)))                                                 rssm.py:145-146
+    DM_TRY(norm_elu_fwd(B, Hd, a.x2 + r0 * Hd, Hd, p[DM_RSSM_POST_G], p[DM_RSSM_POST_B], 1e-3f, a.pin + r0 * Hd, Hd,
+                        a.st2 + r0 * 2, st));
+    DM_TRY(linear(st, ws, skb, B, ZP, Hd, a.pin + r0 * Hd, Hd, p[DM_RSSM_POST_W], p[DM_RSSM_POST_OB], nullptr, 0, post + r0 * ZP,
+                  ZP));
+    return post_sample(t);
+  }
+};
+
 extern "C" int dm_rssm_sequence_fwd(const dm_shape* s, const float* embed, const float* action, const uint8_t* reset,
                                     const float* h0, const float* z0, const float* u, const int32_t* forced_idx,
                                     const dm_rssm_params* P, float* acts, float* feat, float* post, float* prior,
@@ -195,200 +377,54 @@ extern "C" int dm_rssm_sequence_fwd(const dm_shape* s, const float* embed, const
   DmPrecisionScope prec(s->flags & DM_FLAG_BF16);
   DM_TRY(rssm_check(s));
   DM_REQUIRE(ws_bytes >= DM_SPLITK_FLOATS * sizeof(float), DM_E_WORKSPACE, "rssm_sequence_fwd: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  // Z: width of z (S one-hot groups of C, or S Gaussian dimensions when C = 0); ZP: width of the posterior / prior
-  // parameters (logits, or mean | raw std - rssm.py:112,117)
-  const int T = s->T, B = s->B, D = s->D, Hd = s->Hd, S = s->S, C = s->C, Z = S * (C ? C : 1), ZP = S * (C ? C : 2);
-  const int F = D + Z, E = s->E, A = s->A;
-  const bool gauss = C == 0;
-  const int N = T * B;
-  const size_t skb = DM_SPLITK_FLOATS * sizeof(float);
-  RssmActs a;
-  rssm_carve(s, acts, &a);
-  const float* const* p = P->p;
+  PostCtx c = {};
+  rssm_dims(s, &c);
+  rssm_carve(c, acts, &c.a);
+  c.p = P->p; c.st = (hipStream_t)stream; c.ws = ws; c.skb = DM_SPLITK_FLOATS * sizeof(float);
+  c.reset = reset; c.u = u; c.forced = forced_idx; c.feat = feat; c.post = post; c.idx = idx;
+  DM_TRY(gru_stack(s, c.p, nullptr, &c.gk));
+  DM_TRY(c.plan(ws_bytes));
+  const RssmActs& a = c.a;
+  const float* const* p = c.p;
+  const int N = c.N, D = c.D, Hd = c.Hd, Z = c.Z, ZP = c.ZP;
+  hipStream_t st = c.st;
+  const size_t skb = c.skb;
 
-  DM_TRY(linear(st, ws, skb, N, Hd, A, action, A, p[DM_RSSM_A_W], nullptr, nullptr, 0, a.ea, Hd));
-  DM_TRY(linear(st, ws, skb, N, Hd, E, embed, E, p[DM_RSSM_POST_E_W], nullptr, nullptr, 0, a.ee, Hd));
-
-  // Fused schedule (5 launches per step instead of 8) when the <= 64-row products qualify: the two LayerNorm+ELU stages
-  // ride in the PROLOGUE of the product that consumes them (each workgroup recomputes the row statistics of its <= 64
-  // rows from L2) and the straight-through sampler rides in the EPILOGUE of the posterior-logits product (one 32-logit
-  // group per workgroup).  The post-LayerNorm activations `za` / `pin` that only the backward pass needs (weight
-  // gradients, ELU') are then produced for ALL rows by two batched launches after the loop.
-  const int kind = rssm_gru_kind(s);
-  const float* lng[3] = {p[DM_RSSM_GRU_LN_G0], p[DM_RSSM_GRU_LN_G1], p[DM_RSSM_GRU_LN_G2]};
-  const float* lnb[3] = {p[DM_RSSM_GRU_LN_B0], p[DM_RSSM_GRU_LN_B1], p[DM_RSSM_GRU_LN_B2]};
-  DM_REQUIRE(kind == 0 || (lng[0] && lnb[0] && (kind == 2 || (lng[1] && lnb[1] && lng[2] && lnb[2]))), DM_E_NULL,
-             "rssm_sequence_fwd: LayerNorm GRU cell without its LayerNorm parameters");
-  GruStack gk;
-  DM_TRY(gru_stack(s, p, nullptr, &gk));
-  const bool stacked = gk.L > 1;      // GRUCellStack with several layers: the unfused schedule, 3 launches per layer
-  const bool normed = p[DM_RSSM_IN_G] != nullptr;      // layer_norm=False: all three norms are NoNorm (null parameters)
-  DM_REQUIRE((p[DM_RSSM_POST_G] != nullptr) == normed && (p[DM_RSSM_PRIOR_G] != nullptr) == normed, DM_E_NULL,
-             "rssm: the cell's three norms must be all LayerNorm or all NoNorm");
-  const bool fuse_ln = normed && !stacked && !gauss && dm_skinny_ln_ok(B, 3 * D, Hd) && dm_skinny_ln_ok(B, ZP, Hd) &&
-                       (ZP >= 64 * 1024 / Hd);
-  const bool fuse_sample = fuse_ln && C == 32 && (Z & 31) == 0 && (F & 3) == 0 && (D & 3) == 0 &&
-                           (((uintptr_t)feat | (uintptr_t)a.zin) & 15) == 0;
-  // Fragment-major copies of the chain's <= 64-row operands (common.h dm_frag_off), written by the kernel that produces
-  // each operand next to its ordinary copy and read by the product that consumes it: z_in -> x1 -> (gi | gh from h_in)
-  // -> h -> x2 -> z.  One buffer per operand is enough (producer and consumer alternate in stream order).
-  float *zinf = nullptr, *x1f = nullptr, *hinf = nullptr, *hf = nullptr, *x2f = nullptr;
-  DmArena ar(ws, ws_bytes);
-  ar.take(DM_SPLITK_FLOATS);
-  // z_mlp of the sampled (one-hot) latent as a gather-sum over rows of z_mlp^T (dm_z_embed_launch): every step after the
-  // first takes its z from the sampler, whose indices are at hand; the first step's z comes from the caller as a dense
-  // vector and keeps the product.
-  float* wzt = nullptr;
-  if (!gauss && idx && T > 1 && dm_z_embed_ok(Hd)) {
-    const size_t mark = ar.off;
-    float* w = ar.take((size_t)Z * Hd);
-    if (ar.ok) {
-      wzt = w;
-      DM_TRY(transpose(st, p[DM_RSSM_Z_W], wzt, Hd, Z));
-    } else {      // optional: a small workspace keeps the product
-      ar.off = mark; ar.ok = true;
-    }
+  DM_TRY(linear(st, ws, skb, N, Hd, c.A, action, c.A, p[DM_RSSM_A_W], nullptr, nullptr, 0, a.ea, Hd));
+  DM_TRY(linear(st, ws, skb, N, Hd, c.E, embed, c.E, p[DM_RSSM_POST_E_W], nullptr, nullptr, 0, a.ee, Hd));
+  if (c.wzt) DM_TRY(transpose(st, p[DM_RSSM_Z_W], c.wzt, Hd, Z));
+  // step 0's inputs: the caller's state under the first reset mask (every later step's are written by the step before it)
+  DM_TRY(dm_mask_rows2_launch(c.B, D, h0, D, a.hin, D, Z, z0, Z, a.zin, Z, reset, st));
+  if (c.zinf) {
+    DM_TRY(dm_frag_pack_launch(c.B, D, a.hin, D, c.hinf, st));
+    DM_TRY(dm_frag_pack_launch(c.B, Z, a.zin, Z, c.zinf, st));
   }
-  if (fuse_sample && kind == 0 && B <= 64) {
-    float* f0 = ar.take(dm_frag_floats(Z)); float* f1 = ar.take(dm_frag_floats(Hd)); float* f2 = ar.take(dm_frag_floats(D));
-    float* f3 = ar.take(dm_frag_floats(D)); float* f4 = ar.take(dm_frag_floats(Hd));
-    if (ar.ok) { zinf = f0; x1f = f1; hinf = f2; hf = f3; x2f = f4; }
-  }
-  // The fused schedule's steps after the first as ONE persistent kernel with the cell's weights stationary in
-  // LDS (rssm_lds.hip): the first step runs as launches (its z is a dense vector from the caller) and leaves h, the masked
-  // inputs and the indices the kernel's first step continues from.
-  float* psync = nullptr;
-  size_t psync_floats = 0;
-  if (normed && !stacked && !gauss && kind == 0 && wzt && idx && (F & 3) == 0 && T >= 3 && dm_rssm_lds_ok(B, D, Hd, S, C)) {
-    psync_floats = dm_rssm_lds_ws_floats(B, D, Hd, S, C, T - 1);
-    float* sy = ar.take(psync_floats);
-    if (ar.ok) psync = sy;
-    else ar.ok = true;
-  }
-  const int t_launch_end = psync ? 1 : T;
-  // 8 launches per step otherwise: the reset masks of step t+1 are applied by the kernels that produce h_t and z_t (only
-  // the first step needs the stand-alone mask kernel), and the GRU's two gate products share one launch.
-  for (int t = 0; t < t_launch_end; ++t) {
-    const size_t r0 = (size_t)t * B;
-    float* hin = a.hin + r0 * D;
-    float* zin = a.zin + r0 * Z;
-    if (t == 0) {
-      DM_TRY(dm_mask_rows2_launch(B, D, h0, D, hin, D, Z, z0, Z, zin, Z, reset, st));
-      if (zinf) {
-        DM_TRY(dm_frag_pack_launch(B, D, hin, D, hinf, st));
-        DM_TRY(dm_frag_pack_launch(B, Z, zin, Z, zinf, st));
-      }
-    }
-    const bool more = t + 1 < T;
-    float* hin_next = more ? a.hin + (r0 + B) * D : nullptr;
-    float* zin_next = more ? a.zin + (r0 + B) * Z : nullptr;
-    const uint8_t* reset_next = more ? reset + r0 + B : nullptr;
-    // x = z_mlp(z) + a_mlp(a) ; za = ELU(in_norm(x))                                   rssm.py:138-140
-    // (ln_z: the gather kernel owns complete rows, so it also normalises them and the gate product below runs plain - the
-    //  prologue form makes each of that product's 226 workgroups redo the LayerNorm + ELU of the whole operand)
-    const bool ln_z = fuse_ln && wzt && t > 0 && x1f && !stacked && S <= 32;     // the row-per-workgroup form holds <= 32 groups (stoch_dim 64 / 96 take the branch below)
-    if (ln_z) {
-      DM_TRY(dm_z_embed_launch(B, Hd, S, C, idx + (r0 - B) * S, reset + r0, wzt, p[DM_RSSM_Z_B], a.ea + r0 * Hd, Hd,
-                               nullptr, nullptr, a.x1 + r0 * Hd, Hd, nullptr, p[DM_RSSM_IN_G], p[DM_RSSM_IN_B], 1e-3f,
-                               a.za + r0 * Hd, Hd, st, x1f, a.st1 + r0 * 2));
-    } else if (wzt && t > 0) {
-      DM_TRY(dm_z_embed_launch(B, Hd, S, C, idx + (r0 - B) * S, reset + r0, wzt, p[DM_RSSM_Z_B], a.ea + r0 * Hd, Hd,
-                               nullptr, nullptr, a.x1 + r0 * Hd, Hd, x1f, nullptr, nullptr, 0.f, nullptr, 0, st));
-    } else {
-      DmGemm q;
-      q.M = B; q.N = Hd; q.K = Z; q.A = zin; q.lda = Z; q.B = p[DM_RSSM_Z_W]; q.ldb = Z; q.C = a.x1 + r0 * Hd; q.ldc = Hd;
-      q.bias = p[DM_RSSM_Z_B]; q.add = a.ea + r0 * Hd; q.ldadd = Hd;
-      q.A_frag = zinf; q.C_frag = x1f;
-      DM_TRY(dm_gemm_launch(q, ws, skb, st));
-    }
-    if (!fuse_ln)
-      DM_TRY(norm_elu_fwd(B, Hd, a.x1 + r0 * Hd, Hd, p[DM_RSSM_IN_G], p[DM_RSSM_IN_B], 1e-3f, a.za + r0 * Hd, Hd,
-                                  a.st1 + r0 * 2, st));
-    // h = GRUCell(za, h_in)                                                             rssm.py:141
-    if (stacked) {
-      DM_TRY(gru_stack_fwd(st, ws, skb, gk, B, Hd, D, a.za + r0 * Hd, hin, D, a.gi + r0 * 3 * D, a.gh + r0 * 3 * D,
-                           feat + r0 * F, F, hin_next, reset_next, kind ? a.gs + r0 * 3 * D : nullptr,
-                           kind ? a.gst + r0 * 6 * gk.L : nullptr));
-    } else {
-      DmGemm gi_q, gh_q;
-      gi_q.M = B; gi_q.N = 3 * D; gi_q.K = Hd; gi_q.A = a.za + r0 * Hd; gi_q.lda = Hd; gi_q.B = p[DM_RSSM_GRU_WIH]; gi_q.ldb = Hd;
-      if (ln_z) {
-        gi_q.A_frag = x1f;      // (holds ELU(in_norm(x1)) in this form)
-      } else if (fuse_ln) {
-        gi_q.A = a.x1 + r0 * Hd; gi_q.ln_g = p[DM_RSSM_IN_G]; gi_q.ln_b = p[DM_RSSM_IN_B]; gi_q.ln_eps = 1e-3f;
-        gi_q.A_frag = x1f;
-      }
-      gh_q.A_frag = hinf;
-      gi_q.C = a.gi + r0 * 3 * D; gi_q.ldc = 3 * D; gi_q.bias = p[DM_RSSM_GRU_BIH];
-      gh_q.M = B; gh_q.N = 3 * D; gh_q.K = D; gh_q.A = hin; gh_q.lda = D; gh_q.B = p[DM_RSSM_GRU_WHH]; gh_q.ldb = D;
-      gh_q.C = a.gh + r0 * 3 * D; gh_q.ldc = 3 * D; gh_q.bias = p[DM_RSSM_GRU_BHH];
-      DM_TRY(dm_gemm_pair_launch(gi_q, gh_q, ws, skb, st));
-    }
-    if (stacked) {
-    } else if (kind == 0)
-      DM_TRY(dm_gru_gates_fwd_launch(B, D, a.gi + r0 * 3 * D, a.gh + r0 * 3 * D, hin, D, feat + r0 * F, F, hin_next,
-                                     reset_next, hf, more ? hinf : nullptr, st));
-    else
-      DM_TRY(dm_gru_norm_fwd_launch(kind, B, D, a.gi + r0 * 3 * D, a.gh + r0 * 3 * D, hin, D, lng, lnb, feat + r0 * F, F,
-                                    a.gs + r0 * 3 * D, a.gst + r0 * 6, hin_next, reset_next, st));
-    // post = post_mlp(ELU(post_norm(post_mlp_h(h) + post_mlp_e(embed))))               rssm.py:143-146
-    {
-      DmGemm q;
-      q.M = B; q.N = Hd; q.K = D; q.A = feat + r0 * F; q.lda = F; q.B = p[DM_RSSM_POST_H_W]; q.ldb = D;
-      q.C = a.x2 + r0 * Hd; q.ldc = Hd; q.bias = p[DM_RSSM_POST_H_B]; q.add = a.ee + r0 * Hd; q.ldadd = Hd;
-      q.A_frag = hf; q.C_frag = x2f;
-      DM_TRY(dm_gemm_launch(q, ws, skb, st));
-    }
-    if (fuse_ln) {
-      DmGemm pq;      // post = post_mlp(ELU(post_norm(x2))), LayerNorm in the prologue
-      pq.M = B; pq.N = ZP; pq.K = Hd; pq.A = a.x2 + r0 * Hd; pq.lda = Hd; pq.B = p[DM_RSSM_POST_W]; pq.ldb = Hd;
-      pq.C = post + r0 * ZP; pq.ldc = ZP; pq.bias = p[DM_RSSM_POST_OB];
-      pq.ln_g = p[DM_RSSM_POST_G]; pq.ln_b = p[DM_RSSM_POST_B]; pq.ln_eps = 1e-3f;
-      pq.A_frag = x2f;
-      if (fuse_sample) {   // ... and z ~ OneHotCategoricalStraightThrough(post) in the epilogue        rssm.py:147-148
-        DmSample sm;
-        sm.u = u ? u + r0 * S : nullptr; sm.forced = forced_idx ? forced_idx + r0 * S : nullptr;
-        sm.onehot = feat + r0 * F + D; sm.ldo = F; sm.idx = idx ? idx + r0 * S : nullptr;
-        sm.z_next = zin_next; sm.next_reset = reset_next; sm.z_next_frag = zinf;
-        DM_TRY(dm_gemm_sample_launch(pq, sm, st));
-        continue;
-      }
-      DM_TRY(dm_gemm_launch(pq, ws, skb, st));
-    } else {
-      DM_TRY(norm_elu_fwd(B, Hd, a.x2 + r0 * Hd, Hd, p[DM_RSSM_POST_G], p[DM_RSSM_POST_B], 1e-3f, a.pin + r0 * Hd,
-                                  Hd, a.st2 + r0 * 2, st));
-      DM_TRY(linear(st, ws, skb, B, ZP, Hd, a.pin + r0 * Hd, Hd, p[DM_RSSM_POST_W], p[DM_RSSM_POST_OB], nullptr, 0,
-                    post + r0 * ZP, ZP));
-    }
-    // z ~ OneHotCategoricalStraightThrough(post)                                       rssm.py:147-148
-    DM_TRY(dm_sample_onehot_launch(B, S, C, post + r0 * ZP, ZP, u ? u + r0 * S : nullptr,
-                                   forced_idx ? forced_idx + r0 * S : nullptr, feat + r0 * F + D, F,
-                                   idx ? idx + r0 * S : nullptr, zin_next, reset_next, st));
-  }
-  if (psync) {
+  const int t_launch_end = c.psync ? 1 : c.T;
+  for (int t = 0; t < t_launch_end; ++t) DM_TRY(c.fuse_ln ? c.post_step_fused(t) : c.post_step_plain(t));
+  if (c.psync) {
     DmRssmLds pq;
-    pq.B = B; pq.D = D; pq.Hd = Hd; pq.S = S; pq.C = C; pq.F = F; pq.t_begin = 1; pq.t_end = T;
-    pq.wzt = wzt; pq.zb = p[DM_RSSM_Z_B];
+    pq.B = c.B; pq.D = D; pq.Hd = Hd; pq.S = c.S; pq.C = c.C; pq.F = c.F; pq.t_begin = 1; pq.t_end = c.T;
+    pq.wzt = c.wzt; pq.zb = p[DM_RSSM_Z_B];
     pq.wih = p[DM_RSSM_GRU_WIH]; pq.bih = p[DM_RSSM_GRU_BIH]; pq.whh = p[DM_RSSM_GRU_WHH]; pq.bhh = p[DM_RSSM_GRU_BHH];
     pq.wph = p[DM_RSSM_POST_H_W]; pq.bph = p[DM_RSSM_POST_H_B]; pq.wpo = p[DM_RSSM_POST_W]; pq.bpo = p[DM_RSSM_POST_OB];
     pq.in_g = p[DM_RSSM_IN_G]; pq.in_b = p[DM_RSSM_IN_B]; pq.post_g = p[DM_RSSM_POST_G]; pq.post_b = p[DM_RSSM_POST_B];
     pq.ea = a.ea; pq.ee = a.ee; pq.reset = reset; pq.u = u; pq.forced = forced_idx;
     pq.x1 = a.x1; pq.gi = a.gi; pq.gh = a.gh; pq.hin = a.hin; pq.zin = a.zin; pq.feat = feat; pq.x2 = a.x2; pq.post = post;
-    pq.idx = idx; pq.ws = psync; pq.ws_floats = psync_floats;
+    pq.idx = idx; pq.ws = c.psync; pq.ws_floats = c.psync_floats;
     DM_TRY(dm_rssm_lds_launch(pq, st));
   }
-  if (fuse_ln || psync) {     // what only the backward pass reads: post-LayerNorm activations + statistics of every row
+  if (c.fuse_ln || c.psync) {     // what only the backward pass reads: post-LayerNorm activations + statistics of every row
     DM_TRY(norm_elu_fwd(N, Hd, a.x1, Hd, p[DM_RSSM_IN_G], p[DM_RSSM_IN_B], 1e-3f, a.za, Hd, a.st1, st));
     DM_TRY(norm_elu_fwd(N, Hd, a.x2, Hd, p[DM_RSSM_POST_G], p[DM_RSSM_POST_B], 1e-3f, a.pin, Hd, a.st2, st));
   }
   // batch_prior over all (T*B) rows                                                    rssm.py:61,186-193
-  DM_TRY(linear(st, ws, skb, N, Hd, D, feat, F, p[DM_RSSM_PRIOR_H_W], p[DM_RSSM_PRIOR_H_B], nullptr, 0, a.x3, Hd));
+  DM_TRY(linear(st, ws, skb, N, Hd, D, feat, c.F, p[DM_RSSM_PRIOR_H_W], p[DM_RSSM_PRIOR_H_B], nullptr, 0, a.x3, Hd));
   DM_TRY(norm_elu_fwd(N, Hd, a.x3, Hd, p[DM_RSSM_PRIOR_G], p[DM_RSSM_PRIOR_B], 1e-3f, a.prin, Hd, a.st3, st));
   DM_TRY(linear(st, ws, skb, N, ZP, Hd, a.prin, Hd, p[DM_RSSM_PRIOR_W], p[DM_RSSM_PRIOR_OB], nullptr, 0, prior, ZP));
   return DM_OK;
 }
 
+// ---------------------------------------------------------------- BPTT --------------------------
 // A/B switch of the BPTT launch schedule's folded LayerNorm backward (include/dreamer_hip.h dm_bptt_fold_enable)
 static int g_bptt_fold = 1;
 extern "C" int dm_bptt_fold_enable(int on) {
@@ -396,6 +432,294 @@ extern "C" int dm_bptt_fold_enable(int on) {
   if (on >= 0) g_bptt_fold = on ? 1 : 0;
   return was;
 }
+
+struct BpttCtx : RssmDims {
+  RssmActs a; GruStack gk;
+  const float* const* p; float* const* g;
+  // Parameter gradients are leaves of this pass: nothing reads them before the gradient clip.  They go to `sw` - the
+  // library's weight-gradient side stream when the calling thread is armed (include/dreamer_hip.h dm_wgrad_side_arm), else
+  // `st` itself - with a split-K scratch of their own.
+  hipStream_t st, sw;
+  float *sk, *sk_w; size_t skb;
+  const float *embed, *action, *feat, *post; const uint8_t* reset; float *dfeat, *dpost;
+  float *dprin, *dx3, *dpin, *dx2, *dgi, *dgh, *dza, *dx1;
+  float *wt_post, *wt_post_h, *wt_ih, *wt_hh, *wt_z;      // W^T of the five backward-data products of a step
+  float *dgl, *lnpg, *lnpb;      // LayerNorm GRU cells: gradients w.r.t. the LayerNorm outputs; column sums for their parameters
+  // the side stream's own dx2 / dx1 (fused schedule: the LayerNorm backward of a chunk of rows is redone there instead of
+  // being shared with the chain), and whichever pair the side stream reads
+  float *dx2_w, *dx1_w; const float *dx2s, *dx1s;
+  // Fused schedule (5 launches per step instead of 8), mirror of the forward T loop: both LayerNorm+ELU BACKWARD stages
+  // ride in the prologue of the <= 64-row product that consumes their result, and the GRU gates backward rides in the
+  // epilogue of the product that completes dh'.  dx1 / dx2 (needed by the batched weight gradients) are then produced for
+  // all rows by batched launches.
+  bool fuse_b;
+  // ... in FOLDED form (common.h DmGemm::eg_x): the product that makes dpin (dza) also turns it into g = dy ELU'(pre) gamma in
+  // its epilogue - once, by the workgroup that owns the element, instead of once per consuming workgroup in a prologue - and
+  // the consuming product is a plain one whose epilogue applies the two row-mean terms.  That needs x2 W_post_h and x1 W_z for
+  // all rows (xw2, xwz: two batched products before the loop) and the weights' column sums (cs2, csz).
+  // fold_sm (32 classes): step t-1's straight-through softmax backward rides in the epilogue of the product that completes its dz'.
+  bool fold, fold_sm;
+  float *xw2, *xwz, *cs2, *csz, *eps2, *eps1; int nstrip;
+  // fragment-major copies (common.h dm_frag_off) of the two K = 3D operands of a step, dgi and dgh (written by the gates
+  // backward epilogue, read by the two products that follow it), and of dpin, dza (written by the product that makes them)
+  float *dgif, *dghf, *dpinf, *dzaf;
+  // time chunks of the batched weight gradients (single-layer cells): chunk k = steps [T*k/nchunk, T*(k+1)/nchunk); the loop
+  // runs t downwards, so the LAST chunk completes first - it overwrites the gradient, the others accumulate
+  int nchunk, next_chunk;
+  // The RSSM's weight gradients dW = dy^T x, in launch order: [0, 3) post_mlp, post_mlp_h, post_mlp_e; [3, 3 + 2L) W_ih, W_hh
+  // of each cell layer (layer 0 reads za, layer i the new state of layer i-1); then z_mlp, a_mlp.
+  struct Wgrad { const float* dy; int lddy, nout; const float* x; int ldx, kin; float* dW; } wg[3 + 2 * 4 + 2];
+  int nwg;
+
+  // Carves the workspace, decides the schedule and lists the weight gradients; no launches.
+  int plan(void* ws, size_t ws_bytes) {
+    const bool stacked = gk.L > 1;
+    const size_t rows = N;
+    DmArena ar(ws, ws_bytes);
+    sk = ar.take(DM_SPLITK_FLOATS);
+    dprin = ar.take(rows * Hd); dx3 = ar.take(rows * Hd); dpin = ar.take(rows * Hd); dx2 = ar.take(rows * Hd);
+    dgi = ar.take(rows * 3 * D); dgh = ar.take(rows * 3 * D); dza = ar.take(rows * Hd); dx1 = ar.take(rows * Hd);
+    wt_post = ar.take((size_t)ZP * Hd); wt_post_h = ar.take((size_t)Hd * D);
+    wt_ih = ar.take((size_t)3 * D * Hd); wt_hh = ar.take((size_t)3 * D * D); wt_z = ar.take((size_t)Hd * Z);
+    dgl = ar.take(kind ? rows * 3 * D : 0); lnpg = ar.take(kind ? (size_t)3 * D : 0); lnpb = ar.take(kind ? (size_t)3 * D : 0);
+    sk_w = ar.take(DM_SPLITK_FLOATS); dx2_w = ar.take(rows * Hd); dx1_w = ar.take(rows * Hd);
+    DM_REQUIRE(ar.ok, DM_E_WORKSPACE, "rssm_sequence_bwd: workspace too small (need %zu floats)", ar.off);
+    skb = DM_SPLITK_FLOATS * sizeof(float);
+    fuse_b = p[DM_RSSM_IN_G] != nullptr && !stacked && !gauss && kind == 0 && dm_skinny_ln_ok(B, D, Hd) &&
+             dm_skinny_ln_ok(B, Z, Hd) && (F & 3) == 0;
+    fold = fuse_b && g_bptt_fold && B <= 64 && (int64_t)Hd * ZP >= (int64_t)64 * 1024 &&
+           (int64_t)Hd * 3 * D >= (int64_t)64 * 1024 && (ZP & 3) == 0 && ((3 * D) & 3) == 0 && ZP >= 16;
+    nstrip = (Hd + 15) / 16;
+    if (fold) {
+      const size_t mark = ar.off;
+      xw2 = ar.take(rows * D); xwz = ar.take(rows * Z); cs2 = ar.take((size_t)D); csz = ar.take((size_t)Z);
+      eps2 = ar.take((size_t)nstrip * 128); eps1 = ar.take((size_t)nstrip * 128);
+      if (!ar.ok) { ar.off = mark; ar.ok = true; fold = false; }       // a small caller workspace keeps the prologue form
+    }
+    fold_sm = fold && !gauss && C == 32 && Z == ZP;
+    if (fuse_b && B <= 64) {
+      dgif = ar.take(dm_frag_floats(3 * D)); dghf = ar.take(dm_frag_floats(3 * D));
+      dpinf = ar.take(dm_frag_floats(Hd)); dzaf = ar.take(dm_frag_floats(Hd));
+      if (!ar.ok) { dgif = nullptr; dghf = nullptr; dpinf = nullptr; dzaf = nullptr; }
+    }
+    nchunk = (stacked || B < 16) ? 1 : (T >= 16 ? 4 : T >= 8 ? 2 : 1);      // (a few-column shard: the chunks' extra launches cost more than they hide)
+    next_chunk = nchunk - 1;
+    dx2s = fuse_b ? dx2_w : dx2;
+    dx1s = fuse_b ? dx1_w : dx1;
+    const int ls = gk.ls;
+    int n = 0;
+    wg[n++] = {dpost, ZP, ZP, a.pin, Hd, Hd, g[DM_RSSM_POST_W]};
+    wg[n++] = {dx2s, Hd, Hd, feat, F, D, g[DM_RSSM_POST_H_W]};
+    wg[n++] = {dx2s, Hd, Hd, embed, E, E, g[DM_RSSM_POST_E_W]};
+    for (int i = 0; i < gk.L; ++i) {
+      wg[n++] = {dgi + 3 * ls * i, 3 * D, 3 * ls, i == 0 ? a.za : feat + (size_t)(i - 1) * ls, i == 0 ? Hd : F, i == 0 ? Hd : ls,
+                 gk.g_wih[i]};
+      wg[n++] = {dgh + 3 * ls * i, 3 * D, 3 * ls, a.hin + i * ls, D, ls, gk.g_whh[i]};
+    }
+    wg[n++] = {dx1s, Hd, Hd, a.zin, Z, Z, g[DM_RSSM_Z_W]};
+    wg[n++] = {dx1s, Hd, Hd, action, A, A, g[DM_RSSM_A_W]};
+    nwg = n;
+    return DM_OK;
+  }
+  // entries [first, first + count) of the list over rows [c0, c0 + rows), on the side stream
+  int wgrads(int first, int count, size_t c0, int rows, int accum) const {
+    for (const Wgrad* w = wg + first; w < wg + first + count; ++w)
+      DM_TRY(wgrad(sw, sk_w, skb, rows, w->nout, w->kin, w->dy + c0 * w->lddy, w->lddy, w->x + c0 * w->ldx, w->ldx, w->dW, accum));
+    return DM_OK;
+  }
+  // Single-layer cells: the weight gradients of a time chunk, launched as soon as the loop has finished the chunk's rows, so
+  // they run BESIDE the loop (a B-row latency chain that leaves most CUs idle) instead of behind it.  The chunk boundaries,
+  // and with them every sum, are the same whether or not a side stream is used.
+  int side_chunk(int t) {
+    if (gk.L > 1 || next_chunk < 0 || t != (int)((long long)T * next_chunk / nchunk)) return DM_OK;
+    const int k = next_chunk--;
+    const int t0 = (int)((long long)T * k / nchunk), t1 = (int)((long long)T * (k + 1) / nchunk);
+    const size_t c0 = (size_t)t0 * B;
+    const int rows = (t1 - t0) * B;
+    DM_TRY(dm_wgrad_side_fork(st, sw));            // rows [c0, c0 + rows) of dpost, dpin, dgi, dgh, dza (dx2, dx1) are final
+    if (fuse_b) {
+      DM_TRY(post_norm_bwd(c0, rows, dx2_w, sw));
+      DM_TRY(in_norm_bwd(c0, rows, dx1_w, sw));
+    }
+    return wgrads(0, nwg, c0, rows, k != nchunk - 1);
+  }
+  // dx2 / dx1 = the post_norm / in_norm + ELU backward of dpin / dza, rows [c0, c0 + rows)
+  int post_norm_bwd(size_t c0, int rows, float* dx, hipStream_t s) const {
+    return norm_elu_bwd_dx(rows, Hd, a.x2 + c0 * Hd, Hd, a.pin + c0 * Hd, Hd, a.st2 + c0 * 2, p[DM_RSSM_POST_G], dpin + c0 * Hd, Hd,
+                           dx + c0 * Hd, Hd, s);
+  }
+  int in_norm_bwd(size_t c0, int rows, float* dx, hipStream_t s) const {
+    return norm_elu_bwd_dx(rows, Hd, a.x1 + c0 * Hd, Hd, a.za + c0 * Hd, Hd, a.st1 + c0 * 2, p[DM_RSSM_IN_G], dza + c0 * Hd, Hd,
+                           dx + c0 * Hd, Hd, s);
+  }
+
+  // Step t: [dh' | dz'] of step t (complete when the step starts), its dpost rows, step t-1's [dh' | dz'] (null at t = 0)
+  struct Rows { size_t r0; float *dft, *dpt, *dprev; const uint8_t* rz; };
+  Rows rows_of(int t) const {
+    const size_t r0 = (size_t)t * B;
+    return {r0, dfeat + r0 * F, dpost + r0 * ZP, t > 0 ? dfeat + (r0 - B) * F : nullptr, reset + r0};
+  }
+  // dprev[:, :D] += mask * dgh W_hh: the first product of the pair launch that closes a single-layer step
+  DmGemm dprev_h(const Rows& r) const {
+    DmGemm q = dgrad_t_q(B, 3 * D, D, dgh + r.r0 * 3 * D, 3 * D, wt_hh, r.dprev, F, 1, r.rz);
+    q.A_frag = dghf;
+    return q;
+  }
+  // One LayerNorm+ELU stage of step t as the fused schedule's products see it.
+  struct Ln {
+    const float *x, *stats, *gamma, *beta;      // pre-activations, (mean, rstd), parameters
+    float *dy, *gx, *frag, *ps;                 // gradient w.r.t. the output; folded: gx = dy ELU'(pre) gamma and its per-strip row sums; frag: copy of dy (folded: of gx)
+    const float *xw, *cs; int ldxw;             // folded: x W of these rows and W's column sums, W = the consuming product's weight
+  };
+  // C = dy of the stage = A Wt^T (K = lda = ldb).  Prologue form: + its fragment-major copy; folded: + gx and its row sums.
+  DmGemm make_dy(const Ln& n, bool folded, int K, const float* A_, const float* A_frag, const float* Wt) const {
+    DmGemm q = dgrad_t_q(B, K, Hd, A_, K, Wt, n.dy, Hd, 0, nullptr);
+    q.A_frag = A_frag;
+    if (folded) {
+      q.eg_x = n.x; q.eg_ldx = Hd; q.eg_stats = n.stats; q.eg_gamma = n.gamma; q.eg_beta = n.beta;
+      q.eg_G = n.gx; q.eg_ldg = Hd; q.eg_Gf = n.frag; q.eg_ps = n.ps;
+    } else {
+      q.C_frag = n.frag;
+    }
+    return q;
+  }
+  // C_ (ldc = F) += mask * dx Wt^T, dx = the gradient w.r.t. the stage's input.  Prologue form: A = dy, the LayerNorm+ELU
+  // backward in the prologue; folded: a plain product on gx whose epilogue applies the two row-mean terms.
+  DmGemm use_dx(const Ln& n, bool folded, int N_, const float* Wt, float* C_, const uint8_t* rz) const {
+    DmGemm q = dgrad_t_q(B, Hd, N_, folded ? n.gx : n.dy, Hd, Wt, C_, F, 1, rz);
+    q.A_frag = n.frag;
+    if (folded) {
+      q.lnf_ps = n.ps; q.lnf_nps = nstrip; q.lnf_stats = n.stats; q.lnf_xw = n.xw; q.lnf_ldxw = n.ldxw; q.lnf_cs = n.cs;
+    } else {
+      q.ln_g = n.gamma; q.ln_b = n.beta; q.lnb_x = n.x; q.lnb_ldx = Hd; q.lnb_stats = n.stats;
+    }
+    return q;
+  }
+
+  // 4 launches: dpin, dh' + gates backward, dza, the dprev pair - and the sample backward in front, unless fold_sm has moved it
+  // into the pair of step t+1.
+  int bptt_step_fused(int t) const {
+    const Rows r = rows_of(t);
+    const size_t r0 = r.r0;
+    const Ln post_n = {a.x2 + r0 * Hd, a.st2 + r0 * 2, p[DM_RSSM_POST_G], p[DM_RSSM_POST_B], dpin + r0 * Hd, dx2 + r0 * Hd, dpinf,
+                       eps2, fold ? xw2 + r0 * D : nullptr, cs2, D};
+    const Ln in_n = {a.x1 + r0 * Hd, a.st1 + r0 * 2, p[DM_RSSM_IN_G], p[DM_RSSM_IN_B], dza + r0 * Hd, dx1 + r0 * Hd, dzaf,
+                     eps1, fold ? xwz + r0 * Z : nullptr, csz, Z};
+    // straight-through sample: dpost += softmax'(post)^T dz'   (fold_sm: done by the pair launch of step t+1)
+    if (!(fold_sm && t < T - 1)) DM_TRY(dm_st_softmax_bwd_launch(B, S, C, post + r0 * ZP, ZP, r.dft + D, F, r.dpt, ZP, 1, st));
+    // dpin = dpost Wpost   (folded: g2 goes row-major into the dx2 rows - re-made in batch after the loop - and fragment-major)
+    DM_TRY(dm_gemm_launch(make_dy(post_n, fold, ZP, r.dpt, nullptr, wt_post), sk, skb, st));
+    // dh' += LNbwd(dpin) Wph ; then the GRU gates backward on the completed dh' (the direct path dh'*u goes, masked, into dprev)
+    DmGatesBwd gb;
+    gb.gi = a.gi + r0 * 3 * D; gb.gh = a.gh + r0 * 3 * D; gb.h_in = a.hin + r0 * D; gb.ldh = D; gb.D = D;
+    gb.dgi = dgi + r0 * 3 * D; gb.dgh = dgh + r0 * 3 * D; gb.dprev = r.dprev; gb.ldp = F; gb.row_zero = r.rz;
+    gb.dgi_frag = dgif; gb.dgh_frag = dghf;
+    DmGemm q4 = use_dx(post_n, fold, D, wt_post_h, r.dft, nullptr);
+    q4.gates = &gb;
+    DM_TRY(dm_gemm_launch(q4, sk, skb, st));
+    // dza = dgi Wih
+    DM_TRY(dm_gemm_launch(make_dy(in_n, fold, 3 * D, dgi + r0 * 3 * D, dgif, wt_ih), sk, skb, st));
+    if (t == 0) return DM_OK;
+    // both products into step t-1's [dh' | dz']; the second one consumes LNbwd(dza)
+    DmGemm qz = use_dx(in_n, fold, Z, wt_z, r.dprev + D, r.rz);
+    if (fold_sm) { qz.sm_logits = post + (r0 - B) * ZP; qz.sm_ld = ZP; qz.sm_dlogits = dpost + (r0 - B) * ZP; qz.sm_ldd = ZP; }
+    return dm_gemm_pair_launch(dprev_h(r), qz, sk, skb, st);
+  }
+
+  // The head of an unfused step (4 launches): sample backward, post_mlp, post_norm+ELU, post_mlp_h.
+  int post_branch(const Rows& r) const {
+    const size_t r0 = r.r0;
+    // straight-through sample: dpost += softmax'(post)^T dz'   (Gaussian: the reparameterised sample's (dmean, draw std))
+    if (gauss) DM_TRY(dm_gauss_sample_bwd_launch(B, S, post + r0 * ZP, ZP, feat + r0 * F + D, F, r.dft + D, F, r.dpt, ZP, 1, st));
+    else DM_TRY(dm_st_softmax_bwd_launch(B, S, C, post + r0 * ZP, ZP, r.dft + D, F, r.dpt, ZP, 1, st));
+    DM_TRY(dgrad_t(st, sk, skb, B, ZP, Hd, r.dpt, ZP, wt_post, dpin + r0 * Hd, Hd, 0, nullptr));
+    DM_TRY(post_norm_bwd(r0, B, dx2, st));
+    return dgrad_t(st, sk, skb, B, Hd, D, dx2 + r0 * Hd, Hd, wt_post_h, r.dft, F, 1, nullptr);
+  }
+  // 8 launches: the head, the gates (the direct path dh'*u goes, masked, straight into step t-1's dh'), dza, in_norm, the pair.
+  int bptt_step_single(int t) const {
+    const Rows r = rows_of(t);
+    const size_t r0 = r.r0;
+    DM_TRY(post_branch(r));
+    if (kind == 0)
+      DM_TRY(dm_gru_gates_bwd_launch(B, D, a.gi + r0 * 3 * D, a.gh + r0 * 3 * D, a.hin + r0 * D, D, r.dft, F, dgi + r0 * 3 * D,
+                                     dgh + r0 * 3 * D, r.dprev, F, 1, r.rz, st));
+    else
+      DM_TRY(dm_gru_norm_bwd_launch(kind, B, D, a.gh + r0 * 3 * D, a.hin + r0 * D, D, a.gs + r0 * 3 * D, a.gst + r0 * 6, gk.lng[0],
+                                    gk.lnb[0], r.dft, F, dgi + r0 * 3 * D, dgh + r0 * 3 * D, dgl + r0 * 3 * D, r.dprev, F, r.rz, st));
+    DM_TRY(dgrad_t(st, sk, skb, B, 3 * D, Hd, dgi + r0 * 3 * D, 3 * D, wt_ih, dza + r0 * Hd, Hd, 0, nullptr));
+    DM_TRY(in_norm_bwd(r0, B, dx1, st));
+    if (t == 0) return DM_OK;
+    // both products into step t-1's [dh' | dz'], one launch
+    return dm_gemm_pair_launch(dprev_h(r), dgrad_t_q(B, Hd, Z, dx1 + r0 * Hd, Hd, wt_z, r.dprev + D, F, 1, r.rz), sk, skb, st);
+  }
+  // The head, then the layers in reverse: layer i's input gradient lands in the new-state gradient of layer i-1 before that
+  // layer's own gates run; its recurrent-input gradient goes (masked) into step t-1's dh' slice.
+  int bptt_step_stacked(int t) const {
+    const Rows r = rows_of(t);
+    const size_t r0 = r.r0;
+    const int ls = gk.ls;
+    float* dprev = r.dprev;
+    DM_TRY(post_branch(r));
+    for (int i = gk.L - 1; i >= 0; --i) {
+      float* dgi_i = dgi + r0 * 3 * D + 3 * ls * i;
+      float* dgh_i = dgh + r0 * 3 * D + 3 * ls * i;
+      if (kind == 0)
+        DM_TRY(dm_gru_gates_bwd_launch(B, ls, a.gi + r0 * 3 * D + 3 * ls * i, a.gh + r0 * 3 * D + 3 * ls * i,
+                                       a.hin + r0 * D + i * ls, D, r.dft + i * ls, F, dgi_i, dgh_i,
+                                       dprev ? dprev + i * ls : nullptr, F, 1, r.rz, st, 3 * D));
+      else
+        DM_TRY(dm_gru_norm_bwd_launch(kind, B, ls, a.gh + r0 * 3 * D + 3 * ls * i, a.hin + r0 * D + i * ls, D,
+                                      a.gs + r0 * 3 * D + 3 * ls * i, a.gst + r0 * 6 * gk.L + 6 * i, gk.lng[i], gk.lnb[i],
+                                      r.dft + i * ls, F, dgi_i, dgh_i, dgl + r0 * 3 * D + 3 * ls * i,
+                                      dprev ? dprev + i * ls : nullptr, F, r.rz, st, 3 * D, 6 * gk.L));
+      if (i > 0) DM_TRY(dgrad(st, sk, skb, B, 3 * ls, ls, dgi_i, 3 * D, gk.wih[i], r.dft + (i - 1) * ls, F, 1, nullptr));
+      else DM_TRY(dgrad(st, sk, skb, B, 3 * ls, Hd, dgi_i, 3 * D, gk.wih[0], dza + r0 * Hd, Hd, 0, nullptr));
+      if (dprev) DM_TRY(dgrad(st, sk, skb, B, 3 * ls, ls, dgh_i, 3 * D, gk.whh[i], dprev + i * ls, F, 1, r.rz));
+    }
+    DM_TRY(in_norm_bwd(r0, B, dx1, st));
+    if (dprev) DM_TRY(dgrad_t(st, sk, skb, B, Hd, Z, dx1 + r0 * Hd, Hd, wt_z, dprev + D, F, 1, r.rz));
+    return DM_OK;
+  }
+
+  // Gate-bias (nn.GRUCell) or LayerNorm-parameter (the LayerNorm cells) gradients of cell layer i: column passes over the
+  // layer's 3*ls gate columns of all rows; the latter are then split into the cell's (reset, update, newval) parameter slots.
+  int cell_param_grads(int i) const {
+    const int ls = gk.ls;
+    if (kind == 0) {
+      DM_TRY(dm_colsum_launch(N, 3 * ls, dgi + 3 * ls * i, 3 * D, gk.g_bih[i], sk_w, skb, sw));
+      return dm_colsum_launch(N, 3 * ls, dgh + 3 * ls * i, 3 * D, gk.g_bhh[i], sk_w, skb, sw);
+    }
+    DM_TRY(dm_gru_norm_param_grads_launch(kind, N, ls, a.gs + 3 * ls * i, a.gst + 6 * i, dgl + 3 * ls * i, lnpg, lnpb, sw, 3 * D,
+                                          6 * gk.L));
+    const int parts = kind == 1 ? 3 : 1;
+    const size_t len = (size_t)(kind == 1 ? ls : 3 * ls) * sizeof(float);
+    for (int q = 0; q < parts; ++q)
+      if (hipMemcpyAsync(gk.g_lng[i][q], lnpg + (size_t)q * ls, len, hipMemcpyDeviceToDevice, sw) != hipSuccess ||
+          hipMemcpyAsync(gk.g_lnb[i][q], lnpb + (size_t)q * ls, len, hipMemcpyDeviceToDevice, sw) != hipSuccess)
+        return dm_fail(DM_E_HIP, "rssm_sequence_bwd: gradient copy failed");
+    return DM_OK;
+  }
+  // Bias / LayerNorm-parameter gradients (column passes over all rows) and, for cell stacks, the weight gradients: on sw.
+  int param_tail() const {
+    const int L = gk.L;
+    const bool stacked = L > 1;
+    if (stacked) DM_TRY(dm_wgrad_side_fork(st, sw));      // (single-layer cells forked at their last chunk)
+    DM_TRY(dm_colsum_launch(N, ZP, dpost, ZP, g[DM_RSSM_POST_OB], sk_w, skb, sw));
+    DM_TRY(norm_elu_bwd_params(N, Hd, a.x2, Hd, a.pin, Hd, a.st2, dpin, Hd, g[DM_RSSM_POST_G], g[DM_RSSM_POST_B], sk_w, skb, sw));
+    DM_TRY(dm_colsum_launch(N, Hd, dx2s, Hd, g[DM_RSSM_POST_H_B], sk_w, skb, sw));
+    if (stacked) DM_TRY(wgrads(0, 3, 0, N, 0));
+    for (int i = 0; i < L; ++i) {
+      if (stacked) DM_TRY(wgrads(3 + 2 * i, 2, 0, N, 0));
+      DM_TRY(cell_param_grads(i));
+    }
+    DM_TRY(norm_elu_bwd_params(N, Hd, a.x1, Hd, a.za, Hd, a.st1, dza, Hd, g[DM_RSSM_IN_G], g[DM_RSSM_IN_B], sk_w, skb, sw));
+    DM_TRY(dm_colsum_launch(N, Hd, dx1s, Hd, g[DM_RSSM_Z_B], sk_w, skb, sw));
+    if (stacked) DM_TRY(wgrads(3 + 2 * L, 2, 0, N, 0));
+    return dm_wgrad_side_mark(sw, st);
+  }
+};
+
 extern "C" int dm_rssm_sequence_bwd(const dm_shape* s, const float* embed, const float* action, const uint8_t* reset,
                                     const dm_rssm_params* P, const float* acts, const float* feat, const float* post,
                                     float* dfeat, float* dpost, float* dprior, const dm_rssm_grads* G, float* dembed,
@@ -404,331 +728,58 @@ extern "C" int dm_rssm_sequence_bwd(const dm_shape* s, const float* embed, const
              "rssm_sequence_bwd: null pointer");
   DmPrecisionScope prec(s->flags & DM_FLAG_BF16);
   DM_TRY(rssm_check(s));
-  hipStream_t st = (hipStream_t)stream;
-  const int T = s->T, B = s->B, D = s->D, Hd = s->Hd, S = s->S, C = s->C, Z = S * (C ? C : 1), ZP = S * (C ? C : 2);
-  const int F = D + Z, E = s->E, A = s->A;        // Z: width of z, ZP: width of its distribution's parameters (see above)
-  const bool gauss = C == 0;
-  const int N = T * B;
-  RssmActs a;
-  rssm_carve(s, const_cast<float*>(acts), &a);
-  const float* const* p = P->p;
-  float* const* g = G->p;
-
-  DmArena ar(ws, ws_bytes);
-  float* sk = ar.take(DM_SPLITK_FLOATS);
-  float* dprin = ar.take((size_t)N * Hd);
-  float* dx3 = ar.take((size_t)N * Hd);
-  float* dpin = ar.take((size_t)N * Hd);
-  float* dx2 = ar.take((size_t)N * Hd);
-  float* dgi = ar.take((size_t)N * 3 * D);
-  float* dgh = ar.take((size_t)N * 3 * D);
-  float* dza = ar.take((size_t)N * Hd);
-  float* dx1 = ar.take((size_t)N * Hd);
-  float* wt_post = ar.take((size_t)ZP * Hd);
-  float* wt_post_h = ar.take((size_t)Hd * D);
-  float* wt_ih = ar.take((size_t)3 * D * Hd);
-  float* wt_hh = ar.take((size_t)3 * D * D);
-  float* wt_z = ar.take((size_t)Hd * Z);
-  const int kind = rssm_gru_kind(s);
-  float* dgl = ar.take(kind ? (size_t)N * 3 * D : 0);       // LayerNorm GRU cells: gradients w.r.t. the LayerNorm outputs
-  float* lnpg = ar.take(kind ? (size_t)3 * D : 0);
-  float* lnpb = ar.take(kind ? (size_t)3 * D : 0);
-  // the weight-gradient side stream's own split-K scratch and its own dx2 / dx1 (fused schedule: the LayerNorm backward of a
-  // chunk of rows is redone there instead of being shared with the chain)
-  float* sk_w = ar.take(DM_SPLITK_FLOATS);
-  float* dx2_w = ar.take((size_t)N * Hd);
-  float* dx1_w = ar.take((size_t)N * Hd);
-  const float* lng[3] = {p[DM_RSSM_GRU_LN_G0], p[DM_RSSM_GRU_LN_G1], p[DM_RSSM_GRU_LN_G2]};
-  const float* lnb[3] = {p[DM_RSSM_GRU_LN_B0], p[DM_RSSM_GRU_LN_B1], p[DM_RSSM_GRU_LN_B2]};
-  DM_REQUIRE(ar.ok, DM_E_WORKSPACE, "rssm_sequence_bwd: workspace too small (need %zu floats)", ar.off);
-  const size_t skb = DM_SPLITK_FLOATS * sizeof(float);
-
-  // Parameter gradients are leaves of this pass: nothing reads them before the gradient clip.  They go to `sw` - the
-  // library's weight-gradient side stream when the calling thread is armed (include/dreamer_hip.h dm_wgrad_side_arm), else
-  // `st` itself - and the big ones are cut into up to four time chunks that are launched as soon as the BPTT loop has finished
-  // their rows, so they run BESIDE the loop (a B-row latency chain that leaves most CUs idle) instead of behind it.  The chunk
-  // boundaries, and with them every sum, are the same whether or not a side stream is used.
-  hipStream_t const st_main = st;
-  hipStream_t sw = st == (hipStream_t)stream ? dm_wgrad_side_stream(st) : st;      // (no side stream inside a chain-graph capture)
+  BpttCtx c = {};
+  rssm_dims(s, &c);
+  rssm_carve(c, const_cast<float*>(acts), &c.a);
+  c.p = P->p; c.g = G->p; c.st = (hipStream_t)stream; c.sw = dm_wgrad_side_stream(c.st);
+  c.embed = embed; c.action = action; c.feat = feat; c.post = post; c.reset = reset; c.dfeat = dfeat; c.dpost = dpost;
+  DM_TRY(gru_stack(s, c.p, c.g, &c.gk));
+  DM_TRY(c.plan(ws, ws_bytes));
+  const RssmActs& a = c.a;
+  const float* const* p = c.p;
+  float* const* g = c.g;
+  const int N = c.N, D = c.D, Hd = c.Hd, Z = c.Z, ZP = c.ZP, F = c.F;
+  hipStream_t st = c.st, sw = c.sw;
+  float *sk = c.sk, *sk_w = c.sk_w;
+  const size_t skb = c.skb;
 
   // ---- prior branch, batched over all rows: the data gradient on st ...
-  DM_TRY(dgrad(st, sk, skb, N, ZP, Hd, dprior, ZP, p[DM_RSSM_PRIOR_W], dprin, Hd, 0, nullptr));
-  DM_TRY(norm_elu_bwd_dx(N, Hd, a.x3, Hd, a.prin, Hd, a.st3, p[DM_RSSM_PRIOR_G], dprin, Hd, dx3, Hd, st));
-  DM_TRY(dgrad(st, sk, skb, N, Hd, D, dx3, Hd, p[DM_RSSM_PRIOR_H_W], dfeat, F, 1, nullptr));
+  DM_TRY(dgrad(st, sk, skb, N, ZP, Hd, dprior, ZP, p[DM_RSSM_PRIOR_W], c.dprin, Hd, 0, nullptr));
+  DM_TRY(norm_elu_bwd_dx(N, Hd, a.x3, Hd, a.prin, Hd, a.st3, p[DM_RSSM_PRIOR_G], c.dprin, Hd, c.dx3, Hd, st));
+  DM_TRY(dgrad(st, sk, skb, N, Hd, D, c.dx3, Hd, p[DM_RSSM_PRIOR_H_W], dfeat, F, 1, nullptr));
   // ... its parameter gradients on sw
   DM_TRY(dm_wgrad_side_fork(st, sw));
   DM_TRY(wgrad(sw, sk_w, skb, N, ZP, Hd, dprior, ZP, a.prin, Hd, g[DM_RSSM_PRIOR_W]));
   DM_TRY(dm_colsum_launch(N, ZP, dprior, ZP, g[DM_RSSM_PRIOR_OB], sk_w, skb, sw));
-  DM_TRY(norm_elu_bwd_params(N, Hd, a.x3, Hd, a.prin, Hd, a.st3, dprin, Hd, g[DM_RSSM_PRIOR_G],
-                                     g[DM_RSSM_PRIOR_B], sk_w, skb, sw));
-  DM_TRY(wgrad(sw, sk_w, skb, N, Hd, D, dx3, Hd, feat, F, g[DM_RSSM_PRIOR_H_W]));
-  DM_TRY(dm_colsum_launch(N, Hd, dx3, Hd, g[DM_RSSM_PRIOR_H_B], sk_w, skb, sw));
+  DM_TRY(norm_elu_bwd_params(N, Hd, a.x3, Hd, a.prin, Hd, a.st3, c.dprin, Hd, g[DM_RSSM_PRIOR_G], g[DM_RSSM_PRIOR_B], sk_w, skb, sw));
+  DM_TRY(wgrad(sw, sk_w, skb, N, Hd, D, c.dx3, Hd, feat, F, g[DM_RSSM_PRIOR_H_W]));
+  DM_TRY(dm_colsum_launch(N, Hd, c.dx3, Hd, g[DM_RSSM_PRIOR_H_B], sk_w, skb, sw));
 
-  // (The BPTT loop as a second persistent LDS-weight-stationary kernel was built in round 4 - 1.6x faster than these launches
-  // when it has the chip to itself, slower INSIDE the multi-stream step at every shard size measured, because it needs every CU
-  // at once while the decoder backward wants them too: profiles/r04_ab_bptt.txt - and removed in round 5.)
   // ---- BPTT as launches.  The five backward-data products of a step multiply a B-row block by W (not W^T); transposing the
-  // weights once here (22 MB, ~20 us) lets all 5*T of them stream k-contiguous rows.
-  DM_TRY(transpose(st, p[DM_RSSM_POST_W], wt_post, ZP, Hd));
-  DM_TRY(transpose(st, p[DM_RSSM_POST_H_W], wt_post_h, Hd, D));
-  GruStack gk;
-  DM_TRY(gru_stack(s, p, g, &gk));
-  const bool stacked = gk.L > 1;
-  if (!stacked) {
-    DM_TRY(transpose(st, p[DM_RSSM_GRU_WIH], wt_ih, 3 * D, Hd));
-    DM_TRY(transpose(st, p[DM_RSSM_GRU_WHH], wt_hh, 3 * D, D));
+  // weights once here (22 MB, ~20 us) lets all 5*T of them stream k-contiguous rows.  (The loop as a persistent
+  // LDS-weight-stationary kernel is 1.6x faster alone and slower INSIDE the multi-stream step, because it needs every CU at
+  // once while the decoder backward wants them too: profiles/r04_ab_bptt.txt.)
+  DM_TRY(transpose(st, p[DM_RSSM_POST_W], c.wt_post, ZP, Hd));
+  DM_TRY(transpose(st, p[DM_RSSM_POST_H_W], c.wt_post_h, Hd, D));
+  if (c.gk.L == 1) {
+    DM_TRY(transpose(st, p[DM_RSSM_GRU_WIH], c.wt_ih, 3 * D, Hd));
+    DM_TRY(transpose(st, p[DM_RSSM_GRU_WHH], c.wt_hh, 3 * D, D));
   }
-  DM_TRY(transpose(st, p[DM_RSSM_Z_W], wt_z, Hd, Z));
-  // Fused schedule (5 launches per step instead of 8), mirror of the forward T loop: both LayerNorm+ELU BACKWARD stages
-  // ride in the prologue of the <= 64-row product that consumes their result, and the GRU gates backward rides in the
-  // epilogue of the product that completes dh'.  dx1 / dx2 (needed by the batched weight gradients) are then produced for
-  // all rows by two batched launches after the loop.
-  const bool fuse_b = p[DM_RSSM_IN_G] != nullptr && !stacked && !gauss && kind == 0 && dm_skinny_ln_ok(B, D, Hd) &&
-                      dm_skinny_ln_ok(B, Z, Hd) && (F & 3) == 0;
-  // ... in FOLDED form (common.h DmGemm::eg_x): the product that makes dpin (dza) also turns it into g = dy ELU'(pre) gamma in
-  // its epilogue - once, by the workgroup that owns the element, instead of once per consuming workgroup in a prologue - and
-  // the consuming product is a plain one whose epilogue applies the two row-mean terms.  That needs x2 W_post_h and x1 W_z for
-  // all rows (two batched products here) and the weights' column sums.
-  bool fold = fuse_b && g_bptt_fold && B <= 64 && (int64_t)Hd * ZP >= (int64_t)64 * 1024 &&
-              (int64_t)Hd * 3 * D >= (int64_t)64 * 1024 && (ZP & 3) == 0 && ((3 * D) & 3) == 0 && ZP >= 16;
-  float *xw2 = nullptr, *xwz = nullptr, *cs2 = nullptr, *csz = nullptr, *eps2 = nullptr, *eps1 = nullptr;
-  const int nstrip = (Hd + 15) / 16;
-  if (fold) {
-    const size_t mark = ar.off;
-    xw2 = ar.take((size_t)N * D);
-    xwz = ar.take((size_t)N * Z);
-    cs2 = ar.take((size_t)D);
-    csz = ar.take((size_t)Z);
-    eps2 = ar.take((size_t)nstrip * 128);
-    eps1 = ar.take((size_t)nstrip * 128);
-    if (!ar.ok) { ar.off = mark; ar.ok = true; fold = false; }       // a small caller workspace keeps the prologue form
+  DM_TRY(transpose(st, p[DM_RSSM_Z_W], c.wt_z, Hd, Z));
+  if (c.fold) {
+    DM_TRY(dgrad(st, sk, skb, N, Hd, D, a.x2, Hd, p[DM_RSSM_POST_H_W], c.xw2, D, 0, nullptr));      // x2 W_post_h
+    DM_TRY(dgrad(st, sk, skb, N, Hd, Z, a.x1, Hd, p[DM_RSSM_Z_W], c.xwz, Z, 0, nullptr));           // x1 W_z
+    DM_TRY(dm_colsum_launch(Hd, D, p[DM_RSSM_POST_H_W], D, c.cs2, sk, skb, st));
+    DM_TRY(dm_colsum_launch(Hd, Z, p[DM_RSSM_Z_W], Z, c.csz, sk, skb, st));
   }
-  const bool fold_sm = fold && !gauss && C == 32 && Z == ZP;
-  if (fold) {
-    DM_TRY(dgrad(st, sk, skb, N, Hd, D, a.x2, Hd, p[DM_RSSM_POST_H_W], xw2, D, 0, nullptr));      // x2 W_post_h
-    DM_TRY(dgrad(st, sk, skb, N, Hd, Z, a.x1, Hd, p[DM_RSSM_Z_W], xwz, Z, 0, nullptr));           // x1 W_z
-    DM_TRY(dm_colsum_launch(Hd, D, p[DM_RSSM_POST_H_W], D, cs2, sk, skb, st));
-    DM_TRY(dm_colsum_launch(Hd, Z, p[DM_RSSM_Z_W], Z, csz, sk, skb, st));
+  for (int t = c.T - 1; t >= 0; --t) {
+    DM_TRY(c.fuse_b ? c.bptt_step_fused(t) : c.gk.L > 1 ? c.bptt_step_stacked(t) : c.bptt_step_single(t));
+    DM_TRY(c.side_chunk(t));
   }
-  // fragment-major copies (common.h dm_frag_off) of the two K = 3D operands of a step, dgi and dgh: written by the gates
-  // backward epilogue, read by the two products that follow it
-  float* dgif = (fuse_b && B <= 64) ? ar.take(dm_frag_floats(3 * D)) : nullptr;
-  float* dghf = dgif ? ar.take(dm_frag_floats(3 * D)) : nullptr;
-  float* dpinf = dgif ? ar.take(dm_frag_floats(Hd)) : nullptr;      // ... and of dpin, dza (written by the epilogue of the
-  float* dzaf = dgif ? ar.take(dm_frag_floats(Hd)) : nullptr;       // product that makes them)
-  if (!ar.ok) { dgif = nullptr; dghf = nullptr; dpinf = nullptr; dzaf = nullptr; }
-  // time chunks of the batched weight gradients (single-layer cells): chunk c = steps [T*c/nchunk, T*(c+1)/nchunk); the loop
-  // runs t downwards, so the LAST chunk completes first - it overwrites the gradient, the others accumulate
-  const int nchunk = (stacked || B < 16) ? 1 : (T >= 16 ? 4 : T >= 8 ? 2 : 1);      // (a few-column shard: the chunks' extra launches cost more than they hide)
-  int next_chunk = nchunk - 1;
-  const float* dx2s = fuse_b ? dx2_w : dx2;
-  const float* dx1s = fuse_b ? dx1_w : dx1;
-  auto side_chunk = [&](int t) -> int {
-    if (stacked || next_chunk < 0 || t != (int)((long long)T * next_chunk / nchunk)) return DM_OK;
-    const int c = next_chunk--;
-    const int t0 = (int)((long long)T * c / nchunk), t1 = (int)((long long)T * (c + 1) / nchunk);
-    const size_t c0 = (size_t)t0 * B;
-    const int rows = (t1 - t0) * B, acc = c != nchunk - 1;
-    DM_TRY(dm_wgrad_side_fork(st, sw));            // rows [c0, c0 + rows) of dpost, dpin, dgi, dgh, dza (dx2, dx1) are final
-    if (fuse_b) {
-      DM_TRY(norm_elu_bwd_dx(rows, Hd, a.x2 + c0 * Hd, Hd, a.pin + c0 * Hd, Hd, a.st2 + c0 * 2, p[DM_RSSM_POST_G], dpin + c0 * Hd, Hd,
-                             dx2_w + c0 * Hd, Hd, sw));
-      DM_TRY(norm_elu_bwd_dx(rows, Hd, a.x1 + c0 * Hd, Hd, a.za + c0 * Hd, Hd, a.st1 + c0 * 2, p[DM_RSSM_IN_G], dza + c0 * Hd, Hd,
-                             dx1_w + c0 * Hd, Hd, sw));
-    }
-    DM_TRY(wgrad(sw, sk_w, skb, rows, ZP, Hd, dpost + c0 * ZP, ZP, a.pin + c0 * Hd, Hd, g[DM_RSSM_POST_W], acc));
-    DM_TRY(wgrad(sw, sk_w, skb, rows, Hd, D, dx2s + c0 * Hd, Hd, feat + c0 * F, F, g[DM_RSSM_POST_H_W], acc));
-    DM_TRY(wgrad(sw, sk_w, skb, rows, Hd, E, dx2s + c0 * Hd, Hd, embed + c0 * E, E, g[DM_RSSM_POST_E_W], acc));
-    DM_TRY(wgrad(sw, sk_w, skb, rows, 3 * D, Hd, dgi + c0 * 3 * D, 3 * D, a.za + c0 * Hd, Hd, g[DM_RSSM_GRU_WIH], acc));
-    DM_TRY(wgrad(sw, sk_w, skb, rows, 3 * D, D, dgh + c0 * 3 * D, 3 * D, a.hin + c0 * D, D, g[DM_RSSM_GRU_WHH], acc));
-    DM_TRY(wgrad(sw, sk_w, skb, rows, Hd, Z, dx1s + c0 * Hd, Hd, a.zin + c0 * Z, Z, g[DM_RSSM_Z_W], acc));
-    DM_TRY(wgrad(sw, sk_w, skb, rows, Hd, A, dx1s + c0 * Hd, Hd, action + c0 * A, A, g[DM_RSSM_A_W], acc));
-    return DM_OK;
-  };
-  for (int t = T - 1; t >= 0; --t) {
-    const size_t r0 = (size_t)t * B;
-    float* dft = dfeat + r0 * F;             // [dh' | dz'] of step t, complete at this point
-    float* dpt = dpost + r0 * ZP;
-    // straight-through sample: dpost += softmax'(post)^T dz'   (Gaussian: the reparameterised sample's (dmean, draw std))
-    // (folded schedule, 32 classes: done in the epilogue of the product that completed dz' - the pair launch of step t+1)
-    if (gauss) DM_TRY(dm_gauss_sample_bwd_launch(B, S, post + r0 * ZP, ZP, feat + r0 * F + D, F, dft + D, F, dpt, ZP, 1, st));
-    else if (!(fold_sm && t < T - 1)) DM_TRY(dm_st_softmax_bwd_launch(B, S, C, post + r0 * ZP, ZP, dft + D, F, dpt, ZP, 1, st));
-    // post_mlp, post_norm+ELU, post_mlp_h
-    if (fuse_b) {
-      DmGemm q3;   // dpin = dpost Wpost
-      q3.M = B; q3.N = Hd; q3.K = ZP; q3.A = dpt; q3.lda = ZP; q3.B = wt_post; q3.ldb = ZP; q3.C = dpin + r0 * Hd; q3.ldc = Hd;
-      q3.C_frag = dpinf;
-      if (fold) {      // + g2 = dpin ELU'(pre2) gamma (row-major into the dx2 rows - re-made in batch after the loop - and fragment-major)
-        q3.C_frag = nullptr;
-        q3.eg_x = a.x2 + r0 * Hd; q3.eg_ldx = Hd; q3.eg_stats = a.st2 + r0 * 2; q3.eg_gamma = p[DM_RSSM_POST_G]; q3.eg_beta = p[DM_RSSM_POST_B];
-        q3.eg_G = dx2 + r0 * Hd; q3.eg_ldg = Hd; q3.eg_Gf = dpinf; q3.eg_ps = eps2;
-      }
-      DM_TRY(dm_gemm_launch(q3, sk, skb, st));
-    } else {
-      DM_TRY(dgrad_t(st, sk, skb, B, ZP, Hd, dpt, ZP, wt_post, dpin + r0 * Hd, Hd, 0, nullptr));
-    }
-    if (fuse_b) {
-      const uint8_t* rz = reset + r0;
-      float* dprev = t > 0 ? dfeat + (r0 - B) * F : nullptr;
-      DmGatesBwd gb;
-      gb.gi = a.gi + r0 * 3 * D; gb.gh = a.gh + r0 * 3 * D; gb.h_in = a.hin + r0 * D; gb.ldh = D; gb.D = D;
-      gb.dgi = dgi + r0 * 3 * D; gb.dgh = dgh + r0 * 3 * D; gb.dprev = dprev; gb.ldp = F; gb.row_zero = rz;
-      gb.dgi_frag = dgif; gb.dgh_frag = dghf;
-      DmGemm q4;     // dh' += LNbwd(dpin) Wph ; then the GRU gates backward on the completed dh'
-      q4.M = B; q4.N = D; q4.K = Hd; q4.A = dpin + r0 * Hd; q4.lda = Hd; q4.B = wt_post_h; q4.ldb = Hd;
-      q4.C = dft; q4.ldc = F; q4.flags = DM_GEMM_ACCUM;
-      q4.ln_g = p[DM_RSSM_POST_G]; q4.ln_b = p[DM_RSSM_POST_B]; q4.lnb_x = a.x2 + r0 * Hd; q4.lnb_ldx = Hd;
-      q4.lnb_stats = a.st2 + r0 * 2; q4.gates = &gb; q4.A_frag = dpinf;
-      if (fold) {      // a plain product on g2; the row-mean terms enter in the epilogue, in front of the gates backward
-        q4.A = dx2 + r0 * Hd; q4.ln_g = nullptr; q4.ln_b = nullptr; q4.lnb_x = nullptr; q4.lnb_stats = nullptr;
-        q4.lnf_ps = eps2; q4.lnf_nps = nstrip; q4.lnf_stats = a.st2 + r0 * 2; q4.lnf_xw = xw2 + r0 * D; q4.lnf_ldxw = D; q4.lnf_cs = cs2;
-      }
-      DM_TRY(dm_gemm_launch(q4, sk, skb, st));
-      {
-        DmGemm q5;   // dza = dgi Wih
-        q5.M = B; q5.N = Hd; q5.K = 3 * D; q5.A = dgi + r0 * 3 * D; q5.lda = 3 * D; q5.B = wt_ih; q5.ldb = 3 * D;
-        q5.C = dza + r0 * Hd; q5.ldc = Hd; q5.A_frag = dgif; q5.C_frag = dzaf;
-        if (fold) {
-          q5.C_frag = nullptr;
-          q5.eg_x = a.x1 + r0 * Hd; q5.eg_ldx = Hd; q5.eg_stats = a.st1 + r0 * 2; q5.eg_gamma = p[DM_RSSM_IN_G]; q5.eg_beta = p[DM_RSSM_IN_B];
-          q5.eg_G = dx1 + r0 * Hd; q5.eg_ldg = Hd; q5.eg_Gf = dzaf; q5.eg_ps = eps1;
-        }
-        DM_TRY(dm_gemm_launch(q5, sk, skb, st));
-      }
-      if (t > 0) {   // both products into step t-1's [dh' | dz']; the second one consumes LNbwd(dza)
-        DmGemm qh, qz;
-        qh.M = B; qh.N = D; qh.K = 3 * D; qh.A = dgh + r0 * 3 * D; qh.lda = 3 * D; qh.B = wt_hh; qh.ldb = 3 * D;
-        qh.A_frag = dghf;
-        qh.C = dprev; qh.ldc = F; qh.flags = DM_GEMM_ACCUM; qh.row_zero = rz;
-        qz.M = B; qz.N = Z; qz.K = Hd; qz.A = dza + r0 * Hd; qz.lda = Hd; qz.B = wt_z; qz.ldb = Hd;
-        qz.C = dprev + D; qz.ldc = F; qz.flags = DM_GEMM_ACCUM; qz.row_zero = rz;
-        qz.ln_g = p[DM_RSSM_IN_G]; qz.ln_b = p[DM_RSSM_IN_B]; qz.lnb_x = a.x1 + r0 * Hd; qz.lnb_ldx = Hd;
-        qz.lnb_stats = a.st1 + r0 * 2; qz.A_frag = dzaf;
-        if (fold) {
-          qz.A = dx1 + r0 * Hd; qz.ln_g = nullptr; qz.ln_b = nullptr; qz.lnb_x = nullptr; qz.lnb_stats = nullptr;
-          if (fold_sm) { qz.sm_logits = post + (r0 - B) * ZP; qz.sm_ld = ZP; qz.sm_dlogits = dpost + (r0 - B) * ZP; qz.sm_ldd = ZP; }
-          qz.lnf_ps = eps1; qz.lnf_nps = nstrip; qz.lnf_stats = a.st1 + r0 * 2; qz.lnf_xw = xwz + r0 * Z; qz.lnf_ldxw = Z; qz.lnf_cs = csz;
-        }
-        DM_TRY(dm_gemm_pair_launch(qh, qz, sk, skb, st));
-      }
-      DM_TRY(side_chunk(t));
-      continue;
-    }
-    DM_TRY(norm_elu_bwd_dx(B, Hd, a.x2 + r0 * Hd, Hd, a.pin + r0 * Hd, Hd, a.st2 + r0 * 2, p[DM_RSSM_POST_G],
-                                   dpin + r0 * Hd, Hd, dx2 + r0 * Hd, Hd, st));
-    DM_TRY(dgrad_t(st, sk, skb, B, Hd, D, dx2 + r0 * Hd, Hd, wt_post_h, dft, F, 1, nullptr));
-    // GRU gates; the direct path dh'*u goes (masked) straight into step t-1's dh'
-    const uint8_t* rz = reset + r0;
-    float* dprev = t > 0 ? dfeat + (r0 - B) * F : nullptr;
-    if (stacked) {
-      // layers in reverse: layer i's input gradient lands in the new-state gradient of layer i-1 before that layer's own
-      // gates run; its recurrent-input gradient goes (masked) into step t-1's dh' slice
-      const int ls = gk.ls;
-      for (int i = gk.L - 1; i >= 0; --i) {
-        float* dgi_i = dgi + r0 * 3 * D + 3 * ls * i;
-        float* dgh_i = dgh + r0 * 3 * D + 3 * ls * i;
-        if (kind == 0)
-          DM_TRY(dm_gru_gates_bwd_launch(B, ls, a.gi + r0 * 3 * D + 3 * ls * i, a.gh + r0 * 3 * D + 3 * ls * i,
-                                         a.hin + r0 * D + i * ls, D, dft + i * ls, F, dgi_i, dgh_i,
-                                         dprev ? dprev + i * ls : nullptr, F, 1, rz, st, 3 * D));
-        else
-          DM_TRY(dm_gru_norm_bwd_launch(kind, B, ls, a.gh + r0 * 3 * D + 3 * ls * i, a.hin + r0 * D + i * ls, D,
-                                        a.gs + r0 * 3 * D + 3 * ls * i, a.gst + r0 * 6 * gk.L + 6 * i, gk.lng[i], gk.lnb[i],
-                                        dft + i * ls, F, dgi_i, dgh_i, dgl + r0 * 3 * D + 3 * ls * i,
-                                        dprev ? dprev + i * ls : nullptr, F, rz, st, 3 * D, 6 * gk.L));
-        if (i > 0) DM_TRY(dgrad(st, sk, skb, B, 3 * ls, ls, dgi_i, 3 * D, gk.wih[i], dft + (i - 1) * ls, F, 1, nullptr));
-        else DM_TRY(dgrad(st, sk, skb, B, 3 * ls, Hd, dgi_i, 3 * D, gk.wih[0], dza + r0 * Hd, Hd, 0, nullptr));
-        if (dprev) DM_TRY(dgrad(st, sk, skb, B, 3 * ls, ls, dgh_i, 3 * D, gk.whh[i], dprev + i * ls, F, 1, rz));
-      }
-      DM_TRY(norm_elu_bwd_dx(B, Hd, a.x1 + r0 * Hd, Hd, a.za + r0 * Hd, Hd, a.st1 + r0 * 2, p[DM_RSSM_IN_G],
-                                     dza + r0 * Hd, Hd, dx1 + r0 * Hd, Hd, st));
-      if (t > 0) DM_TRY(dgrad_t(st, sk, skb, B, Hd, Z, dx1 + r0 * Hd, Hd, wt_z, dprev + D, F, 1, rz));
-      continue;
-    }
-    if (kind == 0)
-      DM_TRY(dm_gru_gates_bwd_launch(B, D, a.gi + r0 * 3 * D, a.gh + r0 * 3 * D, a.hin + r0 * D, D, dft, F,
-                                     dgi + r0 * 3 * D, dgh + r0 * 3 * D, dprev, F, 1, rz, st));
-    else
-      DM_TRY(dm_gru_norm_bwd_launch(kind, B, D, a.gh + r0 * 3 * D, a.hin + r0 * D, D, a.gs + r0 * 3 * D, a.gst + r0 * 6, lng,
-                                    lnb, dft, F, dgi + r0 * 3 * D, dgh + r0 * 3 * D, dgl + r0 * 3 * D, dprev, F, rz, st));
-    DM_TRY(dgrad_t(st, sk, skb, B, 3 * D, Hd, dgi + r0 * 3 * D, 3 * D, wt_ih, dza + r0 * Hd, Hd, 0, nullptr));
-    DM_TRY(norm_elu_bwd_dx(B, Hd, a.x1 + r0 * Hd, Hd, a.za + r0 * Hd, Hd, a.st1 + r0 * 2, p[DM_RSSM_IN_G],
-                                   dza + r0 * Hd, Hd, dx1 + r0 * Hd, Hd, st));
-    if (t > 0) {     // both products into step t-1's [dh' | dz'], one launch
-      DmGemm qh, qz;
-      qh.M = B; qh.N = D; qh.K = 3 * D; qh.A = dgh + r0 * 3 * D; qh.lda = 3 * D; qh.B = wt_hh; qh.ldb = 3 * D;
-      qh.C = dprev; qh.ldc = F; qh.flags = DM_GEMM_ACCUM; qh.row_zero = rz;
-      qz.M = B; qz.N = Z; qz.K = Hd; qz.A = dx1 + r0 * Hd; qz.lda = Hd; qz.B = wt_z; qz.ldb = Hd;
-      qz.C = dprev + D; qz.ldc = F; qz.flags = DM_GEMM_ACCUM; qz.row_zero = rz;
-      DM_TRY(dm_gemm_pair_launch(qh, qz, sk, skb, st));
-    }
-    DM_TRY(side_chunk(t));
-  }
-
   // ---- the one data gradient left: dembed, for the encoder backward that follows on st
-  if (fuse_b) DM_TRY(norm_elu_bwd_dx(N, Hd, a.x2, Hd, a.pin, Hd, a.st2, p[DM_RSSM_POST_G], dpin, Hd, dx2, Hd, st));
-  if (dembed) DM_TRY(dgrad(st, sk, skb, N, Hd, E, dx2, Hd, p[DM_RSSM_POST_E_W], dembed, E, 0, nullptr));
-  // ---- bias / LayerNorm gradients (column passes over all rows) and, for cell stacks, the weight gradients: on sw
-  st = sw;
-  sk = sk_w;
-  if (stacked) DM_TRY(dm_wgrad_side_fork(st_main, sw));      // (single-layer cells forked at their last chunk)
-  DM_TRY(dm_colsum_launch(N, ZP, dpost, ZP, g[DM_RSSM_POST_OB], sk, skb, st));
-  DM_TRY(norm_elu_bwd_params(N, Hd, a.x2, Hd, a.pin, Hd, a.st2, dpin, Hd, g[DM_RSSM_POST_G], g[DM_RSSM_POST_B],
-                                     sk, skb, st));
-  DM_TRY(dm_colsum_launch(N, Hd, dx2s, Hd, g[DM_RSSM_POST_H_B], sk, skb, st));
-  if (stacked) {
-    DM_TRY(wgrad(st, sk, skb, N, ZP, Hd, dpost, ZP, a.pin, Hd, g[DM_RSSM_POST_W]));
-    DM_TRY(wgrad(st, sk, skb, N, Hd, D, dx2, Hd, feat, F, g[DM_RSSM_POST_H_W]));
-    DM_TRY(wgrad(st, sk, skb, N, Hd, E, dx2, Hd, embed, E, g[DM_RSSM_POST_E_W]));
-  }
-  if (stacked) {
-    const int ls = gk.ls;
-    for (int i = 0; i < gk.L; ++i) {
-      const float* x = i == 0 ? a.za : feat + (size_t)(i - 1) * ls;
-      const int ldx = i == 0 ? Hd : F, kin = i == 0 ? Hd : ls;
-      DM_TRY(wgrad(st, sk, skb, N, 3 * ls, kin, dgi + 3 * ls * i, 3 * D, x, ldx, gk.g_wih[i]));
-      DM_TRY(wgrad(st, sk, skb, N, 3 * ls, ls, dgh + 3 * ls * i, 3 * D, a.hin + i * ls, D, gk.g_whh[i]));
-      if (kind == 0) {
-        DM_TRY(dm_colsum_launch(N, 3 * ls, dgi + 3 * ls * i, 3 * D, gk.g_bih[i], sk, skb, st));
-        DM_TRY(dm_colsum_launch(N, 3 * ls, dgh + 3 * ls * i, 3 * D, gk.g_bhh[i], sk, skb, st));
-      } else {      // the layer's LayerNorm parameters: one column pass over its 3*ls gate columns of all rows
-        DM_TRY(dm_gru_norm_param_grads_launch(kind, N, ls, a.gs + 3 * ls * i, a.gst + 6 * i, dgl + 3 * ls * i, lnpg, lnpb, st,
-                                              3 * D, 6 * gk.L));
-        const int parts = kind == 1 ? 3 : 1;
-        const size_t len = (size_t)(kind == 1 ? ls : 3 * ls) * sizeof(float);
-        for (int q = 0; q < parts; ++q)
-          if (hipMemcpyAsync(gk.g_lng[i][q], lnpg + (size_t)q * ls, len, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-              hipMemcpyAsync(gk.g_lnb[i][q], lnpb + (size_t)q * ls, len, hipMemcpyDeviceToDevice, st) != hipSuccess)
-            return dm_fail(DM_E_HIP, "rssm_sequence_bwd: gradient copy failed");
-      }
-    }
-  }
-  if (stacked) {
-  } else if (kind == 0) {
-    DM_TRY(dm_colsum_launch(N, 3 * D, dgi, 3 * D, g[DM_RSSM_GRU_BIH], sk, skb, st));
-    DM_TRY(dm_colsum_launch(N, 3 * D, dgh, 3 * D, g[DM_RSSM_GRU_BHH], sk, skb, st));
-  } else {      // LayerNorm parameters of the cell: one batched column pass over all rows, then split into the thirds
-    DM_TRY(dm_gru_norm_param_grads_launch(kind, N, D, a.gs, a.gst, dgl, lnpg, lnpb, st));
-    const int parts = kind == 1 ? 3 : 1;
-    const size_t len = (kind == 1 ? (size_t)D : (size_t)3 * D) * sizeof(float);
-    float* const gdst[3] = {g[DM_RSSM_GRU_LN_G0], g[DM_RSSM_GRU_LN_G1], g[DM_RSSM_GRU_LN_G2]};
-    float* const bdst[3] = {g[DM_RSSM_GRU_LN_B0], g[DM_RSSM_GRU_LN_B1], g[DM_RSSM_GRU_LN_B2]};
-    for (int q = 0; q < parts; ++q) {
-      DM_REQUIRE(gdst[q] && bdst[q], DM_E_NULL, "rssm_sequence_bwd: missing LayerNorm-GRU gradient slot %d", q);
-      if (hipMemcpyAsync(gdst[q], lnpg + (size_t)q * D, len, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-          hipMemcpyAsync(bdst[q], lnpb + (size_t)q * D, len, hipMemcpyDeviceToDevice, st) != hipSuccess)
-        return dm_fail(DM_E_HIP, "rssm_sequence_bwd: gradient copy failed");
-    }
-  }
-  DM_TRY(norm_elu_bwd_params(N, Hd, a.x1, Hd, a.za, Hd, a.st1, dza, Hd, g[DM_RSSM_IN_G], g[DM_RSSM_IN_B], sk, skb,
-                                     st));
-  DM_TRY(dm_colsum_launch(N, Hd, dx1s, Hd, g[DM_RSSM_Z_B], sk, skb, st));
-  if (stacked) {
-    DM_TRY(wgrad(st, sk, skb, N, Hd, Z, dx1, Hd, a.zin, Z, g[DM_RSSM_Z_W]));
-    DM_TRY(wgrad(st, sk, skb, N, Hd, A, dx1, Hd, action, A, g[DM_RSSM_A_W]));
-  }
-  DM_TRY(dm_wgrad_side_mark(sw, st_main));
-  return DM_OK;
+  if (c.fuse_b) DM_TRY(c.post_norm_bwd(0, N, c.dx2, st));
+  if (dembed) DM_TRY(dgrad(st, sk, skb, N, Hd, c.E, c.dx2, Hd, p[DM_RSSM_POST_E_W], dembed, c.E, 0, nullptr));
+  return c.param_tail();
 }
 
 // ---------------------------------------------------------------- imagination -------------------
@@ -772,146 +823,107 @@ extern "C" int dm_rollout_fuse_act_enable(int on) {
   return g_rollout_fuse_act;
 }
 
-extern "C" int dm_dream_rollout(const dm_shape* s, int M, const float* start, const dm_rssm_params* P,
-                                const dm_mlp_params* actor, const float* u_act, const float* u_prior, float* feats,
-                                float* actions, int32_t* act_idx, float* actor_acts, float* actor_logits, void* ws,
-                                size_t ws_bytes, void* stream) {
-  DM_REQUIRE(s && start && P && actor && u_act && u_prior && feats && actions && ws, DM_E_NULL,
-             "dream_rollout: null pointer");
-  DmPrecisionScope prec(s->flags & DM_FLAG_BF16);
-  DM_TRY(rssm_check(s));
-  DM_REQUIRE(M >= 1 && s->H >= 1, DM_E_SHAPE, "dream_rollout: M=%d H=%d", M, s->H);
-  hipStream_t st = (hipStream_t)stream;
-  const int H = s->H, D = s->D, Hd = s->Hd, S = s->S, C = s->C, Z = S * (C ? C : 1), ZP = S * (C ? C : 2);   // see dm_rssm_sequence_fwd
-  const int F = D + Z, A = s->A;
-  const int Hm = s->mlp_hidden, L = s->mlp_layers;
-  const int adist = s->flags & 3;                 // 0 onehot, 1 tanh_normal, 2 normal_tanh
-  DM_REQUIRE(adist <= 2, DM_E_SHAPE, "dream_rollout: unknown actor distribution %d", adist);
-  const int AO = adist == 0 ? A : 2 * A;         // actor output width (a2c.py:35)
-  const float* const* p = P->p;
-
-  DmArena ar(ws, ws_bytes);
-  float* sk = ar.take(DM_SPLITK_FLOATS);
-  DM_REQUIRE((actor_acts == nullptr) == (actor_logits == nullptr), DM_E_NULL,
-             "dream_rollout: actor_acts and actor_logits must be given together");
-  float* macts = ar.take(actor_acts ? 0 : dm_mlp_acts_floats(M, Hm, L));
-  float* logits_ws = ar.take(actor_acts ? 0 : (size_t)M * AO);
-  float* ea = ar.take((size_t)M * Hd);
-  float* x1 = ar.take((size_t)M * Hd);
-  float* za = ar.take((size_t)M * Hd);
-  float* stats = ar.take((size_t)M * 2);
-  float* gi = ar.take((size_t)M * 3 * D);
-  float* gh = ar.take((size_t)M * 3 * D);
-  float* prior = ar.take((size_t)M * ZP);
-  const int kind = rssm_gru_kind(s);
-  float* gsw = ar.take(kind ? (size_t)M * 3 * D : 0);
-  float* gstw = ar.take(kind ? (size_t)M * 6 * rssm_gru_layers(s) : 0);
-  const float* lng[3] = {p[DM_RSSM_GRU_LN_G0], p[DM_RSSM_GRU_LN_G1], p[DM_RSSM_GRU_LN_G2]};
-  const float* lnb[3] = {p[DM_RSSM_GRU_LN_B0], p[DM_RSSM_GRU_LN_B1], p[DM_RSSM_GRU_LN_B2]};
+struct RolloutCtx : RssmDims {
+  GruStack gk;
+  int M, H, Hm, L, adist, AO;      // rows, horizon; the actor MLP's width and depth, its distribution (0 onehot, 1 tanh_normal, 2 normal_tanh) and output width (a2c.py:35)
+  const float* const* p; const dm_mlp_params* actor; hipStream_t st; float* sk; size_t skb;
+  const float *u_act, *u_prior; float *feats, *actions; int32_t* act_idx; float *actor_acts, *actor_logits;
+  float *macts, *logits_ws, *ea, *x1, *za, *stats, *gi, *gh, *prior, *gsw, *gstw;
   // bf16 mode, plain single-layer GRU with LayerNorm: the cell's four 2 500-row products read bf16 twins (common.h DmTwinScope) -
   // per-call copies of their weights, za (written by the z_embed / LayerNorm kernels that produce it) and the h columns of
   // `feats` (written by the gates kernel; one range per step, so step 0's h, copied from `start`, stays on the fp32 path)
-  DmTwinScope tw((s->flags & DM_FLAG_BF16) != 0);
-  const bool tw_on = dm_twins_on() && kind == 0 && rssm_gru_layers(s) == 1 && p[DM_RSSM_IN_G] && p[DM_RSSM_PRIOR_G] && (F & 7) == 0;
-  unsigned short* wih_h = (unsigned short*)ar.take(tw_on ? dm_half_floats((size_t)3 * D * Hd) : 0);
-  unsigned short* whh_h = (unsigned short*)ar.take(tw_on ? dm_half_floats((size_t)3 * D * D) : 0);
-  unsigned short* wph_h = (unsigned short*)ar.take(tw_on ? dm_half_floats((size_t)Hd * D) : 0);
-  unsigned short* wp_h = (unsigned short*)ar.take(tw_on ? dm_half_floats((size_t)ZP * Hd) : 0);
-  unsigned short* za_h = (unsigned short*)ar.take(tw_on ? dm_half_floats((size_t)M * Hd) : 0);
-  unsigned short* feats_h = (unsigned short*)ar.take(tw_on ? dm_half_floats((size_t)(H + 1) * M * F) : 0);
-  DM_REQUIRE(ar.ok, DM_E_WORKSPACE, "dream_rollout: workspace too small (need %zu floats)", ar.off);
-  const size_t skb = DM_SPLITK_FLOATS * sizeof(float);
-  DmRolloutMarks marks(st);
-  const bool marks_eager = st == (hipStream_t)stream;
-  // the actor's weights, fragment-major for the whole-MLP kernel: packed once for all H steps
-  GruStack gk;
-  DM_TRY(gru_stack(s, p, nullptr, &gk));
-  if (tw_on) {
-    const DmCvtSeg sg[4] = {{p[DM_RSSM_GRU_WIH], wih_h, (size_t)3 * D * Hd}, {p[DM_RSSM_GRU_WHH], whh_h, (size_t)3 * D * D},
-                            {p[DM_RSSM_PRIOR_H_W], wph_h, (size_t)Hd * D}, {p[DM_RSSM_PRIOR_W], wp_h, (size_t)ZP * Hd}};
-    DM_TRY(dm_to_bf16_multi_launch(sg, 4, st));
-    for (int i = 0; i < 4; ++i) dm_twin_add(sg[i].src, sg[i].n, sg[i].dst, true);
-    dm_twin_add(za, (size_t)M * Hd, za_h, false);
-    for (int i = 1; i <= H && i < 40; ++i)
-      dm_twin_add(feats + (size_t)i * M * F, (size_t)M * F, feats_h + (size_t)i * M * F, false);
-  }
-  // steps 1.. of the rollout read the z the prior sampler of the step before drew: z_mlp + in_norm + ELU become one
-  // gather-sum launch over z_mlp^T (dm_z_embed_launch) instead of a (M x Hd x Z) product and a LayerNorm launch
-  float *wzt = nullptr, *wat = nullptr;
-  int32_t *pidx = nullptr, *aidx = nullptr;
-  if (C != 0 && H > 1 && dm_z_embed_ok(Hd)) {
-    const size_t mark = ar.off;
-    float* w = ar.take((size_t)Z * Hd);
-    float* w2 = ar.take((size_t)A * Hd);
-    int32_t* ix = reinterpret_cast<int32_t*>(ar.take((size_t)M * S));
-    int32_t* ax = reinterpret_cast<int32_t*>(ar.take((size_t)M));
-    if (ar.ok) {
-      wzt = w; pidx = ix;
-      DM_TRY(transpose(st, p[DM_RSSM_Z_W], wzt, Hd, Z));
-      if (adist == 0) {       // one-hot actions: a_mlp(action) is a row of a_mlp^T too
-        wat = w2; aidx = ax;
-        DM_TRY(transpose(st, p[DM_RSSM_A_W], wat, Hd, A));
+  bool tw_on;
+  unsigned short *wih_h, *whh_h, *wph_h, *wp_h, *za_h, *feats_h;
+  // steps 1.. of the rollout read the z the prior sampler of the step before drew (pidx): z_mlp + in_norm + ELU become one
+  // gather-sum launch over z_mlp^T (dm_z_embed_launch) instead of a (M x Hd x Z) product and a LayerNorm launch; with one-hot
+  // actions a_mlp(action) is a row of a_mlp^T too (wat; aidx: scratch for the action's index if the caller wants none)
+  float *wzt, *wat; int32_t *pidx, *aidx;
+  // the actor's weights, fragment-major for the whole-MLP kernel: packed once for all H steps.  The actor's first layer
+  // sees [h | one-hot z]: its z columns are a gathered sum of W0^T rows into actor_add0 (indices from the prior sampler;
+  // step 0's z is a dense vector: its non-zeros are found by ballot), the MFMA product runs over h only
+  float *actor_wpack, *actor_w0t, *actor_add0;
+  // one-hot actors on the whole-MLP kernel: the action draw rides in that kernel's output stage (dm_rollout_fuse_act_enable(0)
+  // keeps the stand-alone sampler launch - same rule, same operation order, bit-identical draws)
+  bool fuse_act;
+
+  // Carves the workspace and takes the optional buffers (the product path needs none of them); no launches.
+  int plan(void* ws, size_t ws_bytes) {
+    DmArena ar(ws, ws_bytes);
+    sk = ar.take(DM_SPLITK_FLOATS);
+    macts = ar.take(actor_acts ? 0 : dm_mlp_acts_floats(M, Hm, L)); logits_ws = ar.take(actor_acts ? 0 : (size_t)M * AO);
+    ea = ar.take((size_t)M * Hd); x1 = ar.take((size_t)M * Hd); za = ar.take((size_t)M * Hd); stats = ar.take((size_t)M * 2);
+    gi = ar.take((size_t)M * 3 * D); gh = ar.take((size_t)M * 3 * D); prior = ar.take((size_t)M * ZP);
+    gsw = ar.take(kind ? (size_t)M * 3 * D : 0); gstw = ar.take(kind ? (size_t)M * 6 * layers : 0);
+    tw_on = dm_twins_on() && kind == 0 && layers == 1 && p[DM_RSSM_IN_G] && p[DM_RSSM_PRIOR_G] && (F & 7) == 0;
+    wih_h = (unsigned short*)ar.take(tw_on ? dm_half_floats((size_t)3 * D * Hd) : 0);
+    whh_h = (unsigned short*)ar.take(tw_on ? dm_half_floats((size_t)3 * D * D) : 0);
+    wph_h = (unsigned short*)ar.take(tw_on ? dm_half_floats((size_t)Hd * D) : 0);
+    wp_h = (unsigned short*)ar.take(tw_on ? dm_half_floats((size_t)ZP * Hd) : 0);
+    za_h = (unsigned short*)ar.take(tw_on ? dm_half_floats((size_t)M * Hd) : 0);
+    feats_h = (unsigned short*)ar.take(tw_on ? dm_half_floats((size_t)(H + 1) * M * F) : 0);
+    DM_REQUIRE(ar.ok, DM_E_WORKSPACE, "dream_rollout: workspace too small (need %zu floats)", ar.off);
+    skb = DM_SPLITK_FLOATS * sizeof(float);
+    if (C != 0 && H > 1 && dm_z_embed_ok(Hd)) {
+      const size_t mark = ar.off;
+      float* w = ar.take((size_t)Z * Hd);
+      float* w2 = ar.take((size_t)A * Hd);
+      int32_t* ix = reinterpret_cast<int32_t*>(ar.take((size_t)M * S));
+      int32_t* ax = reinterpret_cast<int32_t*>(ar.take((size_t)M));
+      if (ar.ok) {
+        wzt = w; pidx = ix;
+        if (adist == 0) { wat = w2; aidx = ax; }
+      } else {
+        ar.off = mark; ar.ok = true;
       }
-    } else {      // optional buffers: the product path below needs none of them
-      ar.off = mark; ar.ok = true;
     }
-  }
-  const float* actor_wpack = nullptr;
-  // the actor's first layer sees [h | one-hot z]: its z columns are a gathered sum of W0^T rows (indices from the prior
-  // sampler; step 0's z is a dense vector: its non-zeros are found by ballot), the MFMA product runs over h only
-  float *actor_w0t = nullptr, *actor_add0 = nullptr;
-  if (dm_mlp_chain_ok(M, F, Hm, L, AO, feats, F, actor) && !dm_panel_ok(M, Hm)) {
-    float* wpk = ar.take(dm_mlp_chain_pack_floats(F, L));
-    if (ar.ok) {
-      int k0 = 0;
-      if (C != 0 && pidx && dm_mlp_chain_sparse_ok(F, Z) && dm_z_embed_ok(Hm)) {
-        const size_t mark = ar.off;
-        float* wt = ar.take((size_t)F * Hm);
-        float* ad = ar.take((size_t)M * Hm);
-        if (ar.ok) {
-          actor_w0t = wt; actor_add0 = ad; k0 = D;
-          DM_TRY(transpose(st, actor->w[0], actor_w0t, Hm, F));
-        } else {
-          ar.off = mark; ar.ok = true;
+    if (dm_mlp_chain_ok(M, F, Hm, L, AO, feats, F, actor) && !dm_panel_ok(M, Hm)) {
+      float* wpk = ar.take(dm_mlp_chain_pack_floats(F, L));
+      if (ar.ok) {
+        actor_wpack = wpk;
+        if (C != 0 && pidx && dm_mlp_chain_sparse_ok(F, Z) && dm_z_embed_ok(Hm)) {
+          const size_t mark = ar.off;
+          float* wt = ar.take((size_t)F * Hm);
+          float* ad = ar.take((size_t)M * Hm);
+          if (ar.ok) { actor_w0t = wt; actor_add0 = ad; }
+          else { ar.off = mark; ar.ok = true; }
         }
       }
-      DM_TRY(dm_mlp_chain_pack_launch(F, L, actor, wpk, st, k0));
-      actor_wpack = wpk;
     }
+    fuse_act = adist == 0 && actor_wpack && g_rollout_fuse_act;
+    return DM_OK;
   }
 
-  hipError_t e = hipMemcpyAsync(feats, start, (size_t)M * F * sizeof(float), hipMemcpyDeviceToDevice, st);
-  if (e != hipSuccess) return dm_fail(DM_E_HIP, "dream_rollout: %s", hipGetErrorString(e));
-  for (int i = 0; i < H; ++i) {
+  // the sampled action's index of step i (scratch if the caller wants none; null when there is neither)
+  int32_t* act_idx_of(int i) const { return act_idx ? act_idx + (size_t)i * M : aidx; }
+
+  // action ~ OneHotCategorical(actor(feature))                                          dreamer.py:195-200
+  // with actor_acts the activations of all H steps are kept (rows i*M..) so ActorCritic's policy-gradient backward
+  // reuses them instead of recomputing forward_actor(features[:-1]) (the reference's own TODO, a2c.py:119)
+  int rollout_actor(int i) const {
     const float* cur = feats + (size_t)i * M * F;
-    float* nxt = feats + (size_t)(i + 1) * M * F;
     float* act = actions + (size_t)i * M * A;
-    // action ~ OneHotCategorical(actor(feature))                                        dreamer.py:195-200
-    // with actor_acts the activations of all H steps are kept (rows i*M..) so ActorCritic's policy-gradient backward
-    // reuses them instead of recomputing forward_actor(features[:-1]) (the reference's own TODO, a2c.py:119)
-    float* logits = actor_acts ? actor_logits + (size_t)i * M * AO : logits_ws;
+    const bool keep = actor_acts != nullptr;
+    float* logits = keep ? actor_logits + (size_t)i * M * AO : logits_ws;
     if (actor_add0) {
       if (i == 0) DM_TRY(dm_sparse_rows_launch(M, Hm, Z, cur + D, F, actor_w0t + (size_t)D * Hm, actor_add0, Hm, st));
       else DM_TRY(dm_z_embed_launch(M, Hm, S, C, pidx, nullptr, actor_w0t + (size_t)D * Hm, nullptr, nullptr, 0, nullptr, nullptr,
                                     actor_add0, Hm, nullptr, nullptr, nullptr, 0.f, nullptr, 0, st));
     }
-    const int asp = actor_add0 ? Z : 0;
-    int32_t* ai = act_idx ? act_idx + (size_t)i * M : aidx;       // the sampled action's index (scratch if the caller wants none)
-    // one-hot actors on the whole-MLP kernel: the action draw rides in that kernel's output stage (round 6; dm_rollout_fuse_act_enable(0)
-    // keeps the stand-alone sampler launch - same rule, same operation order, bit-identical draws)
-    const bool fuse_act = adist == 0 && actor_wpack && g_rollout_fuse_act;
+    int32_t* ai = act_idx_of(i);
     const DmChainSample samp = {u_act + (size_t)i * M, act, A, ai};
-    if (actor_acts)
-      DM_TRY(dm_mlp_fwd_launch(M, F, Hm, L, AO, cur, F, actor, actor_acts, H * M, i * M, logits, AO, sk, skb, st, actor_wpack, asp,
-                               actor_add0, fuse_act ? &samp : nullptr));
-    else DM_TRY(dm_mlp_fwd_launch(M, F, Hm, L, AO, cur, F, actor, macts, M, 0, logits, AO, sk, skb, st, actor_wpack, asp, actor_add0,
-                                  fuse_act ? &samp : nullptr));
-    if (fuse_act) {
-    } else if (adist == 0)
-      DM_TRY(dm_sample_onehot_launch(M, 1, A, logits, A, u_act + (size_t)i * M, nullptr, act, A, ai, nullptr, nullptr, st));
-    else
-      DM_TRY(dm_sample_continuous_launch(adist, M, A, logits, u_act + (size_t)i * M * A, act, st));
-    // cell.forward_prior(action, None, (h, z))                                          rssm.py:155-184
+    DM_TRY(dm_mlp_fwd_launch(M, F, Hm, L, AO, cur, F, actor, keep ? actor_acts : macts, keep ? H * M : M, keep ? i * M : 0, logits,
+                             AO, sk, skb, st, actor_wpack, actor_add0 ? Z : 0, actor_add0, fuse_act ? &samp : nullptr));
+    if (fuse_act) return DM_OK;
+    if (adist == 0)
+      return dm_sample_onehot_launch(M, 1, A, logits, A, u_act + (size_t)i * M, nullptr, act, A, ai, nullptr, nullptr, st);
+    return dm_sample_continuous_launch(adist, M, A, logits, u_act + (size_t)i * M * A, act, st);
+  }
+  // cell.forward_prior(action, None, (h, z)) and z ~ prior                              rssm.py:155-184
+  int rollout_cell(int i) const {
+    const float* cur = feats + (size_t)i * M * F;
+    float* nxt = feats + (size_t)(i + 1) * M * F;
+    const float* act = actions + (size_t)i * M * A;
+    const int32_t* ai = act_idx_of(i);
     const bool embed = wzt && i > 0, embed_a = embed && wat && ai;
     if (!embed_a) DM_TRY(linear(st, sk, skb, M, Hd, A, act, A, p[DM_RSSM_A_W], nullptr, nullptr, 0, ea, Hd));
     if (embed) {
@@ -927,15 +939,62 @@ extern "C" int dm_dream_rollout(const dm_shape* s, int M, const float* start, co
     } else {
       DM_TRY(linear(st, sk, skb, M, 3 * D, Hd, za, Hd, p[DM_RSSM_GRU_WIH], p[DM_RSSM_GRU_BIH], nullptr, 0, gi, 3 * D));
       DM_TRY(linear(st, sk, skb, M, 3 * D, D, cur, F, p[DM_RSSM_GRU_WHH], p[DM_RSSM_GRU_BHH], nullptr, 0, gh, 3 * D));
+      if (kind == 0) DM_TRY(dm_gru_gates_fwd_launch(M, D, gi, gh, cur, F, nxt, F, nullptr, nullptr, nullptr, nullptr, st));
+      else DM_TRY(dm_gru_norm_fwd_launch(kind, M, D, gi, gh, cur, F, gk.lng[0], gk.lnb[0], nxt, F, gsw, gstw, nullptr, nullptr, st));
     }
-    if (gk.L > 1) {
-    } else if (kind == 0) DM_TRY(dm_gru_gates_fwd_launch(M, D, gi, gh, cur, F, nxt, F, nullptr, nullptr, nullptr, nullptr, st));
-    else DM_TRY(dm_gru_norm_fwd_launch(kind, M, D, gi, gh, cur, F, lng, lnb, nxt, F, gsw, gstw, nullptr, nullptr, st));
     DM_TRY(linear(st, sk, skb, M, Hd, D, nxt, F, p[DM_RSSM_PRIOR_H_W], p[DM_RSSM_PRIOR_H_B], nullptr, 0, x1, Hd));
     DM_TRY(norm_elu_fwd(M, Hd, x1, Hd, p[DM_RSSM_PRIOR_G], p[DM_RSSM_PRIOR_B], 1e-3f, za, Hd, stats, st));
     DM_TRY(linear(st, sk, skb, M, ZP, Hd, za, Hd, p[DM_RSSM_PRIOR_W], p[DM_RSSM_PRIOR_OB], nullptr, 0, prior, ZP));
-    DM_TRY(dm_sample_onehot_launch(M, S, C, prior, ZP, u_prior + (size_t)i * M * S, nullptr, nxt + D, F, pidx, nullptr,
-                                   nullptr, st));
+    return dm_sample_onehot_launch(M, S, C, prior, ZP, u_prior + (size_t)i * M * S, nullptr, nxt + D, F, pidx, nullptr, nullptr, st);
+  }
+};
+
+extern "C" int dm_dream_rollout(const dm_shape* s, int M, const float* start, const dm_rssm_params* P,
+                                const dm_mlp_params* actor, const float* u_act, const float* u_prior, float* feats,
+                                float* actions, int32_t* act_idx, float* actor_acts, float* actor_logits, void* ws,
+                                size_t ws_bytes, void* stream) {
+  DM_REQUIRE(s && start && P && actor && u_act && u_prior && feats && actions && ws, DM_E_NULL,
+             "dream_rollout: null pointer");
+  DmPrecisionScope prec(s->flags & DM_FLAG_BF16);
+  DM_TRY(rssm_check(s));
+  DM_REQUIRE(M >= 1 && s->H >= 1, DM_E_SHAPE, "dream_rollout: M=%d H=%d", M, s->H);
+  RolloutCtx c = {};
+  rssm_dims(s, &c);
+  c.M = M; c.H = s->H; c.Hm = s->mlp_hidden; c.L = s->mlp_layers; c.adist = s->flags & 3;
+  DM_REQUIRE(c.adist <= 2, DM_E_SHAPE, "dream_rollout: unknown actor distribution %d", c.adist);
+  c.AO = c.adist == 0 ? c.A : 2 * c.A;
+  DM_REQUIRE((actor_acts == nullptr) == (actor_logits == nullptr), DM_E_NULL,
+             "dream_rollout: actor_acts and actor_logits must be given together");
+  c.p = P->p; c.actor = actor; c.st = (hipStream_t)stream;
+  c.u_act = u_act; c.u_prior = u_prior; c.feats = feats; c.actions = actions; c.act_idx = act_idx;
+  c.actor_acts = actor_acts; c.actor_logits = actor_logits;
+  DmTwinScope tw((s->flags & DM_FLAG_BF16) != 0);
+  DM_TRY(c.plan(ws, ws_bytes));
+  const float* const* p = c.p;
+  const int H = c.H, D = c.D, Hd = c.Hd, Z = c.Z, ZP = c.ZP, F = c.F;
+  hipStream_t st = c.st;
+  DmRolloutMarks marks(st);
+  const bool marks_eager = st == (hipStream_t)stream;
+  DM_TRY(gru_stack(s, p, nullptr, &c.gk));
+
+  if (c.tw_on) {
+    const DmCvtSeg sg[4] = {{p[DM_RSSM_GRU_WIH], c.wih_h, (size_t)3 * D * Hd}, {p[DM_RSSM_GRU_WHH], c.whh_h, (size_t)3 * D * D},
+                            {p[DM_RSSM_PRIOR_H_W], c.wph_h, (size_t)Hd * D}, {p[DM_RSSM_PRIOR_W], c.wp_h, (size_t)ZP * Hd}};
+    DM_TRY(dm_to_bf16_multi_launch(sg, 4, st));
+    for (int i = 0; i < 4; ++i) dm_twin_add(sg[i].src, sg[i].n, sg[i].dst, true);
+    dm_twin_add(c.za, (size_t)M * Hd, c.za_h, false);
+    for (int i = 1; i <= H && i < 40; ++i)
+      dm_twin_add(feats + (size_t)i * M * F, (size_t)M * F, c.feats_h + (size_t)i * M * F, false);
+  }
+  if (c.wzt) DM_TRY(transpose(st, p[DM_RSSM_Z_W], c.wzt, Hd, Z));
+  if (c.wat) DM_TRY(transpose(st, p[DM_RSSM_A_W], c.wat, Hd, c.A));
+  if (c.actor_w0t) DM_TRY(transpose(st, actor->w[0], c.actor_w0t, c.Hm, F));
+  if (c.actor_wpack) DM_TRY(dm_mlp_chain_pack_launch(F, c.L, actor, c.actor_wpack, st, c.actor_w0t ? D : 0));
+  hipError_t e = hipMemcpyAsync(feats, start, (size_t)M * F * sizeof(float), hipMemcpyDeviceToDevice, st);
+  if (e != hipSuccess) return dm_fail(DM_E_HIP, "dream_rollout: %s", hipGetErrorString(e));
+  for (int i = 0; i < H; ++i) {
+    DM_TRY(c.rollout_actor(i));
+    DM_TRY(c.rollout_cell(i));
     marks.at_step(i, st, marks_eager);
   }
   return DM_OK;
