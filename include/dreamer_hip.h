@@ -70,7 +70,7 @@ typedef struct dm_shape {
 #define DM_FLAG_GRU_MASK (3 << DM_FLAG_GRU_SHIFT)
 
 /* ---------------------------------------------------------------- library ---------------------- */
-int dm_version(void);                 /* ABI version, currently 15 (v2: LayerNorm-GRU slots; v3: per-call precision; v4: GRUCellStack layer slots;
+int dm_version(void);                 /* ABI version, currently 16 (v2: LayerNorm-GRU slots; v3: per-call precision; v4: GRUCellStack layer slots;
                                          v5: dm_kl_sampled_gauss_*, dm_chain_graph_*, dm_fp32_mode - additions only;
                                          v6: LayerNorm slots of GRUCellStack layers 1..3, dm_rssm_params grows to 58;
                                          v7: dm_wgrad_side_arm / _join, dm_dream_rollout_marks, dm_mlp_head_fwd_rows - additions only;
@@ -86,7 +86,8 @@ int dm_version(void);                 /* ABI version, currently 15 (v2: LayerNor
                                          v14: dm_conv_encoder_fwd_rows, dm_conv_decoder_mse_fwd_rows, dm_rssm_sequence_fwd_steps removed (the forward
                                               time-chunk pipeline);
                                          v15: the native exchange step dm_rccl_available / _version / _unique_id / _comm_init / _comm_destroy
-                                              and dm_allreduce_grads removed */
+                                              and dm_allreduce_grads removed;
+                                         v16: dm_rssm_last_schedule added */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
 size_t dm_workspace_bytes(const dm_shape* shp);   /* scratch needed by any call below for this shape */
@@ -381,6 +382,29 @@ int dm_rssm_sequence_bwd(const dm_shape* shp, const float* embed, const float* a
                          const dm_rssm_params* p, const float* acts, const float* feat, const float* post,
                          float* dfeat, float* dpost, float* dprior,
                          const dm_rssm_grads* g, float* dembed, void* ws, size_t ws_bytes, void* stream);
+
+/* Schedule of this thread's most recent call: which = 0 dm_rssm_sequence_fwd, 1 dm_rssm_sequence_bwd, 2 dm_dream_rollout
+ * (-1 for any other `which`, 0 before the first call).  The three entry points pick their launch schedule from the shape, the
+ * switches above and the workspace size alone (csrc/rssm.hip plan()); this word is what they decided, stored once per call.
+ * Read-only diagnostic: a parity test asserts with it that the schedule it is about is the one that ran. */
+#define DM_SCHED_FWD_FUSE_LN 1          /* LayerNorm+ELU in the consuming product's prologue / in the z_embed gather */
+#define DM_SCHED_FWD_FUSE_SAMPLE 2      /* the sampler in the posterior-logits product's epilogue */
+#define DM_SCHED_FWD_FRAG 4             /* fragment-major operand copies taken */
+#define DM_SCHED_FWD_WZT 8              /* z_mlp of the sampled latent as a gather-sum over z_mlp^T */
+#define DM_SCHED_FWD_PSYNC 16           /* steps 1.. as the persistent LDS kernel */
+#define DM_SCHED_BWD_FUSE_B 1           /* LayerNorm backward in prologues (or folded), gates backward in an epilogue */
+#define DM_SCHED_BWD_FOLD 2             /* ... in folded form */
+#define DM_SCHED_BWD_FOLD_SM 4          /* ... with the straight-through softmax backward in the closing pair's epilogue */
+#define DM_SCHED_BWD_FRAG 8             /* fragment-major operand copies taken */
+#define DM_SCHED_BWD_NCHUNK_SHIFT 8     /* bits 8-11: time chunks of the batched weight gradients (1, 2 or 4) */
+#define DM_SCHED_BWD_NCHUNK_MASK (15 << DM_SCHED_BWD_NCHUNK_SHIFT)
+#define DM_SCHED_ROLL_WZT 1             /* z_mlp (+ in_norm + ELU) as a gather-sum from the prior sampler's indices */
+#define DM_SCHED_ROLL_WAT 2             /* a_mlp(action) as a row of a_mlp^T */
+#define DM_SCHED_ROLL_ACTOR_WPACK 4     /* the actor on the whole-MLP kernel */
+#define DM_SCHED_ROLL_ACTOR_ADD0 8      /* ... its first layer's z columns as a gathered sum */
+#define DM_SCHED_ROLL_FUSE_ACT 16       /* the one-hot action draw in that kernel's output stage */
+#define DM_SCHED_ROLL_TW_ON 32          /* bf16 twins of the cell's operands */
+int dm_rssm_last_schedule(int which);
 
 /* Progress marks for the NEXT dm_dream_rollout call of the calling thread (n <= 4; cleared by that call): events[i] - a
  * hipEvent_t owned by the caller - is recorded on the rollout's stream when horizon step steps[i] (0-based) has been

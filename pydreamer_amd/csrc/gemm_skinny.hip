@@ -570,15 +570,14 @@ int dm_gemm_skinny_try(const DmGemm& q, hipStream_t stream) {
   return 1;
 }
 // Both products in one launch if both qualify (k-contiguous B); otherwise two ordinary launches.
-// q0 may carry a LayerNorm+ELU prologue (ln_g / ln_b): then the one-launch path is mandatory (callers check
-// dm_skinny_ln_ok first).
+// q0 may carry a LayerNorm+ELU prologue (ln_g / ln_b): then q0 itself must qualify for the skinny kernel (callers check
+// dm_skinny_ln_ok first); q1's backward forms need the one-launch path.
 int dm_gemm_pair_launch(const DmGemm& q0, const DmGemm& q1, void* ws, size_t ws_bytes, hipStream_t stream) {
   const bool ln0 = q0.ln_g != nullptr && !q0.lnb_x, lnb1 = q1.lnb_x != nullptr;
   DM_REQUIRE(!q0.eg_x && !q1.eg_x && !q0.lnf_ps && (!q1.lnf_ps || (q1.lnf_stats && q1.lnf_xw && q1.lnf_cs && q1.lnf_nps >= 1 && !q1.lnb_x && !q1.ln_g)),
              DM_E_SHAPE, "gemm pair: the folded LayerNorm backward is built for the consumer side on the second product");
   DM_REQUIRE(!q0.lnb_x && !(q1.ln_g && !q1.lnb_x) && !q0.gates && !q1.gates, DM_E_SHAPE,
              "gemm pair: built for a forward LayerNorm prologue on the first product or a backward one on the second");
-  const bool fused = ln0 || lnb1;
   if (skinny_ok(q0, 64) && skinny_ok(q1, 64) && q0.b_layout == 0 && q1.b_layout == 0 &&
       (!ln0 || (q0.K <= SK_LN_MAXK && q0.ln_b)) &&
       (!lnb1 || (q1.K <= SK_LN_MAXK && q1.ln_g && q1.ln_b && q1.lnb_stats && (q1.lnb_ldx & 3) == 0 && ((uintptr_t)q1.lnb_x & 15) == 0))) {
@@ -612,7 +611,10 @@ int dm_gemm_pair_launch(const DmGemm& q0, const DmGemm& q1, void* ws, size_t ws_
     DM_LAUNCH_CHECK();
     return DM_OK;
   }
-  DM_REQUIRE(!fused && !q1.lnf_ps && !q1.sm_logits && !q0.sm_logits, DM_E_SHAPE, "gemm pair: LayerNorm prologue / folded backward requested but the one-launch skinny path does not apply");
+  // Not both on the skinny kernel (a short deter_dim puts the 3D x D recurrent product under the 64K floor): two launches.  The
+  // first keeps its forward prologue - the single-product skinny kernel has it, and dm_gemm_launch reports a shape that cannot
+  // take it; the backward forms on the second product exist in the pair kernel only (rssm.hip's fuse_b asks for both).
+  DM_REQUIRE(!lnb1 && !q1.lnf_ps && !q1.sm_logits && !q0.sm_logits, DM_E_SHAPE, "gemm pair: LayerNorm backward prologue / folded backward requested but the one-launch skinny path does not apply");
   DM_TRY(dm_gemm_launch(q0, ws, ws_bytes, stream));
   return dm_gemm_launch(q1, ws, ws_bytes, stream);
 }

@@ -214,6 +214,11 @@ static int gru_stack_fwd(hipStream_t st, void* sk, size_t skb, const GruStack& k
   return DM_OK;
 }
 
+// Schedule of this thread's most recent call of each entry point (include/dreamer_hip.h dm_rssm_last_schedule): one store
+// per call, right after plan() - a report of what plan() decided, read by tests; nothing in the library reads it back.
+static thread_local int tl_last_schedule[3] = {0, 0, 0};
+extern "C" int dm_rssm_last_schedule(int which) { return which >= 0 && which < 3 ? tl_last_schedule[which] : -1; }
+
 // ---------------------------------------------------------------- posterior T loop --------------
 struct PostCtx : RssmDims {
   RssmActs a; GruStack gk;
@@ -384,6 +389,8 @@ extern "C" int dm_rssm_sequence_fwd(const dm_shape* s, const float* embed, const
   c.reset = reset; c.u = u; c.forced = forced_idx; c.feat = feat; c.post = post; c.idx = idx;
   DM_TRY(gru_stack(s, c.p, nullptr, &c.gk));
   DM_TRY(c.plan(ws_bytes));
+  tl_last_schedule[0] = (c.fuse_ln ? DM_SCHED_FWD_FUSE_LN : 0) | (c.fuse_sample ? DM_SCHED_FWD_FUSE_SAMPLE : 0) |
+                        (c.zinf ? DM_SCHED_FWD_FRAG : 0) | (c.wzt ? DM_SCHED_FWD_WZT : 0) | (c.psync ? DM_SCHED_FWD_PSYNC : 0);
   const RssmActs& a = c.a;
   const float* const* p = c.p;
   const int N = c.N, D = c.D, Hd = c.Hd, Z = c.Z, ZP = c.ZP;
@@ -485,8 +492,10 @@ struct BpttCtx : RssmDims {
     sk_w = ar.take(DM_SPLITK_FLOATS); dx2_w = ar.take(rows * Hd); dx1_w = ar.take(rows * Hd);
     DM_REQUIRE(ar.ok, DM_E_WORKSPACE, "rssm_sequence_bwd: workspace too small (need %zu floats)", ar.off);
     skb = DM_SPLITK_FLOATS * sizeof(float);
+    // (the step's closing pair launch carries the LayerNorm backward on its second product: its first, dgh W_hh, must be on the
+    // skinny kernel too - 3D x D over that kernel's 64K floor, i.e. deter_dim >= 148)
     fuse_b = p[DM_RSSM_IN_G] != nullptr && !stacked && !gauss && kind == 0 && dm_skinny_ln_ok(B, D, Hd) &&
-             dm_skinny_ln_ok(B, Z, Hd) && (F & 3) == 0;
+             dm_skinny_ln_ok(B, Z, Hd) && (int64_t)3 * D * D >= (int64_t)64 * 1024 && (F & 3) == 0;
     fold = fuse_b && g_bptt_fold && B <= 64 && (int64_t)Hd * ZP >= (int64_t)64 * 1024 &&
            (int64_t)Hd * 3 * D >= (int64_t)64 * 1024 && (ZP & 3) == 0 && ((3 * D) & 3) == 0 && ZP >= 16;
     nstrip = (Hd + 15) / 16;
@@ -735,6 +744,8 @@ extern "C" int dm_rssm_sequence_bwd(const dm_shape* s, const float* embed, const
   c.embed = embed; c.action = action; c.feat = feat; c.post = post; c.reset = reset; c.dfeat = dfeat; c.dpost = dpost;
   DM_TRY(gru_stack(s, c.p, c.g, &c.gk));
   DM_TRY(c.plan(ws, ws_bytes));
+  tl_last_schedule[1] = (c.fuse_b ? DM_SCHED_BWD_FUSE_B : 0) | (c.fold ? DM_SCHED_BWD_FOLD : 0) | (c.fold_sm ? DM_SCHED_BWD_FOLD_SM : 0) |
+                        (c.dgif ? DM_SCHED_BWD_FRAG : 0) | (c.nchunk << DM_SCHED_BWD_NCHUNK_SHIFT);
   const RssmActs& a = c.a;
   const float* const* p = c.p;
   float* const* g = c.g;
@@ -970,6 +981,9 @@ extern "C" int dm_dream_rollout(const dm_shape* s, int M, const float* start, co
   c.actor_acts = actor_acts; c.actor_logits = actor_logits;
   DmTwinScope tw((s->flags & DM_FLAG_BF16) != 0);
   DM_TRY(c.plan(ws, ws_bytes));
+  tl_last_schedule[2] = (c.wzt ? DM_SCHED_ROLL_WZT : 0) | (c.wat ? DM_SCHED_ROLL_WAT : 0) | (c.actor_wpack ? DM_SCHED_ROLL_ACTOR_WPACK : 0) |
+                        (c.actor_add0 ? DM_SCHED_ROLL_ACTOR_ADD0 : 0) | (c.fuse_act ? DM_SCHED_ROLL_FUSE_ACT : 0) |
+                        (c.tw_on ? DM_SCHED_ROLL_TW_ON : 0);
   const float* const* p = c.p;
   const int H = c.H, D = c.D, Hd = c.Hd, Z = c.Z, ZP = c.ZP, F = c.F;
   hipStream_t st = c.st;

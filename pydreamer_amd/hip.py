@@ -40,6 +40,11 @@ _LN_SLOTS = {
 
 
 DM_FLAG_GRU_LAYERS_SHIFT = 8
+# dm_rssm_last_schedule(which): the bits of include/dreamer_hip.h DM_SCHED_*
+SCHED_FWD = {'fuse_ln': 1, 'fuse_sample': 2, 'frag': 4, 'wzt': 8, 'psync': 16}
+SCHED_BWD = {'fuse_b': 1, 'fold': 2, 'fold_sm': 4, 'frag': 8}
+SCHED_BWD_NCHUNK_SHIFT = 8
+SCHED_ROLL = {'wzt': 1, 'wat': 2, 'actor_wpack': 4, 'actor_add0': 8, 'fuse_act': 16, 'tw_on': 32}
 DM_MAX_GRU_LAYERS = 4
 
 
@@ -189,6 +194,7 @@ _SIGNATURES = {
     'dm_rssm_lds_status_ack': (c_int, []),
     'dm_rssm_lds_gave_up': (c_int, []),
     'dm_rssm_lds_prof': (c_int, [_P, c_int]),
+    'dm_rssm_last_schedule': (c_int, [c_int]),
     'dm_wgrad_side_arm': (c_int, [c_int]),
     'dm_wgrad_side_touch': (c_int, []),
     'dm_wgrad_side_join': (c_int, [_P]),
@@ -198,7 +204,7 @@ _SIGNATURES = {
 }
 
 _lib = None
-DM_ABI_VERSION = 15     # include/dreamer_hip.h dm_version(): the struct layouts above (dm_rssm_params: 58 slots) belong to this one
+DM_ABI_VERSION = 16     # include/dreamer_hip.h dm_version(): the struct layouts above (dm_rssm_params: 58 slots) belong to this one
 
 
 def lib():
@@ -232,6 +238,19 @@ def call(name, *args):
         msg = lib().dm_last_error().decode('utf-8', 'replace')
         raise DreamerHipError(f'{name} failed with code {rc}: {msg}')
     return rc
+
+
+def last_schedule(which):
+    """The schedule of this thread's most recent dm_rssm_sequence_fwd (0) / dm_rssm_sequence_bwd (1) / dm_dream_rollout (2)
+    call as a dict of the named bits (and `nchunk` for the backward)."""
+    word = int(lib().dm_rssm_last_schedule(which))
+    if word < 0:
+        raise DreamerHipError(f'dm_rssm_last_schedule({which}): no such entry point')
+    bits = (SCHED_FWD, SCHED_BWD, SCHED_ROLL)[which]
+    out = {k: bool(word & v) for k, v in bits.items()}
+    if which == 1:
+        out['nchunk'] = (word >> SCHED_BWD_NCHUNK_SHIFT) & 15
+    return out
 
 
 def ptr(t):

@@ -1,0 +1,153 @@
+"""-m gpu: every launch schedule of csrc/rssm.hip's posterior T loop and BPTT loop against the fp64 oracle, at the smallest
+widths that select it.
+
+rssm.hip picks its schedule from the shape alone, and every fused path is gated on N*K >= 64*1024 for the step's <= 64-row
+products: at the tiny configuration (deter 64, hidden 64, stoch 8x8) none of them is ever selected.  The cases below sit at
+deter 256 / hidden 256 / stoch 8x32 - every product of a step exactly ON that threshold - and at the neighbours that switch one
+path each; dm_rssm_sequence_fwd / _bwd are driven stand-alone through the C-ABI by tests/rssm_sequence_case.py (the body of
+test_gpu_training_step.py::test_rssm_sequence_fwd_bwd_vs_oracle).
+
+Every case asserts dm_rssm_last_schedule()'s bits BEFORE any value is compared, so none can pass on a path other than the one it
+names.  The expected bits are read from the predicates of PostCtx::plan / BpttCtx::plan, not from the library's report.
+
+Bars (the Atari-literal test's): features and logits within 2e-5 (logits + 1e-5 relative); every parameter gradient and dembed
+within 2e-4 relative L2 of the fp64 oracle.  Sampled indices: precondition - no uniform of the case within 1e-6 of an fp64 CDF
+edge - then ALL indices equal the fp64 draw.  The seed of each case was chosen on the CPU (free-running oracle, the helper's
+generator layout) so that the precondition holds: 11 unless the case names another; minimum distances at the chosen seeds are
+1.2e-6 .. 4.4e-4, the smallest being (B 16, T 3, seed 12) 4.0e-5 -> see SEEDS for the three cases where seed 11 came closer than
+2e-6 to an edge.
+
+Resets: a random ~15 % of (t, b), one at t = 0, one row at every step.  All cases: action_dim 18, cnn_depth 8, T = 4 unless stated.
+The forward runs at dm_rssm_lds_enable 0 and 2 where the case says so - both against fp64, not against each other; every case
+with fuse_b runs the backward at dm_bptt_fold_enable 1 and 0 (the prologue form), every case with fold once more on a workspace
+cut just below the fold buffers (it must report fold off and still meet the bars).
+"""
+import os
+import sys
+
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rssm_sequence_case as RC                      # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+BASE = (256, 256, 8, 32)
+# (B, T, D, Hd, S, C) -> seed, where seed 11 puts a uniform closer than 2e-6 to an fp64 CDF edge (distance at 11 -> at the seed)
+SEEDS = {(16, 3) + BASE: 12,                          # 1.5e-6 -> 4.0e-5
+         (16, 16, 256, 256, 16, 16): 13,              # 8.2e-7 -> 1.4e-5
+         (33, 16, 256, 256, 16, 16): 12}              # 3.0e-7 -> 1.3e-5
+
+
+def _fwd(fuse_ln=True, sample=True, frag=True, wzt=True, psync_level2=True, T=4):
+    """Expected forward bits as a function of the dm_rssm_lds_enable level: wzt needs a second step, the persistent kernel a
+    third one and level 2 (its default level stops at 32 rows and at models whose slices fill under half a CU's LDS)."""
+    return lambda level: dict(fuse_ln=fuse_ln, fuse_sample=fuse_ln and sample, frag=fuse_ln and sample and frag, wzt=wzt and T > 1,
+                              psync=psync_level2 and level == 2 and T >= 3)
+
+
+def _bwd(fuse_b=True, fold_sm=True, nchunk=1):
+    """Expected backward bits as a function of (dm_bptt_fold_enable, workspace cut): the cut run keeps fuse_b, loses fold; whether
+    the fragment copies still fit behind the mark depends on N and is not asserted there."""
+    def bits(fold, cut):
+        on = fuse_b and fold == 1 and not cut
+        out = dict(fuse_b=fuse_b, fold=on, fold_sm=on and fold_sm, nchunk=nchunk)
+        if not cut:
+            out['frag'] = fuse_b
+        return out
+    return bits
+
+
+def _run(B, T, dims, fwd, bwd, lds=(0,), conf_kw=None, fused_bwd=True, folded=True):
+    D_, Hd, S, C = dims
+    RC.run_case(B, T, D_, Hd, S, C, conf_kw=conf_kw, lds=lds, folds=(1, 0) if fused_bwd else (1,), resets=RC.resets_dense,
+                seed=SEEDS.get((B, T) + tuple(dims), 11), exact_idx=True, expect_fwd=fwd, expect_bwd=bwd,
+                cut_fold_ws=fused_bwd and folded)
+
+
+@pytest.mark.parametrize('B', [1, 8, 9, 16, 17, 32, 33, 64])
+def test_base_all_fused_at_every_row_boundary(hip, B):
+    """deter 256, hidden 256, stoch 8x32: every product of a step exactly on the 64K threshold.  Forward: LayerNorm+ELU in the
+    z_embed gather (`ln_z`) / the gate product's prologue at step 0, the sampler in the logits product's epilogue, fragment
+    copies; at level 2 steps 1.. as the persistent kernel (lane layouts rl = 8 / 16 / 32 / 64 at B <= 8 / 16 / 32 / 64).  Backward:
+    fuse_b + fold + fold_sm.  Rows 1, 8 / 9, 16 / 17, 32 / 33, 64: the NRB = 1 / 2 / 4 strip variants and the quarter / half
+    row splits of the <= 64-row kernels."""
+    _run(B, 4, BASE, _fwd(), _bwd(), lds=(0, 2))
+
+
+def test_base_at_65_rows_falls_back(hip):
+    """65 rows: every fused bit off in both directions (the z_mlp gather `wzt` does not depend on the row count and stays)."""
+    _run(65, 4, BASE, _fwd(fuse_ln=False, psync_level2=False), _bwd(fuse_b=False), fused_bwd=False)
+
+
+@pytest.mark.parametrize('B,T,nchunk', [(16, 1, 1), (16, 2, 1), (16, 3, 1), (16, 8, 2), (16, 16, 4), (16, 17, 4), (15, 16, 1), (64, 17, 4)])
+def test_base_sequence_length_edges(hip, B, T, nchunk):
+    """T = 1: no second step, no z_mlp gather.  T < 3: no persistent kernel.  The side stream's time chunks redo the LayerNorm
+    backward per chunk: 1 chunk for T in {1, 2, 3}, 2 for T = 8, 4 for T in {16, 17} (17: uneven chunk edges 0 / 4 / 8 / 12 / 17);
+    15 rows get 1 chunk at any length.  (64, 17): four chunks of the 64-row strips."""
+    _run(B, T, BASE, _fwd(T=T), _bwd(nchunk=nchunk), lds=(0, 2))
+
+
+@pytest.mark.parametrize('B', [16, 33])
+def test_forward_fused_backward_plain(hip, B):
+    """deter 128, hidden 256, stoch 8x32: the forward qualifies (3D x Hd and ZP x Hd >= 64K), the backward does not (D x Hd = 32K).
+    The recurrent gate product (3D x D = 48K) is below the skinny kernel's floor: the gate pair runs as two launches, the first
+    with its LayerNorm prologue (before this test existed dm_gemm_pair_launch refused that combination with DM_E_SHAPE)."""
+    _run(B, 4, (128, 256, 8, 32), _fwd(), _bwd(fuse_b=False), fused_bwd=False)
+
+
+@pytest.mark.parametrize('B,T,nchunk', [(16, 4, 1), (33, 4, 1), (16, 16, 4), (33, 16, 4)])
+def test_fused_without_the_sampler_epilogue(hip, B, T, nchunk):
+    """stoch 16x16: fuse_ln without fuse_sample (C != 32: the stand-alone sampler, no fragment copies, the prologue form of the
+    gate product at every step) and fold without fold_sm (the stand-alone softmax backward in front of every step)."""
+    _run(B, T, (256, 256, 16, 16), _fwd(sample=False, T=T), _bwd(fold_sm=False, nchunk=nchunk), lds=(0, 2))
+
+
+@pytest.mark.parametrize('B', [7, 17, 50])
+def test_wide_stoch_fused(hip, B):
+    """stoch 40x32 at a fused width: the sampler epilogue over 40 groups, the prologue form of the gate product at every step (the
+    row-per-workgroup gather holds <= 32 groups: no `ln_z`), fold_sm at N = 1280.  The persistent kernel's plan has S*C/4 = 320
+    workgroups, over its 256: refused at any level (the forward runs at level 2)."""
+    _run(B, 4, (256, 256, 40, 32), _fwd(psync_level2=False), _bwd(), lds=(2,))
+
+
+@pytest.mark.parametrize('B', [7, 33, 64])
+def test_ragged_widths(hip, B):
+    """deter 260, hidden 264, stoch 9x32: nstrip = 17 (a non-round strip count of the folded backward), K % 16 != 0 (a ragged last
+    16-k chunk in every product over hidden), 72 workgroups in the persistent kernel's plan."""
+    _run(B, 4, (260, 264, 9, 32), _fwd(), _bwd(), lds=(0, 2))
+
+
+@pytest.mark.parametrize('B', [7, 50])
+def test_layernorm_prologue_at_its_longest_row(hip, B):
+    """hidden 1024 = SK_LN_MAXK, deter 64, stoch 2x32: the forward's prologues and the sampler epilogue at the last K the row
+    cache holds (the `k < SK_LN_MAXK - 3` clamp).  The backward is plain: with deter 64 the step's closing pair launch has a
+    3D x D = 12K product the skinny kernel does not take, and its LayerNorm backward exists in that pair only - BpttCtx::plan
+    admitted the shape before this test existed and the call failed with DM_E_SHAPE; fuse_b now asks for 3D x D >= 64K."""
+    _run(B, 4, (64, 1024, 2, 32), _fwd(), _bwd(fuse_b=False), fused_bwd=False)
+
+
+@pytest.mark.parametrize('B', [7, 50])
+def test_layernorm_backward_at_its_longest_row(hip, B):
+    """hidden 1024 with deter 152 (the smallest multiple of 4 with 3D x D >= 64K): both directions fused at K = SK_LN_MAXK - the
+    prologue form, the folded form and fold_sm of the LayerNorm backward at the longest row."""
+    _run(B, 4, (152, 1024, 2, 32), _fwd(), _bwd())
+
+
+def test_hidden_1028_falls_back(hip):
+    """hidden 1028 is past the row cache of the LayerNorm prologue and past the z_mlp gather's 1024: every fused bit off, no wzt."""
+    _run(7, 4, (64, 1028, 2, 32), _fwd(fuse_ln=False, wzt=False, psync_level2=False), _bwd(fuse_b=False), fused_bwd=False)
+
+
+@pytest.mark.parametrize('gru_type', ['gru_layernorm', 'gru_layernorm_dv2'])
+@pytest.mark.parametrize('B', [16, 33])
+def test_single_layer_layernorm_gru_at_a_fused_width(hip, B, gru_type):
+    """The LayerNorm GRU cells at the base width: the fused forward (prologue form at every step, sampler epilogue) without fragment
+    copies and without the persistent kernel (plain cells only; level 2), the single-step backward."""
+    _run(B, 4, BASE, _fwd(frag=False, psync_level2=False), _bwd(fuse_b=False), lds=(2,), conf_kw=dict(gru_type=gru_type), fused_bwd=False)
+
+
+def test_no_layernorm_at_the_base_width(hip):
+    """layer_norm=False at the base width: every fused bit off; the step's plain products run on the skinny kernel (at the tiny
+    width they are tiled)."""
+    _run(16, 4, BASE, _fwd(fuse_ln=False, psync_level2=False), _bwd(fuse_b=False), conf_kw=dict(layer_norm=False), fused_bwd=False)

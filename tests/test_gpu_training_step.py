@@ -5,7 +5,9 @@ within 2e-5 relative (loss_model additionally within 1e-3 absolute, the north-st
 within 2e-3 relative L2 error; parameters after clip + AdamW within 1e-5 absolute (lr 3e-4 step).
 """
 import ast
+import contextlib
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -14,6 +16,8 @@ import torch.nn.functional as F
 
 from oracle import conv_reference as CR
 from oracle import dreamer_oracle as O
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))      # tests/rssm_sequence_case.py
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -610,8 +614,54 @@ def test_rssm_lds_kernel_with_a_busy_chip(hip):
         assert torch.equal(a, b), what
 
 
-def _run_pair(oconf, steps, forced=False, seed=0, mutate=None):
-    """One or more full trainer iterations (train.py:165-198) on the oracle (CPU) and the HIP model (GPU)."""
+MID = dict(deter_dim=256, hidden_dim=256, stoch_dim=8, stoch_discrete=32)      # the smallest width at which every <= 64-row product of a step reaches the fused schedules' 64K floor
+
+
+@contextlib.contextmanager
+def _record_schedules():
+    """dm_rssm_last_schedule() of every dm_rssm_sequence_fwd / _bwd / dm_dream_rollout call made inside the block, read on the
+    thread that made the call (the word is thread-local, and the model's backward runs on an autograd or launcher thread)."""
+    from pydreamer_amd import hip as H
+    which = {'dm_rssm_sequence_fwd': 0, 'dm_rssm_sequence_bwd': 1, 'dm_dream_rollout': 2}
+    seen, real = {'fwd': [], 'bwd': [], 'rollout': []}, H.call
+
+    def call(name, *args):
+        rc = real(name, *args)
+        if name in which:
+            seen[('fwd', 'bwd', 'rollout')[which[name]]].append(H.last_schedule(which[name]))
+        return rc
+    H.call = call
+    try:
+        yield seen
+    finally:
+        H.call = real
+
+
+def _assert_schedule(seen, **want):
+    """want: fwd / bwd / rollout -> dict of bits the FIRST such call of the block must report (keys left out are not asserted)."""
+    for entry, bits in want.items():
+        assert seen[entry], f'no {entry} call was recorded'
+        got = seen[entry][0]
+        for k, v in bits.items():
+            assert got[k] == v, f'{entry}: schedule bit {k} is {got[k]}, expected {v} (reported {got})'
+
+
+def _mid_schedule(B, T, Hh, rows, sample=True, fold_sm=True, psync=False):
+    """The schedule a trainer iteration must report at a width like MID, read from the predicates of csrc/rssm.hip: <= 64 posterior
+    rows take the fused forward and the folded backward; the rollout's actor runs on the whole-MLP kernel from 256 rows up."""
+    fused = B <= 64
+    return dict(fwd=dict(fuse_ln=fused, fuse_sample=fused and sample, frag=fused and sample, wzt=T > 1, psync=psync),
+                bwd=dict(fuse_b=fused, fold=fused, fold_sm=fused and fold_sm, frag=fused, nchunk=1 if (B < 16 or T < 8) else (2 if T < 16 else 4)),
+                rollout=dict(wzt=Hh > 1, wat=Hh > 1, actor_wpack=rows >= 256, actor_add0=rows >= 256 and Hh > 1, fuse_act=rows >= 256,
+                             tw_on=False))
+
+
+PLAIN_SCHEDULE = dict(fwd=dict(fuse_ln=False, fuse_sample=False, frag=False, psync=False), bwd=dict(fuse_b=False, fold=False, fold_sm=False, frag=False))
+
+
+def _run_pair(oconf, steps, forced=False, seed=0, mutate=None, expect=None):
+    """One or more full trainer iterations (train.py:165-198) on the oracle (CPU) and the HIP model (GPU).  expect: the launch
+    schedule (_assert_schedule's arguments) the first iteration must report - asserted before anything is compared."""
     params = O.make_params(oconf, seed=seed)
     ora = O.OracleDreamer(oconf, params)
     ora.init_optimizers()
@@ -629,12 +679,16 @@ def _run_pair(oconf, steps, forced=False, seed=0, mutate=None):
         lo, st_o2, mo, to, xo = ora.training_step(obs, st_o, noise)
         gmo, go = ora.backward_clip_step(lo)
         fidx = xo['post_idx'].reshape(oconf.batch_length, oconf.batch_size * oconf.iwae_samples, -1).to(DEV) if forced else None
-        lh, st_h2, mh, th, _ = model.training_step(_to_dev(obs), st_h, noise=_to_dev(noise), forced_idx=fidx)
-        for opt in opts:
-            opt.zero_grad()
-        for loss in lh:
-            loss.backward()
-        gmh = model.grad_clip(oconf.grad_clip, oconf.grad_clip_ac)
+        with _record_schedules() as seen:
+            lh, st_h2, mh, th, _ = model.training_step(_to_dev(obs), st_h, noise=_to_dev(noise), forced_idx=fidx)
+            for opt in opts:
+                opt.zero_grad()
+            for loss in lh:
+                loss.backward()
+            gmh = model.grad_clip(oconf.grad_clip, oconf.grad_clip_ac)
+        if expect is not None and s == 0:
+            print('SCHEDULE', {k: v[0] for k, v in seen.items() if v})
+            _assert_schedule(seen, **expect)
         # like the oracle's, gradients are compared AFTER clip_grad_norm_ scaled them in place (norm > 200 for some seeds)
         gh = {k: v.grad.detach().clone() for k, v in model.named_parameters() if v.grad is not None and v.requires_grad}
         for opt in opts:
@@ -705,6 +759,24 @@ def test_training_step_at_dispatch_boundaries_vs_oracle(hip, B, T, Hh):
         _check_pair(r, oconf)
 
 
+@pytest.mark.parametrize('B,T,Hh,seed', [(1, 2, 1, 3), (16, 2, 2, 18), (17, 3, 2, 20), (32, 2, 2, 36), (33, 2, 2, 35), (64, 4, 2, 68), (65, 4, 3, 80)])
+def test_training_step_at_dispatch_boundaries_mid_width_vs_oracle(hip, B, T, Hh, seed):
+    """The sibling of test_training_step_at_dispatch_boundaries_vs_oracle at deter 256 / hidden 256 / stoch 8x32, where the row
+    thresholds are those of the FUSED schedules (at the tiny width 3 D Hd = 12 288 is under the 64K floor of every fused path, so the
+    tiny test walks the plain 8-launch schedule only): LayerNorm+ELU in prologues / in the z_embed gather, the sampler epilogue,
+    fragment copies, the folded LayerNorm backward with fold_sm up to 64 rows, everything plain at 65; the rollout's and the heads'
+    <= 64-row products over the 512-wide feature on the skinny kernel (400 x 512 >= 64K), the whole-MLP actor with its gathered
+    first layer from 256 imagination rows.  The schedule of the first iteration is asserted (fwd, bwd, rollout), then two
+    iterations meet all of _check_pair's bars.
+    Seeds chosen on the CPU (oracle alone, candidates B + T ...): the first whose posterior, prior and action draws of both
+    iterations all stay >= 2e-6 from an fp32-oracle CDF edge.  Minimum distances at the chosen seeds: (1,2,1) 3.3e-4, (16,2,2)
+    3.4e-6, (17,3,2) 1.4e-5, (32,2,2) 3.9e-6 (seeds 34 / 35: 4.8e-7 / 3.6e-7), (33,2,2) 5.0e-6, (64,4,2) 2.2e-6, (65,4,3) 3.8e-6
+    (seeds 69..79: 2.3e-7 .. 1.3e-6)."""
+    oconf = O.tiny_conf(batch_size=B, batch_length=T, imag_horizon=Hh, **MID)
+    for r in _run_pair(oconf, 2, seed=seed, expect=_mid_schedule(B, T, Hh, T * B)):
+        _check_pair(r, oconf)
+
+
 NON_DEFAULT_BOUNDARY_CASES = [
     # Gaussian latents: posterior rows 17 / 32 / 33 / 65, imagination rows T x B = 255 / 256 / 66 / 260
     dict(stoch_discrete=0, batch_size=17, batch_length=15), dict(stoch_discrete=0, batch_size=32, batch_length=8),
@@ -756,14 +828,19 @@ def _extreme_frames(raw, s):
     raw['action_idx'][:] = raw['action_idx'].max()
 
 
-@pytest.mark.parametrize('mutate', [_all_reset, _no_reset, _all_terminal, _extreme_frames], ids=lambda f: f.__name__.strip('_'))
-def test_training_step_on_degenerate_batches_vs_oracle(hip, mutate):
+@pytest.mark.parametrize('mutate,mid', [pytest.param(_all_reset, False, id='all_reset'), pytest.param(_no_reset, False, id='no_reset'),
+                                        pytest.param(_all_terminal, False, id='all_terminal'), pytest.param(_extreme_frames, False, id='extreme_frames'),
+                                        pytest.param(_all_reset, True, id='all_reset-mid'), pytest.param(_no_reset, True, id='no_reset-mid')])
+def test_training_step_on_degenerate_batches_vs_oracle(hip, mutate, mid):
     """Replay batches at the corners of what preprocessing can hand over (preprocessing.py:135-150): every row reset at every step
     (the recurrent state is zeroed before each cell, rssm.py:117-119), no reset at all (two iterations: the second starts from the
     carried state), every step terminal with reward 1, saturated frames (all 255, then all 0) with one repeated action and reward
-    -1.  Two trainer iterations each against the oracle, all of _check_pair's bars."""
-    oconf = O.tiny_conf(batch_size=4, batch_length=6, imag_horizon=3)
-    for r in _run_pair(oconf, 2, seed=11, mutate=mutate):
+    -1.  Two trainer iterations each against the oracle, all of _check_pair's bars.
+    `-mid`: all / no reset again at deter 256 / hidden 256 / stoch 8x32, schedule asserted: there the masks are `row_zero` options
+    inside the fused schedules' products, not the mask kernels of the plain path (seed 11: every draw >= 7.0e-6 from an
+    fp32-oracle CDF edge in both cases)."""
+    oconf = O.tiny_conf(batch_size=4, batch_length=6, imag_horizon=3, **(MID if mid else {}))
+    for r in _run_pair(oconf, 2, seed=11, mutate=mutate, expect=_mid_schedule(4, 6, 3, 24) if mid else PLAIN_SCHEDULE):
         _check_pair(r, oconf)
 
 
@@ -782,19 +859,36 @@ def test_training_step_continuous_actor_vs_oracle(hip):
             _check_pair(r, oconf)
 
 
-@pytest.mark.parametrize('stoch,classes', [(40, 32), (64, 32), (33, 8)])
-def test_training_step_wide_stoch_vs_oracle(hip, stoch, classes):
-    """stoch_dim > 32 (the reference's larger configurations, e.g. 96 x 32 with deter 2048): the fragment-major gather +
-    LayerNorm form of z_mlp (`ln_z`, csrc/rssm.hip) and the lane-per-latent samplers are built for <= 32 latents per row, so these
-    shapes must take the generic kernels - every loss, metric and per-parameter gradient of two consecutive steps against the
-    oracle, with the persistent posterior kernel allowed and refused."""
+@pytest.mark.parametrize('stoch,classes,mid', [pytest.param(40, 32, False, id='40-32'), pytest.param(64, 32, False, id='64-32'),
+                                               pytest.param(33, 8, False, id='33-8'), pytest.param(40, 32, True, id='40-32-mid'),
+                                               pytest.param(16, 16, True, id='16-16-mid')])
+def test_training_step_wide_stoch_vs_oracle(hip, stoch, classes, mid):
+    """stoch_dim > 32 (the reference's larger configurations, e.g. 96 x 32 with deter 2048) and class counts other than 32: every
+    loss, metric and per-parameter gradient of two consecutive steps against the oracle, at two dm_rssm_lds_enable levels, with
+    the schedule of each run asserted.  What each parameter runs:
+      40-32, 64-32, 33-8 (hidden 64): the plain 8-launch schedule in both directions - no fused path is selected under the 64K
+        floor - with the generic sampler and z_mlp kernels over more than 32 latents per row.  The persistent kernel is refused at
+        level 1 and at level 0 alike: its slices need under 80 KiB of LDS (only level 2 takes such a model), and for 40 / 64 x 32
+        its plan has S*C/4 > 256 workgroups at any width.
+      40-32-mid (deter 256, hidden 256): S > 32 at a fused width - the sampler epilogue over 40 groups, the gate product's
+        prologue form at every step (the row-per-workgroup gather holds <= 32 groups: no `ln_z`), fuse_b + fold + fold_sm at
+        N = 1280; persistent kernel refused at levels 1 and 0 (320 workgroups).
+      16-16-mid: fuse_ln without the sampler epilogue and without fragment copies, fold without fold_sm; levels 2 and 0 - at
+        level 2 the persistent kernel takes steps 1.. (C = 16).
+    Seed 0: every posterior, prior and action draw of both iterations stays >= 2.7e-6 (40-32-mid) / 3.8e-5 (16-16-mid) from an
+    fp32-oracle CDF edge."""
     from pydreamer_amd import hip as H
-    oconf = O.tiny_conf(stoch_dim=stoch, stoch_discrete=classes)
+    oconf = O.tiny_conf(stoch_dim=stoch, stoch_discrete=classes, **(dict(deter_dim=256, hidden_dim=256) if mid else {}))
+    B, T, Hh = oconf.batch_size, oconf.batch_length, oconf.imag_horizon
+    levels = (2, 0) if (mid and classes == 16) else (1, 0)
     keep = H.lib().dm_rssm_lds_enable(-1)
     try:
-        for lds in (1, 0):
+        for lds in levels:
             H.lib().dm_rssm_lds_enable(lds)
-            for r in _run_pair(oconf, 2):
+            expect = PLAIN_SCHEDULE
+            if mid:
+                expect = _mid_schedule(B, T, Hh, T * B, sample=classes == 32, fold_sm=classes == 32, psync=lds == 2)
+            for r in _run_pair(oconf, 2, expect=expect):
                 _check_pair(r, oconf)
     finally:
         H.lib().dm_rssm_lds_enable(keep)
@@ -1026,18 +1120,32 @@ def test_iwae_training_step_matches_reference_golden(hip):
         np.testing.assert_allclose(state[0].cpu().numpy(), g[pre + 'out_state_h'], rtol=0, atol=2e-6 if step == 0 else 1e-4)
 
 
-def test_dream_rollout_vs_oracle(hip):
-    oconf = O.tiny_conf()
+@pytest.mark.parametrize('width,M,seed', [('tiny', 37, 5), ('tiny', 64, 5), ('tiny', 65, 5), ('tiny', 300, 5),
+                                          ('mid', 37, 5), ('mid', 64, 6), ('mid', 65, 5), ('mid', 300, 13)])
+def test_dream_rollout_vs_oracle(hip, width, M, seed):
+    """Dreamer.dream (dreamer.py:188-216) over 5 horizon steps against the oracle, at the tiny width and at deter 256 / hidden 256 /
+    stoch 8x32 (a 512-wide feature: the <= 64-row products of the cell, the actor and the heads sit on the skinny kernel there,
+    at the tiny width they are tiled), for 37, 64 / 65 (the skinny kernel's one-chunk limit) and 300 rows (the whole-MLP actor
+    with its gathered first layer and the action draw in its output stage: >= 256 rows).  The rollout's schedule is asserted, then
+    action indices equal, features within 2e-5, reward and terminal means within 1e-4 relative + 1e-5.
+    Seeds chosen on the CPU: the first of 5, 6, ... whose action and prior draws all stay >= 2e-6 from an fp32-oracle CDF edge;
+    minimum distances: tiny 8.0e-5 / 4.9e-5 / 7.5e-6 / 1.6e-5, mid 3.5e-6 / 4.8e-6 (seed 6; seed 5: 2.0e-6) / 2.7e-6 / 5.7e-6
+    (seed 13; seeds 5..12: 9.7e-8 .. 1.5e-6)."""
+    oconf = O.tiny_conf(**(MID if width == 'mid' else {}))
     params = O.make_params(oconf)
     model = _build(oconf, params)
-    M, Hh = 37, 5
-    g = torch.Generator().manual_seed(5)
+    Hh = 5
+    g = torch.Generator().manual_seed(seed)
     h = torch.tanh(torch.randn(M, oconf.deter_dim, generator=g))
     z = F.one_hot(torch.randint(0, oconf.stoch_discrete, (M, oconf.stoch_dim), generator=g), oconf.stoch_discrete).float().reshape(M, -1)
     u_act, u_prior = torch.rand(Hh, M, generator=g), torch.rand(Hh, M, oconf.stoch_dim, generator=g)
     p = {k: v for k, v in params.items()}
     fo, ao, ro, to, xo = O.dream(p, oconf, (h, z), Hh, u_act, u_prior)
-    fh, ah, rh, th = model.dream((h.to(DEV), z.to(DEV)), Hh, u_act=u_act.to(DEV), u_prior=u_prior.to(DEV))
+    with _record_schedules() as seen:
+        fh, ah, rh, th = model.dream((h.to(DEV), z.to(DEV)), Hh, u_act=u_act.to(DEV), u_prior=u_prior.to(DEV))
+    print('SCHEDULE', seen['rollout'][:1])
+    big = M >= 256
+    _assert_schedule(seen, rollout=dict(wzt=True, wat=True, actor_wpack=big, actor_add0=big, fuse_act=big, tw_on=False))
     assert torch.equal(ah.cpu(), ao)
     _close(fh, fo, 0, 2e-5, 'dream features')
     _close(rh.mean, ro, 1e-4, 1e-5, 'dream rewards')
@@ -1082,82 +1190,11 @@ def test_rssm_sequence_fwd_bwd_vs_oracle(hip, B, T):
     the epilogue of the posterior-logits product), the following steps as the LDS-weight-stationary persistent kernel
     (csrc/rssm_lds.hip; B = 6 is the shard of ranks 2-7 of an 8-way split of 50 columns).  Oracle = rssm.py:21-78,125-153,186-193 restated in fp64 (oracle.cell_forward /
     prior_head) with autograd; the loss is a random projection of (features, post, prior).
-    Bars: indices identical (a uniform within 1e-6 of a CDF edge excepted), states / logits 2e-5, every parameter
-    gradient and dembed within 2e-4 relative L2 (posterior indices forced to the HIP draw in the oracle)."""
-    import ctypes
-    from pydreamer_amd import config, hip as H
-    from pydreamer_amd.models import Dreamer
-    D_, Hd, S, C, A, depth = 600, 1000, 32, 32, 18, 8
-    oconf = O.make_conf(deter_dim=D_, hidden_dim=Hd, stoch_dim=S, stoch_discrete=C, cnn_depth=depth, action_dim=A,
-                        batch_size=B, batch_length=T)
-    params = O.make_params(oconf, seed=4)
-    model = _build(oconf, params)
-    cell = model.wm.core.cell
-    E, Z, F_ = 32 * depth, S * C, D_ + S * C
-    g = torch.Generator().manual_seed(11)
-    embed = torch.randn(T, B, E, generator=g)
-    action = F.one_hot(torch.randint(0, A, (T, B), generator=g), A).float()
-    reset = torch.zeros(T, B, dtype=torch.bool)
-    reset[0, 0] = True
-    reset[2, B - 1] = True
-    h0 = torch.tanh(torch.randn(B, D_, generator=g))
-    z0 = F.one_hot(torch.randint(0, C, (B, S), generator=g), C).float().reshape(B, Z)
-    u = torch.rand(T, B, S, generator=g)
-    Gf, Gp, Gq = (torch.randn(T * B, n, generator=g) / (T * B) for n in (F_, Z, Z))
-    shp = model.wm.shape(T, B, 1)
-    ws = model.wm.workspace(shp, torch.device(DEV, 0))
-    N = T * B
-    dev = lambda x: x.to(DEV).contiguous()
-    acts = torch.empty(int(H.lib().dm_rssm_acts_floats(ctypes.byref(shp))), device=DEV)
-    feat, post, prior = torch.empty(N, F_, device=DEV), torch.empty(N, Z, device=DEV), torch.empty(N, Z, device=DEV)
-    idx = torch.empty(N, S, dtype=torch.int32, device=DEV)
-    e_d, a_d, r_d, u_d = dev(embed.view(N, E)), dev(action.view(N, A)), dev(reset.view(N).to(torch.uint8)), dev(u.view(N, S))
-    P = H.rssm_struct(cell.ordered())
-    # (the initial state stays referenced: a pointer taken from a temporary tensor is handed back to the caching allocator at
-    # once, and the next temporary may land on it - round 4 found this test flaky for exactly that reason)
-    h0_d, z0_d = dev(h0), dev(z0)
-    H.call('dm_rssm_sequence_fwd', ctypes.byref(shp), H.fptr(e_d), H.fptr(a_d), H.ptr(r_d), H.fptr(h0_d), H.fptr(z0_d),
-           H.fptr(u_d), None, ctypes.byref(P), H.fptr(acts), H.fptr(feat), H.fptr(post), H.fptr(prior), H.ptr(idx), H.ptr(ws),
-           ws.numel(), H.stream())
-    assert H.lib().dm_rssm_lds_status() == 0
-    # oracle, fp64, posterior indices forced to the HIP draw (compared separately below)
-    pd = {k: v.double().requires_grad_(True) for k, v in params.items() if k.startswith('wm.core.')}
-    emb64 = embed.double().requires_grad_(True)
-    h, z = h0.double(), z0.double()
-    hs, zs, posts, idx_o = [], [], [], []
-    for t in range(T):
-        mask = (~reset[t]).double().unsqueeze(-1)
-        po, h, z, _ = O.cell_forward(pd, oconf, emb64[t], action[t].double(), mask, h, z, u[t].double(),
-                                     forced_idx=idx.view(T, B, S)[t].cpu())
-        with torch.no_grad():
-            lg = po.detach().float().reshape(B, S, C)
-            idx_o.append(O.sample_inverse_cdf(torch.softmax(lg - lg.logsumexp(-1, keepdim=True), -1), u[t]))
-        hs.append(h); zs.append(z); posts.append(po)
-    hs, zs, posts = torch.stack(hs), torch.stack(zs), torch.stack(posts)
-    priors = O.prior_head(pd, hs)
-    feat_o = torch.cat((hs, zs), -1).reshape(N, F_)
-    same = torch.stack(idx_o).reshape(N, S) == idx.cpu().long()
-    print('index agreement with the oracle per step:', same.view(T, B, S).float().mean(dim=(1, 2)).tolist(),
-          'per row:', same.view(T, B, S).float().mean(dim=(0, 2)).tolist())
-    assert same.float().mean() > 0.999, float(same.float().mean())
-    _close(feat, feat_o, 0, 2e-5, 'rssm features')
-    _close(post, posts.reshape(N, Z), 1e-5, 2e-5, 'rssm post logits')
-    _close(prior, priors.reshape(N, Z), 1e-5, 2e-5, 'rssm prior logits')
-    loss = (feat_o * Gf.double()).sum() + (posts.reshape(N, Z) * Gp.double()).sum() + (priors.reshape(N, Z) * Gq.double()).sum()
-    loss.backward()
-    grads = [None if p_ is None else torch.zeros_like(p_) for p_ in cell.ordered()]
-    Gs = H.rssm_struct(grads, cls=H.dm_rssm_grads)
-    dembed = torch.empty(N, E, device=DEV)
-    dfeat, dpost, dprior = dev(Gf), dev(Gp), dev(Gq)
-    H.call('dm_rssm_sequence_bwd', ctypes.byref(shp), H.fptr(e_d), H.fptr(a_d), H.ptr(r_d), ctypes.byref(P), H.fptr(acts),
-           H.fptr(feat), H.fptr(post), H.fptr(dfeat), H.fptr(dpost), H.fptr(dprior), ctypes.byref(Gs), H.fptr(dembed),
-           H.ptr(ws), ws.numel(), H.stream())
-    torch.cuda.synchronize()
-    assert H.lib().dm_rssm_lds_status() == 0
-    for name, gh in zip(H.rssm_param_names('gru'), grads):
-        if name is not None:
-            assert _rel_l2(gh, pd['wm.core.cell.' + name].grad) < 2e-4, name
-    assert _rel_l2(dembed, emb64.grad.reshape(N, E)) < 2e-4, 'dembed'
+    Bars: indices identical (a uniform within 1e-6 of a CDF edge excepted: > 99.9 %), states / logits 2e-5, every parameter
+    gradient and dembed within 2e-4 relative L2 (posterior indices forced to the HIP draw in the oracle).  The smallest widths
+    that select each schedule, with the schedule asserted: test_gpu_rssm_schedules.py."""
+    import rssm_sequence_case as RC      # the body of this test, shared with test_gpu_rssm_schedules.py
+    RC.run_case(B, T, 600, 1000, 32, 32, resets=RC.resets_two, seed=11, exact_idx=False)
 
 
 # ------------------------------------------------------------------------------------------- size-independent properties
