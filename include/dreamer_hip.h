@@ -87,7 +87,9 @@ int dm_version(void);                 /* ABI version, currently 16 (v2: LayerNor
                                               time-chunk pipeline);
                                          v15: the native exchange step dm_rccl_available / _version / _unique_id / _comm_init / _comm_destroy
                                               and dm_allreduce_grads removed;
-                                         v16: dm_rssm_last_schedule added */
+                                         v16: dm_rssm_last_schedule added; later, still 16 (additions only): the per-cell categorical
+                                              loss family dm_cat_target_index / dm_cat_image_loss / dm_cat_image_pred / dm_cat_concat_rows
+                                              of the map probe */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
 size_t dm_workspace_bytes(const dm_shape* shp);   /* scratch needed by any call below for this shape */
@@ -298,6 +300,29 @@ int dm_head_loss(int kind, int rows, const float* out, const float* target, floa
  * out / target / dout / mean_out are (rows,V); loss[r] = 0.5 * sum_v (mu-y)^2 + V * loss_const; dout = scale * (mu-y). */
 int dm_head_loss_normal_nd(int rows, int V, const float* out, const float* target, float scale, float loss_const,
                            float* loss, float* dout, float* mean_out, void* stream);
+
+/* Per-cell categorical losses over a (C, H, W) logit block (csrc/cat_image.hip): the map probe's CatImageDecoder
+ * (decoders.py:183-254, probes.py:32-86).  A logit row is class-major as nn.Unflatten(-1, (C,H,W)) lays it out: class c of
+ * cell p at c*cells + p, cells = H*W.  fp32 arithmetic whatever the precision of the products around it; no float atomics
+ * (the same inputs give the same bits).  Arguments are checked on the host before anything is launched.
+ * idx[r][p] = argmax_c onehot[r][c][p], the lowest class on equal values (decoders.py:221 / probes.py:75 target.argmax(dim=-3)):
+ * onehot (rows, C, cells) -> idx (rows, cells) int32. */
+int dm_cat_target_index(int rows, int C, int cells, const float* onehot, int32_t* idx, void* stream);
+/* F.nll_loss(F.log_softmax(output, 1), target).sum([-1, -2]) (decoders.py:227,234): logits (rows, C*cells) with leading
+ * dimension ld >= C*cells, target (rows / I, cells) int32 - row r reads target row r / I (decoders.py:241 insert_dim), rows % I == 0.
+ * loss[r] = sum_p (logsumexp_c x[c][p] - x[target[p]][p]); dlogits (rows, C*cells), optional: softmax_c - onehot, unscaled. */
+int dm_cat_image_loss(int rows, int I, int C, int cells, const float* logits, int ld, const int32_t* target, float* loss,
+                      float* dlogits, void* stream);
+/* The decoded map and its accuracy for `groups` frames of I rows each (logits (groups*I, C*cells), leading dimension ld).
+ * logp (groups, C, cells), optional: log_softmax over C per row, logsumexp over the I rows, normalised over C again
+ * (decoders.py:247-251).  acc[g] = fraction of cells with argmax_c logp == target (probes.py:79-81; lowest class on a tie).
+ * seen (groups, cells) int32 mask and acc_seen, optional: acc_seen[g] = sum(hit * seen) / sum(seen), NaN for a frame without
+ * a seen cell (probes.py:84; the caller's nanmean skips it).  I <= 256. */
+int dm_cat_image_pred(int groups, int I, int C, int cells, const float* logits, int ld, const int32_t* target,
+                      const int32_t* seen, float* logp, float* acc, float* acc_seen, void* stream);
+/* out (rows, F + E) = [ x[r][0..F) (leading dimension ldx) | extra[r / I][0..E) ]: torch.cat((features, insert_dim(map_coord, 2, I)), -1)
+ * of probes.py:54-55. */
+int dm_cat_concat_rows(int rows, int I, int F, int E, const float* x, int ldx, const float* extra, float* out, void* stream);
 
 /* uint8 ingest (preprocessing.py:21-29 to_image): src (n, h*w, c) uint8 HWC -> dst (n, c, h*w) float32,
  * x/255 - 0.5.  Lets the trainer hand the replay's native uint8 frames to training_step(). */

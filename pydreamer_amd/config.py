@@ -22,7 +22,8 @@ SECTIONS = {
         image_decoder_layers=0, reward_input=False, reward_decoder_layers=4, reward_decoder_categorical=None,
         terminal_decoder_layers=4,
         # probe
-        probe_model='none',
+        probe_model='none', map_key=None, map_size=0, map_channels=0, map_categorical=True, goals_size=0, map_decoder='dense',
+        map_hidden_layers=4, map_hidden_dim=1024,
         # actor critic
         gamma=0.995, lambda_gae=0.95, entropy=0.003, target_interval=100, imag_horizon=15, actor_grad='reinforce',
         actor_dist='onehot',
@@ -31,10 +32,10 @@ SECTIONS = {
     ),
     'atari': dict(action_dim=18, clip_rewards='tanh', deter_dim=1024, kl_weight=0.1, gamma=0.99, entropy=0.001),
     'dmc': dict(action_dim=12, entropy=1.0e-4, actor_grad='dynamics', actor_dist='tanh_normal', clip_rewards='tanh'),
-    # defaults.yaml:143-161, the keys the hot path reads.  probe_model is 'none' here, NOT the reference's 'goals': probe models
-    # are not built, and Dreamer() raises NotImplementedError for them
+    # defaults.yaml:143-161, the keys the hot path reads.  probe_model is 'none' here, NOT the reference's 'goals': the goals
+    # probe is not built, and Dreamer() raises NotImplementedError for it; probe_model='map' (the map keys below) is
     'miniworld': dict(action_dim=3, image_key='image', image_size=64, image_channels=3, image_categorical=False,
-                      reward_input=True, probe_model='none', cnn_depth=32),
+                      reward_input=True, probe_model='none', cnn_depth=32, map_key='map', map_size=9, map_channels=14),
     'minecraft': dict(action_dim=29, vecobs_size=27, clip_rewards='log1p'),      # defaults.yaml:244-248
     'debug': dict(device='cpu', batch_length=15, batch_size=5, imag_horizon=3),
 }

@@ -36,7 +36,7 @@ def attach(optimizers, local_batch, global_batch, group=None, model=None, force=
     model (a pydreamer_amd Dreamer whose init_optimizers() produced `optimizers`): the B_r/B weight is FOLDED into the scale
     argument every backward entry point already takes (models.WorldModel / ActorCritic.grad_weight), so the rank's gradient
     buffers come out of the backward kernels already weighted and no extra pass over the 92 MB buffer runs per step; without
-    it (or for a group fed by autograd, the 1-element probe group) the buffer is multiplied before the collective."""
+    it (or for a group fed by autograd, the 1-element group of probe_model='none') the buffer is multiplied before the collective."""
     if not dist.is_initialized() or (dist.get_world_size(group) == 1 and not force):
         return      # (force: a ONE-rank group still issues its collectives - bench.py --force-dp measures their cost on a 1-GPU box)
     w = float(local_batch) / float(global_batch)
@@ -47,6 +47,9 @@ def attach(optimizers, local_batch, global_batch, group=None, model=None, force=
         model.wm.grad_weight = w
         model.ac.grad_weight = w
         folded = {id(model._opt[k]) for k in ('wm', 'actor', 'critic')}
+        if hasattr(model.probe_model, 'decoder'):      # the map probe scales its own gradient rows (models.MapProbeHead)
+            model.probe_model.grad_weight = w
+            folded.add(id(model._opt['probe']))
     for opt in optimizers:
         opt.dp = (group, w)
         opt.dp_folded = id(opt) in folded

@@ -10,7 +10,8 @@ reference (train.py:184-187).  There is no CPU path: tensors must live on a gfx9
 Supported configuration (everything else raises NotImplementedError): iwae_samples>=1 (also with the logging flags), gru_type in {gru, gru_layernorm,
 gru_layernorm_dv2}, gru_layers 1..4, stoch_discrete>0 or 0 (Gaussian latents, also with iwae_samples>1), layer_norm True or False,
 aux_critic, image_encoder/decoder='cnn' at 64x64, actor_dist in {onehot, tanh_normal, normal_tanh}, actor_grad='reinforce',
-probe_model='none', reward_input (cnn_depth in {8, 16, 32, 48, 64}: the reward and terminal planes are folded into the first
+probe_model in {none, map} (map: the CatImageDecoder probe of the top-down map on the detached features; not with
+probe_gradients=True, whose gradient into the world model's features is not built; the goals probe is not built), reward_input (cnn_depth in {8, 16, 32, 48, 64}: the reward and terminal planes are folded into the first
 convolution), vecobs_size > 0 beside the image (an MLP encoder whose output sits behind the image embedding, a
 DenseNormalDecoder with out_dim = vecobs_size).
 """
@@ -366,6 +367,110 @@ class NoProbeHead(nn.Module):
         return torch.square(self.dummy), {}, {}
 
 
+class MapProbeHead(_Params):
+    """probes.py:32-86 with the dense CatImageDecoder (decoders.py:183-254): an MLP from [features | map_coord] to the
+    (map_channels, map_size, map_size) logits of the top-down map, trained by a per-cell cross-entropy on the DETACHED features -
+    the reference's memory evaluation for maze environments.  `self.decoder` is the MLP holder, so the keys are
+    probe_model.decoder.model.{0,1,3,4,...}.{weight,bias} as the reference's Sequential names them; torch's default Linear
+    init (init_weights_tf2 is applied to the world model only, dreamer.py:283).  The loss, its gradient, the decoded map and the
+    accuracies are the kernels of csrc/cat_image.hip; all of them fp32 (conf.amp reaches the MLP's products only).
+    The gradient INTO the features (probe_gradients=True) is not built: Dreamer() refuses that combination."""
+
+    def __init__(self, map_state_dim, conf):
+        super().__init__()
+        if getattr(conf, 'map_decoder', 'dense') != 'dense':
+            raise NotImplementedError(conf.map_decoder)                    # probes.py:43
+        self.map_channels, self.map_size = int(getattr(conf, 'map_channels', 0)), int(getattr(conf, 'map_size', 0))
+        if self.map_channels < 1 or self.map_size < 1:
+            raise ValueError(f"probe_model='map' needs map_size >= 1 and map_channels >= 1 (got map_size={self.map_size}, "
+                             f'map_channels={self.map_channels})')
+        layers = int(getattr(conf, 'map_hidden_layers', 4))
+        if layers < 1:
+            raise NotImplementedError('map_hidden_layers=0 (a single Linear, decoders.py:205-209) is not built in the HIP path')
+        self.decoder = MLP(map_state_dim, self.map_channels * self.map_size ** 2, int(getattr(conf, 'map_hidden_dim', 1024)), layers,
+                           conf.layer_norm)
+        self._ws = None
+
+    def _workspace(self, rows, device):
+        d = self.decoder
+        need = 4 * int(H.lib().dm_mlp_ws_floats(rows, d.hidden_dim, d.hidden_layers))
+        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
+        return self._ws
+
+    def training_step(self, features, obs, mbuf=None):
+        """features (T,B,I,F), detached.  Returns (loss_probe, metrics, tensors) with the reference's names: metrics loss_map,
+        acc_map, acc_map_seen (only with obs['map_seen_mask']); tensors map_rec (T,B,C,H,W), loss_map (T,B), acc_map (T,B)."""
+        _require_cuda(features, 'features')
+        T, B, I, F_ = features.shape
+        C, S = self.map_channels, self.map_size
+        cells, N, NE, dev = S * S, T * B * I, T * B, features.device
+        for k in ('map', 'map_coord'):
+            if k not in obs:
+                raise ValueError(f"probe_model='map': obs['{k}'] is an input of the map probe (probes.py:54-57)")
+        m = obs['map']
+        onehot = m.is_floating_point()
+        want = dict(map=(T, B, C, S, S) if onehot else (T, B, S, S), map_coord=(T, B, 4))
+        got = dict(map=tuple(m.shape), map_coord=tuple(obs['map_coord'].shape))
+        seen = obs.get('map_seen_mask')
+        if seen is not None:
+            want['map_seen_mask'], got['map_seen_mask'] = (T, B, S, S), tuple(seen.shape)
+        bad = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
+        if bad:
+            raise ValueError('training_step input shapes (got, expected): ' + ', '.join(f'{k}: {v[0]} != {v[1]}' for k, v in bad.items()))
+        train = torch.is_grad_enabled()
+        with torch.no_grad():
+            # target.argmax(dim=-3) (decoders.py:221); an integer class map is taken as it is
+            if onehot:
+                target = torch.empty(NE, cells, dtype=torch.int32, device=dev)
+                H.call('dm_cat_target_index', NE, C, cells, H.fptr(m.float().contiguous()), H.ptr(target), H.stream())
+            else:
+                target = m.to(torch.int32).contiguous().view(NE, cells)
+            # torch.cat((features, insert_dim(map_coord, 2, I)), -1) (probes.py:54-55)
+            feat2d = features.reshape(N, F_)
+            x = torch.empty(N, F_ + 4, device=dev)
+            H.call('dm_cat_concat_rows', N, I, F_, 4, H.fptr(feat2d.contiguous()), F_, H.fptr(obs['map_coord'].float().contiguous()),
+                   H.fptr(x), H.stream())
+            ws = self._workspace(N, dev)
+            dec = self.decoder
+            logits, acts = dec.fwd(x, F_ + 4, N, ws, save_acts=train)
+            ld = C * cells
+            loss_tbi = torch.empty(N, device=dev)
+            dlogits = torch.empty(N, ld, device=dev) if train else None
+            H.call('dm_cat_image_loss', N, I, C, cells, H.fptr(logits), ld, H.ptr(target), H.fptr(loss_tbi), H.fptr(dlogits), H.stream())
+            gw = float(getattr(self, 'grad_weight', 1.0))          # data-parallel shard weight B_r/B (dist.attach), gradients only
+            if I == 1:
+                loss_tb = loss_tbi
+                if train:      # d loss_probe / d loss_tb = 1 / (T*B)
+                    H.call('dm_scale_inplace', H.fptr(dlogits), N * ld, H.fptr(torch.full((1,), gw / NE, device=dev)), H.stream())
+            else:              # loss_tb = -logavgexp_i(-loss_tbi) (decoders.py:245); its importance weights scale the row gradients
+                loss_tb, iw = torch.empty(NE, device=dev), torch.empty(N, device=dev)
+                H.call('dm_reduce_i', NE, I, 1, H.fptr(loss_tbi), 1, H.fptr(loss_tb), H.fptr(iw), H.stream())
+                if train:
+                    H.call('dm_scale_rows', N, ld, H.fptr(dlogits), ld, H.fptr(iw), gw / NE, H.stream())
+            map_rec = torch.empty(T, B, C, S, S, device=dev)
+            acc = torch.empty(NE, device=dev)
+            acc_seen = seen_i = None
+            if seen is not None:
+                seen_i, acc_seen = seen.to(torch.int32).contiguous(), torch.empty(NE, device=dev)
+            H.call('dm_cat_image_pred', NE, I, C, cells, H.fptr(logits), ld, H.ptr(target), H.ptr(seen_i), H.fptr(map_rec), H.fptr(acc),
+                   H.fptr(acc_seen), H.stream())
+            if mbuf is None:
+                mbuf = torch.zeros(METRIC_BUF_FLOATS, device=dev)
+            s0 = METRIC_SLOTS['loss_map']
+            _multi_sum([(loss_tb, 1.0 / NE), (acc, 1.0 / NE)], dev, out=mbuf[s0:s0 + 2])      # acc_map has no NaN: nanmean = mean
+            metrics = dict(loss_map=mbuf[s0], acc_map=mbuf[s0 + 1])
+            if acc_seen is not None:      # nanmean (functions.py:149-150): frames without a seen cell are NaN and do not count
+                mbuf[s0 + 2].copy_(torch.nansum(acc_seen) / (~torch.isnan(acc_seen)).sum())
+                metrics['acc_map_seen'] = mbuf[s0 + 2]
+            tensors = dict(map_rec=map_rec, loss_map=loss_tb.view(T, B), acc_map=acc.view(T, B))
+        if not train:
+            return mbuf[s0].clone(), metrics, tensors
+        pk = dict(loss=mbuf[s0], x=x, ldx=F_ + 4, rows=N, acts=acts, dout=dlogits, ws=ws)
+        self._last_pack = pk
+        return _ProbeLoss.apply(dec, pk, *dec.param_list()), metrics, tensors
+
+
 def _torch_actor_distribution(actor_dist, y):
     """The distribution object Dreamer.inference hands to the acting process (a2c.py:43-55, functions.py:59-78); the
     parameters come from the HIP actor, the torch.distributions wrapper is only the return type of the reference API."""
@@ -441,8 +546,9 @@ def _multi_sum(items, device, out=None):
 METRIC_SLOTS = dict(loss_kl=0, loss_image=1, loss_reward=2, loss_terminal=3, entropy_prior=4, entropy_post=5, loss_model=6,
                     loss_critic=8, loss_actor=9, policy_entropy=10, policy_value=11, policy_value_im=12, policy_reward=13,
                     policy_reward_std=14, grad_norm=16, grad_norm_probe=18, grad_norm_actor=20, grad_norm_critic=22,
-                    loss_critic_aux=24, policy_value_aux=25, loss_vecobs=15)      # slot 7: loss_model + aux_critic_weight * loss_critic_aux
-METRIC_BUF_FLOATS = 28
+                    loss_critic_aux=24, policy_value_aux=25, loss_vecobs=15,      # slot 7: loss_model + aux_critic_weight * loss_critic_aux
+                    loss_map=28, acc_map=29, acc_map_seen=30)      # the map probe's (MapProbeHead); zero with probe_model='none'
+METRIC_BUF_FLOATS = 32
 
 
 def _finish_backward(owner, grads, flat, direct, grad_loss):
@@ -1301,6 +1407,29 @@ class _HeadLoss(torch.autograd.Function):
         return (None, None) + _finish_backward(mlp, grads, flat, direct, grad_loss)
 
 
+class _ProbeLoss(torch.autograd.Function):
+    """loss_probe of the map probe: the gradient of its MLP's parameters is produced by dm_mlp_head_bwd from the scaled
+    softmax - onehot rows, inside backward() on the caller's stream (the probe reads detached features: nothing else waits for
+    it, and it is small enough that pre-launching it on a side stream was not built), straight into the probe optimizer's
+    `.grad` slots when zero_grad() came first."""
+
+    @staticmethod
+    def forward(ctx, mlp, pack, *params):
+        ctx.mlp, ctx.pack = mlp, pack
+        return pack['loss'].clone()
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        mlp, pk = ctx.mlp, ctx.pack
+        if pk.get('consumed'):
+            raise RuntimeError('loss_probe.backward() called twice (saved activations were released)')
+        grads, flat, direct = mlp.bwd(pk['x'], pk['ldx'], pk['rows'], pk['acts'], pk['dout'], pk['ws'])
+        for k in ('acts', 'dout', 'x'):
+            pk.pop(k, None)
+        pk['consumed'] = True
+        return (None, None) + _finish_backward(mlp, grads, flat, direct, grad_loss)
+
+
 class ActorCritic(_Params):
     """a2c.py:11-152."""
 
@@ -1435,8 +1564,12 @@ class Dreamer(nn.Module):
     def __init__(self, conf):
         super().__init__()
         assert conf.action_dim > 0, 'Need to set action_dim to match environment'
-        if conf.probe_model != 'none':
-            raise NotImplementedError('probe models are research heads outside the hot path')
+        if conf.probe_model not in ('none', 'map'):
+            raise NotImplementedError(f'probe_model={conf.probe_model!r}: only the map probe is built (the goals probe and '
+                                      f'map+goals are research heads outside the hot path)')
+        if conf.probe_model != 'none' and conf.probe_gradients:
+            raise NotImplementedError('probe_gradients=True with a probe model: the gradient of the probe loss into the world '
+                                      "model's features is not built (the probe trains on detached features only)")
         features_dim = conf.deter_dim + conf.stoch_dim * (conf.stoch_discrete or 1)
         self.conf = conf
         self.iwae_samples, self.imag_horizon = conf.iwae_samples, conf.imag_horizon
@@ -1445,7 +1578,8 @@ class Dreamer(nn.Module):
                               lambda_gae=conf.lambda_gae, entropy_weight=conf.entropy, target_interval=conf.target_interval,
                               actor_grad=conf.actor_grad, actor_dist=conf.actor_dist)
         self.ac.sparse_cols = conf.stoch_dim * conf.stoch_discrete       # feature = [h | one-hot z] (rssm.py:83-84)
-        self.probe_model = NoProbeHead()
+        # dreamer.py:43-52: the map probe sees [features | map_coord]
+        self.probe_model = MapProbeHead(features_dim + 4, conf) if conf.probe_model == 'map' else NoProbeHead()
         self.probe_gradients = conf.probe_gradients
         self._groups = None
         # conf.amp (defaults.yaml:55; train.py:166 runs the step under autocast): GEMM operands in bf16, fp32 accumulation,
@@ -1475,6 +1609,8 @@ class Dreamer(nn.Module):
                          critic=FusedAdamW(groups['critic'], lr=lr_critic or lr, eps=eps))
         # the backward passes write straight into these optimizers' gradient buffers (see _flat_views)
         self.wm._fused, self.ac.actor._fused, self.ac.critic._fused = self._opt['wm'], self._opt['actor'], self._opt['critic']
+        if isinstance(self.probe_model, MapProbeHead):
+            self.probe_model.decoder._fused = self._opt['probe']
         self.prepare_streams()
         if self.probe_gradients:      # dreamer.py:67-71: three optimizers; the probe head's parameters belong to none of them
             return self._opt['wm'], self._opt['actor'], self._opt['critic']
@@ -1770,7 +1906,10 @@ class Dreamer(nn.Module):
             pk['pre'] = ov.submit(ov.s_wm, ov.ev_wm_fwd, lambda: self.wm._backward(
                 pk, ov.ws_wm, scratch=gens.get(id(self.wm), True), defer_wgrad=True))
         metrics, tensors = dict(metrics), tensors.copy()          # LazyTensors.copy(): image_rec stays a thunk
-        loss_probe, metrics_probe, tensors_probe = self.probe_model.training_step(features.detach(), obs)
+        if isinstance(self.probe_model, MapProbeHead):      # its three scalars land in the step's metric buffer
+            loss_probe, metrics_probe, tensors_probe = self.probe_model.training_step(features.detach(), obs, mbuf=mbuf)
+        else:
+            loss_probe, metrics_probe, tensors_probe = self.probe_model.training_step(features.detach(), obs)
         metrics.update(**metrics_probe)
         tensors.update(**tensors_probe)
 

@@ -273,8 +273,12 @@ class SequentialReplay:
             yield self.fill()
 
 
-def preprocess_batch(batch, action_dim, clip_rewards=None, image_key='image'):
-    """Hot-path subset of Preprocessor.apply (preprocessing.py:87-180), images left uint8 (T,B,H,W,C)."""
+def preprocess_batch(batch, action_dim, clip_rewards=None, image_key='image', map_key=None, map_categorical=None):
+    """Hot-path subset of Preprocessor.apply (preprocessing.py:87-180), images left uint8 (T,B,H,W,C).
+    map_key / map_categorical (preprocessing.py:115-131,152-158; the inputs of the map probe, models.MapProbeHead): `map` =
+    batch[map_key] as a one-hot (T,B,C,H,W) float32 with C = map_categorical, or - not categorical - a float image of that
+    layout; `map_seen_mask` from `map_seen` or `map_vis`; `map_coord` (T,B,4) from `agent_pos`, `agent_dir` and the map's
+    height.  Without map_key nothing of this is emitted.  ReplayFeed does not carry these fields."""
     T, B = batch['reward'].shape[:2]
     out = {}
     img = batch[image_key]
@@ -299,6 +303,24 @@ def preprocess_batch(batch, action_dim, clip_rewards=None, image_key='image'):
     out['reset'] = batch.get('reset', np.zeros((T, B), bool)).astype(bool)
     if 'vecobs' in batch:                                    # preprocessing.py:162-163
         out['vecobs'] = batch['vecobs'].astype(np.float32)
+    if map_key:
+        m = batch[map_key]
+        if map_categorical:                                  # img_to_onehot (preprocessing.py:15-18)
+            m = np.eye(int(map_categorical), dtype=np.float32)[m]
+        elif m.dtype == np.uint8:                            # to_image (preprocessing.py:21-29)
+            m = m.astype(np.float32) / 255.0 - 0.5
+        else:
+            assert 0.0 <= m[0, 0, 0, 0, 0] <= 1.0
+            m = m.astype(np.float32)
+        assert m.ndim == 5, f'expected a (T,B,H,W) class map or a (T,B,H,W,C) image under {map_key!r}, got {batch[map_key].shape}'
+        out['map'] = np.ascontiguousarray(m.transpose(0, 1, 4, 2, 3))      # (T,B,H,W,C) => (T,B,C,H,W)
+        if 'map_seen' in batch:                              # 0 where the cell is unseen, otherwise = map
+            out['map_seen_mask'] = (batch['map_seen'] > 0).astype(int)
+        elif 'map_vis' in batch:                             # steps since the cell was seen; never: max_steps = 500
+            out['map_seen_mask'] = (batch['map_vis'] < 500).astype(int)
+        if 'agent_pos' in batch and 'agent_dir' in batch:
+            pos = batch['agent_pos'] / float(out['map'].shape[-2]) * 2 - 1.0
+            out['map_coord'] = np.concatenate([pos, batch['agent_dir']], axis=-1).astype(np.float32)
     return out
 
 
