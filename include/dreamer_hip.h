@@ -89,7 +89,7 @@ int dm_version(void);                 /* ABI version, currently 16 (v2: LayerNor
                                               and dm_allreduce_grads removed;
                                          v16: dm_rssm_last_schedule added; later, still 16 (additions only): the per-cell categorical
                                               loss family dm_cat_target_index / dm_cat_image_loss / dm_cat_image_pred / dm_cat_concat_rows
-                                              of the map probe */
+                                              of the map probe; dm_replay_gather of the device-resident replay */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
 size_t dm_workspace_bytes(const dm_shape* shp);   /* scratch needed by any call below for this shape */
@@ -511,6 +511,24 @@ int dm_prof_end(double* out, int nkinds);
  * (1 gathered A, 2 gathered B, 4 scatter epilogue, 8 bf16 operands, 32 bf16-storage operands), flops, milliseconds};
  * returns the row count. */
 int dm_prof_rows(double* rows, int max_rows);
+/* Device-resident replay (csrc/replay_gather.hip; pydreamer_amd/replay.py DeviceReplay): assembles the (T, B, ...) batch of up to
+ * 16 fields in ONE launch out of episodes that live in device memory.  Batch column b is one or two pieces of episodes:
+ *   pieces  device int32 (B, 2, 3) = {start row, length, mark}; the two lengths of a column add up to T (a single-piece column
+ *           has length 0 in its second piece);
+ *   src     device pointers (B, 2, nfields): the base of each field in the episode of that piece (an unused second piece may
+ *           repeat the first one's);
+ *   fields  HOST array: destination base, bytes per row, and whether the field is the reset column (one byte per row).
+ * For t in piece p at offset t' :  dst_f[(t*B + b) * row_bytes ...] = src[b][p][f][(start + t') * row_bytes ...], and a piece with
+ * mark != 0 writes 1 into the reset column at its first row (an artificial reset, data.py:280-300).  The access width per field
+ * follows row_bytes: 16 B per lane if divisible by 16, else 4 B if divisible by 4, else bytes; destinations and source bases
+ * must be 16-byte aligned (destinations are checked here, the device tables by whoever uploads them).  No atomics, no
+ * workspace; the tables are read by the kernel, so they must stay valid until the launch has run. */
+#define DM_REPLAY_MAX_FIELDS 16
+typedef struct dm_replay_field {
+  void* dst; int64_t row_bytes; int32_t is_reset; int32_t reserved_;
+} dm_replay_field;
+int dm_replay_gather(int T, int B, int nfields, const dm_replay_field* fields /* host array */, const int32_t* pieces,
+                     const void* const* src, void* stream);
 /* y = a*x + b*y */
 int dm_axpby(int64_t n, float a, const float* x, float b, float* y, void* stream);
 

@@ -106,6 +106,12 @@ class dm_reduce_item(Structure):
     _fields_ = [('x', c_void_p), ('n', c_int64), ('scale', c_float), ('mode', c_int32), ('center', c_void_p)]
 
 
+class dm_replay_field(Structure):
+    _fields_ = [('dst', c_void_p), ('row_bytes', c_int64), ('is_reset', c_int32), ('reserved_', c_int32)]
+
+
+DM_REPLAY_MAX_FIELDS = 16
+
 _P = c_void_p
 _SIGNATURES = {
     'dm_version': (c_int, []),
@@ -205,6 +211,7 @@ _SIGNATURES = {
     'dm_dream_rollout_marks': (c_int, [c_int, POINTER(c_int), POINTER(c_void_p)]),
     'dm_mlp_head_fwd_rows': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, POINTER(dm_mlp_params), _P, _P, _P,
                                      c_size_t, _P]),
+    'dm_replay_gather': (c_int, [c_int, c_int, c_int, POINTER(dm_replay_field), _P, _P, _P]),
 }
 
 _lib = None

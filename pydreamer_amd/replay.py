@@ -18,7 +18,9 @@ Here the same batches are produced as what the HIP path consumes directly:
     `clip_rewards`, float32 terminal, bool reset - and the image is LEFT AS uint8 (T,B,H,W,C): x/255-0.5 and HWC->CHW
     happen inside the first conv's patch loader on the GPU (N1), so a batch crosses PCIe at 1 byte per pixel value;
   * `DeviceRing`              - a background thread fills pinned host buffers; the consumer enqueues the H2D copies on its
-    own stream at a point where that stream is idle (`prefetch()` after `training_step()`), into a ring of device batches.
+    own stream at a point where that stream is idle (`prefetch()` after `training_step()`), into a ring of device batches;
+  * `DeviceReplay`            - the same batches from episodes kept RESIDENT on the device: the planner's windows become two
+    small tables and one gather launch (csrc/replay_gather.hip), so a file's frames cross PCIe once, not once per visit.
 
 parity: pinned against the reference's own DataSequential + Preprocessor run in the build container
 (oracle/gen_replay_golden.py -> tests/golden/replay_reader.npz; tests/test_replay_cpu.py replays it: same episode files,
@@ -28,6 +30,7 @@ so the import statements were satisfied with empty placeholder modules (nothing 
 was a local subclass of the reference's abstract EpisodeRepository instead of MlflowEpisodeRepository.  `DeviceRing` has no
 reference counterpart (the reference uses a DataLoader + `.to(device)`) and is covered by its own tests.
 """
+import ctypes
 import os
 import queue
 import threading
@@ -140,8 +143,11 @@ class SequentialReplay:
     another copy.  `__iter__` (tests, small tools) allocates fresh arrays per batch and fills those."""
 
     def __init__(self, repository, batch_length, batch_size, skip_first=True, reload_interval=0, buffer_size=0, reset_interval=0,
-                 allow_mid_reset=False, seed=0, check_nonempty=True):
+                 allow_mid_reset=False, seed=0, check_nonempty=True, load_episode=None):
         self.repository = repository
+        # how a chosen file becomes an episode object (`fields`, `rows`, `marks`): by default read and prepared afresh on every
+        # visit; DeviceReplay installs its cache here.  Called once per visit, after the draw that chose the file.
+        self.load_episode = load_episode or (lambda info: _Episode(info.load_data()))
         self.batch_length, self.batch_size = int(batch_length), int(batch_size)
         self.buffer_size = buffer_size                       # keep the newest files whose step counts fit (0: all)
         self.reload_interval = reload_interval               # seconds between re-listings of the repository (online training)
@@ -196,7 +202,7 @@ class SequentialReplay:
         info = self.files[self.rs.randint(len(self.files))]
         random_start, col.random_start = col.random_start, False
         try:
-            ep = _Episode(info.load_data())
+            ep = self.load_episode(info)
         except Exception as e:
             print('replay: skipping unreadable episode file', info.path, e)
             return
@@ -249,10 +255,15 @@ class SequentialReplay:
             t += n
 
     # ---- batches
+    def plan_batch(self):
+        """The planning half of fill(): per batch column the pieces [(episode, start, stop), ...] of its next window.  Advances
+        the cursors and draws from the random stream exactly as fill() does; copies nothing."""
+        return [self._plan(col) for col in self.columns]
+
     def fill(self, out=None):
         """Write the next batch into `out` ({key: (T, B, ...) array}; only the keys present are written - all of the files' keys
         when out is None or empty, in freshly allocated arrays).  Returns out."""
-        plans = [self._plan(col) for col in self.columns]
+        plans = self.plan_batch()
         if not out:
             first = plans[0][0][0].fields
             out = {} if out is None else out
@@ -278,7 +289,8 @@ def preprocess_batch(batch, action_dim, clip_rewards=None, image_key='image', ma
     map_key / map_categorical (preprocessing.py:115-131,152-158; the inputs of the map probe, models.MapProbeHead): `map` =
     batch[map_key] as a one-hot (T,B,C,H,W) float32 with C = map_categorical, or - not categorical - a float image of that
     layout; `map_seen_mask` from `map_seen` or `map_vis`; `map_coord` (T,B,4) from `agent_pos`, `agent_dir` and the map's
-    height.  Without map_key nothing of this is emitted.  ReplayFeed does not carry these fields."""
+    height.  Without map_key nothing of this is emitted.  ReplayFeed / DeviceReplay carry the class map as stored (integer
+    (T,B,H,W), which MapProbeHead takes as it is) with the same mask and coord."""
     T, B = batch['reward'].shape[:2]
     out = {}
     img = batch[image_key]
@@ -324,33 +336,82 @@ def preprocess_batch(batch, action_dim, clip_rewards=None, image_key='image', ma
     return out
 
 
+def _map_seen_mask(fields):
+    """preprocess_batch's map_seen_mask of raw fields (any leading dimensions), or None when the files carry neither source."""
+    if 'map_seen' in fields:
+        return (fields['map_seen'] > 0).astype(int)
+    if 'map_vis' in fields:
+        return (fields['map_vis'] < 500).astype(int)
+    return None
+
+
+def _map_coord(fields, height):
+    """preprocess_batch's map_coord of raw fields (any leading dimensions)."""
+    pos = fields['agent_pos'] / float(height) * 2 - 1.0
+    return np.concatenate([pos, fields['agent_dir']], axis=-1).astype(np.float32)
+
+
+def _map_spec(probe, lead, map_key, map_categorical):
+    """{field: (shape, dtype)} of the map probe's inputs as the feeds carry them; `probe`: the raw fields of one episode."""
+    if not map_categorical:
+        raise ValueError('the feeds carry categorical maps only (map_categorical = number of classes); a float map goes through '
+                         'preprocess_batch')
+    m = probe[map_key]
+    if m.ndim != 3 or not np.issubdtype(m.dtype, np.integer):
+        raise ValueError(f'expected an integer (T,H,W) class map under {map_key!r}, got {m.dtype} {m.shape}')
+    spec = {'map': (lead + m.shape[1:], m.dtype.type)}
+    seen = _map_seen_mask({k: probe[k][:1] for k in ('map_seen', 'map_vis') if k in probe})
+    if seen is not None:
+        spec['map_seen_mask'] = (lead + seen.shape[1:], seen.dtype.type)
+    if 'agent_pos' in probe and 'agent_dir' in probe:
+        spec['map_coord'] = (lead + (probe['agent_pos'].shape[-1] + probe['agent_dir'].shape[-1],), np.float32)
+    return spec
+
+
+def _feed_layout(replay, action_dim, image_key, map_key, map_categorical, who):
+    """(raw fields of the repository's first file, {field: ((T, B, ...) shape, dtype)} of a batch as the feeds hand it over)."""
+    if not replay.files:
+        raise ValueError(f'{who} needs at least one episode file to lay out its slots (the repository is empty)')
+    probe = _Episode(replay.files[0].load_data()).fields      # shapes only; draws nothing from the random stream
+    T, B = replay.batch_length, replay.batch_size
+    img = probe[image_key]
+    if img.dtype != np.uint8 or img.ndim != 4:
+        raise ValueError(f'expected uint8 (T,H,W,C) frames in the episode files, got {img.dtype} {img.shape}')
+    spec = {'image': ((T, B) + img.shape[1:], np.uint8), 'action': ((T, B, action_dim), np.float32),
+            'action_next': ((T, B, action_dim), np.float32), 'terminal': ((T, B), np.float32),
+            'reward': ((T, B), np.float32), 'reset': ((T, B), np.bool_)}
+    if 'vecobs' in probe:
+        spec['vecobs'] = ((T, B) + probe['vecobs'].shape[1:], np.float32)
+    if map_key:
+        spec.update(_map_spec(probe, (T, B), map_key, map_categorical))
+    return probe, spec
+
+
 class ReplayFeed:
     """Planner + hot-path preprocessing writing IN PLACE into a slot of host arrays (DeviceRing hands it the numpy views of a
     pinned slot): the uint8 frame windows and the reset flags go from the episode arrays straight into the slot - one copy
     between the file and PCIe - and the small per-step fields (actions, reward, terminal) through a reused scratch batch.
-    Field for field what `preprocess_batch(next(iter(replay)), ...)` returns (tests/test_replay_cpu.py compares the two)."""
+    Field for field what `preprocess_batch(next(iter(replay)), ...)` returns (tests/test_replay_cpu.py compares the two).
+    With map_key / map_categorical the slot also carries the map probe's inputs: `map` as the stored integer class map
+    (T,B,H,W) - not preprocess_batch's one-hot; MapProbeHead takes either - and preprocess_batch's `map_seen_mask` and
+    `map_coord` when the files hold their sources."""
 
-    def __init__(self, replay, action_dim, clip_rewards=None, image_key='image'):
+    def __init__(self, replay, action_dim, clip_rewards=None, image_key='image', map_key=None, map_categorical=None):
         if clip_rewards not in (None, '', False, 'tanh', 'log1p'):
             raise ValueError(clip_rewards)
         self.replay, self.action_dim, self.clip_rewards, self.image_key = replay, int(action_dim), clip_rewards, image_key
-        if not replay.files:
-            raise ValueError('ReplayFeed needs at least one episode file to lay out its slots (the repository is empty)')
-        probe = _Episode(replay.files[0].load_data()).fields      # shapes only; draws nothing from the random stream
+        self.map_key = map_key
+        probe, self._spec = _feed_layout(replay, self.action_dim, image_key, map_key, map_categorical, 'ReplayFeed')
         T, B = replay.batch_length, replay.batch_size
         # `terminal` always has a column: an episode without the field contributes zeros (SequentialReplay._copy), so a
         # repository that mixes files with and without it still yields the flags of those that carry them
         self._small = {k: np.empty((T, B) + probe[k].shape[1:], probe[k].dtype)
                        for k in ('action', 'action_next', 'reward', 'vecobs') if k in probe}
         self._small['terminal'] = np.empty((T, B), probe['terminal'].dtype if 'terminal' in probe else np.float32)
-        img = probe[image_key]
-        if img.dtype != np.uint8 or img.ndim != 4:
-            raise ValueError(f'expected uint8 (T,H,W,C) frames in the episode files, got {img.dtype} {img.shape}')
-        self._spec = {'image': ((T, B) + img.shape[1:], np.uint8), 'action': ((T, B, self.action_dim), np.float32),
-                      'action_next': ((T, B, self.action_dim), np.float32), 'terminal': ((T, B), np.float32),
-                      'reward': ((T, B), np.float32), 'reset': ((T, B), np.bool_)}
-        if 'vecobs' in probe:
-            self._spec['vecobs'] = ((T, B) + probe['vecobs'].shape[1:], np.float32)
+        if map_key:
+            for k in ('map_seen', 'map_vis', 'agent_pos', 'agent_dir'):      # sources of the mask and the coord: scratch
+                if k in probe and k != map_key:
+                    self._small[k] = np.empty((T, B) + probe[k].shape[1:], probe[k].dtype)
 
     def spec(self):
         """{field: (shape, dtype)} of a slot."""
@@ -367,6 +428,8 @@ class ReplayFeed:
         raw = dict(self._small)
         raw[self.image_key] = slot['image']
         raw['reset'] = slot['reset']
+        if self.map_key:
+            raw[self.map_key] = slot['map']
         self.replay.fill(raw)
         self._actions(raw['action'], slot['action'])
         self._actions(raw['action_next'], slot['action_next'])
@@ -379,6 +442,10 @@ class ReplayFeed:
         slot['reward'][...] = r
         if 'vecobs' in raw:
             slot['vecobs'][...] = raw['vecobs']
+        if 'map_seen_mask' in slot:
+            slot['map_seen_mask'][...] = _map_seen_mask(raw)
+        if 'map_coord' in slot:
+            slot['map_coord'][...] = _map_coord(raw, slot['map'].shape[-2])
         return slot
 
 
@@ -489,6 +556,303 @@ class DeviceRing:
             self.copied[i] = ev
         self.free.put(i)                        # the producer waits for `ev` before touching the pinned buffers again
         self.staged = d
+
+    def next(self):
+        self.prefetch()
+        if self.staged is None:
+            if self.error is not None:
+                raise RuntimeError('replay producer failed') from self.error
+            raise StopIteration
+        d, self.staged = self.staged, None
+        return d
+
+    def close(self):
+        self.free.put(None)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Device-resident replay: the episodes live in HBM, a batch is one gather launch (csrc/replay_gather.hip)
+
+_RESIDENT_ALIGN = 256        # every field of an episode starts on a multiple of this inside the episode's flat buffer
+
+
+class _Resident:
+    """A cached episode file: prepared ONCE on the host with the element-wise rules of ReplayFeed.fill / preprocess_batch into
+    one flat byte buffer (field k: `rows` rows of row_bytes[k] at offsets[k]), uploaded once.  After the upload the host keeps
+    only what later plans need: `reset` (the reset scatter reads it) and the row count."""
+    __slots__ = ('path', 'rows', 'reset', 'nbytes', 'offsets', 'host', 'dev')
+
+    def __init__(self, path, rows, reset, nbytes, offsets, host):
+        self.path, self.rows, self.reset, self.nbytes, self.offsets, self.host, self.dev = path, rows, reset, nbytes, offsets, host, None
+
+
+class _ResidentEpisode:
+    """One VISIT of a cached episode - what the planner holds where SequentialReplay holds an _Episode: its own `marks` (the
+    reset scatter is drawn per visit) over the shared entry."""
+    __slots__ = ('entry', 'fields', 'rows', 'marks')
+
+    def __init__(self, entry):
+        self.entry, self.fields, self.rows, self.marks = entry, {'reset': entry.reset}, entry.rows, None
+
+
+class ReplayPlan:
+    """One planned batch, host side.  pieces (B, 2, 3) int32: per column at most two pieces (start row, length, mark), lengths
+    adding up to T, mark = the piece's first row gets an artificial reset; offsets (B, 2, F) int64: byte offset of each field
+    inside the flat buffer of the piece's episode (an unused second piece repeats the first); episodes[b][p]: that episode's
+    cache entry (None for an unused second piece)."""
+    __slots__ = ('pieces', 'offsets', 'episodes')
+
+    def __init__(self, pieces, offsets, episodes):
+        self.pieces, self.offsets, self.episodes = pieces, offsets, episodes
+
+    def entries(self):
+        seen = {}
+        for row in self.episodes:
+            for e in row:
+                if e is not None:
+                    seen[id(e)] = e
+        return list(seen.values())
+
+
+class DeviceReplay:
+    """The second feed: episodes RESIDENT on the device, every (T, B, ...) batch assembled by ONE gather launch
+    (dm_replay_gather) - a step's frames cross PCIe once per episode file instead of once per visit.  Hands training_step()
+    bit for bit what DeviceRing(ReplayFeed(replay, ...)) hands it for the same files, arguments and seed: the windows come from
+    the same planner (`replay`, a SequentialReplay nothing has been drawn from yet - its draws are untouched: file choice,
+    random start, reset scatter, tails, buffer_size / reload_interval), only what a chosen file turns into is replaced
+    (SequentialReplay.load_episode): a visit is a fresh _ResidentEpisode over a cache entry instead of a freshly read _Episode.
+
+    Episode cache, keyed by file path.  On first use a file is read and prepared once on the host with exactly the element-wise
+    rules of ReplayFeed.fill: float32 one-hot action / action_next, float32 reward with reward[0] = 0 and clip_rewards applied
+    by numpy (tanh / log1p are the host's bits), float32 terminal (zeros when the file lacks it), bool reset with reset[0] =
+    True, float32 vecobs, uint8 frames (n, H, W, C) (`image_t` files transposed), and with map_key / map_categorical the stored
+    integer class map plus preprocess_batch's map_seen_mask and map_coord.  A file whose rows do not have the layout of the
+    first file is passed over like an unreadable one.  Eviction is least-recently-VISITED first once the cached bytes pass
+    `capacity_bytes` (0: no limit), and only drops the cache's reference: an episode a column cursor, a carried tail or a
+    planned batch still holds stays alive until they let go, so device residency can exceed the budget by up to those - at
+    most 2 B episodes per batch in flight plus the B cursors'.  A file evicted and chosen again is read and uploaded again.
+
+    Threads and streams, as in DeviceRing: one background thread does host work only (np.load, preparation into pinned
+    memory, planning `depth` batches ahead); ALL device work is enqueued by the consumer on the caller's current stream, from
+    prefetch() (call it right after training_step() returned) or next(): the uploads of episodes the batch is the first to
+    use (non_blocking, from pinned memory), the copy of the two small tables, and the gather into one of `depth` >= 3 device
+    batch slots.  No stream of its own (DeviceRing's docstring records what a fifth stream cost).  A pinned source - an
+    episode's staging buffer, a table - is released or rewritten only after an event recorded behind its copy has fired.
+    Errors of the producer surface from next().
+
+    Without `device` nothing touches the GPU: plan() alone is usable, the prepared episodes stay in ordinary host memory."""
+
+    def __init__(self, replay, action_dim, device=None, depth=3, capacity_bytes=0, clip_rewards=None, image_key='image',
+                 map_key=None, map_categorical=None):
+        if clip_rewards not in (None, '', False, 'tanh', 'log1p'):
+            raise ValueError(clip_rewards)
+        if any(c.episode is not None or c.tail is not None for c in replay.columns):
+            raise ValueError('DeviceReplay needs a SequentialReplay nothing has been drawn from yet')
+        self.replay, self.action_dim, self.clip_rewards, self.image_key = replay, int(action_dim), clip_rewards, image_key
+        self.map_key, self.map_categorical = map_key, map_categorical
+        self.device = None if device is None else torch.device(device)
+        self.depth, self.capacity_bytes = max(3, int(depth)), int(capacity_bytes or 0)
+        _, self._spec = _feed_layout(replay, self.action_dim, image_key, map_key, map_categorical, 'DeviceReplay')
+        self.names = list(self._spec)
+        self._rows = {k: (tuple(shape[2:]), np.dtype(dt)) for k, (shape, dt) in self._spec.items()}
+        self.row_bytes = {k: int(np.prod(shape, dtype=np.int64)) * dt.itemsize for k, (shape, dt) in self._rows.items()}
+        self._cache, self.cached_bytes = {}, 0                 # path -> _Resident, least recently visited first
+        replay.load_episode = self._visit
+        # consumer / producer state (device given)
+        self.free, self.planned = queue.Queue(), queue.Queue()
+        self.thread = None
+        self.dev = None                         # per device slot: {key: device tensor}
+        self._fields = None                     # per device slot: the host descriptor array of dm_replay_gather
+        self._tab_host = self._tab_dev = None   # per device slot: pinned / device tables (source pointers, then the pieces)
+        self._tab_copied = [None] * self.depth  # per device slot: event behind its last table copy
+        self._held = [None] * self.depth        # per device slot: the plan it was gathered from (keeps its episodes alive)
+        self._uploading = []                    # (event, entries): pinned episode buffers still the source of a copy
+        self.next_dev, self.staged, self.error, self.done = 0, None, None, False
+
+    def spec(self):
+        """{field: (shape, dtype)} of a batch: ReplayFeed.spec() of the same arguments."""
+        return dict(self._spec)
+
+    # ---- the cache (producer side; host only)
+    def _onehot(self, src):
+        if src.ndim == 1:                                     # integer actions -> one-hot rows (ReplayFeed._actions)
+            out = np.zeros((src.shape[0], self.action_dim), np.float32)
+            np.put_along_axis(out, src[:, None].astype(np.int64), 1.0, axis=1)
+            return out
+        return src.astype(np.float32)
+
+    def _prepare(self, info):
+        f = _Episode(info.load_data()).fields
+        n = f['reward'].shape[0]
+        r = f['reward'].astype(np.float32)
+        if self.clip_rewards == 'tanh':
+            r = np.tanh(r)
+        elif self.clip_rewards == 'log1p':
+            r = np.log1p(r)
+        vals = {'image': f[self.image_key], 'action': self._onehot(f['action']), 'action_next': self._onehot(f['action_next']),
+                'terminal': f['terminal'].astype(np.float32) if 'terminal' in f else np.zeros(n, np.float32),
+                'reward': r, 'reset': f['reset'].astype(bool)}
+        if 'vecobs' in self._rows:
+            vals['vecobs'] = f['vecobs'].astype(np.float32)
+        if self.map_key:
+            vals['map'] = f[self.map_key]
+            if 'map_seen_mask' in self._rows:
+                vals['map_seen_mask'] = _map_seen_mask(f)
+            if 'map_coord' in self._rows:
+                vals['map_coord'] = _map_coord(f, f[self.map_key].shape[-2])
+        offsets, nbytes = {}, 0
+        for k in self.names:                                  # the gather trusts row_bytes: every file must have the first one's layout
+            shape, dt = self._rows[k]
+            if vals[k] is None or vals[k].shape != (n,) + shape or vals[k].dtype != dt:
+                got = None if vals[k] is None else (vals[k].dtype, vals[k].shape)
+                raise ValueError(f'field {k!r} is {got}, the batches are laid out for {dt} {(n,) + shape}')
+            offsets[k] = nbytes
+            nbytes += -(-n * self.row_bytes[k] // _RESIDENT_ALIGN) * _RESIDENT_ALIGN
+        if self.device is not None:
+            with torch.cuda.device(self.device):              # (a new thread's current device is 0)
+                host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+            flat = host.numpy()
+        else:
+            host = flat = np.empty(nbytes, np.uint8)
+        entry = _Resident(info.path, n, vals['reset'].copy(), nbytes, offsets, host)
+        for k in self.names:                                  # the frames: one copy from the file's array (also for image_t)
+            flat[offsets[k]:offsets[k] + n * self.row_bytes[k]].view(self._rows[k][1]).reshape((n,) + self._rows[k][0])[...] = vals[k]
+        return entry
+
+    def _visit(self, info):
+        """SequentialReplay.load_episode: the cached entry of the file (read and prepared now if it is not cached) as a fresh visit."""
+        entry = self._cache.pop(info.path, None)
+        if entry is None:
+            entry = self._prepare(info)
+            self.cached_bytes += entry.nbytes
+        self._cache[info.path] = entry                         # most recently visited last
+        while self.capacity_bytes and self.cached_bytes > self.capacity_bytes and len(self._cache) > 1:
+            old = self._cache.pop(next(iter(self._cache)))     # only the cache's reference: cursors, tails and plans keep theirs
+            self.cached_bytes -= old.nbytes
+        return _ResidentEpisode(entry)
+
+    def plan(self):
+        """Plan the next batch on the host: the planner's windows as the tables the gather reads (ReplayPlan).  Needs no GPU."""
+        T, B, F = self.replay.batch_length, self.replay.batch_size, len(self.names)
+        pieces, offsets, episodes = np.zeros((B, 2, 3), np.int32), np.zeros((B, 2, F), np.int64), []
+        for b, ps in enumerate(self.replay.plan_batch()):
+            assert 1 <= len(ps) <= 2
+            row = [None, None]
+            for p, (ep, a, z) in enumerate(ps):
+                mark = ep.marks is not None and bool(ep.marks[a:z].any())      # SequentialReplay._copy
+                if mark and ep.fields['reset'][a:z].any():
+                    raise ValueError('an artificial reset fell into a window that holds a real one')
+                assert 0 <= a < z <= ep.entry.rows, (a, z, ep.entry.rows)
+                pieces[b, p] = (a, z - a, mark)
+                offsets[b, p] = [ep.entry.offsets[k] for k in self.names]
+                row[p] = ep.entry
+            if len(ps) == 1:
+                offsets[b, 1] = offsets[b, 0]
+            assert int(pieces[b, :, 1].sum()) == T
+            episodes.append(row)
+        return ReplayPlan(pieces, offsets, episodes)
+
+    # ---- producer thread: host work only
+    def _produce(self):
+        try:
+            while self.free.get() is not None:
+                self.planned.put(self.plan())
+        except Exception as e:                  # surfaced by next()
+            self.error = e
+            self.planned.put(None)
+
+    # ---- consumer: all device work, on the caller's current stream
+    def _start(self):
+        if self.device is None:
+            raise ValueError('DeviceReplay was built without a device: only plan() is available')
+        for _ in range(self.depth):
+            self.free.put(True)
+        self.thread = threading.Thread(target=self._produce, daemon=True, name='dm-device-replay')
+        self.thread.start()
+
+    def _alloc(self):
+        from . import hip as H
+        B, F = self.replay.batch_size, len(self.names)
+        tdt = lambda dt: torch.from_numpy(np.empty(0, dt)).dtype
+        self.dev = [{k: torch.empty(shape, dtype=tdt(dt), device=self.device) for k, (shape, dt) in self._spec.items()}
+                    for _ in range(self.depth)]
+        self._fields = []
+        for d in self.dev:
+            arr = (H.dm_replay_field * F)()
+            for i, k in enumerate(self.names):
+                assert d[k].data_ptr() % 16 == 0
+                arr[i].dst, arr[i].row_bytes, arr[i].is_reset = d[k].data_ptr(), self.row_bytes[k], int(k == 'reset')
+            self._fields.append(arr)
+        words = B * 2 * F + B * 3                # int64 source pointers, then the int32 pieces
+        self._tab_host = [torch.empty(words, dtype=torch.int64, pin_memory=True) for _ in range(self.depth)]
+        self._tab_dev = [torch.empty(words, dtype=torch.int64, device=self.device) for _ in range(self.depth)]
+
+    def _stage(self, plan):
+        B, F = self.replay.batch_size, len(self.names)
+        stream = torch.cuda.current_stream(self.device)
+        if self.dev is None:
+            self._alloc()
+        # pinned episode buffers whose copy has completed are let go
+        still = []
+        for ev, entries in self._uploading:
+            if ev.query():
+                for e in entries:
+                    e.host = None
+            else:
+                still.append((ev, entries))
+        self._uploading = still
+        fresh = [e for e in plan.entries() if e.dev is None]
+        for e in fresh:
+            e.dev = torch.empty(e.nbytes, dtype=torch.uint8, device=self.device)
+            assert e.dev.data_ptr() % 16 == 0 and all(o % 16 == 0 for o in e.offsets.values())
+            e.dev.copy_(e.host, non_blocking=True)
+        if fresh:
+            ev = torch.cuda.Event()
+            ev.record(stream)
+            self._uploading.append((ev, fresh))
+        i = self.next_dev
+        self.next_dev = (i + 1) % self.depth
+        if self._tab_copied[i] is not None:                   # the pinned table is the source of a copy until this fires
+            self._tab_copied[i].synchronize()
+        tab = self._tab_host[i].numpy()
+        base = np.array([[e.dev.data_ptr() for e in (row[0], row[1] or row[0])] for row in plan.episodes], np.int64)
+        tab[:B * 2 * F] = (base[:, :, None] + plan.offsets).ravel()
+        tab[B * 2 * F:].view(np.int32)[:] = plan.pieces.ravel()
+        self._tab_dev[i].copy_(self._tab_host[i], non_blocking=True)
+        ev = self._tab_copied[i] or torch.cuda.Event()
+        ev.record(stream)
+        self._tab_copied[i] = ev
+        self._held[i] = plan
+        self._launch(i, stream)
+        return self.dev[i]
+
+    def _launch(self, i, stream):
+        """The gather of device slot i from the tables last copied for it (scripts/replay_feed_bench.py times this alone)."""
+        from . import hip as H
+        T, B, F = self.replay.batch_length, self.replay.batch_size, len(self.names)
+        src = self._tab_dev[i].data_ptr()
+        H.call('dm_replay_gather', T, B, F, self._fields[i], ctypes.c_void_p(src + 8 * B * 2 * F), ctypes.c_void_p(src),
+               ctypes.c_void_p(stream.cuda_stream))
+
+    def __iter__(self):
+        return self
+
+    __next__ = lambda self: self.next()
+
+    def prefetch(self):
+        """Stage the next batch: enqueue the uploads it needs, its tables and its gather on the current stream (no-op if one is
+        staged already)."""
+        if self.staged is not None or self.done:
+            return
+        if self.thread is None:
+            self._start()
+        plan = self.planned.get()
+        if plan is None:
+            self.done = True
+            return
+        with torch.cuda.device(self.device):
+            self.staged = self._stage(plan)
+        self.free.put(True)
 
     def next(self):
         self.prefetch()
