@@ -89,7 +89,8 @@ int dm_version(void);                 /* ABI version, currently 16 (v2: LayerNor
                                               and dm_allreduce_grads removed;
                                          v16: dm_rssm_last_schedule added; later, still 16 (additions only): the per-cell categorical
                                               loss family dm_cat_target_index / dm_cat_image_loss / dm_cat_image_pred / dm_cat_concat_rows
-                                              of the map probe; dm_replay_gather of the device-resident replay */
+                                              of the map probe; dm_replay_gather of the device-resident replay; dm_goals_stats /
+                                              dm_goals_stats_ws_floats of the goals probe */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
 size_t dm_workspace_bytes(const dm_shape* shp);   /* scratch needed by any call below for this shape */
@@ -323,6 +324,22 @@ int dm_cat_image_pred(int groups, int I, int C, int cells, const float* logits, 
 /* out (rows, F + E) = [ x[r][0..F) (leading dimension ldx) | extra[r / I][0..E) ]: torch.cat((features, insert_dim(map_coord, 2, I)), -1)
  * of probes.py:54-55. */
 int dm_cat_concat_rows(int rows, int I, int F, int E, const float* x, int ldx, const float* extra, float* out, void* stream);
+
+/* The goals probe's metrics (csrc/goals.hip; probes.py:113-135) over `rows` frames and G goals, one call, no host read:
+ * goals, pred (rows, 2G) fp32 - coordinates (2g, 2g+1) belong to goal g, pred is the decoded mean already averaged over I;
+ * visage (rows, G) fp32 or NULL.  out (8 floats, e.g. a slice of the step's metric buffer):
+ *   out[0] mse_goals = mean over rows and goals of dx^2 + dy^2;
+ *   out[1] var_goals = (1/G) * sum over the 2G coordinates of their unbiased (N - 1) variance over the rows, two-pass
+ *          (mean, then sum (x - mean)^2); rows == 1 gives NaN as torch's var() does;
+ *   out[2..7] mse_goal_age{0,5,10,50,200,1000}, written only when visage is given: the mean of dx^2 + dy^2 over the
+ *          (row, goal) entries with vmin <= visage <= vmax, float compares against [0,0] [1,5] [6,10] [11,50] [51,200]
+ *          [201,1000]; an empty bucket is 0 / 0 = NaN (the reference's nanmean(x * mask / mask)).
+ * ws: dm_goals_stats_ws_floats(rows, G) floats of scratch.  No float atomics: the same inputs give the same bits.
+ * Checked on the host before any launch: NULL goals / pred / out (or ws with rows > 0) -> DM_E_NULL, rows < 0 or G < 1 ->
+ * DM_E_SHAPE, rows == 0 -> DM_OK with nothing launched. */
+size_t dm_goals_stats_ws_floats(int rows, int G);
+int dm_goals_stats(int rows, int G, const float* goals, const float* pred, const float* visage, float* out, void* ws,
+                   size_t ws_bytes, void* stream);
 
 /* uint8 ingest (preprocessing.py:21-29 to_image): src (n, h*w, c) uint8 HWC -> dst (n, c, h*w) float32,
  * x/255 - 0.5.  Lets the trainer hand the replay's native uint8 frames to training_step(). */

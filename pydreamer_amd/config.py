@@ -32,8 +32,9 @@ SECTIONS = {
     ),
     'atari': dict(action_dim=18, clip_rewards='tanh', deter_dim=1024, kl_weight=0.1, gamma=0.99, entropy=0.001),
     'dmc': dict(action_dim=12, entropy=1.0e-4, actor_grad='dynamics', actor_dist='tanh_normal', clip_rewards='tanh'),
-    # defaults.yaml:143-161, the keys the hot path reads.  probe_model is 'none' here, NOT the reference's 'goals': the goals
-    # probe is not built, and Dreamer() raises NotImplementedError for it; probe_model='map' (the map keys below) is
+    # defaults.yaml:143-161, the keys the hot path reads.  probe_model stays 'none' here, NOT the reference's 'goals': the goals
+    # probe needs goals_size >= 1, which the environment sets.  probe_model='goals' / 'map+goals' (with goals_size) and 'map' (the
+    # map keys below) are all available
     'miniworld': dict(action_dim=3, image_key='image', image_size=64, image_channels=3, image_categorical=False,
                       reward_input=True, probe_model='none', cnn_depth=32, map_key='map', map_size=9, map_channels=14),
     'minecraft': dict(action_dim=29, vecobs_size=27, clip_rewards='log1p'),      # defaults.yaml:244-248

@@ -47,7 +47,8 @@ def attach(optimizers, local_batch, global_batch, group=None, model=None, force=
         model.wm.grad_weight = w
         model.ac.grad_weight = w
         folded = {id(model._opt[k]) for k in ('wm', 'actor', 'critic')}
-        if hasattr(model.probe_model, 'decoder'):      # the map probe scales its own gradient rows (models.MapProbeHead)
+        if not hasattr(model.probe_model, 'dummy'):      # every probe but NoProbeHead scales its own gradient rows
+            # (models.MapProbeHead, GoalsProbe; MapGoalsProbe hands the weight to both of its heads)
             model.probe_model.grad_weight = w
             folded.add(id(model._opt['probe']))
     for opt in optimizers:

@@ -155,6 +155,8 @@ _SIGNATURES = {
     'dm_cat_image_loss': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P]),
     'dm_cat_image_pred': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P, _P]),
     'dm_cat_concat_rows': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P]),
+    'dm_goals_stats_ws_floats': (c_size_t, [c_int, c_int]),
+    'dm_goals_stats': (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     'dm_preprocess_image_u8': (c_int, [c_int64, c_int, c_int, _P, _P, _P]),
     'dm_conv_encoder_acts_floats': (c_size_t, [POINTER(dm_shape)]),
     'dm_conv_encoder_fwd': (c_int, [POINTER(dm_shape), _P, POINTER(dm_conv_params), _P, _P, _P, c_size_t, _P]),

@@ -10,8 +10,9 @@ reference (train.py:184-187).  There is no CPU path: tensors must live on a gfx9
 Supported configuration (everything else raises NotImplementedError): iwae_samples>=1 (also with the logging flags), gru_type in {gru, gru_layernorm,
 gru_layernorm_dv2}, gru_layers 1..4, stoch_discrete>0 or 0 (Gaussian latents, also with iwae_samples>1), layer_norm True or False,
 aux_critic, image_encoder/decoder='cnn' at 64x64, actor_dist in {onehot, tanh_normal, normal_tanh}, actor_grad='reinforce',
-probe_model in {none, map} (map: the CatImageDecoder probe of the top-down map on the detached features; not with
-probe_gradients=True, whose gradient into the world model's features is not built; the goals probe is not built), reward_input (cnn_depth in {8, 16, 32, 48, 64}: the reward and terminal planes are folded into the first
+probe_model in {none, map, goals, map+goals} (map: the CatImageDecoder probe of the top-down map on the detached features, DESIGN
+4.8; goals: two DenseNormalDecoders of the goal directions with the metrics of csrc/goals.hip, DESIGN 4.9, needs goals_size >= 1;
+not with probe_gradients=True, whose gradient into the world model's features is not built), reward_input (cnn_depth in {8, 16, 32, 48, 64}: the reward and terminal planes are folded into the first
 convolution), vecobs_size > 0 beside the image (an MLP encoder whose output sits behind the image embedding, a
 DenseNormalDecoder with out_dim = vecobs_size).
 """
@@ -398,9 +399,10 @@ class MapProbeHead(_Params):
             self._ws = torch.empty(need, dtype=torch.uint8, device=device)
         return self._ws
 
-    def training_step(self, features, obs, mbuf=None):
+    def training_step(self, features, obs, mbuf=None, _defer=False):
         """features (T,B,I,F), detached.  Returns (loss_probe, metrics, tensors) with the reference's names: metrics loss_map,
-        acc_map, acc_map_seen (only with obs['map_seen_mask']); tensors map_rec (T,B,C,H,W), loss_map (T,B), acc_map (T,B)."""
+        acc_map, acc_map_seen (only with obs['map_seen_mask']); tensors map_rec (T,B,C,H,W), loss_map (T,B), acc_map (T,B).
+        _defer (MapGoalsProbe): in grad mode the first result is the head's backward pack instead of an autograd loss."""
         _require_cuda(features, 'features')
         T, B, I, F_ = features.shape
         C, S = self.map_channels, self.map_size
@@ -466,9 +468,151 @@ class MapProbeHead(_Params):
             tensors = dict(map_rec=map_rec, loss_map=loss_tb.view(T, B), acc_map=acc.view(T, B))
         if not train:
             return mbuf[s0].clone(), metrics, tensors
-        pk = dict(loss=mbuf[s0], x=x, ldx=F_ + 4, rows=N, acts=acts, dout=dlogits, ws=ws)
+        pk = dict(mlp=dec, loss=mbuf[s0], x=x, ldx=F_ + 4, rows=N, acts=acts, dout=dlogits, ws=ws)
         self._last_pack = pk
-        return _ProbeLoss.apply(dec, pk, *dec.param_list()), metrics, tensors
+        if _defer:
+            return pk, metrics, tensors
+        return _ProbeLoss.apply(self, dict(loss=mbuf[s0], heads=[pk]), *dec.param_list()), metrics, tensors
+
+
+GOAL_KEYS = ('goal_direction', 'goals_direction')      # probes.py:93-96, the ModuleDict's order
+
+
+class _Decoders(_Params):
+    """The nn.ModuleDict of probes.py:93: a parameter-only holder whose children keep their insertion order."""
+
+
+class GoalsProbe(_Params):
+    """probes.py:89-137: two DenseNormalDecoders on the DETACHED, bare features (no map_coord behind them) - `goal_direction`
+    (out_dim 2) and `goals_direction` (out_dim 2 * goals_size), each with hidden_layers=4 and layer_norm=True whatever
+    conf.layer_norm says (probes.py:94-95).  Keys probe_model.decoders.{goal_direction,goals_direction}.model.model.{0,1,3,...};
+    torch's default Linear init, as for the map probe.  Forward and backward of the heads are MLP.fwd / dm_mlp_head_bwd, the
+    Normal loss dm_head_loss_normal_nd, the IWAE reduction dm_reduce_i / dm_scale_rows; mse_goals, var_goals and the six
+    mse_goal_age* come from one dm_goals_stats call (csrc/goals.hip) that writes them into the step's metric buffer."""
+
+    def __init__(self, state_dim, conf):
+        super().__init__()
+        self.goals_size = int(getattr(conf, 'goals_size', 0))
+        if self.goals_size < 1:      # the reference would build a zero-width decoder
+            raise NotImplementedError(f"probe_model={getattr(conf, 'probe_model', 'goals')!r} needs goals_size >= 1 "
+                                      f'(got goals_size={self.goals_size}): a zero-width goals decoder is not built in the HIP path')
+        self.decoders = _Decoders()
+        self.decoders.add_module('goal_direction', DenseNormalDecoder(state_dim, 4, True, out_dim=2))
+        self.decoders.add_module('goals_direction', DenseNormalDecoder(state_dim, 4, True, out_dim=2 * self.goals_size))
+        self._ws = None
+
+    def heads(self):
+        return [getattr(self.decoders, k).model for k in GOAL_KEYS]
+
+    def _workspace(self, rows, device):
+        need = 4 * int(H.lib().dm_mlp_ws_floats(rows, MLP_HIDDEN, 4))
+        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
+        return self._ws
+
+    def training_step(self, features, obs, mbuf=None, _defer=False):
+        """features (T,B,I,F), detached.  Returns (loss_probe, metrics, tensors) with the reference's names: metrics
+        loss_goal_direction, loss_goals_direction, mse_goals, var_goals and, with obs['goals_visage'], mse_goal_age{0,5,10,50,200,
+        1000}; tensors loss_<key> (T,B) and <key>_pred (T,B,out_dim).  _defer (MapGoalsProbe): in grad mode the first result is
+        (loss, backward packs) instead of an autograd loss."""
+        _require_cuda(features, 'features')
+        T, B, I, F_ = features.shape
+        G = self.goals_size
+        N, NE, dev = T * B * I, T * B, features.device
+        for k in GOAL_KEYS:
+            if k not in obs:
+                raise ValueError(f"probe_model='goals': obs['{k}'] is a target of the goals probe (probes.py:102-105)")
+        want = dict(goal_direction=(T, B, 2), goals_direction=(T, B, 2 * G))
+        got = {k: tuple(obs[k].shape) for k in GOAL_KEYS}
+        visage = obs.get('goals_visage')
+        if visage is not None:
+            want['goals_visage'], got['goals_visage'] = (T, B, G), tuple(visage.shape)
+        bad = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
+        if bad:
+            raise ValueError('training_step input shapes (got, expected): ' + ', '.join(f'{k}: {v[0]} != {v[1]}' for k, v in bad.items()))
+        train = torch.is_grad_enabled()
+        # -Normal(mu, std).log_prob(y) * std^2 summed over the outputs (decoders.py:296-304), the reward head's constant per output
+        loss_const = REWARD_STD ** 2 * (math.log(REWARD_STD) + math.log(math.sqrt(2 * math.pi)))
+        with torch.no_grad():
+            feat2d = features.reshape(N, F_).contiguous()
+            ws = self._workspace(N, dev)
+            gw = float(getattr(self, 'grad_weight', 1.0))          # data-parallel shard weight B_r/B (dist.attach), gradients only
+            if mbuf is None:
+                mbuf = torch.zeros(METRIC_BUF_FLOATS, device=dev)
+            s0 = GOALS_METRIC_SLOTS['loss_goal_direction']
+            packs, metrics, tensors, means, targets = [], {}, {}, [], {}
+            for n, (key, mlp) in enumerate(zip(GOAL_KEYS, self.heads())):
+                V = mlp.out_dim
+                target = targets[key] = obs[key].float().contiguous().view(NE, V)
+                rows_t = target.repeat_interleave(I, dim=0).contiguous() if I > 1 else target      # insert_dim(target, 2, I), decoders.py:309
+                mu, acts = mlp.fwd(feat2d, F_, N, ws, save_acts=train)
+                loss_tbi, mean_i = torch.empty(N, device=dev), torch.empty(N, V, device=dev)
+                dmu = torch.empty(N, V, device=dev) if train else None
+                # d loss_probe / d loss_tb = 1 / (T*B); with I > 1 the importance weights come in below
+                H.call('dm_head_loss_normal_nd', N, V, H.fptr(mu), H.fptr(rows_t), gw / NE if I == 1 else 1.0, loss_const,
+                       H.fptr(loss_tbi), H.fptr(dmu), H.fptr(mean_i), H.stream())
+                if I == 1:
+                    loss_tb, pred = loss_tbi, mean_i
+                else:          # loss_tb = -logavgexp_i(-loss_tbi), decoded.mean.mean(dim=2) (decoders.py:313-314)
+                    loss_tb, iw, pred = torch.empty(NE, device=dev), torch.empty(N, device=dev), torch.empty(NE, V, device=dev)
+                    H.call('dm_reduce_i', NE, I, 1, H.fptr(loss_tbi), 1, H.fptr(loss_tb), H.fptr(iw), H.stream())
+                    H.call('dm_reduce_i', NE, I, V, H.fptr(mean_i), 0, H.fptr(pred), None, H.stream())
+                    if train:
+                        H.call('dm_scale_rows', N, V, H.fptr(dmu), V, H.fptr(iw), gw / NE, H.stream())
+                means.append((loss_tb, 1.0 / NE))
+                metrics[f'loss_{key}'] = mbuf[s0 + n]
+                tensors[f'loss_{key}'] = loss_tb.view(T, B)
+                tensors[f'{key}_pred'] = pred.view(T, B, V)
+                if train:
+                    packs.append(dict(mlp=mlp, x=feat2d, ldx=F_, rows=N, acts=acts, dout=dmu, ws=ws))
+            _multi_sum(means, dev, out=mbuf[s0:s0 + 2])
+            loss = mbuf[s0] + mbuf[s0 + 1]          # loss_total = sum over the keys of loss.mean() (probes.py:106)
+            # mse_goals, var_goals and the age buckets (probes.py:113-135): one call, straight into the metric slots
+            s1 = GOALS_METRIC_SLOTS['mse_goals']
+            vis = None if visage is None else visage.float().contiguous()
+            gws = torch.empty(max(1, int(H.lib().dm_goals_stats_ws_floats(NE, G))), device=dev)
+            H.call('dm_goals_stats', NE, G, H.fptr(targets['goals_direction']), H.fptr(tensors['goals_direction_pred'].contiguous()),
+                   H.fptr(vis), ctypes.c_void_p(mbuf.data_ptr() + 4 * s1), H.fptr(gws), gws.numel() * 4, H.stream())
+            names = GOALS_STAT_NAMES if vis is not None else GOALS_STAT_NAMES[:2]
+            metrics.update({k: mbuf[GOALS_METRIC_SLOTS[k]] for k in names})
+        if not train:
+            return loss, metrics, tensors
+        self._last_packs = packs
+        if _defer:
+            return (loss, packs), metrics, tensors
+        return _ProbeLoss.apply(self, dict(loss=loss, heads=packs), *self.parameters()), metrics, tensors
+
+
+class MapGoalsProbe(_Params):
+    """probes.py:15-29: the map probe on [features | map_coord] and the goals probe on the bare features; the loss is the sum of
+    both, metrics and tensors are the union.  Keys probe_model.map_probe.decoder.* then probe_model.goals_probe.decoders.*.
+    One autograd node and ONE claim of the probe optimizer's gradient buffer serve the three MLPs (_ProbeLoss)."""
+
+    def __init__(self, state_dim, conf):
+        super().__init__()
+        self.map_probe = MapProbeHead(state_dim + 4, conf)
+        self.goals_probe = GoalsProbe(state_dim, conf)
+
+    @property
+    def grad_weight(self):
+        return getattr(self.map_probe, 'grad_weight', 1.0)
+
+    @grad_weight.setter
+    def grad_weight(self, w):
+        self.map_probe.grad_weight = self.goals_probe.grad_weight = w
+
+    def training_step(self, features, obs, mbuf=None):
+        if mbuf is None:
+            mbuf = torch.zeros(METRIC_BUF_FLOATS, device=features.device)
+        r_map, metrics_map, tensors_map = self.map_probe.training_step(features, obs, mbuf=mbuf, _defer=True)
+        r_goals, metrics_goals, tensors_goals = self.goals_probe.training_step(features, obs, mbuf=mbuf, _defer=True)
+        metrics, tensors = dict(**metrics_map, **metrics_goals), dict(**tensors_map, **tensors_goals)
+        if not torch.is_grad_enabled():
+            return r_map + r_goals, metrics, tensors
+        loss_goals, packs = r_goals
+        with torch.no_grad():
+            loss = r_map['loss'] + loss_goals
+        return _ProbeLoss.apply(self, dict(loss=loss, heads=[r_map] + packs), *self.parameters()), metrics, tensors
 
 
 def _torch_actor_distribution(actor_dist, y):
@@ -513,7 +657,9 @@ def _flat_views(plist, device, fused=None, scratch=False):
         views = fused.claim_fresh_grads(plist)
         if views is not None:
             return fused.flat_grad, views, True
-    flat = torch.empty(sum(p.numel() for p in plist), device=device)
+    # zeros, not empty: a parameter no kernel of the pass writes (the auxiliary ActorCritic's actor, dreamer.py:347-358) would
+    # otherwise hand autograd whatever the allocator's block held before
+    flat = torch.zeros(sum(p.numel() for p in plist), device=device)
     views, off = [], 0
     for p in plist:
         views.append(flat[off:off + p.numel()].view(p.shape))
@@ -548,7 +694,11 @@ METRIC_SLOTS = dict(loss_kl=0, loss_image=1, loss_reward=2, loss_terminal=3, ent
                     policy_reward_std=14, grad_norm=16, grad_norm_probe=18, grad_norm_actor=20, grad_norm_critic=22,
                     loss_critic_aux=24, policy_value_aux=25, loss_vecobs=15,      # slot 7: loss_model + aux_critic_weight * loss_critic_aux
                     loss_map=28, acc_map=29, acc_map_seen=30)      # the map probe's (MapProbeHead); zero with probe_model='none'
-METRIC_BUF_FLOATS = 32
+# the goals probe's ten scalars (GoalsProbe): appended behind METRIC_SLOTS, named by packed_metrics() only for a model that has a
+# goals probe, zero otherwise.  Slots 34-41 are the eight floats dm_goals_stats writes.
+GOALS_STAT_NAMES = ('mse_goals', 'var_goals') + tuple(f'mse_goal_age{a}' for a in (0, 5, 10, 50, 200, 1000))
+GOALS_METRIC_SLOTS = {k: 32 + i for i, k in enumerate(('loss_goal_direction', 'loss_goals_direction') + GOALS_STAT_NAMES)}
+METRIC_BUF_FLOATS = 48
 
 
 def _finish_backward(owner, grads, flat, direct, grad_loss):
@@ -1408,26 +1558,37 @@ class _HeadLoss(torch.autograd.Function):
 
 
 class _ProbeLoss(torch.autograd.Function):
-    """loss_probe of the map probe: the gradient of its MLP's parameters is produced by dm_mlp_head_bwd from the scaled
-    softmax - onehot rows, inside backward() on the caller's stream (the probe reads detached features: nothing else waits for
-    it, and it is small enough that pre-launching it on a side stream was not built), straight into the probe optimizer's
-    `.grad` slots when zero_grad() came first."""
+    """loss_probe of a probe with one (map), two (goals) or three (map+goals) MLP heads that share ONE probe optimizer: the
+    gradients of every head's parameters are produced by dm_mlp_head_bwd from the head's scaled output-gradient rows, inside
+    backward() on the caller's stream (the probe reads detached features: nothing else waits for it, and it is small enough
+    that pre-launching it on a side stream was not built).  `owner` is the probe (its `_fused` is the probe optimizer), `params`
+    are ALL its parameters in parameters() order = the optimizer group's: the gradient buffer is claimed ONCE for that union
+    (FusedAdamW.claim_fresh_grads hands out the `.grad` slots only for exactly the group's set) and each head writes its own
+    slice, straight into the `.grad` slots when zero_grad() came first, else into a scratch buffer autograd accumulates."""
 
     @staticmethod
-    def forward(ctx, mlp, pack, *params):
-        ctx.mlp, ctx.pack = mlp, pack
+    def forward(ctx, owner, pack, *params):
+        ctx.owner, ctx.pack, ctx.params = owner, pack, params
         return pack['loss'].clone()
 
     @staticmethod
     def backward(ctx, grad_loss):
-        mlp, pk = ctx.mlp, ctx.pack
+        owner, pk = ctx.owner, ctx.pack
         if pk.get('consumed'):
             raise RuntimeError('loss_probe.backward() called twice (saved activations were released)')
-        grads, flat, direct = mlp.bwd(pk['x'], pk['ldx'], pk['rows'], pk['acts'], pk['dout'], pk['ws'])
-        for k in ('acts', 'dout', 'x'):
-            pk.pop(k, None)
+        plist = list(ctx.params)
+        flat, views, direct = _flat_views(plist, grad_loss.device, getattr(owner, '_fused', None))
+        gof = {id(p): v for p, v in zip(plist, views)}
+        for hp in pk['heads']:
+            mlp = hp['mlp']
+            st, gs = mlp.struct(), mlp.grad_struct(gof)
+            H.call('dm_mlp_head_bwd', hp['rows'], mlp.in_dim, mlp.hidden_dim, mlp.hidden_layers, mlp.out_dim, H.fptr(hp['x']), hp['ldx'],
+                   ctypes.byref(st), H.fptr(hp['acts']), H.fptr(hp['dout']), ctypes.byref(gs), None, 0, 0, H.ptr(hp['ws']),
+                   hp['ws'].numel(), H.stream())
+            for k in ('acts', 'dout', 'x'):
+                hp.pop(k, None)
         pk['consumed'] = True
-        return (None, None) + _finish_backward(mlp, grads, flat, direct, grad_loss)
+        return (None, None) + _finish_backward(owner, views, flat, direct, grad_loss)
 
 
 class ActorCritic(_Params):
@@ -1564,9 +1725,11 @@ class Dreamer(nn.Module):
     def __init__(self, conf):
         super().__init__()
         assert conf.action_dim > 0, 'Need to set action_dim to match environment'
-        if conf.probe_model not in ('none', 'map'):
-            raise NotImplementedError(f'probe_model={conf.probe_model!r}: only the map probe is built (the goals probe and '
-                                      f'map+goals are research heads outside the hot path)')
+        if conf.probe_model not in ('none', 'map', 'goals', 'map+goals'):
+            raise NotImplementedError(f'probe_model={conf.probe_model!r}: the probes built are none, map, goals and map+goals')
+        if conf.probe_model in ('goals', 'map+goals') and int(getattr(conf, 'goals_size', 0)) < 1:
+            raise NotImplementedError(f'probe_model={conf.probe_model!r} needs goals_size >= 1 (got goals_size='
+                                      f"{getattr(conf, 'goals_size', 0)}): a zero-width goals decoder is not built in the HIP path")
         if conf.probe_model != 'none' and conf.probe_gradients:
             raise NotImplementedError('probe_gradients=True with a probe model: the gradient of the probe loss into the world '
                                       "model's features is not built (the probe trains on detached features only)")
@@ -1578,8 +1741,15 @@ class Dreamer(nn.Module):
                               lambda_gae=conf.lambda_gae, entropy_weight=conf.entropy, target_interval=conf.target_interval,
                               actor_grad=conf.actor_grad, actor_dist=conf.actor_dist)
         self.ac.sparse_cols = conf.stoch_dim * conf.stoch_discrete       # feature = [h | one-hot z] (rssm.py:83-84)
-        # dreamer.py:43-52: the map probe sees [features | map_coord]
-        self.probe_model = MapProbeHead(features_dim + 4, conf) if conf.probe_model == 'map' else NoProbeHead()
+        # dreamer.py:43-52: the map probe sees [features | map_coord], the goals probe the bare features
+        if conf.probe_model == 'map':
+            self.probe_model = MapProbeHead(features_dim + 4, conf)
+        elif conf.probe_model == 'goals':
+            self.probe_model = GoalsProbe(features_dim, conf)
+        elif conf.probe_model == 'map+goals':
+            self.probe_model = MapGoalsProbe(features_dim, conf)
+        else:
+            self.probe_model = NoProbeHead()
         self.probe_gradients = conf.probe_gradients
         self._groups = None
         # conf.amp (defaults.yaml:55; train.py:166 runs the step under autocast): GEMM operands in bf16, fp32 accumulation,
@@ -1609,8 +1779,8 @@ class Dreamer(nn.Module):
                          critic=FusedAdamW(groups['critic'], lr=lr_critic or lr, eps=eps))
         # the backward passes write straight into these optimizers' gradient buffers (see _flat_views)
         self.wm._fused, self.ac.actor._fused, self.ac.critic._fused = self._opt['wm'], self._opt['actor'], self._opt['critic']
-        if isinstance(self.probe_model, MapProbeHead):
-            self.probe_model.decoder._fused = self._opt['probe']
+        if not isinstance(self.probe_model, NoProbeHead):      # _ProbeLoss claims the group's gradient buffer once for all heads
+            self.probe_model._fused = self._opt['probe']
         self.prepare_streams()
         if self.probe_gradients:      # dreamer.py:67-71: three optimizers; the probe head's parameters belong to none of them
             return self._opt['wm'], self._opt['actor'], self._opt['critic']
@@ -1723,8 +1893,11 @@ class Dreamer(nn.Module):
         logged step (train.py:204-214) with a single device-to-host copy.  No kernel runs here: the kernels of the step
         wrote their results straight into this buffer."""
         self.join_optimizers()      # (pipelined mode: the actor / critic gradient norms were written on the actor-critic stream)
-        names = list(METRIC_SLOTS)
-        return names, self.metric_buffer, [METRIC_SLOTS[n] for n in names]
+        slots = dict(METRIC_SLOTS)
+        if isinstance(self.probe_model, (GoalsProbe, MapGoalsProbe)):
+            slots.update(GOALS_METRIC_SLOTS)
+        names = list(slots)
+        return names, self.metric_buffer, [slots[n] for n in names]
 
     def packed_metrics_host(self):
         """{name: float} of packed_metrics() with ONE device-to-host copy (= the step's only sync), followed by
@@ -1906,7 +2079,7 @@ class Dreamer(nn.Module):
             pk['pre'] = ov.submit(ov.s_wm, ov.ev_wm_fwd, lambda: self.wm._backward(
                 pk, ov.ws_wm, scratch=gens.get(id(self.wm), True), defer_wgrad=True))
         metrics, tensors = dict(metrics), tensors.copy()          # LazyTensors.copy(): image_rec stays a thunk
-        if isinstance(self.probe_model, MapProbeHead):      # its three scalars land in the step's metric buffer
+        if not isinstance(self.probe_model, NoProbeHead):      # the probe's scalars land in the step's metric buffer
             loss_probe, metrics_probe, tensors_probe = self.probe_model.training_step(features.detach(), obs, mbuf=mbuf)
         else:
             loss_probe, metrics_probe, tensors_probe = self.probe_model.training_step(features.detach(), obs)

@@ -284,13 +284,19 @@ class SequentialReplay:
             yield self.fill()
 
 
-def preprocess_batch(batch, action_dim, clip_rewards=None, image_key='image', map_key=None, map_categorical=None):
+GOAL_SOURCES = ('targets_vec', 'target_vec')      # the files' fields behind goals_direction / goal_direction
+
+
+def preprocess_batch(batch, action_dim, clip_rewards=None, image_key='image', map_key=None, map_categorical=None, goals=False):
     """Hot-path subset of Preprocessor.apply (preprocessing.py:87-180), images left uint8 (T,B,H,W,C).
     map_key / map_categorical (preprocessing.py:115-131,152-158; the inputs of the map probe, models.MapProbeHead): `map` =
     batch[map_key] as a one-hot (T,B,C,H,W) float32 with C = map_categorical, or - not categorical - a float image of that
     layout; `map_seen_mask` from `map_seen` or `map_vis`; `map_coord` (T,B,4) from `agent_pos`, `agent_dir` and the map's
     height.  Without map_key nothing of this is emitted.  ReplayFeed / DeviceReplay carry the class map as stored (integer
-    (T,B,H,W), which MapProbeHead takes as it is) with the same mask and coord."""
+    (T,B,H,W), which MapProbeHead takes as it is) with the same mask and coord.
+    goals=True (preprocessing.py:171-178; the targets of the goals probe, models.GoalsProbe): `goals_direction` = `targets_vec`
+    (T,B,G,2) reshaped to (T,B,2G), `goal_direction` = `target_vec`, both float32, and `goals_visage` passed through as float32
+    when the batch holds it.  With the default nothing of this is emitted."""
     T, B = batch['reward'].shape[:2]
     out = {}
     img = batch[image_key]
@@ -333,6 +339,25 @@ def preprocess_batch(batch, action_dim, clip_rewards=None, image_key='image', ma
         if 'agent_pos' in batch and 'agent_dir' in batch:
             pos = batch['agent_pos'] / float(out['map'].shape[-2]) * 2 - 1.0
             out['map_coord'] = np.concatenate([pos, batch['agent_dir']], axis=-1).astype(np.float32)
+    if goals:
+        _require_goal_sources(batch, 'the batch')
+        out.update(_goal_fields(batch))
+    return out
+
+
+def _require_goal_sources(fields, what):
+    missing = [k for k in GOAL_SOURCES if k not in fields]
+    if missing:
+        raise ValueError(f'goals=True: {what} holds no {" / ".join(missing)} (the sources of goals_direction / goal_direction)')
+
+
+def _goal_fields(fields):
+    """preprocess_batch's goal fields of raw fields (any leading dimensions): (*,G,2) => (*,2G), float32."""
+    tv = fields['targets_vec']
+    out = {'goals_direction': tv.reshape(tv.shape[:-2] + (-1,)).astype(np.float32),
+           'goal_direction': fields['target_vec'].astype(np.float32)}
+    if 'goals_visage' in fields:
+        out['goals_visage'] = fields['goals_visage'].astype(np.float32)
     return out
 
 
@@ -368,7 +393,7 @@ def _map_spec(probe, lead, map_key, map_categorical):
     return spec
 
 
-def _feed_layout(replay, action_dim, image_key, map_key, map_categorical, who):
+def _feed_layout(replay, action_dim, image_key, map_key, map_categorical, who, goals=False):
     """(raw fields of the repository's first file, {field: ((T, B, ...) shape, dtype)} of a batch as the feeds hand it over)."""
     if not replay.files:
         raise ValueError(f'{who} needs at least one episode file to lay out its slots (the repository is empty)')
@@ -384,6 +409,10 @@ def _feed_layout(replay, action_dim, image_key, map_key, map_categorical, who):
         spec['vecobs'] = ((T, B) + probe['vecobs'].shape[1:], np.float32)
     if map_key:
         spec.update(_map_spec(probe, (T, B), map_key, map_categorical))
+    if goals:
+        _require_goal_sources(probe, f'the first episode file of {who}')
+        for k, v in _goal_fields({k: probe[k][:1] for k in GOAL_SOURCES + ('goals_visage',) if k in probe}).items():
+            spec[k] = ((T, B) + v.shape[1:], np.float32)
     return probe, spec
 
 
@@ -394,14 +423,15 @@ class ReplayFeed:
     Field for field what `preprocess_batch(next(iter(replay)), ...)` returns (tests/test_replay_cpu.py compares the two).
     With map_key / map_categorical the slot also carries the map probe's inputs: `map` as the stored integer class map
     (T,B,H,W) - not preprocess_batch's one-hot; MapProbeHead takes either - and preprocess_batch's `map_seen_mask` and
-    `map_coord` when the files hold their sources."""
+    `map_coord` when the files hold their sources.  With goals=True it carries preprocess_batch's `goals_direction`,
+    `goal_direction` and (when the files hold it) `goals_visage`; files without targets_vec / target_vec raise at construction."""
 
-    def __init__(self, replay, action_dim, clip_rewards=None, image_key='image', map_key=None, map_categorical=None):
+    def __init__(self, replay, action_dim, clip_rewards=None, image_key='image', map_key=None, map_categorical=None, goals=False):
         if clip_rewards not in (None, '', False, 'tanh', 'log1p'):
             raise ValueError(clip_rewards)
         self.replay, self.action_dim, self.clip_rewards, self.image_key = replay, int(action_dim), clip_rewards, image_key
         self.map_key = map_key
-        probe, self._spec = _feed_layout(replay, self.action_dim, image_key, map_key, map_categorical, 'ReplayFeed')
+        probe, self._spec = _feed_layout(replay, self.action_dim, image_key, map_key, map_categorical, 'ReplayFeed', goals)
         T, B = replay.batch_length, replay.batch_size
         # `terminal` always has a column: an episode without the field contributes zeros (SequentialReplay._copy), so a
         # repository that mixes files with and without it still yields the flags of those that carry them
@@ -412,6 +442,9 @@ class ReplayFeed:
             for k in ('map_seen', 'map_vis', 'agent_pos', 'agent_dir'):      # sources of the mask and the coord: scratch
                 if k in probe and k != map_key:
                     self._small[k] = np.empty((T, B) + probe[k].shape[1:], probe[k].dtype)
+        self._goal_sources = [k for k in GOAL_SOURCES + ('goals_visage',) if k in probe] if goals else []
+        for k in self._goal_sources:                                         # sources of the goal fields: scratch
+            self._small[k] = np.empty((T, B) + probe[k].shape[1:], probe[k].dtype)
 
     def spec(self):
         """{field: (shape, dtype)} of a slot."""
@@ -446,6 +479,9 @@ class ReplayFeed:
             slot['map_seen_mask'][...] = _map_seen_mask(raw)
         if 'map_coord' in slot:
             slot['map_coord'][...] = _map_coord(raw, slot['map'].shape[-2])
+        if self._goal_sources:
+            for k, v in _goal_fields(raw).items():
+                slot[k][...] = v
         return slot
 
 
@@ -626,7 +662,8 @@ class DeviceReplay:
     rules of ReplayFeed.fill: float32 one-hot action / action_next, float32 reward with reward[0] = 0 and clip_rewards applied
     by numpy (tanh / log1p are the host's bits), float32 terminal (zeros when the file lacks it), bool reset with reset[0] =
     True, float32 vecobs, uint8 frames (n, H, W, C) (`image_t` files transposed), and with map_key / map_categorical the stored
-    integer class map plus preprocess_batch's map_seen_mask and map_coord.  A file whose rows do not have the layout of the
+    integer class map plus preprocess_batch's map_seen_mask and map_coord, and with goals=True preprocess_batch's float32
+    goals_direction, goal_direction and goals_visage - three more resident fields the same gather copies.  A file whose rows do not have the layout of the
     first file is passed over like an unreadable one.  Eviction is least-recently-VISITED first once the cached bytes pass
     `capacity_bytes` (0: no limit), and only drops the cache's reference: an episode a column cursor, a carried tail or a
     planned batch still holds stays alive until they let go, so device residency can exceed the budget by up to those - at
@@ -643,7 +680,7 @@ class DeviceReplay:
     Without `device` nothing touches the GPU: plan() alone is usable, the prepared episodes stay in ordinary host memory."""
 
     def __init__(self, replay, action_dim, device=None, depth=3, capacity_bytes=0, clip_rewards=None, image_key='image',
-                 map_key=None, map_categorical=None):
+                 map_key=None, map_categorical=None, goals=False):
         if clip_rewards not in (None, '', False, 'tanh', 'log1p'):
             raise ValueError(clip_rewards)
         if any(c.episode is not None or c.tail is not None for c in replay.columns):
@@ -652,7 +689,8 @@ class DeviceReplay:
         self.map_key, self.map_categorical = map_key, map_categorical
         self.device = None if device is None else torch.device(device)
         self.depth, self.capacity_bytes = max(3, int(depth)), int(capacity_bytes or 0)
-        _, self._spec = _feed_layout(replay, self.action_dim, image_key, map_key, map_categorical, 'DeviceReplay')
+        self.goals = bool(goals)
+        _, self._spec = _feed_layout(replay, self.action_dim, image_key, map_key, map_categorical, 'DeviceReplay', goals)
         self.names = list(self._spec)
         self._rows = {k: (tuple(shape[2:]), np.dtype(dt)) for k, (shape, dt) in self._spec.items()}
         self.row_bytes = {k: int(np.prod(shape, dtype=np.int64)) * dt.itemsize for k, (shape, dt) in self._rows.items()}
@@ -700,11 +738,14 @@ class DeviceReplay:
                 vals['map_seen_mask'] = _map_seen_mask(f)
             if 'map_coord' in self._rows:
                 vals['map_coord'] = _map_coord(f, f[self.map_key].shape[-2])
+        if self.goals:
+            _require_goal_sources(f, f'the episode file {info.path}')
+            vals.update(_goal_fields(f))
         offsets, nbytes = {}, 0
         for k in self.names:                                  # the gather trusts row_bytes: every file must have the first one's layout
             shape, dt = self._rows[k]
-            if vals[k] is None or vals[k].shape != (n,) + shape or vals[k].dtype != dt:
-                got = None if vals[k] is None else (vals[k].dtype, vals[k].shape)
+            if vals.get(k) is None or vals[k].shape != (n,) + shape or vals[k].dtype != dt:
+                got = None if vals.get(k) is None else (vals[k].dtype, vals[k].shape)
                 raise ValueError(f'field {k!r} is {got}, the batches are laid out for {dt} {(n,) + shape}')
             offsets[k] = nbytes
             nbytes += -(-n * self.row_bytes[k] // _RESIDENT_ALIGN) * _RESIDENT_ALIGN
