@@ -90,7 +90,8 @@ int dm_version(void);                 /* ABI version, currently 16 (v2: LayerNor
                                          v16: dm_rssm_last_schedule added; later, still 16 (additions only): the per-cell categorical
                                               loss family dm_cat_target_index / dm_cat_image_loss / dm_cat_image_pred / dm_cat_concat_rows
                                               of the map probe; dm_replay_gather of the device-resident replay; dm_goals_stats /
-                                              dm_goals_stats_ws_floats of the goals probe */
+                                              dm_goals_stats_ws_floats of the goals probe; the dm_gru_sequence_ family of the
+                                              gru_probe baseline */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
 size_t dm_workspace_bytes(const dm_shape* shp);   /* scratch needed by any call below for this shape */
@@ -447,6 +448,44 @@ int dm_rssm_sequence_bwd(const dm_shape* shp, const float* embed, const float* a
 #define DM_SCHED_ROLL_FUSE_ACT 16       /* the one-hot action draw in that kernel's output stage */
 #define DM_SCHED_ROLL_TW_ON 32          /* bf16 twins of the cell's operands */
 int dm_rssm_last_schedule(int which);
+
+/* Plain GRU over a sequence (csrc/gru_seq.hip): the recurrent core of the `gru_probe` baseline, torch.nn.GRU(In, D), one
+ * layer, time-major (baselines.py:322 self.rnn = nn.GRU(...), :339-341 the [squeezed embedding | action_next] input, :352
+ * self.rnn(input, in_state)).  Gate order r, z, n as in torch's GRU: w_ih (3D, In), w_hh (3D, D), b_ih (3D), b_hh (3D), rows
+ * [0, D) reset, [D, 2D) update, [2D, 3D) new:
+ *   GI = X w_ih^T + b_ih (all T*B rows, one product);  per step GH_t = h_{t-1} w_hh^T + b_hh,
+ *   r = sig(GI_r + GH_r), z = sig(GI_z + GH_z), n = tanh(GI_n + r GH_n), h_t = (h_{t-1} - n) z + n.
+ * fp32 throughout, whatever other calls of the thread run in.  T, B, In, D >= 1 and D % 4 == 0, else DM_E_SHAPE.
+ * x (T*B, In; leading dimension ldx), h0 (B, D), reset0 (B) bytes or NULL: h_0 = reset0[b] ? 0 : h0[b].  Resets of later
+ * steps are not an input (nn.GRU has none).  H (T*B, D; leading dimension ldh) receives h_1 .. h_T; the final state is
+ * its last B rows.  acts (dm_gru_sequence_acts_floats floats) keeps GI, GH and h_0 for dm_gru_sequence_bwd; acts == NULL:
+ * forward only, nothing is kept and H has the same bits.  ws: dm_gru_sequence_ws_bytes bytes of scratch for either call.
+ * Launch schedule of the forward step (dm_gru_sequence_last_schedule: that of this thread's last forward call):
+ *   1  B <= 64, 3*D*D < 65536 (D <= 144) and H, w_hh, acts and ws 16-byte aligned with ldh % 4 == 0: ONE launch per step - a workgroup
+ *      owns 4 hidden units, their r, z, n rows of w_hh share one v_mfma_f32_16x16x4_f32 tile, the gate arithmetic is that
+ *      launch's epilogue;
+ *   0  otherwise: the h w_hh^T product through the GEMM entry, then the dm_gru_gates_fwd kernel (measured faster than the
+ *      one-launch step at D 600 / 1024 / 2048).
+ * No atomics, no persistent kernel; every launch on `stream`; the same inputs give the same bits.
+ * Backward: dH (T*B, D; leading dimension lddh, read-only) is dL/dH of every step.  Gradient buffers are OVERWRITTEN, as
+ * dm_rssm_sequence_bwd and dm_mlp_head_bwd overwrite theirs: g->w_ih, g->w_hh, g->b_ih, g->b_hh and dx (T*B, In; leading
+ * dimension lddx; nullable) hold this call's gradients alone afterwards, so a second call into the same buffers leaves the
+ * same bits and a caller that accumulates over several calls adds them up itself.  No gradient goes to h0.  x, H and acts
+ * must be those of the forward call. */
+typedef struct dm_gru_params { const float* w_ih; const float* w_hh; const float* b_ih; const float* b_hh; } dm_gru_params;
+typedef struct dm_gru_grads { float* w_ih; float* w_hh; float* b_ih; float* b_hh; } dm_gru_grads;
+size_t dm_gru_sequence_acts_floats(int T, int B, int In, int D);
+size_t dm_gru_sequence_ws_bytes(int T, int B, int In, int D);
+int dm_gru_sequence_fwd(int T, int B, int In, int D, const float* x, int ldx, const float* h0, const uint8_t* reset0,
+                        const dm_gru_params* p, float* acts, float* H, int ldh, void* ws, size_t ws_bytes, void* stream);
+int dm_gru_sequence_bwd(int T, int B, int In, int D, const float* x, int ldx, const dm_gru_params* p, const float* acts,
+                        const float* H, int ldh, const float* dH, int lddh, const dm_gru_grads* g, float* dx, int lddx,
+                        void* ws, size_t ws_bytes, void* stream);
+int dm_gru_sequence_last_schedule(void);
+/* Which forward calls take schedule 1: 1 (default) = B <= 64 with 3*D*D < 65536; 0 = none; 2 = every B <= 64 call, whatever the
+ * width (how scripts/gru_probe_bench.py regenerates the comparison of DESIGN 4.10 and how the tests reach the one-launch kernel
+ * at wide states); -1 queries.  Process-wide; returns the state.  Alignment still applies: an unaligned call runs schedule 0. */
+int dm_gru_sequence_fuse_enable(int on);
 
 /* Progress marks for the NEXT dm_dream_rollout call of the calling thread (n <= 4; cleared by that call): events[i] - a
  * hipEvent_t owned by the caller - is recorded on the rollout's stream when horizon step steps[i] (0-based) has been

@@ -112,6 +112,19 @@ class dm_replay_field(Structure):
 
 DM_REPLAY_MAX_FIELDS = 16
 
+
+class dm_gru_params(Structure):      # torch.nn.GRU layer 0, gate rows r, z, n (include/dreamer_hip.h dm_gru_sequence_fwd)
+    _fields_ = [('w_ih', c_void_p), ('w_hh', c_void_p), ('b_ih', c_void_p), ('b_hh', c_void_p)]
+
+
+dm_gru_grads = dm_gru_params
+
+
+def gru_struct(w_ih, w_hh, b_ih, b_hh):
+    s = dm_gru_params()
+    s.w_ih, s.w_hh, s.b_ih, s.b_hh = w_ih.data_ptr(), w_hh.data_ptr(), b_ih.data_ptr(), b_hh.data_ptr()
+    return s
+
 _P = c_void_p
 _SIGNATURES = {
     'dm_version': (c_int, []),
@@ -214,6 +227,14 @@ _SIGNATURES = {
     'dm_mlp_head_fwd_rows': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, POINTER(dm_mlp_params), _P, _P, _P,
                                      c_size_t, _P]),
     'dm_replay_gather': (c_int, [c_int, c_int, c_int, POINTER(dm_replay_field), _P, _P, _P]),
+    'dm_gru_sequence_acts_floats': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'dm_gru_sequence_ws_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'dm_gru_sequence_fwd': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, _P, POINTER(dm_gru_params), _P, _P, c_int,
+                                    _P, c_size_t, _P]),
+    'dm_gru_sequence_bwd': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, POINTER(dm_gru_params), _P, _P, c_int, _P, c_int,
+                                    POINTER(dm_gru_grads), _P, c_int, _P, c_size_t, _P]),
+    'dm_gru_sequence_last_schedule': (c_int, []),
+    'dm_gru_sequence_fuse_enable': (c_int, [c_int]),
 }
 
 _lib = None

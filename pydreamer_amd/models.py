@@ -2165,3 +2165,13 @@ class Dreamer(nn.Module):
         for sub in (self.wm.encoder, self.wm.decoder, self.wm.core, self.ac, self.probe_model):
             s.append(f'  {type(sub).__name__:<15}: {count(sub)} parameters')
         return '\n'.join(s)
+
+
+
+def __getattr__(name):
+    """`from pydreamer_amd.models import WorldModelProbe` (train.py:104-107 picks Dreamer or WorldModelProbe from one module): the
+    class lives in baselines.py, which imports this module, so it is looked up on first use instead of imported here."""
+    if name == 'WorldModelProbe':
+        from .baselines import WorldModelProbe
+        return WorldModelProbe
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
