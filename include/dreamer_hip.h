@@ -91,7 +91,8 @@ int dm_version(void);                 /* ABI version, currently 16 (v2: LayerNor
                                               loss family dm_cat_target_index / dm_cat_image_loss / dm_cat_image_pred / dm_cat_concat_rows
                                               of the map probe; dm_replay_gather of the device-resident replay; dm_goals_stats /
                                               dm_goals_stats_ws_floats of the goals probe; the dm_gru_sequence_ family of the
-                                              gru_probe baseline */
+                                              gru_probe baseline; dm_dense_image_rows / dm_elu_rows_fwd / dm_elu_rows_bwd /
+                                              dm_cat_image_loss_mix of the dense categorical image path */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
 size_t dm_workspace_bytes(const dm_shape* shp);   /* scratch needed by any call below for this shape */
@@ -325,6 +326,32 @@ int dm_cat_image_pred(int groups, int I, int C, int cells, const float* logits, 
 /* out (rows, F + E) = [ x[r][0..F) (leading dimension ldx) | extra[r / I][0..E) ]: torch.cat((features, insert_dim(map_coord, 2, I)), -1)
  * of probes.py:54-55. */
 int dm_cat_concat_rows(int rows, int I, int F, int E, const float* x, int ldx, const float* extra, float* out, void* stream);
+
+/* The dense categorical image path (csrc/dense_image.hip): image_encoder = image_decoder = 'dense' on a categorical image, the
+ * `minigrid` section of defaults.yaml.  DenseEncoder (encoders.py:99-125) is dm_dense_image_rows -> dm_mlp_head_fwd ->
+ * dm_elu_rows_fwd, CatImageDecoder (decoders.py:183-254) is dm_mlp_head_fwd -> dm_cat_image_loss(_mix) / dm_cat_image_pred.
+ * fp32 arithmetic, no float atomics (the same inputs give the same bits).  Checked on the host before any launch: a NULL
+ * required pointer -> DM_E_NULL; rows < 0, any other size < 1 or a leading dimension below the row width -> DM_E_SHAPE;
+ * rows == 0 -> DM_OK with nothing launched (as the dm_cat_image_ entries).
+ * The encoder's input rows (encoders.py:50-61 followed by nn.Flatten, encoders.py:106):
+ *   out[r] (leading dimension ldo) = [ image, class-major C*cells | reward[r] x cells | terminal[r] x cells ].
+ * Exactly one of image_f32 (rows, C, cells) and class_i32 (rows, cells) is non-null: a float image is copied as it is (a
+ * non-one-hot float image then gives the reference's result), a class map is expanded to 0/1 - a class outside [0, C) gives a
+ * zero column and reads nothing out of bounds.  reward and terminal (rows,) come together or not at all (reward_input,
+ * encoders.py:52-59); without them a row is C*cells wide.  Columns of `out` past the row width are not touched. */
+int dm_dense_image_rows(int rows, int C, int cells, const float* image_f32, const int32_t* class_i32, const float* reward,
+                        const float* terminal, float* out, int ldo, void* stream);
+/* The activation() behind DenseEncoder's last Linear (encoders.py:116-118; dm_mlp_head_fwd ends in a bare Linear):
+ * y = ELU(x) over (rows, n) with leading dimensions; dx = dy * ELU'(x) with the derivative taken from y (1 for y > 0, else
+ * y + 1).  In place is allowed (x == y, dy == dx). */
+int dm_elu_rows_fwd(int rows, int n, const float* x, int ldx, float* y, int ldy, void* stream);
+int dm_elu_rows_bwd(int rows, int n, const float* y, int ldy, const float* dy, int lddy, float* dx, int lddx, void* stream);
+/* CatImageDecoder.loss with 0 < min_prob < 1 (decoders.py:229-231): per cell s = softmax_c, p = (1 - m) s + m / C,
+ * loss[r] = -sum_cells log p_target; dlogits (rows, C*cells), optional: -(1 - m) s_t (delta_ct - s_c) / p_t, unscaled.
+ * logits, ld, target and I as in dm_cat_image_loss.  p_t >= m / C: loss and gradient stay finite when s_t underflows; a target
+ * outside [0, C) contributes -log(m / C) and a zero gradient.  min_prob == 0 is dm_cat_image_loss (DM_E_SHAPE here). */
+int dm_cat_image_loss_mix(int rows, int I, int C, int cells, const float* logits, int ld, const int32_t* target, float min_prob,
+                          float* loss, float* dlogits, void* stream);
 
 /* The goals probe's metrics (csrc/goals.hip; probes.py:113-135) over `rows` frames and G goals, one call, no host read:
  * goals, pred (rows, 2G) fp32 - coordinates (2g, 2g+1) belong to goal g, pred is the decoded mean already averaged over I;

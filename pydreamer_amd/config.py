@@ -37,6 +37,11 @@ SECTIONS = {
     # map keys below) are all available
     'miniworld': dict(action_dim=3, image_key='image', image_size=64, image_channels=3, image_categorical=False,
                       reward_input=True, probe_model='none', cnn_depth=32, map_key='map', map_size=9, map_channels=14),
+    # defaults.yaml:122-141, the keys the hot path reads: the dense categorical image path (models.dense_image_gate) with the
+    # map probe.  The class image reaches the model as replay.preprocess_batch(image_categorical=image_channels) makes it
+    'minigrid': dict(image_key='image', image_size=7, image_channels=4, image_categorical=True, map_key='map', map_size=11,
+                     map_channels=4, map_categorical=True, action_dim=7, reward_input=True, image_encoder='dense',
+                     image_encoder_layers=3, image_decoder='dense', image_decoder_layers=2, probe_model='map', imag_horizon=1),
     'minecraft': dict(action_dim=29, vecobs_size=27, clip_rewards='log1p'),      # defaults.yaml:244-248
     'debug': dict(device='cpu', batch_length=15, batch_size=5, imag_horizon=3),
 }

@@ -168,6 +168,10 @@ _SIGNATURES = {
     'dm_cat_image_loss': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P]),
     'dm_cat_image_pred': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P, _P]),
     'dm_cat_concat_rows': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P]),
+    'dm_dense_image_rows': (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P]),
+    'dm_elu_rows_fwd': (c_int, [c_int, c_int, _P, c_int, _P, c_int, _P]),
+    'dm_elu_rows_bwd': (c_int, [c_int, c_int, _P, c_int, _P, c_int, _P, c_int, _P]),
+    'dm_cat_image_loss_mix': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, c_float, _P, _P, _P]),
     'dm_goals_stats_ws_floats': (c_size_t, [c_int, c_int]),
     'dm_goals_stats': (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     'dm_preprocess_image_u8': (c_int, [c_int64, c_int, c_int, _P, _P, _P]),

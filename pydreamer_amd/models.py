@@ -9,7 +9,8 @@ reference (train.py:184-187).  There is no CPU path: tensors must live on a gfx9
 
 Supported configuration (everything else raises NotImplementedError): iwae_samples>=1 (also with the logging flags), gru_type in {gru, gru_layernorm,
 gru_layernorm_dv2}, gru_layers 1..4, stoch_discrete>0 or 0 (Gaussian latents, also with iwae_samples>1), layer_norm True or False,
-aux_critic, image_encoder/decoder='cnn' at 64x64, actor_dist in {onehot, tanh_normal, normal_tanh}, actor_grad='reinforce',
+aux_critic, image_encoder/decoder='cnn' at 64x64 or both 'dense' on a categorical image of at most 16x16 cells (the `minigrid`
+section; the gate is dense_image_gate()), actor_dist in {onehot, tanh_normal, normal_tanh}, actor_grad='reinforce',
 probe_model in {none, map, goals, map+goals} (map: the CatImageDecoder probe of the top-down map on the detached features, DESIGN
 4.8; goals: two DenseNormalDecoders of the goal directions with the metrics of csrc/goals.hip, DESIGN 4.9, needs goals_size >= 1;
 not with probe_gradients=True, whose gradient into the world model's features is not built), reward_input (cnn_depth in {8, 16, 32, 48, 64}: the reward and terminal planes are folded into the first
@@ -95,26 +96,28 @@ class MLP(_Params):
     """common.py:37-65: model = Sequential[Linear, LayerNorm | NoNorm, ELU]*L + [Linear] (+Flatten if out_dim==1).
     layer_norm=False: the norm slots are parameter-free (common.py:68-74) and the library gets null LayerNorm pointers."""
 
+    _base = 0          # Sequential index of the first Linear (DenseEncoder: 1, behind its nn.Flatten)
+
     def __init__(self, in_dim, out_dim, hidden_dim, hidden_layers, layer_norm=True):
         super().__init__()
         self.in_dim, self.out_dim, self.hidden_dim, self.hidden_layers = in_dim, out_dim, hidden_dim, hidden_layers
         self.layer_norm = bool(layer_norm)
-        layers, dim = [], in_dim
+        layers, dim = [_Slot()] * self._base, in_dim
         for _ in range(hidden_layers):
             layers += [LinearP(dim, hidden_dim), LayerNormP(hidden_dim) if layer_norm else _Slot(), _Slot()]
             dim = hidden_dim
         layers += [LinearP(dim, out_dim)]
-        if out_dim == 1:
+        if out_dim == 1 or self._base:      # nn.Flatten of a scalar head; DenseEncoder's trailing activation()
             layers += [_Slot()]
         self.model = nn.Sequential(*layers)
 
     # --- C-ABI marshalling
     def tensors(self):
-        L = self.hidden_layers
-        w = [self.model[3 * i].weight for i in range(L)] + [self.model[3 * L].weight]
-        b = [self.model[3 * i].bias for i in range(L)] + [self.model[3 * L].bias]
-        g = [self.model[3 * i + 1].weight for i in range(L)] if self.layer_norm else []
-        be = [self.model[3 * i + 1].bias for i in range(L)] if self.layer_norm else []
+        L, o = self.hidden_layers, self._base
+        w = [self.model[o + 3 * i].weight for i in range(L)] + [self.model[o + 3 * L].weight]
+        b = [self.model[o + 3 * i].bias for i in range(L)] + [self.model[o + 3 * L].bias]
+        g = [self.model[o + 3 * i + 1].weight for i in range(L)] if self.layer_norm else []
+        be = [self.model[o + 3 * i + 1].bias for i in range(L)] if self.layer_norm else []
         return w, b, g, be
 
     def param_list(self):
@@ -199,6 +202,59 @@ class ConvEncoder(_Params):
 
 
 VECOBS_EMBED = 256        # encoders.py:34
+DENSE_EMBED = 256         # encoders.py:25
+DENSE_IMAGE_MAX_SIZE = 16
+
+
+def dense_image_gate(conf):
+    """True when conf selects the dense categorical image path, False for the convolution path.  The path is built
+    for exactly one combination - every other use of 'dense' raises NotImplementedError naming what is outside:
+    image_encoder == image_decoder == 'dense' on a categorical image (image_categorical) of at most 16 x 16 cells and at least 2
+    classes, image_encoder_layers and image_decoder_layers in 1..DM_MAX_MLP_LAYERS - 1, no vecobs beside it, fp32 (amp off),
+    image_decoder_min_prob in [0, 1); reward_input, layer_norm and the probe are free."""
+    enc, dec = conf.image_encoder, conf.image_decoder
+    if enc != 'dense' and dec != 'dense':
+        return False
+    top = H.DM_MAX_MLP_LAYERS - 1
+    min_prob = float(getattr(conf, 'image_decoder_min_prob', 0) or 0)
+    checks = [
+        (enc == 'dense' and dec == 'dense', f'image_encoder={enc!r} with image_decoder={dec!r} (both must be dense)'),
+        (bool(getattr(conf, 'image_categorical', False)), 'image_categorical is off (the decoder is a per-cell cross-entropy)'),
+        (1 <= conf.image_size <= DENSE_IMAGE_MAX_SIZE, f'image_size={conf.image_size} (1..{DENSE_IMAGE_MAX_SIZE})'),
+        (conf.image_channels >= 2, f'image_channels={conf.image_channels} (>= 2 classes)'),
+        (1 <= conf.image_encoder_layers <= top, f'image_encoder_layers={conf.image_encoder_layers} (1..{top})'),
+        (1 <= conf.image_decoder_layers <= top, f'image_decoder_layers={conf.image_decoder_layers} (1..{top})'),
+        (not conf.vecobs_size, f'vecobs_size={conf.vecobs_size} (must be 0)'),
+        (not getattr(conf, 'amp', False), 'amp=True (the dense image path is fp32)'),
+        (0.0 <= min_prob < 1.0, f'image_decoder_min_prob={min_prob} (must lie in [0, 1))'),
+    ]
+    bad = [msg for ok, msg in checks if not ok]
+    if bad:
+        raise NotImplementedError("image_encoder / image_decoder = 'dense' is built for a categorical image only (both dense, "
+                                  f'image_categorical, image_size <= {DENSE_IMAGE_MAX_SIZE}, image_channels >= 2, 1..{top} layers '
+                                  'each, vecobs_size = 0, amp off, image_decoder_min_prob in [0, 1)); outside that gate: '
+                                  + '; '.join(bad))
+    return True
+
+
+class DenseEncoder(MLP):
+    """encoders.py:99-125: model = Sequential[Flatten, (Linear, LayerNorm | NoNorm, ELU) x L, Linear, ELU] - the Linears sit at
+    1, 4, ..., 3L + 1, one behind the indices of `MLP`.  The marshalling, forward and backward are MLP's; the trailing ELU is
+    dm_elu_rows_fwd / _bwd (WorldModel._dense_encode)."""
+    _base = 1
+
+    def __init__(self, in_dim, hidden_layers, layer_norm=True):
+        super().__init__(in_dim, DENSE_EMBED, MLP_HIDDEN, hidden_layers, layer_norm)
+
+
+class CatImageDecoder(MLP):
+    """decoders.py:183-254 with hidden_layers >= 1: model = Sequential[(Linear, LayerNorm | NoNorm, ELU) x L, Linear, Unflatten],
+    the index layout of `MLP`; the loss and the decoded image are the kernels of csrc/cat_image.hip and dm_cat_image_loss_mix."""
+
+    def __init__(self, in_dim, out_shape, hidden_layers, layer_norm=True, min_prob=0.0):
+        C, S1, S2 = (int(x) for x in out_shape)
+        super().__init__(in_dim, C * S1 * S2, MLP_HIDDEN, hidden_layers, layer_norm)
+        self.out_shape, self.min_prob = (C, S1, S2), float(min_prob or 0)
 REWARD_INPUT_DEPTHS = (8, 16, 32, 48, 64)     # the depths of the direct layer-1 kernels (csrc/conv_direct.hip dm_enc_l1_direct_ok)
 
 
@@ -207,9 +263,16 @@ class MultiEncoder(_Params):
 
     def __init__(self, conf):
         super().__init__()
-        if conf.image_encoder != 'cnn':
-            raise NotImplementedError('only image_encoder=cnn (with or without vecobs beside it) is built in the HIP path')
         self.reward_input = bool(conf.reward_input)
+        if dense_image_gate(conf):      # encoders.py:23-27: the flattened (C [+ 2], S, S) block through a DenseEncoder
+            self.encoder_image = DenseEncoder(conf.image_size ** 2 * (conf.image_channels + (2 if self.reward_input else 0)),
+                                              conf.image_encoder_layers, conf.layer_norm)
+            self.encoder_vecobs = None
+            self.out_dim = self.encoder_image.out_dim
+            return
+        if conf.image_encoder != 'cnn':
+            raise NotImplementedError("only image_encoder=cnn (with or without vecobs beside it) and the dense categorical image "
+                                      'path (dense_image_gate) are built in the HIP path')
         if self.reward_input and (conf.cnn_depth not in REWARD_INPUT_DEPTHS or conf.image_channels != 3):
             raise NotImplementedError(f'reward_input is built for 3-channel frames and cnn_depth in {REWARD_INPUT_DEPTHS} '
                                       f'(got image_channels={conf.image_channels}, cnn_depth={conf.cnn_depth})')
@@ -260,10 +323,16 @@ class MultiDecoder(_Params):
 
     def __init__(self, features_dim, conf):
         super().__init__()
-        if conf.image_decoder != 'cnn' or conf.reward_decoder_categorical:
-            raise NotImplementedError('only image_decoder=cnn with Normal reward decoder is built in the HIP path')
+        dense = dense_image_gate(conf)
+        if (conf.image_decoder != 'cnn' and not dense) or conf.reward_decoder_categorical:
+            raise NotImplementedError('only image_decoder=cnn (or the dense categorical image path, dense_image_gate) with Normal '
+                                      'reward decoder is built in the HIP path')
         self.image_weight, self.reward_weight, self.terminal_weight = conf.image_weight, conf.reward_weight, conf.terminal_weight
-        self.image = ConvDecoder(in_dim=features_dim, out_channels=conf.image_channels, cnn_depth=conf.cnn_depth)
+        if dense:      # decoders.py:23-28
+            self.image = CatImageDecoder(features_dim, (conf.image_channels, conf.image_size, conf.image_size),
+                                         conf.image_decoder_layers, conf.layer_norm, conf.image_decoder_min_prob)
+        else:
+            self.image = ConvDecoder(in_dim=features_dim, out_channels=conf.image_channels, cnn_depth=conf.cnn_depth)
         self.reward = DenseNormalDecoder(features_dim, conf.reward_decoder_layers, conf.layer_norm)
         self.terminal = DenseBernoulliDecoder(features_dim, conf.terminal_decoder_layers, conf.layer_norm)
         self.vecobs_weight = conf.vecobs_weight
@@ -911,7 +980,7 @@ class _WMStep(torch.autograd.Function):
             torch.cuda.current_stream().wait_stream(ov.s_wm)
         else:
             grads, flat, direct = wm._backward(pk, pk['ws'])
-        for k in ('enc_acts', 'rssm_acts', 'dec_acts', 'r_acts', 't_acts', 'aux', 'v_acts', 'ev_acts'):
+        for k in ('enc_acts', 'rssm_acts', 'dec_acts', 'r_acts', 't_acts', 'aux', 'v_acts', 'ev_acts', 'enc_x', 'dlogits'):
             pk.pop(k, None)                               # only now: the side stream may have been reading them
         pk['consumed'] = True
         return (None, None) + _finish_backward(wm, grads, flat, direct, grad_loss)
@@ -924,7 +993,8 @@ class WorldModel(_Params):
         super().__init__()
         if conf.aux_critic and conf.iwae_samples != 1:
             raise NotImplementedError('aux_critic assumes iwae_samples = 1 (as the reference does, dreamer.py:349)')
-        if conf.image_size != 64:
+        self.dense = dense_image_gate(conf)      # the dense categorical image path instead of the convolution stacks
+        if not self.dense and conf.image_size != 64:
             raise NotImplementedError('conv geometry is built for 64x64 observations')
         self.conf = conf
         self.deter_dim, self.stoch_dim, self.stoch_discrete = conf.deter_dim, conf.stoch_dim, conf.stoch_discrete
@@ -960,16 +1030,63 @@ class WorldModel(_Params):
         c = self.conf
         return H.make_shape(T=T, B=B, I=1, H=H_, D=c.deter_dim, Hd=c.hidden_dim, S=c.stoch_dim, C=c.stoch_discrete,
                             E=self.encoder.out_dim, A=c.action_dim, mlp_hidden=MLP_HIDDEN, mlp_layers=4,
-                            cnn_depth=c.cnn_depth, img=c.image_size, img_ch=c.image_channels,
+                            cnn_depth=1 if self.dense else c.cnn_depth,      # (dense: no convolution scratch in dm_workspace_bytes)
+                            img=c.image_size, img_ch=c.image_channels,
                             flags=ACTOR_KINDS.get(c.actor_dist, 0) | (H.GRU_KINDS[c.gru_type] << H.DM_FLAG_GRU_SHIFT) |
                             ((c.gru_layers - 1) << H.DM_FLAG_GRU_LAYERS_SHIFT) |
                             (H.DM_FLAG_BF16 if getattr(c, 'amp', False) else 0))
 
     def workspace(self, shp, device):
         need = H.workspace_bytes(shp)
+        if self.dense:      # the image MLPs may be deeper than the four layers dm_workspace_bytes sizes the heads for
+            deep = max(4, self.encoder.encoder_image.hidden_layers, self.decoder.image.hidden_layers)
+            need = max(need, 4 * int(H.lib().dm_mlp_ws_floats(shp.T * shp.B * max(shp.I, 1), MLP_HIDDEN, deep)))
         if self._ws is None or self._ws.numel() < need or self._ws.device != device:
             self._ws = torch.empty(need, dtype=torch.uint8, device=device)
         return self._ws
+
+    # ---- the dense categorical image path: DenseEncoder / CatImageDecoder beside the convolution stacks
+    def _dense_encode(self, image, plane_r, plane_t, embed, NE, ws, save):
+        """encoders.py:50-61,121-125: rows [image | reward plane | terminal plane] -> MLP -> ELU, written into `embed`.
+        `image`: float one-hot (T,B,C,S,S), copied as it is, or an int32 class map (T,B,S,S).  Returns (rows, activations)."""
+        c, enc = self.conf, self.encoder.encoder_image
+        onehot = image.is_floating_point()
+        x = torch.empty(NE, enc.in_dim, device=embed.device)
+        H.call('dm_dense_image_rows', NE, c.image_channels, c.image_size ** 2, H.fptr(image) if onehot else None,
+               None if onehot else H.ptr(image), H.fptr(plane_r), H.fptr(plane_t), H.fptr(x), enc.in_dim, H.stream())
+        pre, acts = enc.fwd(x, enc.in_dim, NE, ws, save_acts=save)
+        H.call('dm_elu_rows_fwd', NE, enc.out_dim, H.fptr(pre), enc.out_dim, H.fptr(embed), embed.shape[1], H.stream())
+        return x, acts
+
+    def _dense_target(self, image, NE):
+        """target.argmax(dim=-3) (decoders.py:221) of a float image; an integer class map is taken as it is."""
+        c = self.conf
+        cells = c.image_size ** 2
+        if not image.is_floating_point():
+            return image.view(NE, cells)
+        target = torch.empty(NE, cells, dtype=torch.int32, device=image.device)
+        H.call('dm_cat_target_index', NE, c.image_channels, cells, H.fptr(image), H.ptr(target), H.stream())
+        return target
+
+    def _dense_loss(self, logits, target, N, loss, dlogits):
+        """CatImageDecoder.loss (decoders.py:219-236) per row; min_prob = 0 is the map probe's kernel, bit for bit."""
+        c, dec = self.conf, self.decoder.image
+        C, cells = c.image_channels, c.image_size ** 2
+        if dec.min_prob == 0:
+            H.call('dm_cat_image_loss', N, 1, C, cells, H.fptr(logits), C * cells, H.ptr(target), H.fptr(loss), H.fptr(dlogits),
+                   H.stream())
+        else:
+            H.call('dm_cat_image_loss_mix', N, 1, C, cells, H.fptr(logits), C * cells, H.ptr(target), dec.min_prob, H.fptr(loss),
+                   H.fptr(dlogits), H.stream())
+
+    def _dense_logp(self, logits, target, NE):
+        """The decoded image (decoders.py:247-251 with I = 1): per-cell normalised log-probabilities (NE, C, cells)."""
+        c = self.conf
+        C, cells = c.image_channels, c.image_size ** 2
+        logp, acc = torch.empty(NE, C, cells, device=logits.device), torch.empty(NE, device=logits.device)
+        H.call('dm_cat_image_pred', NE, 1, C, cells, H.fptr(logits), C * cells, H.ptr(target), None, H.fptr(logp), H.fptr(acc), None,
+               H.stream())
+        return logp
 
     def forward(self, obs, in_state, u_post=None):
         """dreamer.py:289-295: features and out_state only (used by Dreamer.inference)."""
@@ -999,8 +1116,14 @@ class WorldModel(_Params):
         shp = self.shape(T, B, imag_horizon)
         shp.I = I
         ws = self.workspace(shp, dev)
-        u8 = image.dtype == torch.uint8
-        if u8:
+        u8 = image.dtype == torch.uint8 and not self.dense
+        if self.dense:
+            # the reference's float one-hot (T,B,C,S,S) (preprocessing.py:108-109) or an integer class map (T,B,S,S): same bits
+            if not image.is_floating_point() and image.dim() == 5:
+                raise ValueError(f'the dense image path takes a float one-hot (T,B,C,S,S) image or an integer class map (T,B,S,S), '
+                                 f'not a {image.dtype} frame of shape {tuple(image.shape)}')
+            image = image.float().contiguous() if image.is_floating_point() else image.to(torch.int32).contiguous()
+        elif u8:
             # the replay's native frames (T,B,H,W,C) uint8 are consumed AS THEY ARE: x/255-0.5 and HWC->CHW
             # (preprocessing.py:21-29) happen inside the first conv's patch loader and inside the MSE kernel
             # (dm_shape.flags bit DM_FLAG_IMAGE_U8); no float image is ever written
@@ -1016,6 +1139,8 @@ class WorldModel(_Params):
         # the C side sizes every access from dm_shape alone: check what the caller handed over before packing pointers
         want = dict(image=(T, B, c.image_size, c.image_size, c.image_channels) if u8 else
                     (T, B, c.image_channels, c.image_size, c.image_size), action=(T, B, c.action_dim), reset=(T, B))
+        if self.dense and not image.is_floating_point():
+            want['image'] = (T, B, c.image_size, c.image_size)
         got = dict(image=tuple(image.shape), action=tuple(action.shape), reset=tuple(reset.shape))
         planes = self.encoder.reward_input
         for k in ('reward', 'terminal'):
@@ -1054,8 +1179,10 @@ class WorldModel(_Params):
             shp_r.B, shp_r.I = BI, 1
 
         enc = self.encoder.encoder_image
-        enc_p = H.conv_struct([m.weight for m in enc.convs()], [m.bias for m in enc.convs()])
-        enc_acts = torch.empty(int(lib.dm_conv_encoder_acts_floats(ctypes.byref(shp_e))), device=dev)
+        enc_p = enc_acts = None
+        if not self.dense:
+            enc_p = H.conv_struct([m.weight for m in enc.convs()], [m.bias for m in enc.convs()])
+            enc_acts = torch.empty(int(lib.dm_conv_encoder_acts_floats(ctypes.byref(shp_e))), device=dev)
         embed = torch.empty(NE, E, device=dev)
         cell = self.core.cell
         rssm_p = H.rssm_struct(cell.ordered())
@@ -1078,10 +1205,13 @@ class WorldModel(_Params):
         fidx = forced_idx.to(torch.int32).contiguous() if forced_idx is not None else None
         u_ptr = H.fptr(u_post) if u_post is not None else None
         dec = self.decoder
-        dl = dec.image.layers()
-        dec_p = H.conv_struct([m.weight for m in dl], [m.bias for m in dl])
+        dec_p = dec_acts = None
+        if not self.dense:
+            dl = dec.image.layers()
+            dec_p = H.conv_struct([m.weight for m in dl], [m.bias for m in dl])
         if not forward_only:
-            dec_acts = torch.empty(int(lib.dm_conv_decoder_acts_floats(ctypes.byref(shp))), device=dev)
+            if not self.dense:
+                dec_acts = torch.empty(int(lib.dm_conv_decoder_acts_floats(ctypes.byref(shp))), device=dev)
             loss_image = torch.empty(N, device=dev)
             image_rec = None          # materialised lazily from the decoder's saved prediction (see LazyTensors)
 
@@ -1098,7 +1228,11 @@ class WorldModel(_Params):
         if planes:      # encoders.py:52-59: per-frame constants, (T,B) -> (N,); never expanded to image planes
             plane_r = obs['reward'].float().contiguous().view(NE)
             plane_t = obs['terminal'].float().contiguous().view(NE)
-        if planes or V:
+        enc_x = None
+        if self.dense:
+            enc_x, enc_acts = self._dense_encode(image, plane_r, plane_t, embed, NE, ws,
+                                                 save=not forward_only and torch.is_grad_enabled())
+        elif planes or V:
             # the image embedding is written as the leading E - 256 columns of the (NE, E) buffer (leading dimension E), the
             # vecobs embedding behind it: one buffer for the RSSM, no copy pass over the image embedding
             shp_c = H.dm_shape.from_buffer_copy(shp_e)
@@ -1125,7 +1259,7 @@ class WorldModel(_Params):
         out_state = (last[:, :D_].clone(), last[:, D_:].clone())                  # detached by construction (rssm.py:77)
         pk = dict(shp=shp, shp_e=shp_e, shp_r=shp_r, T=T, B=B, I=I, feat=feat, post=post, prior=prior, idx=idx,
                   out_state=out_state, embed=embed, embed_x=embed_x, action_x=action_x, reset_x=reset_x,
-                  plane_r=plane_r, plane_t=plane_t, vecobs=vecobs, ev_acts=ev_acts)
+                  plane_r=plane_r, plane_t=plane_t, vecobs=vecobs, ev_acts=ev_acts, enc_x=enc_x)
         if forward_only:
             return pk
         # The tail of the world-model forward - decoder + MSE, reward / terminal heads, KL, the loss sums (dreamer.py:311-365) -
@@ -1154,8 +1288,19 @@ class WorldModel(_Params):
         D_, F_ = c.deter_dim, self.features_dim
         gauss = not c.stoch_discrete
         Z = c.stoch_dim * (c.stoch_discrete or 1)
-        H.call('dm_conv_decoder_mse_fwd', ctypes.byref(shp), H.fptr(feat), F_, H.ptr(image), ctypes.byref(dec_p),
-               H.fptr(dec_acts), H.fptr(loss_image), None, H.ptr(ws), ws.numel(), H.stream())
+        if self.dense:      # CatImageDecoder.training_step (decoders.py:238-254): MLP -> per-cell cross-entropy, I = 1
+            train = torch.is_grad_enabled()
+            target = pk['target'] = self._dense_target(image, NE)
+            logits, dec_acts = dec.image.fwd(feat, F_, N, ws, save_acts=train)
+            dlogits = torch.empty_like(logits) if train else None
+            self._dense_loss(logits, target, N, loss_image, dlogits)
+            if train:      # d loss_model / d loss_image[r] = image_weight / (T*B), times the data-parallel shard weight
+                scale = torch.full((1,), float(getattr(self, 'grad_weight', 1.0)) * dec.image_weight / NE, device=dev)
+                H.call('dm_scale_inplace', H.fptr(dlogits), dlogits.numel(), H.fptr(scale), H.stream())
+            pk.update(dec_logits=logits, dlogits=dlogits)
+        else:
+            H.call('dm_conv_decoder_mse_fwd', ctypes.byref(shp), H.fptr(feat), F_, H.ptr(image), ctypes.byref(dec_p),
+                   H.fptr(dec_acts), H.fptr(loss_image), None, H.ptr(ws), ws.numel(), H.stream())
 
         reward_t = obs['reward'].float().contiguous()
         terminal_t = obs['terminal'].float().contiguous()
@@ -1285,13 +1430,18 @@ class WorldModel(_Params):
                                     loss_reward=t_lr, reward_rec=t_rr,
                                     loss_terminal=t_lt, terminal_rec=t_tr)
         Cc, hw = c.image_channels, c.image_size * c.image_size
-        pred_off = int(lib.dm_conv_decoder_pred_offset(ctypes.byref(shp)))
+        if self.dense:
+            def image_rec_thunk(logits=pk['dec_logits'], target=pk['target']):      # holds the logits alive until the dict is dropped
+                with torch.no_grad():
+                    return self._dense_logp(logits, target, NE).view(T, B, Cc, c.image_size, c.image_size)
+        else:
+            pred_off = int(lib.dm_conv_decoder_pred_offset(ctypes.byref(shp)))
 
-        def image_rec_thunk(acts=dec_acts):       # holds the decoder activations alive until the dict is dropped
-            with torch.no_grad():
-                pred = acts[pred_off:pred_off + N * hw * Cc].view(N, hw, Cc)                       # NHWC
-                rec = pred.transpose(1, 2).contiguous().view(T, B, I, Cc, c.image_size, c.image_size)   # -> (T,B,I,C,H,W)
-                return rec[:, :, 0] if I == 1 else rec.mean(2)       # decoded.mean(dim=2), decoders.py:171 (logging only)
+            def image_rec_thunk(acts=dec_acts):       # holds the decoder activations alive until the dict is dropped
+                with torch.no_grad():
+                    pred = acts[pred_off:pred_off + N * hw * Cc].view(N, hw, Cc)                       # NHWC
+                    rec = pred.transpose(1, 2).contiguous().view(T, B, I, Cc, c.image_size, c.image_size)   # -> (T,B,I,C,H,W)
+                    return rec[:, :, 0] if I == 1 else rec.mean(2)       # decoded.mean(dim=2), decoders.py:171 (logging only)
         pk['tensors'].lazy('image_rec', image_rec_thunk)
         pk['metrics'] = dict(loss_model=mbuf[6], loss_kl=means[0], entropy_prior=means[4], entropy_post=means[5],
                              loss_image=means[1], loss_reward=means[2], loss_terminal=means[3])
@@ -1332,14 +1482,17 @@ class WorldModel(_Params):
             heads.append((dec.vecobs.model, pk['v_acts'], pk['dmu_v']))
         if pk.get('aux') is not None:          # the auxiliary critic trains on the world model's own features (not detached)
             heads.append((self.ac_aux.critic, pk['aux']['acts'], pk['aux']['dvalue']))
+        if self.dense:                         # the image decoder is one more dense head: its dx accumulates into dfeat
+            heads.append((dec.image, pk['dec_acts'], pk['dlogits']))
         for head, acts, dout in heads:
             st, gs = head.struct(), head.grad_struct(gof)
             H.call('dm_mlp_head_bwd', N, F_, head.hidden_dim, head.hidden_layers, head.out_dim, H.fptr(feat), F_, ctypes.byref(st),
                    H.fptr(acts), H.fptr(dout), ctypes.byref(gs), H.fptr(dfeat), F_, 1, H.ptr(ws), ws.numel(), H.stream())
         # image decoder
-        dl = dec.image.layers()
-        dec_p = H.conv_struct([m.weight for m in dl], [m.bias for m in dl])
-        dec_g = H.conv_struct([gof[id(m.weight)] for m in dl], [gof[id(m.bias)] for m in dl], cls=H.dm_conv_grads)
+        if not self.dense:
+            dl = dec.image.layers()
+            dec_p = H.conv_struct([m.weight for m in dl], [m.bias for m in dl])
+            dec_g = H.conv_struct([gof[id(m.weight)] for m in dl], [gof[id(m.bias)] for m in dl], cls=H.dm_conv_grads)
         # Parameter gradients are leaves: nothing waits for them before the gradient clip, while the DATA gradients are the
         # chain decoder -> BPTT -> encoder.  Armed, the library enqueues the decoder's and the RSSM's parameter gradients on its
         # low-priority side stream, where they run beside the BPTT loop (a 50-row latency chain that leaves most CUs idle); they
@@ -1348,7 +1501,7 @@ class WorldModel(_Params):
         # (measured: no gain on a 7-column shard, -1.1 ms at 25 columns.  Rounds 3-5 switched it off under data parallelism, unmeasured;
         #  round 6 measured it over a one-rank RCCL group: off costs +0.9 ... +1.2 ms at 25 / 50 columns, on costs nothing beside the
         #  all-reduce - profiles/r06_force_dp.txt run K: it stays on there.)
-        side = defer_wgrad and _WGRAD_SIDE and B * I >= 16 and not torch.cuda.is_current_stream_capturing()
+        side = defer_wgrad and _WGRAD_SIDE and B * I >= 16 and not torch.cuda.is_current_stream_capturing() and not self.dense
         ws_dec = ws_enc = ws
         if side:
             need = H.workspace_bytes(shp)
@@ -1358,9 +1511,10 @@ class WorldModel(_Params):
             ws_dec, ws_enc = self._ws_dec, self._ws_enc       # decoder / BPTT (`ws`) / encoder: one workspace each until the join
             H.call('dm_wgrad_side_arm', 1)
         try:
-            H.call('dm_conv_decoder_mse_bwd_rows', ctypes.byref(shp), H.fptr(feat), F_, H.ptr(pk['image']), ctypes.byref(dec_p),
-                   H.fptr(pk['dec_acts']), gw * dec.image_weight / NE, H.fptr(iw), ctypes.byref(dec_g), H.fptr(dfeat), F_,
-                   H.ptr(ws_dec), ws_dec.numel(), H.stream())
+            if not self.dense:
+                H.call('dm_conv_decoder_mse_bwd_rows', ctypes.byref(shp), H.fptr(feat), F_, H.ptr(pk['image']), ctypes.byref(dec_p),
+                       H.fptr(pk['dec_acts']), gw * dec.image_weight / NE, H.fptr(iw), ctypes.byref(dec_g), H.fptr(dfeat), F_,
+                       H.ptr(ws_dec), ws_dec.numel(), H.stream())
             # KL (dreamer.py:334-343)
             dpost = torch.empty(N, Z, device=dev)
             dprior = torch.empty(N, Z, device=dev)
@@ -1394,6 +1548,13 @@ class WorldModel(_Params):
                 dembed = dsum
             # encoder
             enc = self.encoder.encoder_image
+            if self.dense:      # through the trailing ELU (derivative from embed = ELU(pre), in place), then the MLP; no input gradient
+                H.call('dm_elu_rows_bwd', NE, E, H.fptr(pk['embed']), E, H.fptr(dembed), E, H.fptr(dembed), E, H.stream())
+                st, gs = enc.struct(), enc.grad_struct(gof)
+                H.call('dm_mlp_head_bwd', NE, enc.in_dim, enc.hidden_dim, enc.hidden_layers, enc.out_dim, H.fptr(pk['enc_x']),
+                       enc.in_dim, ctypes.byref(st), H.fptr(pk['enc_acts']), H.fptr(dembed), ctypes.byref(gs), None, 0, 0,
+                       H.ptr(ws_enc), ws_enc.numel(), H.stream())
+                return views, flat, direct
             enc_p = H.conv_struct([m.weight for m in enc.convs()], [m.bias for m in enc.convs()])
             enc_g = H.conv_struct([gof[id(m.weight)] for m in enc.convs()], [gof[id(m.bias)] for m in enc.convs()],
                                   cls=H.dm_conv_grads)
@@ -1442,13 +1603,18 @@ class WorldModel(_Params):
             idx = torch.empty(N, S, dtype=torch.int32, device=dev)
             H.call('dm_sample_onehot', N, S, C, H.fptr(pk['prior']), S * (C or 2), H.fptr(u_pred), None,
                    ctypes.c_void_p(fp.data_ptr() + 4 * D_), F_, H.ptr(idx), H.stream())
-            dl = dec.image.layers()
-            dec_p = H.conv_struct([m.weight for m in dl], [m.bias for m in dl])
-            acts = torch.empty(int(lib.dm_conv_decoder_acts_floats(ctypes.byref(shp))), device=dev)
             li = torch.empty(N, device=dev)
-            image_pred = torch.empty(T, B, I, c.image_channels, c.image_size, c.image_size, device=dev)
-            H.call('dm_conv_decoder_mse_fwd', ctypes.byref(shp), H.fptr(fp), F_, H.ptr(pk['image']), ctypes.byref(dec_p),
-                   H.fptr(acts), H.fptr(li), H.fptr(image_pred), H.ptr(ws), ws.numel(), H.stream())
+            if self.dense:      # loss and normalised log-probabilities of the decoder on the prior-sample features (I = 1)
+                logits, _ = dec.image.fwd(fp, F_, N, ws, save_acts=False)
+                self._dense_loss(logits, pk['target'], N, li, None)
+                image_pred = self._dense_logp(logits, pk['target'], NE).view(T, B, I, c.image_channels, c.image_size, c.image_size)
+            else:
+                dl = dec.image.layers()
+                dec_p = H.conv_struct([m.weight for m in dl], [m.bias for m in dl])
+                acts = torch.empty(int(lib.dm_conv_decoder_acts_floats(ctypes.byref(shp))), device=dev)
+                image_pred = torch.empty(T, B, I, c.image_channels, c.image_size, c.image_size, device=dev)
+                H.call('dm_conv_decoder_mse_fwd', ctypes.byref(shp), H.fptr(fp), F_, H.ptr(pk['image']), ctypes.byref(dec_p),
+                       H.fptr(acts), H.fptr(li), H.fptr(image_pred), H.ptr(ws), ws.numel(), H.stream())
             mu, _ = dec.reward.model.fwd(fp, F_, N, ws, save_acts=False)
             tl, _ = dec.terminal.model.fwd(fp, F_, N, ws, save_acts=False)
             lr, lt, rp, tp, scratch = (torch.empty(N, device=dev) for _ in range(5))
@@ -1501,6 +1667,8 @@ class WorldModel(_Params):
                       u_post=None, forced_idx=None, imag_horizon=1, u_pred=None, mbuf=None, _tail=None):
         """dreamer.py:297-396. Returns (loss, features (T,B,1,F), states, out_state, metrics, tensors)."""
         I = int(iwae_samples)
+        if self.dense and I > 1:
+            raise NotImplementedError('iwae_samples > 1 is not built on the dense image path (DESIGN 4.11)')
         if do_open_loop and torch.is_grad_enabled():
             raise NotImplementedError('do_open_loop is an evaluation variant: call it under torch.no_grad() like '
                                       'train.py:353-359 does (its backward is not built)')
@@ -2018,6 +2186,8 @@ class Dreamer(nn.Module):
             assert k in obs, f'`{k}` required in observation'
         iwae_samples = int(iwae_samples or self.iwae_samples)
         imag_horizon = int(imag_horizon or self.imag_horizon)
+        if self.wm.dense and iwae_samples > 1:      # before anything is allocated or launched
+            raise NotImplementedError('iwae_samples > 1 is not built on the dense image path (DESIGN 4.11)')
         T, B = obs['action'].shape[:2]
         noise = noise or {}
         I = iwae_samples
@@ -2128,14 +2298,18 @@ class Dreamer(nn.Module):
                 f2, a2, r2, t2 = self._dream_from_features(
                     pk['feat'][:B * I:I].contiguous(), T - 1,
                     noise.get('u_act_log') if kind == 0 else noise.get('eps_act_log'), noise.get('u_prior_log'), _pack=dpk2)
-                dl = self.wm.decoder.image.layers()
-                dec_p = H.conv_struct([m.weight for m in dl], [m.bias for m in dl])
                 shp, dev = pk['shp_e'], pk['feat'].device          # (T,B,1): the log dream has one row per (step, column)
-                acts = torch.empty(int(H.lib().dm_conv_decoder_acts_floats(ctypes.byref(shp))), device=dev)
-                image_dream = torch.empty(T, B, self.conf.image_channels, self.conf.image_size, self.conf.image_size, device=dev)
                 ws = self.wm.workspace(shp, dev)
-                H.call('dm_conv_decoder_mse_fwd', ctypes.byref(shp), H.fptr(f2), self.wm.features_dim, H.ptr(pk['image']),
-                       ctypes.byref(dec_p), H.fptr(acts), None, H.fptr(image_dream), H.ptr(ws), ws.numel(), H.stream())
+                if self.wm.dense:      # decoder.image.forward (dreamer.py:171): the raw logits, not normalised
+                    image_dream, _ = self.wm.decoder.image.fwd(f2.view(T * B, -1), self.wm.features_dim, T * B, ws, save_acts=False)
+                    image_dream = image_dream.view(T, B, self.conf.image_channels, self.conf.image_size, self.conf.image_size)
+                else:
+                    dl = self.wm.decoder.image.layers()
+                    dec_p = H.conv_struct([m.weight for m in dl], [m.bias for m in dl])
+                    acts = torch.empty(int(H.lib().dm_conv_decoder_acts_floats(ctypes.byref(shp))), device=dev)
+                    image_dream = torch.empty(T, B, self.conf.image_channels, self.conf.image_size, self.conf.image_size, device=dev)
+                    H.call('dm_conv_decoder_mse_fwd', ctypes.byref(shp), H.fptr(f2), self.wm.features_dim, H.ptr(pk['image']),
+                           ctypes.byref(dec_p), H.fptr(acts), None, H.fptr(image_dream), H.ptr(ws), ws.numel(), H.stream())
                 _, _, t_ac2 = self.ac.training_step(f2, a2, r2.mean, t2.mean, log_only=True, act_idx=dpk2['act_idx'],
                                                     ws=dpk2['ws'], actor_acts=dpk2['actor_acts'],
                                                     actor_logits=dpk2['actor_logits'], values=dpk2['values'])
@@ -2149,7 +2323,7 @@ class Dreamer(nn.Module):
             # ... and ALLOCATED from that stream's pool: what leaves training_step() is read on the caller's stream from here on, so the
             # caching allocator must not hand such a block to the next s_wm allocation while a caller-stream read is still queued
             # (the actor-critic outputs are guarded the same way)
-            leaving = [loss_model, pk.get('dec_acts')] + [v for v in dict.values(pk['tensors']) if torch.is_tensor(v)]
+            leaving = [loss_model, pk.get('dec_acts'), pk.get('dec_logits'), pk.get('target')] + [v for v in dict.values(pk['tensors']) if torch.is_tensor(v)]
             for t in leaving:
                 if torch.is_tensor(t) and t.is_cuda:
                     t.record_stream(cur)

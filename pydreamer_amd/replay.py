@@ -287,8 +287,11 @@ class SequentialReplay:
 GOAL_SOURCES = ('targets_vec', 'target_vec')      # the files' fields behind goals_direction / goal_direction
 
 
-def preprocess_batch(batch, action_dim, clip_rewards=None, image_key='image', map_key=None, map_categorical=None, goals=False):
+def preprocess_batch(batch, action_dim, clip_rewards=None, image_key='image', map_key=None, map_categorical=None, goals=False,
+                     image_categorical=None):
     """Hot-path subset of Preprocessor.apply (preprocessing.py:87-180), images left uint8 (T,B,H,W,C).
+    image_categorical = C (preprocessing.py:108-109; the input of the dense categorical image path, models.dense_image_gate):
+    `image` = the integer class image (T,B,H,W) as a one-hot (T,B,C,H,W) float32.  With the default the frames stay uint8.
     map_key / map_categorical (preprocessing.py:115-131,152-158; the inputs of the map probe, models.MapProbeHead): `map` =
     batch[map_key] as a one-hot (T,B,C,H,W) float32 with C = map_categorical, or - not categorical - a float image of that
     layout; `map_seen_mask` from `map_seen` or `map_vis`; `map_coord` (T,B,4) from `agent_pos`, `agent_dir` and the map's
@@ -300,8 +303,12 @@ def preprocess_batch(batch, action_dim, clip_rewards=None, image_key='image', ma
     T, B = batch['reward'].shape[:2]
     out = {}
     img = batch[image_key]
-    assert img.dtype == np.uint8 and img.ndim == 5, f'expected uint8 (T,B,H,W,C) frames, got {img.dtype} {img.shape}'
-    out['image'] = np.ascontiguousarray(img)
+    if image_categorical:                                    # img_to_onehot (preprocessing.py:15-18)
+        assert img.ndim == 4, f'expected a (T,B,H,W) class image under {image_key!r}, got {img.shape}'
+        out['image'] = np.ascontiguousarray(np.eye(int(image_categorical), dtype=np.float32)[img].transpose(0, 1, 4, 2, 3))
+    else:
+        assert img.dtype == np.uint8 and img.ndim == 5, f'expected uint8 (T,B,H,W,C) frames, got {img.dtype} {img.shape}'
+        out['image'] = np.ascontiguousarray(img)
     for k in ('action', 'action_next'):
         if k in batch:
             a = batch[k]
