@@ -92,7 +92,7 @@ int dm_version(void);                 /* ABI version, currently 16 (v2: LayerNor
                                               of the map probe; dm_replay_gather of the device-resident replay; dm_goals_stats /
                                               dm_goals_stats_ws_floats of the goals probe; the dm_gru_sequence_ family of the
                                               gru_probe baseline; dm_dense_image_rows / dm_elu_rows_fwd / dm_elu_rows_bwd /
-                                              dm_cat_image_loss_mix of the dense categorical image path */
+                                              dm_cat_image_loss_mix of the dense categorical image path; dm_convt_kskip_enable */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
 size_t dm_workspace_bytes(const dm_shape* shp);   /* scratch needed by any call below for this shape */
@@ -145,6 +145,13 @@ int dm_bf16_twins_enable(int on);
  * work item up, the register-staged loop (higher residency) below.  1 / 0 switches it on / off, 2 = on for every k extent (the
  * bit-identity test), -1 queries; returns the state (default 1). */
 int dm_gemm_dma_enable(int on);
+/* The gather-form transposed convolutions (decoder layer 3 forward, the encoder's data gradients; csrc/conv.hip) are one product
+ * over the (hs + k/2 - 1)^2 class pixels of a frame, whose patches reach into a zero border.  In fp32 mode the rows of that
+ * product are enumerated (chunk of 128 frames, yy, xx, frame in chunk), so that a row tile lies inside one class pixel, and the
+ * tile loops walk a per-tile list of the 32-k tiles that hold a valid tap instead of all of them.  The terms left out are 0 * w:
+ * same bits for finite weights.  1 / 0 switches it on / off (off: rows ordered (frame, yy, xx), every k-tile), -1 queries;
+ * returns the state (default 1).  bf16-mode calls are not affected. */
+int dm_convt_kskip_enable(int on);
 /* The image layer of the decoder (ConvTranspose2d(d -> 3, k6, s2), decoders.py:154-155) runs its backward - data gradient with
  * the ELU' of the layer below folded in, weight gradient - as two direct MFMA kernels that read the 3-channel output gradient
  * of a frame from LDS (csrc/conv_direct.hip) instead of as gather-form products through the generic tile (3 -> 4 channel pad, 48

@@ -150,6 +150,12 @@ struct DmGemm {
   const unsigned short* B_h = nullptr;
   unsigned short* C_h = nullptr;
   bool no_twin = false;                           // do not write the result's twin even if the call's twin map has room for it
+  // k-tile lists (fp32 tile loops, scatter-epilogue products only; conv.hip convt_tables_kernel): rows [b * k_list_rows,
+  // (b+1) * k_list_rows) walk only the 32-k tiles k_list[b * k_list_stride + 1 ..], k_list[b * k_list_stride] of them, in
+  // ascending order - every tile left out multiplies zeros for all of those rows.  Such a product is not split in K and takes
+  // a tile whose BM divides k_list_rows.  The bf16 loops ignore the list.
+  const int* k_list = nullptr; int k_list_rows = 0, k_list_stride = 0;
+  double k_list_mean = 0.0;                       // mean tile count of a list: what the tile choice costs the product with
 };
 // Fragment-major layout of a <= 64-row block X[row][k]: the 16 B a lane of v_mfma_f32_16x16x4_f32 loads for a 16-k chunk
 // (lane l: row 16*mb + (l&15), k = 16*c + 4*(l>>4) .. +3) sit at ((c*4 + mb)*4 + (l>>4))*16 + (l&15) in units of 16 B, so

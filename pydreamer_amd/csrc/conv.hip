@@ -233,7 +233,26 @@ static int conv_tables_launch(int n, int hb, int wb, int c, int k, int* rowoff, 
 //   M = n*Hc*Wc class pixels (Hc = hs + k/2 - 1),  K = (k/2)^2 * cin (gathered from a zero-padded copy of X),
 //   N = 4*cout (the four classes side by side), result scattered straight into the NHWC big image (gemm.hip SC epilogue).
 // vs. the column-matrix form: no Ycol write + col2im read (2 x 2.9 GB for decoder layer 3 at Atari-literal), at the price
-// of (Hc/hs)^2 more MACs (the zero border is multiplied too: 1.33x for 13 -> 30).
+// of (Hc/hs)^2 more MACs where the zero border is multiplied too (1.33x for 13 -> 30).
+// Not multiplying it (fp32 products, dm_convt_kskip_enable): a class pixel (yy, xx) has tap (a, b) inside the input iff
+// 0 <= yy-a < hs and 0 <= xx-b < ws - between one and k/2 taps per dimension - and the reduction index is (a, b, i), so an
+// invalid tap is a run of cin zeros in the patch.  Rows are therefore enumerated frame-chunk-major, (chunk of CONVT_G frames,
+// yy, xx, frame in chunk): a 64- or 128-row tile of the product then lies inside ONE class pixel, consecutive tiles walk
+// neighbouring pixels of the same frames (their overlapping patches meet in L2), and the table launch writes, per block of
+// CONVT_G rows, the ascending list of the 32-k tiles that hold at least one tap valid for some row of the block
+// (DmGemm::k_list).  The tile loops walk that list instead of every tile.  The terms left out are 0 * w and the terms kept are
+// added in the same order, so the result has the same bits for every finite weight (a non-finite weight would turn 0 * w into
+// NaN; such a run is broken already, the border contributes nothing by definition, and the skipped form is the right one).
+// The zero-padded copy stays: a kept tile may still hold invalid taps (cin not a multiple of 32, the short last chunk whose
+// blocks straddle pixels), so the list only has to be a superset and correctness never depends on its being tight.
+constexpr int CONVT_G = 128;
+static int g_convt_kskip = 1;
+// 1 / 0: the chunk-major row order with k-tile lists / the (frame, yy, xx) order with every tile, -1: query.  Returns the state.
+extern "C" int dm_convt_kskip_enable(int on) {
+  if (on >= 0) g_convt_kskip = on ? 1 : 0;
+  return g_convt_kskip;
+}
+static inline size_t convt_klist_ints(size_t rows, int kdim) { return (size_t)dm_cdiv((int64_t)rows, CONVT_G) * (dm_cdiv(kdim, 32) + 1); }
 __global__ void __launch_bounds__(256) convt_pad_kernel(int n, int hs, int ws, int c4, int P, const float4* __restrict__ x,
                                                         float4* __restrict__ xp) {
   const int hp = hs + 2 * P, wp = ws + 2 * P;
@@ -265,23 +284,78 @@ __global__ void __launch_bounds__(256) convt_pad_h_kernel(int n, int hs, int ws,
 }
 // rowoff[(n,yy,xx)] = offset of padded pixel (yy+P, xx+P);  koff[(a,b,i)] = -(a*wp + b)*cin + i;
 // ctab[(n,yy,xx)] = {offset of big[n, 2yy, 2xx, 0], bit 1: 2yy+1 < hb, bit 0: 2xx+1 < wb}
+// Row e of the product: G == 0: (frame, yy, xx); G > 0: (chunk of G frames, yy, xx, frame in chunk), the last chunk possibly
+// short (no padded rows).  Both tables are indexed by e, and they are all the product knows about its rows.
+__device__ __forceinline__ void convt_row_of(int e, int n, int Hc, int Wc, int G, int* i, int* pix) {
+  if (G == 0) { *i = e / (Wc * Hc); *pix = e - *i * (Wc * Hc); return; }
+  const int per = G * Hc * Wc;
+  const int c = e / per, r = e - c * per;
+  const int gl = min(G, n - c * G);
+  *pix = r / gl;
+  *i = c * G + (r - *pix * gl);
+}
+// klist (G > 0): for block j of G rows, klist[j * (nkt + 1)] = count and then the ascending indices of the 32-k tiles that hold a
+// tap (a, b) with 0 <= yy-a < hs and 0 <= xx-b < ws for some row of the block.  A block lies inside one chunk (a full chunk is
+// a multiple of G rows), so its rows are a run of pixels in raster order: the rows yy0..yy1 and, when the run stays in one
+// pixel row, the columns xx0..xx1 (all columns otherwise) bound the valid taps per dimension - a superset, tight when the
+// block is one pixel.
 __global__ void __launch_bounds__(256) convt_tables_kernel(int n, int hs, int ws, int cin, int ta, int hb, int wb, int cout,
                                                            int* __restrict__ rowoff, int* __restrict__ koff,
-                                                           int2* __restrict__ ctab) {
+                                                           int2* __restrict__ ctab, int G, int* __restrict__ klist) {
   const int P = ta - 1, hp = hs + 2 * P, wp = ws + 2 * P;
   const int Hc = hs + ta - 1, Wc = ws + ta - 1;
   const int rows = n * Hc * Wc, kdim = ta * ta * cin;
-  for (int e = blockIdx.x * 256 + threadIdx.x; e < rows + kdim; e += gridDim.x * 256) {
+  const int nkt = (kdim + 31) / 32, nblk = G > 0 ? (rows + G - 1) / G : 0;
+  for (int e = blockIdx.x * 256 + threadIdx.x; e < rows + kdim + nblk; e += gridDim.x * 256) {
     if (e < rows) {
-      const int xx = e % Wc, yy = (e / Wc) % Hc, i = e / (Wc * Hc);
+      int i, pix;
+      convt_row_of(e, n, Hc, Wc, G, &i, &pix);
+      const int xx = pix % Wc, yy = pix / Wc;
       rowoff[e] = ((i * hp + yy + P) * wp + xx + P) * cin;
       ctab[e] = make_int2(((i * hb + 2 * yy) * wb + 2 * xx) * cout, ((2 * yy + 1 < hb) ? 2 : 0) | ((2 * xx + 1 < wb) ? 1 : 0));
-    } else {
+    } else if (e < rows + kdim) {
       const int q = e - rows;
       const int ci = q % cin, b = (q / cin) % ta, a = q / (cin * ta);
       koff[q] = -(a * wp + b) * cin + ci;
+    } else {
+      const int j = e - rows - kdim;
+      int i0, p0, i1, p1;
+      convt_row_of(j * G, n, Hc, Wc, G, &i0, &p0);
+      convt_row_of(min(rows, (j + 1) * G) - 1, n, Hc, Wc, G, &i1, &p1);
+      const int y0 = p0 / Wc, y1 = p1 / Wc;
+      const int x0 = y0 == y1 ? p0 % Wc : 0, x1 = y0 == y1 ? p1 % Wc : Wc - 1;
+      int* kl = klist + (size_t)j * (nkt + 1);
+      int cnt = 0;
+      for (int t = 0; t < nkt; ++t) {
+        const int q0 = (32 * t) / cin, q1 = min(32 * t + 31, kdim - 1) / cin;
+        bool keep = false;
+        for (int q = q0; q <= q1; ++q) {
+          const int a = q / ta, b = q % ta;
+          keep = keep || (a <= y1 && y0 <= hs - 1 + a && b <= x1 && x0 <= ws - 1 + b);
+        }
+        if (keep) kl[1 + cnt++] = t;
+      }
+      kl[0] = cnt;
     }
   }
+}
+// One launch of the tables (and, with klist, of the chunk-major order and the k-tile lists)
+static int convt_tables_launch(int n, int hs, int cin, int ta, int hb, int cout, int* rowoff, int* koff, int2* ctab, int* klist,
+                               hipStream_t st) {
+  const int Hc = hs + ta - 1, kdim = ta * ta * cin;
+  const size_t total = (size_t)n * Hc * Hc + kdim + (klist ? (size_t)dm_cdiv((int64_t)n * Hc * Hc, CONVT_G) : 0);
+  hipLaunchKernelGGL(convt_tables_kernel, dim3(grid_for(total)), dim3(256), 0, st, n, hs, hs, cin, ta, hb, hb, cout, rowoff, koff,
+                     ctab, klist ? CONVT_G : 0, klist);
+  DM_LAUNCH_CHECK();
+  return DM_OK;
+}
+// attach the lists written by convt_tables_launch to the product over those tables
+static void convt_attach_klist(DmGemm& q, const int* klist, int hs, int ta) {
+  if (!klist) return;
+  const int Hc = hs + ta - 1, nkt = dm_cdiv(q.K, 32);
+  q.k_list = klist; q.k_list_rows = CONVT_G; q.k_list_stride = nkt + 1;
+  q.k_list_mean = (double)nkt * hs * hs / ((double)Hc * Hc);      // the valid-tap share of the class grid: (ta hs)^2 of (ta Hc)^2
+  if (q.k_list_mean < 1.0) q.k_list_mean = 1.0;
 }
 // Wcat[(py,px,o)][(a,b,i)] = W[i][o][py+2a][px+2b]      (W: torch ConvTranspose2d layout (cin, cout, k, k))
 __global__ void __launch_bounds__(256) convt_repack_kernel(int cin, int cout, int k, const float* __restrict__ w,
@@ -296,8 +370,9 @@ __global__ void __launch_bounds__(256) convt_repack_kernel(int cin, int cout, in
   }
 }
 // layers this form is used for: even kernel, 16-byte gathers, and enough output channels that N = 4*cout fills MFMA tiles
-// (and an input large enough that the multiplied zero border stays under 40 % extra MACs: (Hc/hs)^2 <= 1.4, i.e. hs >= 6 for
-// k = 4 and hs >= 11 for k = 6)
+// (and an input large enough that the zero border stays under 40 % extra MACs: (Hc/hs)^2 <= 1.4, i.e. hs >= 6 for k = 4 and
+// hs >= 11 for k = 6.  The fp32 products skip the border's k-tiles - see above - wherever a tap is a whole number of tiles;
+// the bound is kept as it is: admitting more layers changes which form, and so which summation order, a layer takes)
 static bool convt_gather_ok(int k, int cin, int cout, int hs, size_t n) {
   const int Hc = hs + k / 2 - 1;
   return (k & 1) == 0 && (cin & 3) == 0 && cout >= 16 && 10 * Hc * Hc <= 14 * hs * hs &&
@@ -638,6 +713,14 @@ static int conv_encoder_bwd_impl(const dm_shape* shp, const float* image, const 
   int2* t_ctab = (int2*)ar.take(2 * tabmax);
   int* t_koff = (int*)ar.take(wcmax ? 4 * 1024 : 0);
   float* wcat = ar.take(wcmax);
+  size_t klmax = 0;
+  for (int l = 1; l < 4; ++l)
+    if (convt_gather_ok(4, g.cout[l], g.cin[l], g.hs[l], (size_t)g.N)) {
+      const size_t kl = convt_klist_ints((size_t)g.N * (g.hs[l] + 1) * (g.hs[l] + 1), 4 * g.cout[l]);
+      if (kl > klmax) klmax = kl;
+    }
+  int* t_klist = (int*)ar.take(klmax);      // (sized whether or not the switch is on)
+  const bool kskip = g_convt_kskip && !(shp->flags & DM_FLAG_BF16);
   // bf16 mode: twins of the two gradient ping-pong buffers and of the class-concatenated weights; the zero-padded gradient
   // copy is written as bf16 only (it lives in the fp32 copy's storage)
   DmTwinScope tw((shp->flags & DM_FLAG_BF16) != 0);
@@ -713,9 +796,7 @@ static int conv_encoder_bwd_impl(const dm_shape* shp, const float* image, const 
       else hipLaunchKernelGGL(convt_pad_kernel, dim3(grid_for(padn)), dim3(256), 0, st, g.N, hs, hs, co / 4, 1, (const float4*)G,
                               (float4*)gpad);
       DM_LAUNCH_CHECK();
-      hipLaunchKernelGGL(convt_tables_kernel, dim3(grid_for((size_t)g.N * Hc * Hc + kdim4)), dim3(256), 0, st, g.N, hs, hs, co, 2,
-                         hb, hb, ci, t_rowoff, t_koff, t_ctab);
-      DM_LAUNCH_CHECK();
+      DM_TRY(convt_tables_launch(g.N, hs, co, 2, hb, ci, t_rowoff, t_koff, t_ctab, kskip ? t_klist : nullptr, st));
       hipLaunchKernelGGL(convt_repack_kernel, dim3(grid_for((size_t)4 * ci * kdim4)), dim3(256), 0, st, co, ci, 4, p->w[l], wcat);
       DM_LAUNCH_CHECK();
       if (hpath) {
@@ -737,6 +818,7 @@ static int conv_encoder_bwd_impl(const dm_shape* shp, const float* image, const 
       d.c_tab = t_ctab; d.sc_cout = ci; d.sc_wpitch = hb * ci;
       d.mulref = a.y[l - 1];
       d.no_twin = l == 1;      // the layer-0 gradient is read by the direct weight-gradient kernel and the bias sum only (fp32)
+      convt_attach_klist(d, kskip ? t_klist : nullptr, hs, 2);
       DM_TRY(dm_gemm_launch(d, splitk, skb, st));
       G = Gn;
     } else if (l > 0) {
@@ -891,6 +973,15 @@ extern "C" int dm_conv_decoder_mse_fwd(const dm_shape* shp, const float* feat, i
   int* t_koff = (int*)ar.take(wcmax ? 9 * 1024 : 0);
   float* wcat = ar.take(wcmax);
   unsigned short* wcat_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(wcmax) : 0);
+  size_t klmax = 0;
+  for (int l = 1; l <= 4; ++l)
+    if (convt_gather_ok(g.k[l], g.cin[l], g.cout[l], g.hsm[l], (size_t)n)) {
+      const int ta = g.k[l] / 2, Hc = g.hsm[l] + ta - 1;
+      const size_t kl = convt_klist_ints((size_t)n * Hc * Hc, ta * ta * g.cin[l]);
+      if (kl > klmax) klmax = kl;
+    }
+  int* t_klist = (int*)ar.take(klmax);      // (sized whether or not the switch is on)
+  const bool kskip = g_convt_kskip && !(shp->flags & DM_FLAG_BF16);
   DM_REQUIRE(ar.ok, DM_E_WORKSPACE, "conv_decoder_fwd: workspace too small (need %zu floats)", ar.off);
   const size_t skb = DM_SPLITK_FLOATS * sizeof(float);
   {
@@ -919,9 +1010,7 @@ extern "C" int dm_conv_decoder_mse_fwd(const dm_shape* shp, const float* feat, i
       else hipLaunchKernelGGL(convt_pad_kernel, dim3(grid_for(padn)), dim3(256), 0, st, n, hs, hs, g.cin[l] / 4, ta - 1,
                               (const float4*)xin, (float4*)xpad);
       DM_LAUNCH_CHECK();
-      hipLaunchKernelGGL(convt_tables_kernel, dim3(grid_for((size_t)n * Hc * Hc + kdim)), dim3(256), 0, st, n, hs, hs, g.cin[l],
-                         ta, hb, hb, g.cout[l], t_rowoff, t_koff, t_ctab);
-      DM_LAUNCH_CHECK();
+      DM_TRY(convt_tables_launch(n, hs, g.cin[l], ta, hb, g.cout[l], t_rowoff, t_koff, t_ctab, kskip ? t_klist : nullptr, st));
       hipLaunchKernelGGL(convt_repack_kernel, dim3(grid_for((size_t)4 * g.cout[l] * kdim)), dim3(256), 0, st, g.cin[l], g.cout[l],
                          g.k[l], p->w[l], wcat);
       DM_LAUNCH_CHECK();
@@ -938,6 +1027,7 @@ extern "C" int dm_conv_decoder_mse_fwd(const dm_shape* shp, const float* feat, i
       q.c_tab = t_ctab; q.sc_cout = g.cout[l]; q.sc_wpitch = hb * g.cout[l];
       q.bias = p->b[l];
       q.flags = l < 4 ? DM_GEMM_ELU : 0;
+      convt_attach_klist(q, kskip ? t_klist : nullptr, hs, ta);
       DM_TRY(dm_gemm_launch(q, splitk, skb, st));
       continue;
     }

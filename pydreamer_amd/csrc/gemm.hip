@@ -55,7 +55,17 @@ struct GemmKArgs {
   int a_vec, b_vec;
   unsigned short* Ch;         // optional bf16 twin of C (same ldc), written with the final value
   int use_dma;                // host-side: this launch takes gemm_dma_kernel (not read by the kernels)
+  const int* k_list;          // optional k-tile lists (DmGemm::k_list): read by the scatter-epilogue instances of the fp32 loops only
+  int kl_rows, kl_stride;
 };
+// pins the first use of a list entry loaded earlier to this point of the program (the compiler puts the wait for the load here)
+__device__ __forceinline__ void kl_landed(int& t) { asm volatile("" : "+v"(t)); }
+// The k-tile list of the work item whose rows start at m0: *nkt = its tile count, returns the tile indices (ascending).
+__device__ __forceinline__ const int* gemm_k_list(const GemmKArgs& g, int m0, int* nkt) {
+  const int* kl = g.k_list + (size_t)(m0 / g.kl_rows) * g.kl_stride;
+  *nkt = kl[0];
+  return kl + 1;
+}
 
 // Load a (ROWS x 32) operand tile into registers, zero-filled outside [0,nrows) x [k0,kend).  Branch-free: out-of-range
 // groups read a clamped (always valid) address and are zeroed by a select, so edge tiles cost the same instruction
@@ -376,6 +386,21 @@ __global__ void __launch_bounds__(256) gemm_f32_kernel(const GemmKArgs g) {
   const int wm = wave / WGN, wn = wave % WGN;
 
   const GemmItem cur = gemm_decode<BM, BN>(g, blockIdx.x);
+  // k-tile list (DmGemm::k_list; scatter-epilogue instances only, every other instance compiles to the plain walk): tile t of
+  // this work item starts at 32 * kl[t] instead of kbeg + 32 t.  The entry of the tile after next is read one step ahead.
+  constexpr bool KL = SC && GA && BF == 0;
+  int nkt = cur.nkt;
+  const int* kl = nullptr;
+  if constexpr (KL) {
+    if (g.k_list) kl = gemm_k_list(g, cur.m0, &nkt);
+  }
+  auto tile_k0 = [&](int t) {
+    if constexpr (KL) {
+      if (kl) return 32 * kl[min(t, nkt - 1)];
+    }
+    return cur.kbeg + t * BK;
+  };
+  int knext = KL ? tile_k0(1) : 0;
 
   f32x16 acc[MB][NB];
 #pragma unroll
@@ -387,11 +412,12 @@ __global__ void __launch_bounds__(256) gemm_f32_kernel(const GemmKArgs g) {
 
   float4 ra[A_F4], rb[B_F4];
   unsigned ma = 0u, mb_ = 0u;
-  if (cur.nkt > 0) {
-    gemm_load_tile<BM, AL, A_F4, GA, VEC, A_KSEQ>(ra, g.A, g.lda, cur.m0, g.M, cur.kbeg, cur.kend, g.a_maj, g.a_min, tid, ma);
-    gemm_load_tile<BN, BL, B_F4, GB, VEC, B_KSEQ>(rb, g.B, g.ldb, cur.n0, g.N, cur.kbeg, cur.kend, g.b_maj, g.b_min, tid, mb_);
+  if (nkt > 0) {
+    const int k0 = tile_k0(0);
+    gemm_load_tile<BM, AL, A_F4, GA, VEC, A_KSEQ>(ra, g.A, g.lda, cur.m0, g.M, k0, cur.kend, g.a_maj, g.a_min, tid, ma);
+    gemm_load_tile<BN, BL, B_F4, GB, VEC, B_KSEQ>(rb, g.B, g.ldb, cur.n0, g.N, k0, cur.kend, g.b_maj, g.b_min, tid, mb_);
   }
-  for (int kt = 0; kt < cur.nkt; ++kt) {
+  for (int kt = 0; kt < nkt; ++kt) {
     unsigned short* Ah = reinterpret_cast<unsigned short*>(smem);
     unsigned short* Bh = Ah + BM * LDKB;
     if (BF == 1) {
@@ -402,11 +428,12 @@ __global__ void __launch_bounds__(256) gemm_f32_kernel(const GemmKArgs g) {
       gemm_store_tile<BN, BL, B_F4>(rb, mb_, Bs, tid);
     }
     __syncthreads();
-    if (kt + 1 < cur.nkt) {                                   // register prefetch under the MFMAs below
-      const int k0 = cur.kbeg + (kt + 1) * BK;
+    if (kt + 1 < nkt) {                                       // register prefetch under the MFMAs below
+      const int k0 = KL ? knext : cur.kbeg + (kt + 1) * BK;
       gemm_load_tile<BM, AL, A_F4, GA, VEC, A_KSEQ>(ra, g.A, g.lda, cur.m0, g.M, k0, cur.kend, g.a_maj, g.a_min, tid, ma);
       gemm_load_tile<BN, BL, B_F4, GB, VEC, B_KSEQ>(rb, g.B, g.ldb, cur.n0, g.N, k0, cur.kend, g.b_maj, g.b_min, tid, mb_);
     }
+    if constexpr (KL) knext = tile_k0(kt + 2);
     __builtin_amdgcn_sched_barrier(0);                        // keep the loads AHEAD of the MFMAs (hipcc sinks them otherwise)
     if (BF == 1) {
 #pragma unroll
@@ -499,6 +526,24 @@ __global__ void __launch_bounds__(256) gemm_dma_kernel(const GemmKArgs g) {
   const int lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
   const int wm = wave / WGN, wn = wave % WGN;
   const GemmItem cur = gemm_decode<BM, BN>(g, blockIdx.x);
+  // k-tile list (DmGemm::k_list), as in gemm_f32_kernel: only the k0 handed to issue / fetch_tab changes - the ring, the waits,
+  // the barriers and the MFMA order are those of the plain walk.  t1 / t2: index of the next tile to issue / to fetch the table
+  // for.  The list entry behind t2 is an ordinary load placed right BEHIND a step's LDS-DMA issue (in front of it, it would be
+  // a pending VGPR load the issue has to drain) and first touched behind the step's last MFMAs (kl_landed), where fetch_tab
+  // needs it: it has the whole tile of MFMAs to land, like the table entries themselves.
+  constexpr bool KL = SC && GA;
+  static_assert(!KL || NS == 2, "the listed walk is written for the two-stage ring");
+  int nkt = cur.nkt;
+  const int* kl = nullptr;
+  if constexpr (KL) {
+    if (g.k_list) kl = gemm_k_list(g, cur.m0, &nkt);
+  }
+  auto tile_idx = [&](int t) {
+    if constexpr (KL) {
+      if (kl) return kl[min(t, nkt - 1)];
+    }
+    return (cur.kbeg >> 5) + t;
+  };
 
   f32x16 acc[MB][NB];
 #pragma unroll
@@ -508,7 +553,7 @@ __global__ void __launch_bounds__(256) gemm_dma_kernel(const GemmKArgs g) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  if (cur.nkt > 0) {
+  if (nkt > 0) {
     DmaOperand<BM, AL, GA> sa;
     DmaOperand<BN, BL, GB> sb;
     sa.init(g.A, g.lda, cur.m0, g.M, g.a_maj, g.a_min, wave, lane);
@@ -554,22 +599,27 @@ __global__ void __launch_bounds__(256) gemm_dma_kernel(const GemmKArgs g) {
     // tile t+2 sits at the END of step t, behind the last MFMAs, where that drain coincides with the wait the two-stage ring
     // performs anyway at the top of step t+1.
     static_assert(!(GA || GB) || NS == 2, "gathered operands take the two-stage ring");
-    sa.fetch_tab(cur.kbeg, cur.kend);
-    sb.fetch_tab(cur.kbeg, cur.kend);
+    int t1 = tile_idx(1), t2 = t1;
+    {
+      const int k0 = KL ? 32 * tile_idx(0) : cur.kbeg;
+      sa.fetch_tab(k0, cur.kend);
+      sb.fetch_tab(k0, cur.kend);
 #pragma unroll
-    for (int s = 0; s < NS - 1; ++s) {
-      if (s < cur.nkt) {
-        sa.issue(cur.kbeg + s * 32, cur.kend, dma_smem + s * STAGE, wave);
-        sb.issue(cur.kbeg + s * 32, cur.kend, dma_smem + s * STAGE + A_BYTES, wave);
+      for (int s = 0; s < NS - 1; ++s) {
+        if (s < nkt) {
+          const int ks = KL ? k0 : cur.kbeg + s * 32;
+          sa.issue(ks, cur.kend, dma_smem + s * STAGE, wave);
+          sb.issue(ks, cur.kend, dma_smem + s * STAGE + A_BYTES, wave);
+        }
       }
     }
-    sa.fetch_tab(cur.kbeg + 32, cur.kend);
-    sb.fetch_tab(cur.kbeg + 32, cur.kend);
+    sa.fetch_tab(KL ? 32 * t1 : cur.kbeg + 32, cur.kend);
+    sb.fetch_tab(KL ? 32 * t1 : cur.kbeg + 32, cur.kend);
 
     int stage = 0;
-    for (int kt = 0; kt < cur.nkt; ++kt) {
+    for (int kt = 0; kt < nkt; ++kt) {
       // this wave's pieces of tile kt have landed once at most the (NS - 2) younger tiles are outstanding
-      if (NS == 3 && kt + 1 < cur.nkt) dma_wait_vm<NPT>();
+      if (NS == 3 && kt + 1 < nkt) dma_wait_vm<NPT>();
       else dma_wait_vm<0>();
       __builtin_amdgcn_s_barrier();           // ... and everybody else's; every wave is also done reading stage (kt - 1) % NS
       const unsigned so = (unsigned)stage * STAGE;
@@ -584,10 +634,12 @@ __global__ void __launch_bounds__(256) gemm_dma_kernel(const GemmKArgs g) {
       // and M0 writes then cost no matrix-pipe time - was measured and is SLOWER (profiles/r05_dma_issue_placement.txt: 4096^3
       // 117.4 vs 118.8 TF/s, 2500 x 1800 x 1000 103.7 vs 99.8 us, step 34.03 vs 33.84 ms): with two stages a load has one
       // k-tile to land, and a quarter to a half of it was given away; the other resident workgroup covers the issue gap.
-      if (nt < cur.nkt) {
-        sa.issue(cur.kbeg + nt * 32, cur.kend, dma_smem + ns * STAGE, wave);
-        sb.issue(cur.kbeg + nt * 32, cur.kend, dma_smem + ns * STAGE + A_BYTES, wave);
+      if (nt < nkt) {
+        const int ki = KL ? 32 * t1 : cur.kbeg + nt * 32;
+        sa.issue(ki, cur.kend, dma_smem + ns * STAGE, wave);
+        sb.issue(ki, cur.kend, dma_smem + ns * STAGE + A_BYTES, wave);
       }
+      if constexpr (KL) t2 = tile_idx(kt + 2);
 #pragma unroll
       for (int kg = 0; kg < 4; ++kg) {
         const int c = kg & 1, n = c ^ 1;
@@ -605,10 +657,13 @@ __global__ void __launch_bounds__(256) gemm_dma_kernel(const GemmKArgs g) {
               acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[c][mb].get(j), b[c][nb].get(j), acc[mb][nb], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
       }
-      if ((GA || GB) && nt + 1 < cur.nkt) {
-        sa.fetch_tab(cur.kbeg + (nt + 1) * 32, cur.kend);
-        sb.fetch_tab(cur.kbeg + (nt + 1) * 32, cur.kend);
+      if ((GA || GB) && nt + 1 < nkt) {
+        if constexpr (KL) kl_landed(t2);
+        const int kf = KL ? 32 * t2 : cur.kbeg + (nt + 1) * 32;
+        sa.fetch_tab(kf, cur.kend);
+        sb.fetch_tab(kf, cur.kend);
       }
+      if constexpr (KL) t1 = t2;
       if (++stage == NS) stage = 0;
     }
   }
@@ -1384,6 +1439,11 @@ int dm_gemm_launch(const DmGemm& q, void* ws, size_t ws_bytes, hipStream_t strea
   DM_REQUIRE(!q.c_tab || (q.sc_cout > 0 && q.N % q.sc_cout == 0 && q.N / q.sc_cout == 4 && !q.add && !(q.flags & DM_GEMM_ACCUM)),
              DM_E_SHAPE, "gemm: scatter epilogue needs N = 4 * sc_cout, no addend, no accumulate");
   if (hstore) { a.A = reinterpret_cast<const float*>(Ah); a.B = reinterpret_cast<const float*>(Bh); }
+  // k-tile lists: the fp32 tile loops of the scatter-epilogue product walk them; the bf16 loops (BK = 64) ignore them
+  const bool klist = q.k_list && !hstore && !q.bf16;
+  DM_REQUIRE(!klist || (q.c_tab && q.a_maj && q.k_list_rows > 0 && q.k_list_stride > 0), DM_E_SHAPE,
+             "gemm: k-tile lists are built for the gathered-A scatter-epilogue product (rows %d, stride %d)", q.k_list_rows, q.k_list_stride);
+  a.k_list = klist ? q.k_list : nullptr; a.kl_rows = q.k_list_rows; a.kl_stride = q.k_list_stride;
   // 16-byte load path: aligned base, rows a multiple of 4 floats apart, and the vectorised (minor) extent a multiple
   // of 4 so that no group of 4 straddles the edge.  Minor extent: K for layout 0, M (resp. N) for layout 1.
   a.a_vec = hstore ? 1 : (((uintptr_t)q.A & 15) == 0 && (q.a_maj ? q.a_tab_vec != 0 : (q.lda & 3) == 0) &&
@@ -1424,6 +1484,7 @@ int dm_gemm_launch(const DmGemm& q, void* ws, size_t ws_bytes, hipStream_t strea
   static const int force_tile = getenv("DM_GEMM_TILE") ? atoi(getenv("DM_GEMM_TILE")) : 0;
   static const int force_split = getenv("DM_GEMM_SPLIT") ? atoi(getenv("DM_GEMM_SPLIT")) : 0;
   int BM = 64, BN = 64, nsplit = 1;
+  DM_REQUIRE(!klist || q.k_list_rows % 64 == 0, DM_E_SHAPE, "gemm: k-tile lists cover a multiple of 64 rows (%d)", q.k_list_rows);
   double best_cost = -1.0;
   const int kt1 = ktiles > 0 ? ktiles : 1;
   const bool dma_shape_pre = !hstore && !q.bf16 && a.a_vec && a.b_vec;
@@ -1431,6 +1492,7 @@ int dm_gemm_launch(const DmGemm& q, void* ws, size_t ws_bytes, hipStream_t strea
     if (force_tile && c != force_tile - 1) continue;
     if (!(a.a_vec && a.b_vec) && c != 2) continue;        // the scalar-load variant exists for the 64x64 tile only
     const int bm = cand[c][0], bn = cand[c][1];
+    if (klist && q.k_list_rows % bm != 0) continue;       // a work item reads ONE list: its rows must lie inside one list block
     const int64_t t = (int64_t)dm_cdiv(q.M, bm) * dm_cdiv(q.N, bn);
     int sp_fill = 1;
     if (t < 256) {
@@ -1461,7 +1523,7 @@ int dm_gemm_launch(const DmGemm& q, void* ws, size_t ws_bytes, hipStream_t strea
       const double R = resid[c];
       const double waves = avg > R ? ceil(avg / R) : 1.0;
       const double conc = avg > R ? avg / waves : (avg > 1.0 ? ceil(avg - 1e-9) : 1.0);
-      const double nkt = (double)dm_cdiv(kt1, sp);
+      const double nkt = klist ? q.k_list_mean : (double)dm_cdiv(kt1, sp);      // (a listed product is never split: c_tab)
       const double tm = (double)bm * bn * 32.0 / rate[c];
       const double per_kt = conc * tm > lat_macs ? conc * tm : lat_macs;
       double cost = waves * (nkt * per_kt + conc * bm * bn * keq[c] / rate[c]);
@@ -1492,7 +1554,8 @@ int dm_gemm_launch(const DmGemm& q, void* ws, size_t ws_bytes, hipStream_t strea
   // rows to the last row, layout 1 to the last full group of 4: >= 1 / >= 4 rows.
   constexpr int dma_min_kt = 14;
   const bool dma_shape = !hstore && !q.bf16 && a.a_vec && a.b_vec && (q.a_layout == 0 ? q.M >= 1 : q.M >= 4) && (q.b_layout == 0 ? q.N >= 1 : q.N >= 4);
-  auto dma_for = [&](int sp) { return g_dma_enabled && dma_shape && (dm_cdiv(kt1, sp) >= dma_min_kt || g_dma_enabled >= 2); };
+  const int kt_item = klist ? (int)(q.k_list_mean + 0.5) : 0;      // a listed product: the mean tile count of a work item
+  auto dma_for = [&](int sp) { return g_dma_enabled && dma_shape && ((klist ? kt_item : dm_cdiv(kt1, sp)) >= dma_min_kt || g_dma_enabled >= 2); };
   // (A one-round 128 x 160 tile for the rollout's 2 500 x 1 800 gate products - 240 workgroups, one per CU, instead of 1 160
   // tiles of 64 x 64 = 4.53 per CU - was built and measured: 104.8 vs 106.3 us at K = 1000, 71.3 vs 68.4 at K = 600, step 33.94
   // vs 33.50 ms.  One 4-wave workgroup per CU leaves nobody to hide its barrier skew, prologue and epilogue: removed.)

@@ -146,6 +146,7 @@ extern "C" size_t dm_workspace_bytes(const dm_shape* s) {
   const size_t tw = (s->flags & DM_FLAG_BF16) ? 1 : 0;
   const size_t enc_bwd = SK + pad64(N * 961 * d) + pad64(N * 196 * 2 * d) + pad64(8 * d * 64 * d) + pad64(xc) + pad64(epad) +
                          3 * pad64(N * 225) + pad64(4 * 1024) + pad64(16 * 2 * d * 4 * d) + 1024 +
+                         pad64((N * 225 / 128 + 1) * (d + 2)) +      // + k-tile lists (conv.hip CONVT_G): blocks x (K / 32 + 1), K <= 32 d
                          tw * (pad64(N * 961 * d / 2 + 1) + pad64(N * 196 * d + 1) + pad64(8 * 2 * d * 4 * d + 1));
   // decoder: column matrices rows_small * k*k*cout for layers 1..4
   size_t col = N * 25 * 4 * d;
@@ -168,6 +169,7 @@ extern "C" size_t dm_workspace_bytes(const dm_shape* s) {
   const size_t gtab = N * 32 * 32;
   const size_t dec_fwd = SK + pad64(col) + pad64(gpad) + 3 * pad64(gtab) + pad64(9 * 1024) + pad64(4 * 2 * d * 9 * 2 * d) +
                          pad64(144 * d) + 1024 +      // + the direct layer-4 kernel's class-ordered weights
+                         pad64((N * 1024 / 128 + 1) * (18 * d / 32 + 2)) +      // + k-tile lists: K <= 18 d
                          tw * pad64(2 * 2 * d * 9 * 2 * d + 1);
   // decoder backward: one gradient buffer per layer, one gather-table pair per layer, two split-K scratches (the weight
   // gradients may run on the side stream, conv.hip conv_decoder_mse_bwd_impl)
