@@ -92,7 +92,8 @@ int dm_version(void);                 /* ABI version, currently 16 (v2: LayerNor
                                               of the map probe; dm_replay_gather of the device-resident replay; dm_goals_stats /
                                               dm_goals_stats_ws_floats of the goals probe; the dm_gru_sequence_ family of the
                                               gru_probe baseline; dm_dense_image_rows / dm_elu_rows_fwd / dm_elu_rows_bwd /
-                                              dm_cat_image_loss_mix of the dense categorical image path; dm_convt_kskip_enable */
+                                              dm_cat_image_loss_mix of the dense categorical image path; dm_convt_kskip_enable;
+                                              dm_kl_staged_enable; dm_dec_l4_fwd_shared_enable */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
 size_t dm_workspace_bytes(const dm_shape* shp);   /* scratch needed by any call below for this shape */
@@ -152,12 +153,24 @@ int dm_gemm_dma_enable(int on);
  * same bits for finite weights.  1 / 0 switches it on / off (off: rows ordered (frame, yy, xx), every k-tile), -1 queries;
  * returns the state (default 1).  bf16-mode calls are not affected. */
 int dm_convt_kskip_enable(int on);
+/* The categorical KL-balance kernels behind dm_kl_balance_fwd / _bwd address one group of C logits per lane.  Where the shape
+ * fits (C <= 63: two tensors of 128 groups at pitch C + 1 in 64 KB of LDS; forward also S <= 32, where a wave takes two rows) a
+ * workgroup first copies its groups into LDS with coalesced 16-byte loads, and the backward writes both gradients back through
+ * LDS the same way (csrc/elementwise.hip).  Same arithmetic in the same order: same bits.  1 / 0 switches it on / off (off: the
+ * per-lane-addressed kernels at every shape), -1 queries; returns the state (default 1).  Gaussian latents (C = 0) are not affected. */
+int dm_kl_staged_enable(int on);
 /* The image layer of the decoder (ConvTranspose2d(d -> 3, k6, s2), decoders.py:154-155) runs its backward - data gradient with
  * the ELU' of the layer below folded in, weight gradient - as two direct MFMA kernels that read the 3-channel output gradient
  * of a frame from LDS (csrc/conv_direct.hip) instead of as gather-form products through the generic tile (3 -> 4 channel pad, 48
  * columns in a 64-wide tile).  Same sums in another order (fp32 rounding only).  1 / 0 switches it on / off, -1 queries; returns
  * the state (default 1). */
 int dm_dec_l4_bwd_direct_enable(int on);
+/* The same layer's forward is, per parity class of the output, a 3 x 3 convolution over the input, and the four classes of a
+ * class pixel read the same patch.  On: one kernel reads each patch element from LDS once for all 4 x 3 outputs, as the
+ * (9 d) -> 12 product on v_mfma_f32_16x16x4_f32 - per output the same k-ordered chain of f32 FMAs from the bias - with the weights
+ * in LDS.  Off: one class per wave on packed FMAs, the class weights as wave-uniform vector loads.  Same bits either way.
+ * 1 / 0 switches it on / off, -1 queries; returns the state (default 1). */
+int dm_dec_l4_fwd_shared_enable(int on);
 /* The posterior T loop (rssm.py:38-58, cell rssm.py:125-153, nn.GRUCell rnn.py:40-67) runs, when the shape qualifies (plain
  * single-layer GRU, LayerNorm, categorical latents, B <= 64, the layer slices fit one CU's LDS), as ONE persistent kernel with
  * one workgroup per compute unit that keeps its 4-column slice of every layer's weights in LDS for all T steps and exchanges

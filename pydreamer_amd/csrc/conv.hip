@@ -369,6 +369,33 @@ __global__ void __launch_bounds__(256) convt_repack_kernel(int cin, int cout, in
     wcat[e] = w[(((size_t)ci * cout + o) * k + (py + 2 * a)) * k + (px + 2 * b)];
   }
 }
+// The big image of a scatter product whose extent hb is odd (encoder layer 1's 31 x 31 output under the layer-2 data gradient):
+// the class grid covers rows / columns 0 .. E-1 with E = 2*Hc = hb - 1 and the epilogue writes every one of those (each class
+// pixel has its four parities inside, c_tab's two range bits all set; M and N of the product are exact), so only the rows and
+// columns E .. hb-1, which no window reaches, have to be cleared: (hb^2 - E^2) pixels per frame instead of the whole buffer
+// (29 MB of 461 MB at Atari-literal).  V channels per thread (4: 16-byte stores); out_h: optional bf16 twin.
+template <int V>
+__global__ void __launch_bounds__(256) convt_border_zero_kernel(int n, int hb, int E, int cv, float* __restrict__ out,
+                                                                unsigned short* __restrict__ out_h) {
+  const int side = hb - E, nb = hb * hb - E * E;      // border pixels of a frame: E rows of `side`, then hb - E whole rows
+  const size_t total = (size_t)n * nb * cv;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+    size_t t = e;
+    const int cc = (int)(t % cv); t /= cv;
+    const int j = (int)(t % nb);
+    const int i = (int)(t / nb);
+    const int y = j < E * side ? j / side : E + (j - E * side) / hb;
+    const int x = j < E * side ? E + j % side : (j - E * side) % hb;
+    const size_t at = ((((size_t)i * hb + y) * hb + x) * cv + cc) * V;
+    if (V == 4) {
+      *reinterpret_cast<float4*>(out + at) = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (out_h) *reinterpret_cast<uint2*>(out_h + at) = make_uint2(0u, 0u);
+    } else {
+      out[at] = 0.f;
+      if (out_h) out_h[at] = 0;
+    }
+  }
+}
 // layers this form is used for: even kernel, 16-byte gathers, and enough output channels that N = 4*cout fills MFMA tiles
 // (and an input large enough that the zero border stays under 40 % extra MACs: (Hc/hs)^2 <= 1.4, i.e. hs >= 6 for k = 4 and
 // hs >= 11 for k = 6.  The fp32 products skip the border's k-tiles - see above - wherever a tap is a whole number of tiles;
@@ -804,10 +831,15 @@ static int conv_encoder_bwd_impl(const dm_shape* shp, const float* image, const 
         DM_TRY(dm_to_bf16_multi_launch(&sg, 1, st));
       }
       if (2 * Hc != hb) {      // odd input extent (31): the last row / column is reached by no window - its gradient is zero
-        hipError_t e = hipMemsetAsync(Gn, 0, (size_t)g.N * hb * hb * ci * sizeof(float), st);
-        if (e == hipSuccess && dm_twin_of(Gn, false))
-          e = hipMemsetAsync(dm_twin_of(Gn, false), 0, (size_t)g.N * hb * hb * ci * sizeof(unsigned short), st);
-        if (e != hipSuccess) return dm_fail(DM_E_HIP, "conv_encoder_bwd: %s", hipGetErrorString(e));
+        const int E = 2 * Hc, nb = hb * hb - E * E;      // the scatter epilogue below writes everything else (convt_border_zero_kernel)
+        unsigned short* gnh = (unsigned short*)dm_twin_of(Gn, false);
+        if ((ci & 3) == 0)
+          hipLaunchKernelGGL(convt_border_zero_kernel<4>, dim3(grid_for((size_t)g.N * nb * (ci / 4))), dim3(256), 0, st, g.N, hb, E,
+                             ci / 4, Gn, gnh);
+        else
+          hipLaunchKernelGGL(convt_border_zero_kernel<1>, dim3(grid_for((size_t)g.N * nb * ci)), dim3(256), 0, st, g.N, hb, E, ci, Gn,
+                             gnh);
+        DM_LAUNCH_CHECK();
       }
       DmGemm d;
       d.M = g.N * Hc * Hc; d.N = 4 * ci; d.K = kdim4;

@@ -17,6 +17,8 @@
 //   dec_l4_fwd_kernel    lane = output pixel of ONE parity class (2yy+py, 2xx+px): an even-k stride-2 transposed convolution
 //                        is, per class, a 3x3 convolution over the input; the class's 9 x d x 3 weights are wave-uniform
 //                        (scalar loads), the input pixel vectors are 16-byte loads
+//   dec_l4_fwd_mfma_kernel the same layer as the (9 d) -> 12 product per class pixel on v_mfma_f32_16x16x4_f32: the four classes
+//                        share one LDS read of the patch, weights in LDS; same bits (the default, dm_dec_l4_fwd_shared_enable)
 // fp32 VALU arithmetic (v_fmac with an SGPR operand); bound: VALU issue (13 / 5.5 GFMA-lanes) and the output write.
 //
 // reward_input (encoders.py:52-59): the encoder's first Conv2d sees two more input planes, the frame's reward and its terminal
@@ -357,7 +359,13 @@ __global__ void __launch_bounds__(256) dec_l4_repack_kernel(int d, const float* 
 // kernel at Atari-literal (the column-matrix path it replaces: 0.97 ms): pixel vectors read from global memory, 64 lanes x
 // 16 B at a 192-byte stride per load: 4.1 ms (address-coalescing bound); LDS-staged input, one pixel per lane: 1.95 ms - the
 // class's weights are wave-uniform, but behind a barrier the compiler does not scalarise global loads, so they arrive as
-// vector loads, 4 per 12 FMAs; four pixels per lane share each weight load (4 per 48 FMAs).
+// vector loads, 4 per 12 FMAs; four pixels per lane share each weight load (4 per 48 FMAs): 0.56-0.60 ms, about 2.5x its
+// packed-FMA time - per (tap, 4 channels) a wave issues 32 v_pk_fma_f32 against 4 wave-uniform 16-byte vector loads, and the
+// four class-waves read the same patch from LDS four times.  One pixel x four classes per lane with the weights as scalar
+// operands through the constant address space: 0.70 ms (profiles/r06_mlp_chain_anatomy.txt).  The four classes as the columns
+// of an fp32 MFMA, input rows and weights in LDS (dec_l4_fwd_mfma_kernel below, dm_dec_l4_fwd_shared_enable), one workgroup per
+// tile: 0.51 ms; 512 workgroups walking the tiles with the weights staged once and the next tile's rows prefetched into
+// registers: 0.36 ms against 0.60 ms for this kernel in the same session (profiles/image_layer_kl_bench.txt).
 constexpr int DEC_ROWS = 10, DEC_COLS = 34;
 template <int D>
 __global__ void __launch_bounds__(256) dec_l4_fwd_kernel(int frames, const float* __restrict__ x, const float* __restrict__ w4,
@@ -414,6 +422,109 @@ __global__ void __launch_bounds__(256) dec_l4_fwd_kernel(int frames, const float
   }
 }
 
+// The same layer with ONE read of the patch for all four classes and the weights off the vector memory path
+// (dm_dec_l4_fwd_shared_enable, the default).  The four classes of a class pixel read the same 3 x 3 patch, so the layer is,
+// per class pixel, a (9 d) -> 12 product: 4 classes x 3 channels.  v_mfma_f32_16x16x4_f32 computes exactly the chain above - its
+// result is, per output element, the k-ordered chain of single-rounded f32 FMAs fma(a_k3, b_k3, fma(a_k2, b_k2, fma(a_k1, b_k1,
+// fma(a_k0, b_k0, C)))) - so with rows = 16 class pixels of one class row, columns = (class, channel) (12 used, 4 idle: the
+// same 4 slots per 3 channels as the packed form, but no pad slot is ever loaded or stored) and k = 4 consecutive input
+// channels of one tap, walking taps ab = 0 .. 8 and channels ascending from C = bias gives every output the bits of
+// dec_l4_fwd_kernel (tests/test_gpu_image_layer_fwd.py compares them with ==).
+//   wm[(ab*d + c)*12 + cls*3 + o] = W[c][o][py+2a][px+2b]: the B operand of k-step (ab, c0) is 4 x 12 consecutive floats.
+//   Workgroup = (frame, 4 class rows yy0 .. yy0+3): the 6 input rows yy0-2 .. yy0+3 (zero outside the image, pixel pitch d + 2
+//   floats: the 16 pixels x 2 channels a half-wave reads fall on 32 distinct banks) and all of wm in LDS - 61.5 KB at d = 48, two
+//   workgroups per CU.  Wave = class row yy0 + wave, two blocks of 16 pixels: per k-step 1 weight + 2 patch ds_read_b32 feed 2
+//   MFMAs (64 matrix-pipe cycles); no weight ever passes the vector memory path inside the loop, and a patch element is read once
+//   for its 12 outputs.  At most DECM_WGS workgroups (two per CU) walk the tiles.
+__global__ void __launch_bounds__(256) dec_l4_repack12_kernel(int d, const float* __restrict__ w, float* __restrict__ wm) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= 9 * d * 12) return;
+  const int nn = e % 12, c = (e / 12) % d, ab = e / (12 * d);
+  const int cls = nn / 3, o = nn - cls * 3;
+  const int ky = (cls >> 1) + 2 * (ab / 3), kx = (cls & 1) + 2 * (ab % 3);
+  wm[e] = w[(((size_t)c * 3 + o) * 6 + ky) * 6 + kx];
+}
+constexpr int DECM_ROWS = 6, DECM_CROWS = 4, DECM_WGS = 512;
+template <int D>
+__global__ void __launch_bounds__(256) dec_l4_fwd_mfma_kernel(int frames, const float* __restrict__ x, const float* __restrict__ wm,
+                                                              const float* __restrict__ bias, float* __restrict__ out) {
+  constexpr int LDP = D + 2, D4 = D / 4;
+  constexpr int TOT = DECM_ROWS * DEC_COLS * D4, NPRE = (TOT + 255) / 256;      // 16-byte pieces of a tile's rows, per thread
+  extern __shared__ __attribute__((aligned(16))) float rows[];      // [6 rows][34 columns (ix = -2 .. 31)][D + 2], then wm
+  float* wl = rows + DECM_ROWS * DEC_COLS * LDP;                    // (a multiple of 4 floats in: 16-byte aligned)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ntiles = frames * 8;                                    // tile = (frame, 4 class rows)
+  for (int e = tid; e < 9 * D * 3; e += 256) reinterpret_cast<float4*>(wl)[e] = reinterpret_cast<const float4*>(wm)[e];
+  // A workgroup walks tiles blockIdx.x, + gridDim.x, ...: the weights are staged once, and the next tile's rows are loaded into
+  // registers before this tile's products start, so their latency passes under the MFMAs.
+  float4 pre[NPRE];
+  auto fetch = [&](int tile) {
+    const int n = tile >> 3, yy0 = (tile & 7) * DECM_CROWS;
+#pragma unroll
+    for (int i = 0; i < NPRE; ++i) {
+      const int e = tid + 256 * i;
+      const int c4 = e % D4, col = (e / D4) % DEC_COLS, r = e / (D4 * DEC_COLS);
+      const int iy = yy0 - 2 + r, ix = col - 2;
+      pre[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (e < TOT && iy >= 0 && iy < 30 && ix >= 0 && ix < 30)
+        pre[i] = *reinterpret_cast<const float4*>(x + (((size_t)n * 30 + iy) * 30 + ix) * D + 4 * c4);
+    }
+  };
+  // operand maps of the 16x16x4 MFMA: A[row = lane & 15][k = lane >> 4], B[k = lane >> 4][col = lane & 15],
+  // C/D[row = 4*(lane >> 4) + r][col = lane & 15]
+  const int l15 = lane & 15, q = lane >> 4;
+  const float b0 = l15 < 12 ? bias[l15 % 3] : 0.f;
+  const float* wq = wl + q * 12 + (l15 < 12 ? l15 : 11);      // an idle column multiplies a copy of column 11 and is dropped
+  const int cls = l15 / 3, o = l15 - cls * 3, py = cls >> 1, px = cls & 1;
+  int tile = blockIdx.x;
+  if (tile < ntiles) fetch(tile);
+  for (; tile < ntiles; tile += gridDim.x) {
+    __syncthreads();                                           // the previous tile's readers are done (first pass: nothing)
+#pragma unroll
+    for (int i = 0; i < NPRE; ++i) {
+      const int e = tid + 256 * i;
+      const int c4 = e % D4, col = (e / D4) % DEC_COLS, r = e / (D4 * DEC_COLS);
+      if (e < TOT) {
+        float2* dst = reinterpret_cast<float2*>(&rows[(r * DEC_COLS + col) * LDP + 4 * c4]);      // LDP even: 8-byte aligned
+        dst[0] = make_float2(pre[i].x, pre[i].y);
+        dst[1] = make_float2(pre[i].z, pre[i].w);
+      }
+    }
+    __syncthreads();                                           // (and the weights, first pass)
+    if (tile + (int)gridDim.x < ntiles) fetch(tile + gridDim.x);
+    f32x4c acc[2] = {(f32x4c){b0, b0, b0, b0}, (f32x4c){b0, b0, b0, b0}};
+#pragma unroll 1
+    for (int ab = 0; ab < 9; ++ab) {
+      // LDS row of class row yy0 + wave under tap row a: (yy0 + wave - a) - (yy0 - 2); column of pixel xx under tap column b: xx - b + 2
+      const float* src = &rows[((wave + 2 - ab / 3) * DEC_COLS + (l15 + 2 - ab % 3)) * LDP + q];
+      const float* wk = wq + ab * D * 12;
+#pragma unroll
+      for (int c4 = 0; c4 < D4; ++c4) {
+        const float bv = wk[c4 * 48];
+        const float a0 = src[4 * c4], a1 = src[16 * LDP + 4 * c4];
+        acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, bv, acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, bv, acc[1], 0, 0, 0);
+      }
+    }
+    if (l15 < 12) {
+      const int n = tile >> 3, yy = (tile & 7) * DECM_CROWS + wave;
+      float* orow = out + (((size_t)n * 64 + 2 * yy + py) * 64 + px) * 3 + o;
+#pragma unroll
+      for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) orow[(size_t)(2 * (mb * 16 + 4 * q + r)) * 3] = acc[mb][r];
+    }
+  }
+}
+
+static int g_l4_fwd_shared = 1;
+// 1 / 0: the image layer's forward with the four classes as MFMA columns / one class per wave on the packed FMAs, -1: query.
+// Returns the state.
+extern "C" int dm_dec_l4_fwd_shared_enable(int on) {
+  if (on >= 0) g_l4_fwd_shared = on ? 1 : 0;
+  return g_l4_fwd_shared;
+}
+
 bool dm_dec_l4_direct_ok(int ch, int d, int hs, int k) {
   return ch == 3 && hs == 30 && k == 6 && (d == 8 || d == 16 || d == 32 || d == 48 || d == 64);
 }
@@ -421,6 +532,27 @@ size_t dm_dec_l4_w4_floats(int d) { return (size_t)4 * 9 * d * 4; }
 int dm_dec_l4_fwd_launch(int frames, int d, const float* x, const float* w, const float* bias, float* w4, float* out,
                          hipStream_t st) {
   if (frames <= 0) return DM_OK;
+  if (g_l4_fwd_shared) {      // wm: 108 d of the 144 d floats of w4
+    hipLaunchKernelGGL(dec_l4_repack12_kernel, dim3(grid_for_px((size_t)108 * d, 256)), dim3(256), 0, st, d, w, w4);
+    DM_LAUNCH_CHECK();
+    const size_t ldsm = ((size_t)DECM_ROWS * DEC_COLS * (d + 2) + (size_t)108 * d) * sizeof(float);      // 81.5 KB at d = 64
+#define DM_DEC_L4M(D_)                                                                                                 \
+  if (d == D_) {                                                                                                       \
+    static bool attr_set[DM_MAX_DEVICES] = {false};                                                                    \
+    int dev_ = 0;                                                                                                      \
+    if (hipGetDevice(&dev_) != hipSuccess || dev_ < 0 || dev_ >= DM_MAX_DEVICES) return dm_fail(DM_E_DEVICE, "dec_l4_fwd: hipGetDevice"); \
+    if (!attr_set[dev_]) {                                                                                             \
+      if (hipFuncSetAttribute((const void*)dec_l4_fwd_mfma_kernel<D_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) \
+        return dm_fail(DM_E_HIP, "dec_l4_fwd: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");                \
+      attr_set[dev_] = true;                                                                                           \
+    }                                                                                                                  \
+    hipLaunchKernelGGL((dec_l4_fwd_mfma_kernel<D_>), dim3(frames * 8 < DECM_WGS ? frames * 8 : DECM_WGS), dim3(256), ldsm, st, frames, x, w4, bias, out);   \
+  }
+    DM_DEC_L4M(8) DM_DEC_L4M(16) DM_DEC_L4M(32) DM_DEC_L4M(48) DM_DEC_L4M(64)
+#undef DM_DEC_L4M
+    DM_LAUNCH_CHECK();
+    return DM_OK;
+  }
   hipLaunchKernelGGL(dec_l4_repack_kernel, dim3(grid_for_px(dm_dec_l4_w4_floats(d), 256)), dim3(256), 0, st, d, w, w4);
   DM_LAUNCH_CHECK();
   const size_t lds = (size_t)DEC_ROWS * DEC_COLS * (d + 4) * sizeof(float);       // 70.7 KB at d = 48: above the 64 KB default

@@ -1412,6 +1412,134 @@ __global__ void __launch_bounds__(256) kl_bwd_kernel(int rows, int S, int C, con
   }
 }
 
+// The staged form of the two kernels above (dm_kl_staged_enable).  Above, a lane addresses its own group: lane i reads
+// base + 4 C i + 4 k, so at C = 32 every load and store instruction touches 64 cache lines, and both kernels run at a few
+// times their HBM time.  Here a workgroup of 128 threads owns KL_G = 128 consecutive groups - a contiguous run of 128 C floats of
+// each tensor - copies both runs into LDS with coalesced 16-byte loads, and every lane then does the arithmetic above, in the
+// same order, on its group in LDS.  Group pitch C + 1 floats: lane = group reads of one k fall on distinct banks for odd pitch
+// (C even; 2-way at most otherwise).  Same bits as the kernels above: the per-group sums, the lane-strided sum over groups and
+// the wave reduction are the same expressions over the same values.
+constexpr int KL_G = 128;
+static int g_kl_staged = 1;
+// 1 / 0: the LDS-staged kernels where the shape fits / the per-lane-addressed kernels everywhere, -1: query.  Returns the state.
+extern "C" int dm_kl_staged_enable(int on) {
+  if (on >= 0) g_kl_staged = on ? 1 : 0;
+  return g_kl_staged;
+}
+// 2 tensors x 128 groups x (C + 1) floats within the 64 KB a kernel gets without asking for more: C <= 63
+static bool kl_staged_ok(int C) { return g_kl_staged && C >= 1 && (size_t)2 * KL_G * (C + 1) * sizeof(float) <= 64 * 1024; }
+// forward: a wave reduces one row over its 64 lanes; with S <= 32 its upper half is idle above, and here takes a second row
+static bool kl_fwd_staged_ok(int S, int C) { return kl_staged_ok(C) && S >= 1 && S <= 32; }
+
+// nfl floats from src (16-byte aligned at src, or not: the scalar path) into rows of pitch C + 1
+__device__ __forceinline__ void kl_stage_in(const float* __restrict__ src, int nfl, int C, float* dst, bool vec) {
+  const int tid = threadIdx.x;
+  const int n4 = vec ? nfl >> 2 : 0;
+  for (int e = tid; e < n4; e += KL_G) {
+    const float4 v = reinterpret_cast<const float4*>(src)[e];
+    int gi = (4 * e) / C, k = 4 * e - gi * C;
+    const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      dst[gi * (C + 1) + k] = vv[j];
+      if (++k == C) { k = 0; ++gi; }
+    }
+  }
+  for (int e = 4 * n4 + tid; e < nfl; e += KL_G) dst[(e / C) * (C + 1) + e % C] = src[e];
+}
+__device__ __forceinline__ void kl_stage_out(const float* src, int nfl, int C, float* __restrict__ dst, bool vec) {
+  const int tid = threadIdx.x;
+  const int n4 = vec ? nfl >> 2 : 0;
+  for (int e = tid; e < n4; e += KL_G) {
+    int gi = (4 * e) / C, k = 4 * e - gi * C;
+    float vv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      vv[j] = src[gi * (C + 1) + k];
+      if (++k == C) { k = 0; ++gi; }
+    }
+    reinterpret_cast<float4*>(dst)[e] = make_float4(vv[0], vv[1], vv[2], vv[3]);
+  }
+  for (int e = 4 * n4 + tid; e < nfl; e += KL_G) dst[e] = src[(e / C) * (C + 1) + e % C];
+}
+
+// S <= 32.  Workgroup = 4 rows (4 S <= 128 groups), wave = 2 rows: lanes 0-31 the first, 32-63 the second, lane & 31 = group.
+// A row's 64-lane tree above is: off = 32 adds the idle upper half's zeros (v + 0.f == v: an accumulator is 0.f + gk, never
+// -0), then off = 16 .. 1 inside the lower half.  Here each half runs off = 16 .. 1 on the same values: the same tree.
+__global__ void __launch_bounds__(KL_G) kl_fwd_staged_kernel(int rows, int S, int C, int vec, const float* __restrict__ post,
+                                                             const float* __restrict__ prior, float* __restrict__ kl,
+                                                             float* __restrict__ ent_post, float* __restrict__ ent_prior) {
+  extern __shared__ __attribute__((aligned(16))) float kl_lds[];
+  float* pa = kl_lds;
+  float* pb = kl_lds + KL_G * (C + 1);
+  const int row0 = blockIdx.x * 4, nrow = min(4, rows - row0);
+  const size_t base = (size_t)row0 * S * C;
+  kl_stage_in(post + base, nrow * S * C, C, pa, vec != 0);
+  kl_stage_in(prior + base, nrow * S * C, C, pb, vec != 0);
+  __syncthreads();
+  const int lane = threadIdx.x & 63, rl = (threadIdx.x >> 6) * 2 + (lane >> 5), s = lane & 31;
+  float akl = 0.f, aep = 0.f, aeq = 0.f;
+  if (rl < nrow && s < S) {
+    const float* a = pa + (rl * S + s) * (C + 1);
+    const float* b = pb + (rl * S + s) * (C + 1);
+    const float la = dm_group_lse(a, C), lb = dm_group_lse(b, C);
+    float gk = 0.f, ep = 0.f, eq = 0.f;
+    for (int k = 0; k < C; ++k) {
+      const float lp = a[k] - la, lq = b[k] - lb;
+      const float p = expf(lp), q = expf(lq);
+      gk += p * (lp - lq);
+      ep -= p * lp;
+      eq -= q * lq;
+    }
+    akl += gk; aep += ep; aeq += eq;
+  }
+#pragma unroll
+  for (int off = 16; off > 0; off >>= 1) {
+    akl += __shfl_xor(akl, off, 64);
+    aep += __shfl_xor(aep, off, 64);
+    aeq += __shfl_xor(aeq, off, 64);
+  }
+  if (s == 0 && rl < nrow) {
+    kl[row0 + rl] = akl;
+    if (ent_post) ent_post[row0 + rl] = aep;
+    if (ent_prior) ent_prior[row0 + rl] = aeq;
+  }
+}
+
+// Workgroup = groups g0 .. g0 + 127 of the flat (rows S) list, lane = group.  A lane overwrites its own group's logits in LDS
+// with the two gradients (element k is read before it is written, and by this lane only); they leave as coalesced 16-byte stores.
+__global__ void __launch_bounds__(KL_G) kl_bwd_staged_kernel(int total, int C, int vec, const float* __restrict__ post,
+                                                             const float* __restrict__ prior, float sp, float sq,
+                                                             float* __restrict__ dpost, float* __restrict__ dprior) {
+  extern __shared__ __attribute__((aligned(16))) float kl_lds[];
+  float* pa = kl_lds;
+  float* pb = kl_lds + KL_G * (C + 1);
+  const int g0 = blockIdx.x * KL_G, ng = min(KL_G, total - g0);
+  const size_t base = (size_t)g0 * C;
+  kl_stage_in(post + base, ng * C, C, pa, vec != 0);
+  kl_stage_in(prior + base, ng * C, C, pb, vec != 0);
+  __syncthreads();
+  if ((int)threadIdx.x < ng) {
+    float* a = pa + threadIdx.x * (C + 1);
+    float* b = pb + threadIdx.x * (C + 1);
+    const float la = dm_group_lse(a, C), lb = dm_group_lse(b, C);
+    float gk = 0.f;
+    for (int k = 0; k < C; ++k) {
+      const float lp = a[k] - la, lq = b[k] - lb;
+      gk += expf(lp) * (lp - lq);
+    }
+    for (int k = 0; k < C; ++k) {
+      const float lp = a[k] - la, lq = b[k] - lb;
+      const float p = expf(lp), q = expf(lq);
+      a[k] = sp * p * ((lp - lq) - gk);
+      b[k] = sq * (q - p);
+    }
+  }
+  __syncthreads();
+  kl_stage_out(pa, ng * C, C, dpost + base, vec != 0);
+  kl_stage_out(pb, ng * C, C, dprior + base, vec != 0);
+}
+
 // ---- IWAE (iwae_samples = I > 1; dreamer.py:340-343,362-365, functions.py:97-102, rssm.py:35-41) ------------------
 // Sampled KL term: loss_kl[n] = log q(z_n) - log p(z_n) with z the drawn one-hot sample.  OneHotCategorical.log_prob
 // goes through value.max(-1) (indices), so no gradient flows through z itself:
@@ -1661,6 +1789,13 @@ int dm_kl_fwd_launch(int rows, int S, int C, const float* post, const float* pri
     DM_LAUNCH_CHECK();
     return DM_OK;
   }
+  if (kl_fwd_staged_ok(S, C)) {
+    const int vec = (((uintptr_t)post | (uintptr_t)prior) & 15) == 0;      // a workgroup's run starts a multiple of 16 bytes in
+    hipLaunchKernelGGL(kl_fwd_staged_kernel, dim3(dm_cdiv(rows, 4)), dim3(KL_G), (size_t)2 * KL_G * (C + 1) * sizeof(float), st,
+                       rows, S, C, vec, post, prior, kl, ep, eq);
+    DM_LAUNCH_CHECK();
+    return DM_OK;
+  }
   hipLaunchKernelGGL(kl_fwd_kernel, dim3(dm_cdiv(rows, 4)), dim3(256), 0, st, rows, S, C, post, prior, kl, ep, eq);
   DM_LAUNCH_CHECK();
   return DM_OK;
@@ -1671,6 +1806,13 @@ int dm_kl_bwd_launch(int rows, int S, int C, const float* post, const float* pri
   if (C == 0) {
     hipLaunchKernelGGL(gauss_kl_bwd_kernel, dim3(ew_blocks((size_t)rows * S)), dim3(256), 0, st, rows, S, post, prior, sp, sq,
                        dpost, dprior);
+    DM_LAUNCH_CHECK();
+    return DM_OK;
+  }
+  if (kl_staged_ok(C)) {
+    const int vec = (((uintptr_t)post | (uintptr_t)prior | (uintptr_t)dpost | (uintptr_t)dprior) & 15) == 0;
+    hipLaunchKernelGGL(kl_bwd_staged_kernel, dim3(dm_cdiv(rows * S, KL_G)), dim3(KL_G), (size_t)2 * KL_G * (C + 1) * sizeof(float),
+                       st, rows * S, C, vec, post, prior, sp, sq, dpost, dprior);
     DM_LAUNCH_CHECK();
     return DM_OK;
   }

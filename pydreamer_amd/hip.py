@@ -217,7 +217,9 @@ _SIGNATURES = {
     'dm_bf16_twins_enable': (c_int, [c_int]),
     'dm_gemm_dma_enable': (c_int, [c_int]),
     'dm_convt_kskip_enable': (c_int, [c_int]),
+    'dm_kl_staged_enable': (c_int, [c_int]),
     'dm_dec_l4_bwd_direct_enable': (c_int, [c_int]),
+    'dm_dec_l4_fwd_shared_enable': (c_int, [c_int]),
     'dm_rssm_lds_enable': (c_int, [c_int]),
     'dm_bptt_fold_enable': (c_int, [c_int]),
     'dm_rssm_lds_status': (c_int, []),
