@@ -43,7 +43,9 @@ typedef struct dm_shape {
   int32_t H;                /* imag_horizon */
   int32_t D, Hd;            /* deter_dim, hidden_dim */
   int32_t S, C;             /* stoch_dim, stoch_discrete (Z = S*C) */
-  int32_t E;                /* embed dim = 32*cnn_depth (encoders.py:76) */
+  int32_t E;                /* embed dim: the RSSM takes any E >= 1.  32*cnn_depth for the convolution encoder (encoders.py:76), + 256
+                               with a vecobs MLP beside it, 256 for the dense image encoder and for an image-less model
+                               (encoders.py:25,34; then cnn_depth = img = img_ch = 0: no image geometry is read or sized) */
   int32_t A;                /* action_dim */
   int32_t mlp_hidden;       /* 400 (a2c.py:16, decoders.py:259,289) */
   int32_t mlp_layers;       /* 4  (defaults.yaml:83,85; a2c.py:17) */

@@ -42,6 +42,8 @@ SECTIONS = {
     'minigrid': dict(image_key='image', image_size=7, image_channels=4, image_categorical=True, map_key='map', map_size=11,
                      map_channels=4, map_categorical=True, action_dim=7, reward_input=True, image_encoder='dense',
                      image_encoder_layers=3, image_decoder='dense', image_decoder_layers=2, probe_model='map', imag_horizon=1),
+    # defaults.yaml:236-242: no image at all - the vector observation is the only input (models.imageless_gate)
+    'vectorenv': dict(action_dim=2, vecobs_size=4, image_key=None, image_encoder=None, image_decoder=None),
     'minecraft': dict(action_dim=29, vecobs_size=27, clip_rewards='log1p'),      # defaults.yaml:244-248
     'debug': dict(device='cpu', batch_length=15, batch_size=5, imag_horizon=3),
 }

@@ -15,7 +15,10 @@ probe_model in {none, map, goals, map+goals} (map: the CatImageDecoder probe of 
 4.8; goals: two DenseNormalDecoders of the goal directions with the metrics of csrc/goals.hip, DESIGN 4.9, needs goals_size >= 1;
 not with probe_gradients=True, whose gradient into the world model's features is not built), reward_input (cnn_depth in {8, 16, 32, 48, 64}: the reward and terminal planes are folded into the first
 convolution), vecobs_size > 0 beside the image (an MLP encoder whose output sits behind the image embedding, a
-DenseNormalDecoder with out_dim = vecobs_size).
+DenseNormalDecoder with out_dim = vecobs_size), or vecobs_size > 0 with NO image at all - image_encoder and image_decoder both
+empty (None or ''), the `vectorenv` section; the gate is imageless_gate(), DESIGN 4.12: the vecobs MLP's output is the RSSM's
+embedding, the loss has no image term, obs needs no `image`, probe_model must be 'none', reward_input is ignored as in the
+reference; everything in the RSSM, the heads and the actor-critic works as beside an image).
 """
 import contextlib
 import ctypes
@@ -237,6 +240,27 @@ def dense_image_gate(conf):
     return True
 
 
+def _empty(x):
+    return x is None or x == ''
+
+
+def imageless_gate(conf):
+    """True when conf selects a world model with no image at all (the `vectorenv` section): image_encoder and
+    image_decoder BOTH empty (None or ''), vecobs_size >= 1.  Both empty without a vector observation is the reference's own
+    assertion (encoders.py:38) -> ValueError; exactly one of the two empty stays NotImplementedError."""
+    enc, dec = _empty(conf.image_encoder), _empty(conf.image_decoder)
+    if not enc and not dec:
+        return False
+    if enc != dec:
+        raise NotImplementedError(f'image_encoder={conf.image_encoder!r} with image_decoder={conf.image_decoder!r}: the image-less '
+                                  'path needs both or neither of them empty (an encoder without its decoder, or the reverse, is '
+                                  'not built in the HIP path)')
+    if int(conf.vecobs_size or 0) < 1:
+        raise ValueError('image_encoder and image_decoder are both empty and vecobs_size is 0: the encoder has no input at all '
+                         '(the reference asserts `encoder_image or encoder_vecobs`, encoders.py:38)')
+    return True
+
+
 class DenseEncoder(MLP):
     """encoders.py:99-125: model = Sequential[Flatten, (Linear, LayerNorm | NoNorm, ELU) x L, Linear, ELU] - the Linears sit at
     1, 4, ..., 3L + 1, one behind the indices of `MLP`.  The marshalling, forward and backward are MLP's; the trailing ELU is
@@ -259,7 +283,8 @@ REWARD_INPUT_DEPTHS = (8, 16, 32, 48, 64)     # the depths of the direct layer-1
 
 
 class MultiEncoder(_Params):
-    """encoders.py:10-69 (image encoder, with or without the reward / terminal planes of reward_input)."""
+    """encoders.py:10-69 (image encoder, with or without the reward / terminal planes of reward_input; the vecobs MLP beside it,
+    or alone on the image-less path)."""
 
     def __init__(self, conf):
         super().__init__()
@@ -269,6 +294,12 @@ class MultiEncoder(_Params):
                                               conf.image_encoder_layers, conf.layer_norm)
             self.encoder_vecobs = None
             self.out_dim = self.encoder_image.out_dim
+            return
+        if imageless_gate(conf):        # encoders.py:28-40,64-69: no image branch; reward_input is read inside it only, so it is ignored
+            self.reward_input = False
+            self.encoder_image = None
+            self.encoder_vecobs = MLP(conf.vecobs_size, VECOBS_EMBED, MLP_HIDDEN, 2, conf.layer_norm)
+            self.out_dim = VECOBS_EMBED
             return
         if conf.image_encoder != 'cnn':
             raise NotImplementedError("only image_encoder=cnn (with or without vecobs beside it) and the dense categorical image "
@@ -324,13 +355,16 @@ class MultiDecoder(_Params):
     def __init__(self, features_dim, conf):
         super().__init__()
         dense = dense_image_gate(conf)
-        if (conf.image_decoder != 'cnn' and not dense) or conf.reward_decoder_categorical:
+        imageless = not dense and imageless_gate(conf)
+        if (conf.image_decoder != 'cnn' and not dense and not imageless) or conf.reward_decoder_categorical:
             raise NotImplementedError('only image_decoder=cnn (or the dense categorical image path, dense_image_gate) with Normal '
                                       'reward decoder is built in the HIP path')
         self.image_weight, self.reward_weight, self.terminal_weight = conf.image_weight, conf.reward_weight, conf.terminal_weight
         if dense:      # decoders.py:23-28
             self.image = CatImageDecoder(features_dim, (conf.image_channels, conf.image_size, conf.image_size),
                                          conf.image_decoder_layers, conf.layer_norm, conf.image_decoder_min_prob)
+        elif imageless:      # decoders.py:29-30: no image term in loss_reconstr, no image tensors
+            self.image = None
         else:
             self.image = ConvDecoder(in_dim=features_dim, out_channels=conf.image_channels, cnn_depth=conf.cnn_depth)
         self.reward = DenseNormalDecoder(features_dim, conf.reward_decoder_layers, conf.layer_norm)
@@ -994,7 +1028,9 @@ class WorldModel(_Params):
         if conf.aux_critic and conf.iwae_samples != 1:
             raise NotImplementedError('aux_critic assumes iwae_samples = 1 (as the reference does, dreamer.py:349)')
         self.dense = dense_image_gate(conf)      # the dense categorical image path instead of the convolution stacks
-        if not self.dense and conf.image_size != 64:
+        # no image at all: image_size, image_channels and cnn_depth are not read on that path
+        self.imageless = not self.dense and imageless_gate(conf)
+        if not self.dense and not self.imageless and conf.image_size != 64:
             raise NotImplementedError('conv geometry is built for 64x64 observations')
         self.conf = conf
         self.deter_dim, self.stoch_dim, self.stoch_discrete = conf.deter_dim, conf.stoch_dim, conf.stoch_discrete
@@ -1030,8 +1066,9 @@ class WorldModel(_Params):
         c = self.conf
         return H.make_shape(T=T, B=B, I=1, H=H_, D=c.deter_dim, Hd=c.hidden_dim, S=c.stoch_dim, C=c.stoch_discrete,
                             E=self.encoder.out_dim, A=c.action_dim, mlp_hidden=MLP_HIDDEN, mlp_layers=4,
-                            cnn_depth=1 if self.dense else c.cnn_depth,      # (dense: no convolution scratch in dm_workspace_bytes)
-                            img=c.image_size, img_ch=c.image_channels,
+                            # (dense: no convolution scratch in dm_workspace_bytes; image-less: no image geometry at all)
+                            cnn_depth=0 if self.imageless else 1 if self.dense else c.cnn_depth,
+                            img=0 if self.imageless else c.image_size, img_ch=0 if self.imageless else c.image_channels,
                             flags=ACTOR_KINDS.get(c.actor_dist, 0) | (H.GRU_KINDS[c.gru_type] << H.DM_FLAG_GRU_SHIFT) |
                             ((c.gru_layers - 1) << H.DM_FLAG_GRU_LAYERS_SHIFT) |
                             (H.DM_FLAG_BF16 if getattr(c, 'amp', False) else 0))
@@ -1102,12 +1139,17 @@ class WorldModel(_Params):
         encoder sees the T*B frames once.  Three geometry structs: `shp` (T,B,I: conv decoder + workspace), `shp_e`
         (T,B,1: encoder), `shp_r` (T, B*I, 1: the RSSM calls take the expanded batch as their batch)."""
         c = self.conf
-        image, action = obs['image'], obs['action']
-        _require_cuda(image, "obs['image']")
+        action = obs['action']
+        if self.imageless:      # no frame ingest, no obs['image'] (DESIGN 4.12): the step's device is the action's
+            image = None
+            _require_cuda(action, "obs['action']")
+        else:
+            image = obs['image']
+            _require_cuda(image, "obs['image']")
         T, B = action.shape[:2]
         I = int(iwae)
         BI, NE = B * I, T * B
-        N, dev = T * B * I, image.device
+        N, dev = T * B * I, action.device if self.imageless else image.device
         D_, F_, E = c.deter_dim, self.features_dim, self.encoder.out_dim
         gauss = not c.stoch_discrete         # Gaussian latents: z is stoch_dim wide, its parameters (mean | raw std) twice that
         Z, ZP = c.stoch_dim * (c.stoch_discrete or 1), c.stoch_dim * (c.stoch_discrete or 2)
@@ -1116,8 +1158,10 @@ class WorldModel(_Params):
         shp = self.shape(T, B, imag_horizon)
         shp.I = I
         ws = self.workspace(shp, dev)
-        u8 = image.dtype == torch.uint8 and not self.dense
-        if self.dense:
+        u8 = not self.imageless and image.dtype == torch.uint8 and not self.dense
+        if self.imageless:
+            pass
+        elif self.dense:
             # the reference's float one-hot (T,B,C,S,S) (preprocessing.py:108-109) or an integer class map (T,B,S,S): same bits
             if not image.is_floating_point() and image.dim() == 5:
                 raise ValueError(f'the dense image path takes a float one-hot (T,B,C,S,S) image or an integer class map (T,B,S,S), '
@@ -1141,7 +1185,11 @@ class WorldModel(_Params):
                     (T, B, c.image_channels, c.image_size, c.image_size), action=(T, B, c.action_dim), reset=(T, B))
         if self.dense and not image.is_floating_point():
             want['image'] = (T, B, c.image_size, c.image_size)
-        got = dict(image=tuple(image.shape), action=tuple(action.shape), reset=tuple(reset.shape))
+        got = dict(action=tuple(action.shape), reset=tuple(reset.shape))
+        if self.imageless:
+            del want['image']
+        else:
+            got['image'] = tuple(image.shape)
         planes = self.encoder.reward_input
         for k in ('reward', 'terminal'):
             if planes and k not in obs:
@@ -1180,10 +1228,11 @@ class WorldModel(_Params):
 
         enc = self.encoder.encoder_image
         enc_p = enc_acts = None
-        if not self.dense:
+        conv = not self.dense and not self.imageless
+        if conv:
             enc_p = H.conv_struct([m.weight for m in enc.convs()], [m.bias for m in enc.convs()])
             enc_acts = torch.empty(int(lib.dm_conv_encoder_acts_floats(ctypes.byref(shp_e))), device=dev)
-        embed = torch.empty(NE, E, device=dev)
+        embed = None if self.imageless else torch.empty(NE, E, device=dev)      # image-less: the vecobs MLP's own output buffer
         cell = self.core.cell
         rssm_p = H.rssm_struct(cell.ordered())
         if open_loop:
@@ -1205,14 +1254,15 @@ class WorldModel(_Params):
         fidx = forced_idx.to(torch.int32).contiguous() if forced_idx is not None else None
         u_ptr = H.fptr(u_post) if u_post is not None else None
         dec = self.decoder
-        dec_p = dec_acts = None
-        if not self.dense:
+        dec_p = dec_acts = loss_image = None
+        if conv:
             dl = dec.image.layers()
             dec_p = H.conv_struct([m.weight for m in dl], [m.bias for m in dl])
         if not forward_only:
-            if not self.dense:
+            if conv:
                 dec_acts = torch.empty(int(lib.dm_conv_decoder_acts_floats(ctypes.byref(shp))), device=dev)
-            loss_image = torch.empty(N, device=dev)
+            if not self.imageless:
+                loss_image = torch.empty(N, device=dev)
             image_rec = None          # materialised lazily from the decoder's saved prediction (see LazyTensors)
 
         # rssm.py:35-41: (T,B,X) -> (T,B*I,X), pure data movement (I = 1: the caller's tensors as they are)
@@ -1229,7 +1279,11 @@ class WorldModel(_Params):
             plane_r = obs['reward'].float().contiguous().view(NE)
             plane_t = obs['terminal'].float().contiguous().view(NE)
         enc_x = None
-        if self.dense:
+        if self.imageless:
+            # encoders.py:64-69 with encoder_image = None: the vecobs MLP's (T*B, 256) output IS the RSSM's embed, no copy pass
+            vecobs = obs['vecobs'].float().contiguous().view(NE, V)
+            embed, ev_acts = self.encoder.encoder_vecobs.fwd(vecobs, V, NE, ws, save_acts=not forward_only and torch.is_grad_enabled())
+        elif self.dense:
             enc_x, enc_acts = self._dense_encode(image, plane_r, plane_t, embed, NE, ws,
                                                  save=not forward_only and torch.is_grad_enabled())
         elif planes or V:
@@ -1288,7 +1342,12 @@ class WorldModel(_Params):
         D_, F_ = c.deter_dim, self.features_dim
         gauss = not c.stoch_discrete
         Z = c.stoch_dim * (c.stoch_discrete or 1)
-        if self.dense:      # CatImageDecoder.training_step (decoders.py:238-254): MLP -> per-cell cross-entropy, I = 1
+        # image-less (decoders.py:29-30,59-64): no image term.  `none` stands in the image's place in the one-launch sums below: an
+        # item of zero elements sums to an exact 0.0, so metric slot 1 stays zero and is never named
+        none = torch.empty(0, device=dev) if self.imageless else None
+        if self.imageless:
+            pass
+        elif self.dense:      # CatImageDecoder.training_step (decoders.py:238-254): MLP -> per-cell cross-entropy, I = 1
             train = torch.is_grad_enabled()
             target = pk['target'] = self._dense_target(image, NE)
             logits, dec_acts = dec.image.fwd(feat, F_, N, ws, save_acts=train)
@@ -1367,14 +1426,16 @@ class WorldModel(_Params):
             _multi_sum([(lc, 1.0 / rows), (value.view(T, B)[:-1], 1.0 / rows)], dev, out=mbuf[24:26])
             aux = dict(acts=aux_acts, dvalue=dvalue, value=value, lc=lc, rows=rows)
         if I == 1:
-            means = _multi_sum([(kl, 1.0 / N), (loss_image, 1.0 / N), (loss_reward, 1.0 / N), (loss_terminal, 1.0 / N),
-                                (ent_prior, 1.0 / N), (ent_post, 1.0 / N)], dev, out=mbuf[0:6])
+            means = _multi_sum([(kl, 1.0 / N), (none if self.imageless else loss_image, 1.0 / N), (loss_reward, 1.0 / N),
+                                (loss_terminal, 1.0 / N), (ent_prior, 1.0 / N), (ent_post, 1.0 / N)], dev, out=mbuf[0:6])
             terms = [(kl, 1.0 / N), (loss_image, 1.0 / N), (loss_reward, 1.0 / N), (loss_terminal, 1.0 / N)]
             wts = [self.kl_weight, dec.image_weight, dec.reward_weight, dec.terminal_weight]
-            if V:      # loss_reconstr += vecobs_weight * loss_vecobs (decoders.py:68): a fifth term of loss_model
+            if self.imageless:      # four terms: kl, reward, terminal and (below) vecobs
+                del terms[1], wts[1]
+            if V:      # loss_reconstr += vecobs_weight * loss_vecobs (decoders.py:68): one more term of loss_model
                 _multi_sum([(loss_vecobs, 1.0 / N)], dev, out=mbuf[15:16])
                 terms, wts = terms + [(loss_vecobs, 1.0 / N)], wts + [dec.vecobs_weight]
-                H.call('dm_combine', 5, H.fptr(_multi_sum(terms, dev)), (ctypes.c_float * 5)(*wts),
+                H.call('dm_combine', len(wts), H.fptr(_multi_sum(terms, dev)), (ctypes.c_float * len(wts))(*wts),
                        ctypes.c_void_p(mbuf.data_ptr() + 24), H.stream())
             else:
                 H.call('dm_combine', 4, H.fptr(means), w, ctypes.c_void_p(mbuf.data_ptr() + 24), H.stream())   # dreamer.py:362-365
@@ -1383,7 +1444,7 @@ class WorldModel(_Params):
                 H.call('dm_combine', len(wts), H.fptr(_multi_sum(terms, dev)), (ctypes.c_float * len(wts))(*wts),
                        ctypes.c_void_p(mbuf.data_ptr() + 28), H.stream())
                 loss = mbuf[7]
-            tb = lambda x: x.view(T, B)
+            tb = lambda x: None if x is None else x.view(T, B)
             t_kl, t_ep, t_eq, t_li, t_lr, t_lt, t_rr, t_tr = (tb(x) for x in (kl, ent_prior, ent_post, loss_image, loss_reward,
                                                                               loss_terminal, reward_rec, terminal_rec))
             if V:
@@ -1401,6 +1462,8 @@ class WorldModel(_Params):
                        H.stream())
             l_tbi = torch.empty(N, device=dev)
             rows_l, rows_w = [kl_s, loss_image, loss_reward, loss_terminal], list(w)
+            if self.imageless:
+                del rows_l[1], rows_w[1]
             if V:
                 rows_l, rows_w = rows_l + [loss_vecobs], rows_w + [dec.vecobs_weight]
             ptrs = (ctypes.c_void_p * len(rows_l))(*[x.data_ptr() for x in rows_l])
@@ -1410,9 +1473,10 @@ class WorldModel(_Params):
             H.call('dm_reduce_i', NE, I, 1, H.fptr(l_tbi), 1, H.fptr(red[0]), H.fptr(iw), H.stream())
             for j, (x, mode) in enumerate(((kl, 1), (loss_image, 1), (loss_reward, 1), (loss_terminal, 1), (ent_prior, 0),
                                            (ent_post, 0), (reward_rec, 0), (terminal_rec, 0))):
-                H.call('dm_reduce_i', NE, I, 1, H.fptr(x), mode, H.fptr(red[j + 1]), None, H.stream())
-            _multi_sum([(red[1], 1.0 / NE), (red[2], 1.0 / NE), (red[3], 1.0 / NE), (red[4], 1.0 / NE), (red[5], 1.0 / NE),
-                        (red[6], 1.0 / NE), (red[0], 1.0 / NE)], dev, out=mbuf[0:7])
+                if x is not None:      # (image-less: row 2 of `red` is never written nor read)
+                    H.call('dm_reduce_i', NE, I, 1, H.fptr(x), mode, H.fptr(red[j + 1]), None, H.stream())
+            _multi_sum([(red[1], 1.0 / NE), (none if self.imageless else red[2], 1.0 / NE), (red[3], 1.0 / NE), (red[4], 1.0 / NE),
+                        (red[5], 1.0 / NE), (red[6], 1.0 / NE), (red[0], 1.0 / NE)], dev, out=mbuf[0:7])
             means = mbuf[0:6]
             tb = lambda x: x.view(T, B)
             t_kl, t_li, t_lr, t_lt, t_ep, t_eq, t_rr, t_tr = (tb(red[j]) for j in range(1, 9))
@@ -1429,22 +1493,25 @@ class WorldModel(_Params):
                                     loss_image=t_li, image_rec=None,
                                     loss_reward=t_lr, reward_rec=t_rr,
                                     loss_terminal=t_lt, terminal_rec=t_tr)
-        Cc, hw = c.image_channels, c.image_size * c.image_size
-        if self.dense:
-            def image_rec_thunk(logits=pk['dec_logits'], target=pk['target']):      # holds the logits alive until the dict is dropped
-                with torch.no_grad():
-                    return self._dense_logp(logits, target, NE).view(T, B, Cc, c.image_size, c.image_size)
-        else:
-            pred_off = int(lib.dm_conv_decoder_pred_offset(ctypes.byref(shp)))
-
-            def image_rec_thunk(acts=dec_acts):       # holds the decoder activations alive until the dict is dropped
-                with torch.no_grad():
-                    pred = acts[pred_off:pred_off + N * hw * Cc].view(N, hw, Cc)                       # NHWC
-                    rec = pred.transpose(1, 2).contiguous().view(T, B, I, Cc, c.image_size, c.image_size)   # -> (T,B,I,C,H,W)
-                    return rec[:, :, 0] if I == 1 else rec.mean(2)       # decoded.mean(dim=2), decoders.py:171 (logging only)
-        pk['tensors'].lazy('image_rec', image_rec_thunk)
         pk['metrics'] = dict(loss_model=mbuf[6], loss_kl=means[0], entropy_prior=means[4], entropy_post=means[5],
                              loss_image=means[1], loss_reward=means[2], loss_terminal=means[3])
+        if self.imageless:      # decoders.py:59-64: there is no loss_image metric and no loss_image / image_rec tensor
+            del pk['metrics']['loss_image'], pk['tensors']['loss_image'], pk['tensors']['image_rec']
+        else:
+            Cc, hw = c.image_channels, c.image_size * c.image_size
+            if self.dense:
+                def image_rec_thunk(logits=pk['dec_logits'], target=pk['target']):      # holds the logits alive until the dict is dropped
+                    with torch.no_grad():
+                        return self._dense_logp(logits, target, NE).view(T, B, Cc, c.image_size, c.image_size)
+            else:
+                pred_off = int(lib.dm_conv_decoder_pred_offset(ctypes.byref(shp)))
+
+                def image_rec_thunk(acts=dec_acts):       # holds the decoder activations alive until the dict is dropped
+                    with torch.no_grad():
+                        pred = acts[pred_off:pred_off + N * hw * Cc].view(N, hw, Cc)                       # NHWC
+                        rec = pred.transpose(1, 2).contiguous().view(T, B, I, Cc, c.image_size, c.image_size)   # -> (T,B,I,C,H,W)
+                        return rec[:, :, 0] if I == 1 else rec.mean(2)       # decoded.mean(dim=2), decoders.py:171 (logging only)
+            pk['tensors'].lazy('image_rec', image_rec_thunk)
         if V:
             pk['metrics'].update(loss_vecobs=mbuf[15])
             pk['tensors'].update(loss_vecobs=t_lv, vecobs_rec=t_vr)
@@ -1489,7 +1556,8 @@ class WorldModel(_Params):
             H.call('dm_mlp_head_bwd', N, F_, head.hidden_dim, head.hidden_layers, head.out_dim, H.fptr(feat), F_, ctypes.byref(st),
                    H.fptr(acts), H.fptr(dout), ctypes.byref(gs), H.fptr(dfeat), F_, 1, H.ptr(ws), ws.numel(), H.stream())
         # image decoder
-        if not self.dense:
+        conv = not self.dense and not self.imageless
+        if conv:
             dl = dec.image.layers()
             dec_p = H.conv_struct([m.weight for m in dl], [m.bias for m in dl])
             dec_g = H.conv_struct([gof[id(m.weight)] for m in dl], [gof[id(m.bias)] for m in dl], cls=H.dm_conv_grads)
@@ -1501,7 +1569,8 @@ class WorldModel(_Params):
         # (measured: no gain on a 7-column shard, -1.1 ms at 25 columns.  Rounds 3-5 switched it off under data parallelism, unmeasured;
         #  round 6 measured it over a one-rank RCCL group: off costs +0.9 ... +1.2 ms at 25 / 50 columns, on costs nothing beside the
         #  all-reduce - profiles/r06_force_dp.txt run K: it stays on there.)
-        side = defer_wgrad and _WGRAD_SIDE and B * I >= 16 and not torch.cuda.is_current_stream_capturing() and not self.dense
+        # (off on the dense and the image-less paths: no decoder call to hide the weight gradients behind, not measured there)
+        side = defer_wgrad and _WGRAD_SIDE and B * I >= 16 and not torch.cuda.is_current_stream_capturing() and conv
         ws_dec = ws_enc = ws
         if side:
             need = H.workspace_bytes(shp)
@@ -1511,7 +1580,7 @@ class WorldModel(_Params):
             ws_dec, ws_enc = self._ws_dec, self._ws_enc       # decoder / BPTT (`ws`) / encoder: one workspace each until the join
             H.call('dm_wgrad_side_arm', 1)
         try:
-            if not self.dense:
+            if conv:
                 H.call('dm_conv_decoder_mse_bwd_rows', ctypes.byref(shp), H.fptr(feat), F_, H.ptr(pk['image']), ctypes.byref(dec_p),
                        H.fptr(pk['dec_acts']), gw * dec.image_weight / NE, H.fptr(iw), ctypes.byref(dec_g), H.fptr(dfeat), F_,
                        H.ptr(ws_dec), ws_dec.numel(), H.stream())
@@ -1554,6 +1623,13 @@ class WorldModel(_Params):
                 H.call('dm_mlp_head_bwd', NE, enc.in_dim, enc.hidden_dim, enc.hidden_layers, enc.out_dim, H.fptr(pk['enc_x']),
                        enc.in_dim, ctypes.byref(st), H.fptr(pk['enc_acts']), H.fptr(dembed), ctypes.byref(gs), None, 0, 0,
                        H.ptr(ws_enc), ws_enc.numel(), H.stream())
+                return views, flat, direct
+            if self.imageless:      # the whole (T*B, 256) dembed is the vecobs MLP's output gradient; no input gradient
+                ev = self.encoder.encoder_vecobs
+                st, gs = ev.struct(), ev.grad_struct(gof)
+                H.call('dm_mlp_head_bwd', NE, ev.in_dim, ev.hidden_dim, ev.hidden_layers, ev.out_dim, H.fptr(pk['vecobs']), ev.in_dim,
+                       ctypes.byref(st), H.fptr(pk['ev_acts']), H.fptr(dembed), ctypes.byref(gs), None, 0, 0, H.ptr(ws_enc),
+                       ws_enc.numel(), H.stream())
                 return views, flat, direct
             enc_p = H.conv_struct([m.weight for m in enc.convs()], [m.bias for m in enc.convs()])
             enc_g = H.conv_struct([gof[id(m.weight)] for m in enc.convs()], [gof[id(m.bias)] for m in enc.convs()],
@@ -1603,8 +1679,12 @@ class WorldModel(_Params):
             idx = torch.empty(N, S, dtype=torch.int32, device=dev)
             H.call('dm_sample_onehot', N, S, C, H.fptr(pk['prior']), S * (C or 2), H.fptr(u_pred), None,
                    ctypes.c_void_p(fp.data_ptr() + 4 * D_), F_, H.ptr(idx), H.stream())
-            li = torch.empty(N, device=dev)
-            if self.dense:      # loss and normalised log-probabilities of the decoder on the prior-sample features (I = 1)
+            li = image_pred = None
+            if not self.imageless:
+                li = torch.empty(N, device=dev)
+            if self.imageless:      # decoders.py:59-64: no logprob_image, no image_pred
+                pass
+            elif self.dense:      # loss and normalised log-probabilities of the decoder on the prior-sample features (I = 1)
                 logits, _ = dec.image.fwd(fp, F_, N, ws, save_acts=False)
                 self._dense_loss(logits, pk['target'], N, li, None)
                 image_pred = self._dense_logp(logits, pk['target'], NE).view(T, B, I, c.image_channels, c.image_size, c.image_size)
@@ -1642,15 +1722,21 @@ class WorldModel(_Params):
             if I > 1:                              # TBI => TB
                 red = torch.empty(5, NE, device=dev)
                 for j, (x, mode) in enumerate(((li, 1), (lr, 1), (lt, 1), (rp, 0), (tp, 0))):
-                    H.call('dm_reduce_i', NE, I, 1, H.fptr(x), mode, H.fptr(red[j]), None, H.stream())
-                li, lr, lt, rp, tp = (red[j] for j in range(5))
-                image_pred = image_pred.mean(2)                               # decoded.mean(dim=2), decoders.py:171
-            else:
+                    if x is not None:
+                        H.call('dm_reduce_i', NE, I, 1, H.fptr(x), mode, H.fptr(red[j]), None, H.stream())
+                li, lr, lt, rp, tp = (None if self.imageless and j == 0 else red[j] for j in range(5))
+                if image_pred is not None:
+                    image_pred = image_pred.mean(2)                           # decoded.mean(dim=2), decoders.py:171
+            elif image_pred is not None:
                 image_pred = image_pred[:, :, 0]
             tb = lambda x: x.view(T, B)
-            tensors = dict(logprob_image=tb(li), logprob_reward=tb(lr), logprob_terminal=tb(lt),
-                           image_pred=image_pred, reward_pred=tb(rp), terminal_pred=tb(tp))
-            metrics = dict(logprob_image=li.mean(), logprob_reward=lr.mean(), logprob_terminal=lt.mean())
+            if self.imageless:
+                tensors = dict(logprob_reward=tb(lr), logprob_terminal=tb(lt), reward_pred=tb(rp), terminal_pred=tb(tp))
+                metrics = dict(logprob_reward=lr.mean(), logprob_terminal=lt.mean())
+            else:
+                tensors = dict(logprob_image=tb(li), logprob_reward=tb(lr), logprob_terminal=tb(lt),
+                               image_pred=image_pred, reward_pred=tb(rp), terminal_pred=tb(tp))
+                metrics = dict(logprob_image=li.mean(), logprob_reward=lr.mean(), logprob_terminal=lt.mean())
             if V:
                 tensors.update(logprob_vecobs=tb(lv), vecobs_pred=vp.view(T, B, V))
                 metrics.update(logprob_vecobs=lv.mean())
@@ -1901,6 +1987,8 @@ class Dreamer(nn.Module):
         if conf.probe_model != 'none' and conf.probe_gradients:
             raise NotImplementedError('probe_gradients=True with a probe model: the gradient of the probe loss into the world '
                                       "model's features is not built (the probe trains on detached features only)")
+        if conf.probe_model != 'none' and not dense_image_gate(conf) and imageless_gate(conf):
+            raise NotImplementedError(f'probe_model={conf.probe_model!r} on an image-less world model is not built (DESIGN 4.12)')
         features_dim = conf.deter_dim + conf.stoch_dim * (conf.stoch_discrete or 1)
         self.conf = conf
         self.iwae_samples, self.imag_horizon = conf.iwae_samples, conf.imag_horizon
@@ -2291,7 +2379,7 @@ class Dreamer(nn.Module):
                                 ac_tensors=tensors_ac, post=pk['post'], prior=pk['prior'], pred_idx=pk.get('pred_idx'))
         # Dream for a log sample (dreamer.py:163-180): T-1 imagined steps from the B first states, decoded to images
         dream_tensors = {}
-        if do_dream_tensors:
+        if do_dream_tensors and not self.wm.imageless:      # dreamer.py:164: skipped when there is no image decoder
             with torch.no_grad():
                 kind, dpk2 = self.ac.dist_kind, {}
                 # states[0, :, 0] (dreamer.py:170): the first of the I samples of every batch column at t = 0 = rows b*I

@@ -299,11 +299,15 @@ def preprocess_batch(batch, action_dim, clip_rewards=None, image_key='image', ma
     (T,B,H,W), which MapProbeHead takes as it is) with the same mask and coord.
     goals=True (preprocessing.py:171-178; the targets of the goals probe, models.GoalsProbe): `goals_direction` = `targets_vec`
     (T,B,G,2) reshaped to (T,B,2G), `goal_direction` = `target_vec`, both float32, and `goals_visage` passed through as float32
-    when the batch holds it.  With the default nothing of this is emitted."""
+    when the batch holds it.  With the default nothing of this is emitted.
+    image_key=None (or ''; preprocessing.py:106, the `vectorenv` section): the result has no `image`; `vecobs` is float32 and the
+    other fields are as always."""
     T, B = batch['reward'].shape[:2]
     out = {}
-    img = batch[image_key]
-    if image_categorical:                                    # img_to_onehot (preprocessing.py:15-18)
+    img = batch[image_key] if image_key else None
+    if not image_key:                                        # preprocessing.py:106: no `image` at all (an image-less world model)
+        pass
+    elif image_categorical:                                    # img_to_onehot (preprocessing.py:15-18)
         assert img.ndim == 4, f'expected a (T,B,H,W) class image under {image_key!r}, got {img.shape}'
         out['image'] = np.ascontiguousarray(np.eye(int(image_categorical), dtype=np.float32)[img].transpose(0, 1, 4, 2, 3))
     else:
@@ -406,12 +410,18 @@ def _feed_layout(replay, action_dim, image_key, map_key, map_categorical, who, g
         raise ValueError(f'{who} needs at least one episode file to lay out its slots (the repository is empty)')
     probe = _Episode(replay.files[0].load_data()).fields      # shapes only; draws nothing from the random stream
     T, B = replay.batch_length, replay.batch_size
-    img = probe[image_key]
-    if img.dtype != np.uint8 or img.ndim != 4:
-        raise ValueError(f'expected uint8 (T,H,W,C) frames in the episode files, got {img.dtype} {img.shape}')
-    spec = {'image': ((T, B) + img.shape[1:], np.uint8), 'action': ((T, B, action_dim), np.float32),
-            'action_next': ((T, B, action_dim), np.float32), 'terminal': ((T, B), np.float32),
-            'reward': ((T, B), np.float32), 'reset': ((T, B), np.bool_)}
+    spec = {}
+    if image_key:
+        img = probe[image_key]
+        if img.dtype != np.uint8 or img.ndim != 4:
+            raise ValueError(f'expected uint8 (T,H,W,C) frames in the episode files, got {img.dtype} {img.shape}')
+        spec['image'] = ((T, B) + img.shape[1:], np.uint8)
+    elif 'vecobs' not in probe:      # image_key=None: an image-less world model, whose only observation is the vector
+        raise ValueError(f"{who}(image_key=None): the episode files hold no 'vecobs' field - the only observation of an image-less "
+                         'world model')
+    spec.update({'action': ((T, B, action_dim), np.float32),
+                 'action_next': ((T, B, action_dim), np.float32), 'terminal': ((T, B), np.float32),
+                 'reward': ((T, B), np.float32), 'reset': ((T, B), np.bool_)})
     if 'vecobs' in probe:
         spec['vecobs'] = ((T, B) + probe['vecobs'].shape[1:], np.float32)
     if map_key:
@@ -431,7 +441,9 @@ class ReplayFeed:
     With map_key / map_categorical the slot also carries the map probe's inputs: `map` as the stored integer class map
     (T,B,H,W) - not preprocess_batch's one-hot; MapProbeHead takes either - and preprocess_batch's `map_seen_mask` and
     `map_coord` when the files hold their sources.  With goals=True it carries preprocess_batch's `goals_direction`,
-    `goal_direction` and (when the files hold it) `goals_visage`; files without targets_vec / target_vec raise at construction."""
+    `goal_direction` and (when the files hold it) `goals_visage`; files without targets_vec / target_vec raise at construction.
+    image_key=None (an image-less world model, the `vectorenv` section): the slot has no `image`, and files without `vecobs` - the
+    only observation then - raise ValueError at construction."""
 
     def __init__(self, replay, action_dim, clip_rewards=None, image_key='image', map_key=None, map_categorical=None, goals=False):
         if clip_rewards not in (None, '', False, 'tanh', 'log1p'):
@@ -466,7 +478,8 @@ class ReplayFeed:
 
     def fill(self, slot):
         raw = dict(self._small)
-        raw[self.image_key] = slot['image']
+        if self.image_key:
+            raw[self.image_key] = slot['image']
         raw['reset'] = slot['reset']
         if self.map_key:
             raw[self.map_key] = slot['map']
@@ -684,7 +697,8 @@ class DeviceReplay:
     episode's staging buffer, a table - is released or rewritten only after an event recorded behind its copy has fired.
     Errors of the producer surface from next().
 
-    Without `device` nothing touches the GPU: plan() alone is usable, the prepared episodes stay in ordinary host memory."""
+    Without `device` nothing touches the GPU: plan() alone is usable, the prepared episodes stay in ordinary host memory.
+    image_key=None: no frames are cached, uploaded or gathered (one field fewer; the files must hold `vecobs`, as for ReplayFeed)."""
 
     def __init__(self, replay, action_dim, device=None, depth=3, capacity_bytes=0, clip_rewards=None, image_key='image',
                  map_key=None, map_categorical=None, goals=False):
@@ -734,7 +748,7 @@ class DeviceReplay:
             r = np.tanh(r)
         elif self.clip_rewards == 'log1p':
             r = np.log1p(r)
-        vals = {'image': f[self.image_key], 'action': self._onehot(f['action']), 'action_next': self._onehot(f['action_next']),
+        vals = {'image': f[self.image_key] if self.image_key else None, 'action': self._onehot(f['action']), 'action_next': self._onehot(f['action_next']),
                 'terminal': f['terminal'].astype(np.float32) if 'terminal' in f else np.zeros(n, np.float32),
                 'reward': r, 'reset': f['reset'].astype(bool)}
         if 'vecobs' in self._rows:
