@@ -95,7 +95,8 @@ int dm_version(void);                 /* ABI version, currently 16 (v2: LayerNor
                                               dm_goals_stats_ws_floats of the goals probe; the dm_gru_sequence_ family of the
                                               gru_probe baseline; dm_dense_image_rows / dm_elu_rows_fwd / dm_elu_rows_bwd /
                                               dm_cat_image_loss_mix of the dense categorical image path; dm_convt_kskip_enable;
-                                              dm_kl_staged_enable; dm_dec_l4_fwd_shared_enable */
+                                              dm_kl_staged_enable; dm_dec_l4_fwd_shared_enable; dm_policy_draw /
+                                              dm_policy_draw_ws_floats of the acting path */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
 size_t dm_workspace_bytes(const dm_shape* shp);   /* scratch needed by any call below for this shape */
@@ -571,6 +572,30 @@ int dm_sample_continuous(int kind, int rows, int A, const float* params, const f
 int dm_actor_loss_continuous(int kind, int rows, int A, const float* params, const float* actions, const float* adv_gae,
                              const float* weight, float ent_w, float scale, float* loss, float* entropy, float* dparams,
                              void* stream);
+/* The acting path's draw (csrc/act.hip; generator.py:317-331 for `rows` environments): action, log-probability, entropy and the
+ * generator's three logged means from the actor's output rows, explicit noise and the critic's outputs.  kind follows
+ * dm_shape.flags bits 0-1: 0 = onehot, 1 = tanh_normal, 2 = normal_tanh.
+ *   params   (rows, A) logits for kind 0, (rows, 2A) [mean_raw | std_raw] for kinds 1, 2; leading dimension ldp
+ *   noise    kind 0: (rows) uniforms in [0,1); kinds 1, 2: (rows, A) standard normals
+ *   value    (rows) critic outputs, or NULL
+ *   action   (rows, A), leading dimension lda: the one-hot row (kind 0) or the continuous action
+ *   act_idx  (rows) the drawn class (kind 0), zero-filled for kinds 1, 2; or NULL
+ *   log_prob, entropy  (rows) each, or NULL
+ *   stats    4 floats: mean value (0 with value == NULL), mean exp(log_prob), mean entropy, 0
+ *   ws       dm_policy_draw_ws_floats(rows) floats of scratch
+ * kind 0: the index is the one dm_sample_onehot(rows, 1, A, ...) gives for the same logits and uniforms, bit for bit (softmax,
+ *   sequential fp32 cumsum in class order, idx = #{k : cdf_k <= u cdf_last} clamped to A - 1); log_prob = log_softmax[idx],
+ *   entropy = -sum p log p.
+ * kinds 1, 2: the action is the one dm_sample_continuous gives for the same params and noise, bit for bit; entropy is the base
+ *   Normal's summed over A for both kinds (functions.py:77); log_prob is the Normal's at the draw x = mean + std eps, for kind 1
+ *   plus sum_a -2 (log 2 - x_a - softplus(-2 x_a)), computed from the pre-tanh x - not from atanh of the (saturating) action.
+ * Two launches, no float atomics: the same inputs give the same bits.  Checked on the host before any launch: NULL params,
+ * noise, action, stats or ws -> DM_E_NULL; rows < 1, A < 1, kind outside {0, 1, 2}, ldp below the row width or lda < A ->
+ * DM_E_SHAPE; ws_bytes below the scratch size -> DM_E_WORKSPACE. */
+size_t dm_policy_draw_ws_floats(int rows);
+int dm_policy_draw(int kind, int rows, int A, const float* params, int ldp, const float* noise, const float* value, float* action,
+                   int lda, int32_t* act_idx, float* log_prob, float* entropy, float* stats, void* ws, size_t ws_bytes,
+                   void* stream);
 /* critic loss rows (a2c.py:112-115): loss[r] = 0.5*(vt-v)^2*w ; dvalue = scale * -(vt-v)*w. */
 int dm_critic_loss(int rows, const float* value, const float* value_target, const float* weight, float scale,
                    float* loss, float* dvalue, void* stream);

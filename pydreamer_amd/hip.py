@@ -242,6 +242,8 @@ _SIGNATURES = {
                                     POINTER(dm_gru_grads), _P, c_int, _P, c_size_t, _P]),
     'dm_gru_sequence_last_schedule': (c_int, []),
     'dm_gru_sequence_fuse_enable': (c_int, [c_int]),
+    'dm_policy_draw_ws_floats': (c_size_t, [c_int]),
+    'dm_policy_draw': (c_int, [c_int, c_int, c_int, _P, c_int, _P, _P, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

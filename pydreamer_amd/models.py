@@ -2183,6 +2183,53 @@ class Dreamer(nn.Module):
         action_distr = _torch_actor_distribution(self.ac.actor_dist, logits.view(1, B, -1))
         return action_distr, out_state, dict(policy_value=value.mean())
 
+    # ---- acting (generator.py:311-331 for B environments)
+    def act(self, obs, in_state, noise=None, return_rows=False):
+        """inference() followed, on the device, by what the reference's NetworkPolicy does with the distribution object: the draw,
+        log_prob(action).exp().mean(), entropy().mean() and policy_value - one dm_policy_draw call behind the actor and critic MLPs,
+        no torch op after them and no host synchronisation.  Returns (action (1,B,A) float32, out_state, metrics): metrics =
+        {policy_value, action_prob, policy_entropy}, 0-dim views of ONE 4-float device tensor (reading all three is one copy).
+        `obs`, `in_state`: as inference().  `noise`: dict with u_post (1,B,S) as for inference() and / or u_act - (B,) uniforms for
+        the one-hot actor, (B,A) standard normals for the continuous ones; what is missing is drawn on the device.  The action is
+        the one dm_sample_onehot / dm_sample_continuous give for the actor's output and u_act: the acting and the imagined policy
+        are the same function of the same numbers.  tanh_normal's log-probability is taken at the pre-tanh draw, not through atanh
+        of the action as the reference's log_prob(action) does (that loses the draw near saturation).
+        return_rows=True: metrics also holds log_prob, entropy, value (each (B,)) and, for the one-hot actor, act_idx ((B,) int32)."""
+        assert 'action' in obs, 'Observation should contain previous action'
+        act_shape = obs['action'].shape
+        assert len(act_shape) == 3 and act_shape[0] == 1, f'Expected shape (1,B,A), got {act_shape}'
+        B, A, kind = act_shape[1], self.conf.action_dim, self.ac.dist_kind
+        noise = noise or {}
+        u_act = noise.get('u_act')
+        ua_shape = (B,) if kind == 0 else (B, A)
+        if u_act is not None and tuple(u_act.shape) != ua_shape:
+            raise ValueError(f'actor noise has shape {tuple(u_act.shape)}, expected {ua_shape}')
+        with torch.no_grad():
+            self.join_optimizers()
+            features, out_state = self.wm.forward(obs, in_state, noise.get('u_post'))
+            feat = features.reshape(B, -1)
+            dev = feat.device
+            ws = self.wm.workspace(self.wm.shape(1, B, 1), dev)
+            logits, _ = self.ac.actor.fwd(feat, feat.shape[1], B, ws, save_acts=False)
+            value, _ = self.ac.critic.fwd(feat, feat.shape[1], B, ws, save_acts=False)
+            if u_act is None:
+                u_act = torch.rand(ua_shape, device=dev) if kind == 0 else torch.randn(ua_shape, device=dev)
+            u_act = u_act.float().contiguous()
+            action = torch.empty(1, B, A, device=dev)
+            stats = torch.empty(4, device=dev)
+            dws = torch.empty(int(H.lib().dm_policy_draw_ws_floats(B)), device=dev)
+            rows = torch.empty(2, B, device=dev) if return_rows else None
+            act_idx = torch.empty(B, dtype=torch.int32, device=dev) if return_rows and kind == 0 else None
+            H.call('dm_policy_draw', kind, B, A, H.fptr(logits), logits.shape[1], H.fptr(u_act), H.fptr(value), H.fptr(action), A,
+                   H.ptr(act_idx), H.fptr(rows), None if rows is None else H.fptr(rows[1]), H.fptr(stats), H.fptr(dws),
+                   dws.numel() * 4, H.stream())
+        metrics = dict(policy_value=stats[0], action_prob=stats[1], policy_entropy=stats[2])
+        if return_rows:
+            metrics.update(log_prob=rows[0], entropy=rows[1], value=value.view(B))
+            if kind == 0:
+                metrics['act_idx'] = act_idx
+        return action, out_state, metrics
+
     # ---- imagination (dreamer.py:188-216)
     def dream(self, in_state, imag_horizon, dynamics_gradients=False, u_act=None, u_prior=None, _pack=None):
         if dynamics_gradients:

@@ -1,0 +1,78 @@
+"""The acting process's policy object (generator.py:311-331) on Dreamer.act: preprocess -> one device call -> ONE device-to-host
+copy per environment step.  batch_size = 1 is the reference's generator; batch_size = N drives N environments as one batch."""
+import numpy as np
+import torch
+
+from .replay import preprocess_batch
+
+METRIC_KEYS = ('policy_value', 'action_prob', 'policy_entropy')
+_LOGGED_BY_ACTOR = METRIC_KEYS      # preprocessing.py:100: what an earlier policy call logged is not an observation
+
+
+class StepPreprocessor:
+    """Preprocessor.apply(obs, expandTB=True) (preprocessing.py:91-180) for one environment step, over replay.preprocess_batch:
+    the environment's observation dict -> numpy (1, B, ...) fields.  batched=False: `obs` holds one environment's fields, (*) =>
+    (1, 1, *); batched=True: every field carries a leading environment axis, (B, *) => (1, B, *).  The other arguments are
+    preprocess_batch's."""
+
+    def __init__(self, action_dim, clip_rewards=None, image_key='image', image_categorical=None, batched=False):
+        self.action_dim, self.clip_rewards, self.image_key = action_dim, clip_rewards, image_key
+        self.image_categorical, self.batched = image_categorical, batched
+
+    def __call__(self, obs):
+        lead = (np.newaxis,) if self.batched else (np.newaxis, np.newaxis)
+        batch = {k: np.asarray(v)[lead] for k, v in obs.items() if k not in _LOGGED_BY_ACTOR}
+        return preprocess_batch(batch, self.action_dim, clip_rewards=self.clip_rewards, image_key=self.image_key,
+                                image_categorical=self.image_categorical)
+
+
+class NetworkPolicy:
+    """generator.py:311-331.  `preprocess`: any callable from the environment's observation dict to numpy (1, B, ...) fields
+    (StepPreprocessor above; an object with the reference's `.apply(obs, expandTB=True)` is taken too).  __call__ returns
+    (action ndarray, {policy_value, action_prob, policy_entropy} as Python floats); the action is (A,) for batch_size == 1 as in
+    the reference, (B, A) otherwise.  The recurrent state is carried on the device between calls."""
+
+    def __init__(self, model, preprocess, batch_size=1, device=None):
+        self.model, self.preprocess, self.batch_size = model, preprocess, int(batch_size)
+        if device is None:
+            device = next(model.parameters()).device
+        self.device = torch.device(device)
+        self.state = self._to_device(model.init_state(self.batch_size))
+
+    def _to_device(self, state):
+        if isinstance(state, (tuple, list)):
+            return tuple(self._to_device(s) for s in state)
+        return state.to(self.device)
+
+    def reset_state(self, mask=None):
+        """Zero the carried state of the environments where `mask` ((B,) bools) is set - all of them without a mask - for callers
+        whose preprocessing does not emit `reset`."""
+        fresh = self._to_device(self.model.init_state(self.batch_size))
+        if mask is None:
+            self.state = fresh
+            return
+        m = torch.as_tensor(np.asarray(mask, dtype=bool)).to(self.device)
+        if tuple(m.shape) != (self.batch_size,):
+            raise ValueError(f'reset mask has shape {tuple(m.shape)}, expected ({self.batch_size},)')
+
+        def pick(old, new):      # states are (..., B, width): the mask runs over the batch axis
+            if isinstance(old, (tuple, list)):
+                return tuple(pick(o, n) for o, n in zip(old, new))
+            return torch.where(m.view((1,) * (old.dim() - 2) + (-1, 1)), new, old)
+
+        self.state = pick(self.state, fresh)
+
+    def __call__(self, obs):
+        batch = self.preprocess.apply(obs, expandTB=True) if hasattr(self.preprocess, 'apply') else self.preprocess(obs)
+        obs_model = {k: torch.from_numpy(np.ascontiguousarray(v)).to(self.device, non_blocking=True) for k, v in batch.items()}
+        B = obs_model['action'].shape[1]
+        if B != self.batch_size:
+            raise ValueError(f'the preprocessed observation holds {B} environments, this policy was built for {self.batch_size}')
+        action, self.state, metrics = self.model.act(obs_model, self.state)
+        # the step's single device-to-host wait: the action and the three scalars in one buffer
+        host = torch.cat([action.reshape(-1)] + [metrics[k].reshape(1) for k in METRIC_KEYS]).cpu().numpy()
+        A = action.shape[-1]
+        act = host[:B * A].reshape(B, A)
+        if B == 1:
+            act = act[0]      # (1,1,A) => A
+        return act.copy(), {k: float(host[B * A + i]) for i, k in enumerate(METRIC_KEYS)}
