@@ -1,16 +1,22 @@
 """WorldModelProbe(model='gru_probe'): the supervised baseline the probe numbers are read against (reference:
 pydreamer/models/baselines.py:19-111 WorldModelProbe, :314-357 GRUEncoderOnly).
 
-conv encoder -> Linear(E, 32) -> nn.GRU(32 + action_dim, deter_dim) -> probe, trained end to end through the probe loss
-(probe_gradients=True) with ONE optimizer.  As everywhere in this package the modules only own parameters; the step runs on the
+encoder -> Linear(E, 32) -> nn.GRU(32 + action_dim, deter_dim) -> probe, trained end to end through the probe loss
+(probe_gradients=True) with ONE optimizer.  The encoder is whatever MultiEncoder builds for the section: the convolution stack on
+64x64 frames, or - when models.dense_image_gate(conf) holds, the `minigrid` section - the DenseEncoder on a
+categorical image.  As everywhere in this package the modules only own parameters; the step runs on the
 C-ABI of libdreamer_hip.so: dm_conv_encoder_fwd(_planes), one dm_gemm_f32 for the squeeze (written straight into the leading 32
 columns of the GRU's input rows), dm_gru_sequence_fwd (csrc/gru_seq.hip), the probe heads of models.py unchanged,
 and in loss.backward() - on the caller's stream - the heads' backward WITH their input gradient, dm_gru_sequence_bwd, the squeeze
-backward and dm_conv_encoder_bwd(_planes), all into the one flat gradient buffer of the optimizer.
+backward and dm_conv_encoder_bwd(_planes), all into the one flat gradient buffer of the optimizer.  On the dense branch the two
+encoder calls are replaced by the entry points WorldModel uses for it: dm_dense_image_rows (from the float one-hot (T,B,C,S,S) or
+the integer class map (T,B,S,S): same bits), MLP.fwd, dm_elu_rows_fwd into `embed`; backward dm_elu_rows_bwd in place on dembed,
+then dm_mlp_head_bwd without an input gradient.  No entry point is new.
 
 Not built (NotImplementedError at construction): model in {vae, gru_vae, transformer_vae}; probe_gradients=False (the reference
 then returns the Python float 0.0 as its first loss, which train.py:187 cannot backpropagate); probe_model='none';
-vecobs_size > 0; amp=True.  Mid-sequence resets are not read, as in the reference (baselines.py:339: only reset[0] masks the
+vecobs_size > 0; amp=True; frames other than 64x64 outside the dense gate; image_encoder / image_decoder = 'dense' outside the
+gate (the gate's own NotImplementedError).  Mid-sequence resets are not read, as in the reference (baselines.py:339: only reset[0] masks the
 carried state).
 """
 import ctypes
@@ -102,7 +108,8 @@ class WorldModelProbe(nn.Module):
             raise NotImplementedError("model='gru_probe' with vecobs_size > 0 is not built in the HIP path")
         if getattr(conf, 'amp', False):
             raise NotImplementedError("model='gru_probe' with amp=True is not built: the GRU sequence kernels are fp32")
-        if conf.image_size != 64:
+        self.dense = M.dense_image_gate(conf)      # the DenseEncoder of the minigrid section; 'dense' outside the gate raises in it
+        if not self.dense and conf.image_size != 64:
             raise NotImplementedError('the HIP convolution stack is built for 64x64 images')
         assert conf.action_dim > 0, 'Need to set action_dim to match environment'
         if conf.deter_dim % 4:
@@ -145,11 +152,15 @@ class WorldModelProbe(nn.Module):
         c = self.conf
         return H.make_shape(T=T, B=B, I=1, H=1, D=c.deter_dim, Hd=getattr(c, 'hidden_dim', 0), S=getattr(c, 'stoch_dim', 0),
                             C=getattr(c, 'stoch_discrete', 0), E=self.wm.encoder.out_dim, A=c.action_dim, mlp_hidden=M.MLP_HIDDEN,
-                            mlp_layers=4, cnn_depth=c.cnn_depth, img=c.image_size, img_ch=c.image_channels, flags=0)
+                            # (dense: no convolution scratch in dm_workspace_bytes, as WorldModel.shape())
+                            mlp_layers=4, cnn_depth=1 if self.dense else c.cnn_depth, img=c.image_size, img_ch=c.image_channels, flags=0)
 
     def _workspace(self, shp, T, B, device):
         In = SQUEEZE_DIM + self.conf.action_dim
         need = max(H.workspace_bytes(shp), int(H.lib().dm_gru_sequence_ws_bytes(T, B, In, self.conf.deter_dim)))
+        if self.dense:      # the encoder MLP may be deeper than the four layers dm_workspace_bytes sizes the heads for
+            deep = max(4, self.wm.encoder.encoder_image.hidden_layers)
+            need = max(need, 4 * int(H.lib().dm_mlp_ws_floats(T * B, M.MLP_HIDDEN, deep)))
         if self._ws is None or self._ws.numel() < need or self._ws.device != device:
             self._ws = torch.empty(need, dtype=torch.uint8, device=device)
         return self._ws
@@ -165,7 +176,8 @@ class WorldModelProbe(nn.Module):
                       do_dream_tensors=False):
         """Returns (losses, out_state, metrics, tensors, {}) with losses = (loss_probe,) (baselines.py:110: 0.0 + loss_probe),
         out_state (1, B, D) detached, metrics / tensors exactly the probe's.  imag_horizon and the three flags are accepted and
-        have no effect, as in the reference.  obs: image (uint8 (T,B,64,64,C) or float (T,B,C,64,64)), reset (T,B) - only
+        have no effect, as in the reference.  obs: image (uint8 (T,B,64,64,C) or float (T,B,C,64,64); on the dense branch the float one-hot (T,B,C,S,S) or an
+        integer class map (T,B,S,S), as WorldModel takes them), reset (T,B) - only
         reset[0] is read -, action_next (T,B,A), reward / terminal (T,B) with reward_input, and the probe's targets."""
         if iwae_samples != 1:
             raise AssertionError('iwae_samples must be 1 for the gru_probe baseline (baselines.py:335)')
@@ -183,8 +195,13 @@ class WorldModelProbe(nn.Module):
         In = SQUEEZE_DIM + A_
         train = torch.is_grad_enabled()
         shp = self._shape(T, B)
-        u8 = image.dtype == torch.uint8
-        if u8:
+        u8 = image.dtype == torch.uint8 and not self.dense
+        if self.dense:
+            if not image.is_floating_point() and image.dim() == 5:
+                raise ValueError(f'the dense image path takes a float one-hot (T,B,C,S,S) image or an integer class map (T,B,S,S), '
+                                 f'not a {image.dtype} frame of shape {tuple(image.shape)}')
+            image = image.float().contiguous() if image.is_floating_point() else image.to(torch.int32).contiguous()
+        elif u8:
             image = image.contiguous()
             shp.flags |= H.DM_FLAG_IMAGE_U8
         else:
@@ -192,6 +209,8 @@ class WorldModelProbe(nn.Module):
         planes = wm.encoder.reward_input
         want = dict(image=(T, B, c.image_size, c.image_size, c.image_channels) if u8 else
                     (T, B, c.image_channels, c.image_size, c.image_size), action_next=(T, B, A_), reset=(T, B))
+        if self.dense and not image.is_floating_point():
+            want['image'] = (T, B, c.image_size, c.image_size)
         got = dict(image=tuple(image.shape), action_next=tuple(obs['action_next'].shape), reset=tuple(obs['reset'].shape))
         for k in ('reward', 'terminal'):
             if planes:
@@ -209,18 +228,30 @@ class WorldModelProbe(nn.Module):
         with torch.no_grad():
             ws = self._workspace(shp, T, B, dev)
             reset0 = obs['reset'][0].to(torch.uint8).contiguous()          # baselines.py:339-341: the batch start only
-            enc_p = self._enc_struct()
-            enc_acts = torch.empty(int(lib.dm_conv_encoder_acts_floats(ctypes.byref(shp))), device=dev)
             embed = torch.empty(N, E, device=dev)
-            plane_r = plane_t = None
+            plane_r = plane_t = enc_x = None
             if planes:
                 plane_r = obs['reward'].float().contiguous().view(N)
                 plane_t = obs['terminal'].float().contiguous().view(N)
-                H.call('dm_conv_encoder_fwd_planes', ctypes.byref(shp), H.ptr(image), ctypes.byref(enc_p), H.fptr(plane_r),
-                       H.fptr(plane_t), H.fptr(enc_acts), H.fptr(embed), E, H.ptr(ws), ws.numel(), H.stream())
+            if self.dense:
+                # encoders.py:50-61,121-125: rows [image | reward plane | terminal plane] -> MLP -> ELU (WorldModel._dense_encode)
+                enc = wm.encoder.encoder_image
+                enc_x = torch.empty(N, enc.in_dim, device=dev)
+                onehot = image.is_floating_point()
+                H.call('dm_dense_image_rows', N, c.image_channels, c.image_size ** 2, H.fptr(image) if onehot else None,
+                       None if onehot else H.ptr(image), H.fptr(plane_r), H.fptr(plane_t), H.fptr(enc_x), enc.in_dim, H.stream())
+                pre, enc_acts = enc.fwd(enc_x, enc.in_dim, N, ws, save_acts=train)
+                H.call('dm_elu_rows_fwd', N, E, H.fptr(pre), E, H.fptr(embed), E, H.stream())
+                del pre
             else:
-                H.call('dm_conv_encoder_fwd', ctypes.byref(shp), H.ptr(image), ctypes.byref(enc_p), H.fptr(enc_acts), H.fptr(embed),
-                       H.ptr(ws), ws.numel(), H.stream())
+                enc_p = self._enc_struct()
+                enc_acts = torch.empty(int(lib.dm_conv_encoder_acts_floats(ctypes.byref(shp))), device=dev)
+                if planes:
+                    H.call('dm_conv_encoder_fwd_planes', ctypes.byref(shp), H.ptr(image), ctypes.byref(enc_p), H.fptr(plane_r),
+                           H.fptr(plane_t), H.fptr(enc_acts), H.fptr(embed), E, H.ptr(ws), ws.numel(), H.stream())
+                else:
+                    H.call('dm_conv_encoder_fwd', ctypes.byref(shp), H.ptr(image), ctypes.byref(enc_p), H.fptr(enc_acts), H.fptr(embed),
+                           H.ptr(ws), ws.numel(), H.stream())
             # the GRU's input rows [squeeze(embed) | action_next] (baselines.py:346-348): the squeeze product writes the
             # leading 32 columns through its leading dimension
             x = torch.empty(N, In, device=dev)
@@ -259,7 +290,7 @@ class WorldModelProbe(nn.Module):
                 loss = l_ if loss is None else loss + l_
         if not train:
             return (loss,), out_state, metrics, tensors, {}
-        pk = dict(loss=loss, heads=heads, T=T, B=B, shp=shp, image=image, plane_r=plane_r, plane_t=plane_t, enc_acts=enc_acts,
+        pk = dict(loss=loss, heads=heads, T=T, B=B, shp=shp, image=image, enc_x=enc_x, plane_r=plane_r, plane_t=plane_t, enc_acts=enc_acts,
                   embed=embed, x=x, gru_acts=gru_acts, Hs=Hs, ws=ws)
         self._last_pack = pk
         loss_probe = _GruProbeLoss.apply(self, pk, *self.parameters())
@@ -300,6 +331,16 @@ class WorldModelProbe(nn.Module):
         dembed = torch.empty(N, E, device=dev)
         H.call('dm_gemm_f32', 0, 1, N, E, SQUEEZE_DIM, H.fptr(dx), In, H.fptr(sq.weight), E, H.fptr(dembed), E, None, None, 0, 0,
                H.ptr(ws), ws.numel(), H.stream())
+        if self.dense:      # through the trailing ELU (derivative from embed = ELU(pre), in place), then the MLP; no input gradient
+            enc = wm.encoder.encoder_image
+            H.call('dm_elu_rows_bwd', N, E, H.fptr(pk['embed']), E, H.fptr(dembed), E, H.fptr(dembed), E, H.stream())
+            st, gs = enc.struct(), enc.grad_struct(gof)
+            H.call('dm_mlp_head_bwd', N, enc.in_dim, enc.hidden_dim, enc.hidden_layers, enc.out_dim, H.fptr(pk['enc_x']), enc.in_dim,
+                   ctypes.byref(st), H.fptr(pk['enc_acts']), H.fptr(dembed), ctypes.byref(gs), None, 0, 0, H.ptr(ws), ws.numel(),
+                   H.stream())
+            for k in ('gru_acts', 'enc_acts', 'enc_x', 'embed', 'x', 'Hs'):
+                pk.pop(k, None)
+            return
         enc_p, enc_g = self._enc_struct(), self._enc_struct(gof)
         if pk['plane_r'] is not None:
             H.call('dm_conv_encoder_bwd_planes', ctypes.byref(pk['shp']), H.ptr(pk['image']), ctypes.byref(enc_p), H.fptr(pk['plane_r']),

@@ -10,7 +10,9 @@ reference (train.py:184-187).  There is no CPU path: tensors must live on a gfx9
 Supported configuration (everything else raises NotImplementedError): iwae_samples>=1 (also with the logging flags), gru_type in {gru, gru_layernorm,
 gru_layernorm_dv2}, gru_layers 1..4, stoch_discrete>0 or 0 (Gaussian latents, also with iwae_samples>1), layer_norm True or False,
 aux_critic, image_encoder/decoder='cnn' at 64x64 or both 'dense' on a categorical image of at most 16x16 cells (the `minigrid`
-section; the gate is dense_image_gate()), actor_dist in {onehot, tanh_normal, normal_tanh}, actor_grad='reinforce',
+section; the gate is dense_image_gate(); obs['image'] is then the float one-hot (T,B,C,S,S) or the integer class map
+(T,B,S,S) that ReplayFeed / DeviceReplay(image_categorical=C) hand over - same bits; the gru_probe baseline of baselines.py runs on
+that path's DenseEncoder too), actor_dist in {onehot, tanh_normal, normal_tanh}, actor_grad='reinforce',
 probe_model in {none, map, goals, map+goals} (map: the CatImageDecoder probe of the top-down map on the detached features, DESIGN
 4.8; goals: two DenseNormalDecoders of the goal directions with the metrics of csrc/goals.hip, DESIGN 4.9, needs goals_size >= 1;
 not with probe_gradients=True, whose gradient into the world model's features is not built), reward_input (cnn_depth in {8, 16, 32, 48, 64}: the reward and terminal planes are folded into the first

@@ -13,7 +13,8 @@ Here the same batches are produced as what the HIP path consumes directly:
     seed (random start in a column's first file, tails carried into the next file with `allow_mid_reset`, artificial resets
     every `reset_interval`, `buffer_size` / `reload_interval` file selection); the random stream is an explicit
     `numpy.random.RandomState` (the reference uses the global one);
-  * `ReplayFeed`              - planner + preprocessing writing IN PLACE into a ring slot;
+  * `ReplayFeed`              - planner + preprocessing writing IN PLACE into a ring slot; with image_categorical = C the frames
+    are the files' integer class image (n,H,W), carried as stored (the `minigrid` section);
   * `preprocess_batch`        - the hot-path subset of Preprocessor.apply: one-hot float32 actions, float32 reward with
     `clip_rewards`, float32 terminal, bool reset - and the image is LEFT AS uint8 (T,B,H,W,C): x/255-0.5 and HWC->CHW
     happen inside the first conv's patch loader on the GPU (N1), so a batch crosses PCIe at 1 byte per pixel value;
@@ -292,6 +293,8 @@ def preprocess_batch(batch, action_dim, clip_rewards=None, image_key='image', ma
     """Hot-path subset of Preprocessor.apply (preprocessing.py:87-180), images left uint8 (T,B,H,W,C).
     image_categorical = C (preprocessing.py:108-109; the input of the dense categorical image path, models.dense_image_gate):
     `image` = the integer class image (T,B,H,W) as a one-hot (T,B,C,H,W) float32.  With the default the frames stay uint8.
+    ReplayFeed / DeviceReplay(image_categorical=C) carry the class image as stored (integer (T,B,H,W): the argmax over the class
+    axis of this one-hot), which the dense image path takes with the same bits.
     map_key / map_categorical (preprocessing.py:115-131,152-158; the inputs of the map probe, models.MapProbeHead): `map` =
     batch[map_key] as a one-hot (T,B,C,H,W) float32 with C = map_categorical, or - not categorical - a float image of that
     layout; `map_seen_mask` from `map_seen` or `map_vis`; `map_coord` (T,B,4) from `agent_pos`, `agent_dir` and the map's
@@ -404,17 +407,27 @@ def _map_spec(probe, lead, map_key, map_categorical):
     return spec
 
 
-def _feed_layout(replay, action_dim, image_key, map_key, map_categorical, who, goals=False):
-    """(raw fields of the repository's first file, {field: ((T, B, ...) shape, dtype)} of a batch as the feeds hand it over)."""
+def _feed_layout(replay, action_dim, image_key, map_key, map_categorical, who, goals=False, image_categorical=None):
+    """(raw fields of the repository's first file, {field: ((T, B, ...) shape, dtype)} of a batch as the feeds hand it over).
+    image_categorical = C: the files hold an integer class image (n,H,W), carried as stored (T,B,H,W), not one-hot."""
     if not replay.files:
         raise ValueError(f'{who} needs at least one episode file to lay out its slots (the repository is empty)')
     probe = _Episode(replay.files[0].load_data()).fields      # shapes only; draws nothing from the random stream
     T, B = replay.batch_length, replay.batch_size
     spec = {}
-    if image_key:
+    if image_key and image_categorical:
+        img = probe[image_key]
+        if img.ndim != 3 or not np.issubdtype(img.dtype, np.integer):
+            raise ValueError(f'image_categorical={image_categorical}: expected an integer (T,H,W) class image in the episode files, '
+                             f'got {img.dtype} {img.shape}')
+        spec['image'] = ((T, B) + img.shape[1:], img.dtype.type)
+    elif image_key:
         img = probe[image_key]
         if img.dtype != np.uint8 or img.ndim != 4:
-            raise ValueError(f'expected uint8 (T,H,W,C) frames in the episode files, got {img.dtype} {img.shape}')
+            hint = ''
+            if img.ndim == 3 and np.issubdtype(img.dtype, np.integer):
+                hint = ' - an integer (T,H,W) class image, and image_categorical (the number of classes) is not set'
+            raise ValueError(f'expected uint8 (T,H,W,C) frames in the episode files, got {img.dtype} {img.shape}' + hint)
         spec['image'] = ((T, B) + img.shape[1:], np.uint8)
     elif 'vecobs' not in probe:      # image_key=None: an image-less world model, whose only observation is the vector
         raise ValueError(f"{who}(image_key=None): the episode files hold no 'vecobs' field - the only observation of an image-less "
@@ -443,14 +456,22 @@ class ReplayFeed:
     `map_coord` when the files hold their sources.  With goals=True it carries preprocess_batch's `goals_direction`,
     `goal_direction` and (when the files hold it) `goals_visage`; files without targets_vec / target_vec raise at construction.
     image_key=None (an image-less world model, the `vectorenv` section): the slot has no `image`, and files without `vecobs` - the
-    only observation then - raise ValueError at construction."""
+    only observation then - raise ValueError at construction.
+    image_categorical = C (the number of classes, as in preprocess_batch; the `minigrid` section): the files hold an integer class
+    image (n,H,W) and the slot carries it as stored, (T,B,H,W) in the stored dtype - the argmax over the class axis of
+    preprocess_batch's one-hot, which WorldModel and the gru_probe baseline take with the same bits as the one-hot.  Integer
+    (n,H,W) frames without it, or uint8 (n,H,W,C) frames with it, raise ValueError at construction.  fill() is the hot path and
+    does NOT check that the classes lie in [0, C) (DeviceReplay does, once per file): a class outside is safe on the device -
+    dm_dense_image_rows writes a zero column for it and dm_cat_image_loss reads nothing out of bounds - but is not a one-hot."""
 
-    def __init__(self, replay, action_dim, clip_rewards=None, image_key='image', map_key=None, map_categorical=None, goals=False):
+    def __init__(self, replay, action_dim, clip_rewards=None, image_key='image', map_key=None, map_categorical=None, goals=False,
+                 image_categorical=None):
         if clip_rewards not in (None, '', False, 'tanh', 'log1p'):
             raise ValueError(clip_rewards)
         self.replay, self.action_dim, self.clip_rewards, self.image_key = replay, int(action_dim), clip_rewards, image_key
         self.map_key = map_key
-        probe, self._spec = _feed_layout(replay, self.action_dim, image_key, map_key, map_categorical, 'ReplayFeed', goals)
+        probe, self._spec = _feed_layout(replay, self.action_dim, image_key, map_key, map_categorical, 'ReplayFeed', goals,
+                                         image_categorical)
         T, B = replay.batch_length, replay.batch_size
         # `terminal` always has a column: an episode without the field contributes zeros (SequentialReplay._copy), so a
         # repository that mixes files with and without it still yields the flags of those that carry them
@@ -698,20 +719,25 @@ class DeviceReplay:
     Errors of the producer surface from next().
 
     Without `device` nothing touches the GPU: plan() alone is usable, the prepared episodes stay in ordinary host memory.
-    image_key=None: no frames are cached, uploaded or gathered (one field fewer; the files must hold `vecobs`, as for ReplayFeed)."""
+    image_key=None: no frames are cached, uploaded or gathered (one field fewer; the files must hold `vecobs`, as for ReplayFeed).
+    image_categorical = C: the files hold an integer class image (n,H,W), resident and gathered as stored - (T,B,H,W) in the stored
+    dtype, ReplayFeed's field; a 7 x 7 uint8 image is a 49-byte row, which the gather copies through its byte lanes.  Preparation
+    checks once per file that every class lies in [0, C); a file that fails is passed over like a file of another layout."""
 
     def __init__(self, replay, action_dim, device=None, depth=3, capacity_bytes=0, clip_rewards=None, image_key='image',
-                 map_key=None, map_categorical=None, goals=False):
+                 map_key=None, map_categorical=None, goals=False, image_categorical=None):
         if clip_rewards not in (None, '', False, 'tanh', 'log1p'):
             raise ValueError(clip_rewards)
         if any(c.episode is not None or c.tail is not None for c in replay.columns):
             raise ValueError('DeviceReplay needs a SequentialReplay nothing has been drawn from yet')
         self.replay, self.action_dim, self.clip_rewards, self.image_key = replay, int(action_dim), clip_rewards, image_key
         self.map_key, self.map_categorical = map_key, map_categorical
+        self.image_categorical = int(image_categorical) if image_categorical else None
         self.device = None if device is None else torch.device(device)
         self.depth, self.capacity_bytes = max(3, int(depth)), int(capacity_bytes or 0)
         self.goals = bool(goals)
-        _, self._spec = _feed_layout(replay, self.action_dim, image_key, map_key, map_categorical, 'DeviceReplay', goals)
+        _, self._spec = _feed_layout(replay, self.action_dim, image_key, map_key, map_categorical, 'DeviceReplay', goals,
+                                     self.image_categorical)
         self.names = list(self._spec)
         self._rows = {k: (tuple(shape[2:]), np.dtype(dt)) for k, (shape, dt) in self._spec.items()}
         self.row_bytes = {k: int(np.prod(shape, dtype=np.int64)) * dt.itemsize for k, (shape, dt) in self._rows.items()}
@@ -743,6 +769,10 @@ class DeviceReplay:
     def _prepare(self, info):
         f = _Episode(info.load_data()).fields
         n = f['reward'].shape[0]
+        if self.image_key and self.image_categorical:
+            img = f[self.image_key]
+            if not np.issubdtype(img.dtype, np.integer) or (img.size and (img.min() < 0 or img.max() >= self.image_categorical)):
+                raise ValueError(f'{self.image_key!r} holds classes outside [0, {self.image_categorical}) (or is not an integer array)')
         r = f['reward'].astype(np.float32)
         if self.clip_rewards == 'tanh':
             r = np.tanh(r)
