@@ -96,7 +96,8 @@ int dm_version(void);                 /* ABI version, currently 16 (v2: LayerNor
                                               gru_probe baseline; dm_dense_image_rows / dm_elu_rows_fwd / dm_elu_rows_bwd /
                                               dm_cat_image_loss_mix of the dense categorical image path; dm_convt_kskip_enable;
                                               dm_kl_staged_enable; dm_dec_l4_fwd_shared_enable; dm_policy_draw /
-                                              dm_policy_draw_ws_floats of the acting path */
+                                              dm_policy_draw_ws_floats of the acting path; dm_policy_draw_mode of the
+                                              collection loop */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
 size_t dm_workspace_bytes(const dm_shape* shp);   /* scratch needed by any call below for this shape */
@@ -596,6 +597,29 @@ size_t dm_policy_draw_ws_floats(int rows);
 int dm_policy_draw(int kind, int rows, int A, const float* params, int ldp, const float* noise, const float* value, float* action,
                    int lda, int32_t* act_idx, float* log_prob, float* entropy, float* stats, void* ws, size_t ws_bytes,
                    void* stream);
+/* dm_policy_draw with a draw mode (csrc/act.hip; generator.py:317-331 acts, DreamerV2's behaviour policy adds the noise).  kind,
+ * params, value, the outputs, stats and ws are dm_policy_draw's; the same two launches, no float atomics, the same bits for the same
+ * inputs.
+ *   mode 0   sample: dm_policy_draw for the same arguments, bit for bit on every output; noise2 and amount are not read
+ *   mode 1   the distribution's mode, for evaluation; noise and noise2 are not read and may be NULL
+ *            kind 0: idx = the lowest k with x_k == max_k x_k, the action its one-hot row, log_prob = (x_idx - max) - log(sum) with
+ *              the sample path's sequential sum, the entropy unchanged
+ *            kinds 1, 2: every output is what mode 0 gives for an all-zero noise array, bit for bit: action = tanh(5 tanh(m / 5))
+ *              (tanh_normal) or tanh(m) (normal_tanh).  This is the mode of the BASE Normal pushed through the transform - not the
+ *              sample-based mode (the best of a number of draws under log_prob) some Dreamer code uses.
+ *   mode 2   sample, then action noise of size amount >= 0 (DreamerV2's rule for its behaviour policy)
+ *            kind 0: noise2 (rows, 2) uniforms in [0,1).  idx is drawn from noise as in mode 0; where noise2[r][0] < amount (strict,
+ *              fp32) it is replaced by min(A - 1, (int)floorf(noise2[r][1] * A)): the executed index is distributed as
+ *              amount / A + (1 - amount) onehot(idx).  log_prob is the POLICY's log-probability of the executed index, not the
+ *              mixture's.
+ *            kinds 1, 2: noise2 (rows, A) standard normals.  action = clamp(a + amount noise2, -1, 1) with a the mode 0 action;
+ *              the clamp is applied only with amount > 0.  log_prob and entropy stay those of the policy's own draw.
+ *            amount == 0 gives the mode 0 outputs bit for bit for every kind, and noise2 is not read.
+ * Checked on the host before any launch, beyond dm_policy_draw's checks: mode outside {0, 1, 2}, amount < 0 or NaN -> DM_E_SHAPE;
+ * NULL noise with mode 0 or 2, NULL noise2 with mode 2 and amount > 0 -> DM_E_NULL. */
+int dm_policy_draw_mode(int kind, int mode, float amount, int rows, int A, const float* params, int ldp, const float* noise,
+                        const float* noise2, const float* value, float* action, int lda, int32_t* act_idx, float* log_prob,
+                        float* entropy, float* stats, void* ws, size_t ws_bytes, void* stream);
 /* critic loss rows (a2c.py:112-115): loss[r] = 0.5*(vt-v)^2*w ; dvalue = scale * -(vt-v)*w. */
 int dm_critic_loss(int rows, const float* value, const float* value_target, const float* weight, float scale,
                    float* loss, float* dvalue, void* stream);

@@ -3,7 +3,10 @@ __version__ = '0.1.0'
 
 
 def __getattr__(name):      # `from pydreamer_amd import NetworkPolicy` without importing torch for `import pydreamer_amd` alone
-    if name in ('NetworkPolicy', 'StepPreprocessor'):
+    if name in ('NetworkPolicy', 'RandomPolicy', 'StepPreprocessor'):
         from . import policy
         return getattr(policy, name)
+    if name == 'EpisodeRecorder':      # (the loop itself is pydreamer_amd.collect.collect: the name is the submodule's)
+        from .collect import EpisodeRecorder
+        return EpisodeRecorder
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -1,0 +1,153 @@
+"""The collection loop (generator.py:123-257 for B environments): a policy drives a list of environments as one batch,
+and what happened becomes the episode files SequentialReplay / ReplayFeed / DeviceReplay read.
+
+  * `EpisodeRecorder`  - the per-environment row lists of the reference's CollectWrapper (wrappers.py:75-93), the three policy
+    columns of generator.py:140-149 and the npz writer of generator.py:218-253, for B environments at once;
+  * `collect`          - reset, stack, one policy call per step, step, record, reset what is done.
+
+Host code only: the device work of a step is the policy's (policy.NetworkPolicy: one Dreamer.act call, one device-to-host copy).
+Not here, and not needed by the readers: gym adapters and wrappers, mlflow logging, checkpoint polling, rate limiting
+(generator.py:103-121), the train / eval repository split and episode chunking (generator.py:237-240)."""
+import numpy as np
+
+from .policy import METRIC_KEYS
+
+
+def stack_obs(obs_list):
+    """B observation dicts -> one dict of arrays with a leading (B,) axis."""
+    keys = list(obs_list[0])
+    for o in obs_list[1:]:
+        if list(o) != keys:
+            raise ValueError(f'the environments emit different fields: {keys} and {list(o)}')
+    return {k: np.stack([np.asarray(o[k]) for o in obs_list]) for k in keys}
+
+
+class EpisodeRecorder:
+    """Turns the steps of `num_envs` environments into episode files of `repository` (replay.LocalEpisodeRepository, or anything
+    with its count_steps() and save_data(data, episode_from, episode_to)).
+
+    add(obs, done, metrics=None, envs=None) takes one step of all environments.  `obs`: dict of arrays with a leading (B,) axis,
+    the fields the reference's wrapped environment emits (wrappers.py:43-72) - action, reward, terminal, reset - plus the
+    observation fields; row b is what environment b returned from reset() (reset = True: the row opens an episode, and an
+    unfinished one of that environment is dropped) or from step().  `done`: (B,) bools, the row closes its episode.  `metrics`:
+    the policy's per-environment dict (NetworkPolicy(per_env=True): policy_value, action_prob, policy_entropy, (B,) each) of the
+    call that chose the action this row carries, or None; rows with reset = True carry no action and take none.  `envs`: the
+    environments the leading axis holds, for a call that carries the rows of some of them only (the reset rows after a step);
+    all of them, in order, by default.
+
+    A closed episode is one dict, its fields stacked over time.  With metrics, policy_value and policy_entropy get a trailing
+    NaN (no policy call on the last row) and action_prob a leading one (no action on the first); without, all three are NaN
+    with the shape of `reward` - generator.py:140-149, so every file has the same keys; float64 as there.  Closed episodes queue
+    up; when their steps (rows - 1 each, generator.py:222) reach steps_per_npz they are concatenated and written as ONE file: a
+    (T,H,W,C) `image` as `image_t` (H,W,C,T), an integer class image as it is (generator.py:246-252).  Episode numbers go on from
+    repository.count_steps(); episodes are numbered in the order they close, the lower environment index first within a step.
+    flush() writes what is queued.  An episode is always written whole: the reference cuts a queue of 2 steps_per_npz steps or
+    more into chunks (generator.py:237-240, chunk_episode_data), this recorder does not."""
+
+    def __init__(self, repository, num_envs, steps_per_npz=1000):
+        self.repository, self.num_envs, self.steps_per_npz = repository, int(num_envs), int(steps_per_npz)
+        if self.num_envs < 1:
+            raise ValueError(f'num_envs={num_envs}')
+        self.episodes = int(repository.count_steps()[2])      # the number the next closed episode gets
+        self.rows = [[] for _ in range(self.num_envs)]        # per environment: the open episode's row dicts
+        self.mets = [[] for _ in range(self.num_envs)]        # per environment: (value, prob, entropy) per policy call, or None
+        self.queue, self.queued_steps = [], 0
+        self.steps_saved, self.files = 0, []
+
+    def add(self, obs, done, metrics=None, envs=None):
+        envs = range(self.num_envs) if envs is None else [int(e) for e in envs]
+        n = len(envs)
+        done = np.asarray(done, dtype=bool).reshape(-1)
+        if done.shape != (n,):
+            raise ValueError(f'done has shape {done.shape}, expected ({n},)')
+        for k in ('action', 'reward', 'terminal', 'reset'):
+            if k not in obs:
+                raise KeyError(f'the observation lacks {k!r} (fields: {list(obs)})')
+        obs = {k: np.asarray(v) for k, v in obs.items() if k not in METRIC_KEYS}
+        for k, v in obs.items():
+            if v.shape[:1] != (n,):
+                raise ValueError(f'{k} has shape {v.shape}, expected a leading axis of {n}')
+        if metrics is not None:
+            metrics = [np.asarray(metrics[k], dtype=np.float64).reshape(-1) for k in METRIC_KEYS]
+            if any(m.shape != (n,) for m in metrics):
+                raise ValueError(f'per-environment metrics have shapes {[m.shape for m in metrics]}, expected ({n},) each')
+        for i, b in enumerate(envs):
+            if not 0 <= b < self.num_envs:
+                raise ValueError(f'environment {b} of {self.num_envs}')
+            first = bool(obs['reset'][i])
+            if first:
+                self.rows[b], self.mets[b] = [], []
+            elif not self.rows[b]:
+                raise ValueError(f'environment {b}: a step row without an open episode (the first row of an episode has reset = True)')
+            self.rows[b].append({k: v[i].copy() for k, v in obs.items()})
+            if not first:
+                self.mets[b].append(None if metrics is None else tuple(m[i] for m in metrics))
+            if done[i]:
+                self._close(b)
+        if self.queued_steps >= self.steps_per_npz:
+            self.flush()
+
+    def _close(self, b):
+        rows, mets = self.rows[b], self.mets[b]
+        self.rows[b], self.mets[b] = [], []
+        data = {k: np.array([r[k] for r in rows]) for k in rows[0]}
+        nan = np.full(data['reward'].shape, np.nan)
+        if mets and all(m is not None for m in mets):
+            value, prob, ent = (np.array([m[j] for m in mets], dtype=np.float64) for j in range(3))
+            data['policy_value'] = np.concatenate([value, [np.nan]])       # no policy call on the last row
+            data['policy_entropy'] = np.concatenate([ent, [np.nan]])
+            data['action_prob'] = np.concatenate([[np.nan], prob])         # no action on the first row
+        else:
+            data['policy_value'], data['policy_entropy'], data['action_prob'] = nan, nan.copy(), nan.copy()
+        self.queue.append(data)
+        self.queued_steps += len(rows) - 1
+        self.episodes += 1
+
+    def flush(self):
+        """Writes the queued episodes as one file; returns its path (None with an empty queue)."""
+        if not self.queue:
+            return None
+        datas, steps = self.queue, self.queued_steps
+        self.queue, self.queued_steps = [], 0
+        data = {k: np.concatenate([d[k] for d in datas], axis=0) for k in datas[0]}
+        if 'image' in data and data['image'].ndim == 4:      # THWC => HWCT for better compression; a class image stays
+            data['image_t'] = data.pop('image').transpose(1, 2, 3, 0)
+        path = self.repository.save_data(data, self.episodes - len(datas), self.episodes - 1)
+        self.steps_saved += steps
+        self.files.append(path)
+        return path
+
+
+def collect(envs, policy, recorder, num_steps):
+    """Drives the B = len(envs) environments for `num_steps` steps of all of them (num_steps policy calls, B num_steps transitions)
+    and flushes the recorder.  Environment protocol - the reference's wrapped one (wrappers.py:43-72), no gym needed:
+    reset() -> obs dict, step(action) -> (obs dict, reward, done, info), the dict carrying action / reward / terminal / reset.
+    `policy`: (stacked obs dict) -> (actions (B, A) - (A,) for B = 1 -, metrics); NetworkPolicy(batch_size=B, per_env=True),
+    RandomPolicy, or any callable of that shape (a metrics dict without the per-environment columns records NaNs).  Every
+    environment is reset first.  A done environment is reset in place: the row the policy sees next for it carries reset = True,
+    on which the world model zeroes that row's state, so the policy's carried state needs no other care.  Episodes still open
+    when the loop stops are not written.  Returns dict(steps, episodes, files): transitions taken, episodes closed, files
+    written by this call."""
+    B = len(envs)
+    if B != recorder.num_envs:
+        raise ValueError(f'{B} environments, the recorder was built for {recorder.num_envs}')
+    num_steps = int(num_steps)
+    episodes0, files0 = recorder.episodes, len(recorder.files)
+    cur = [env.reset() for env in envs]
+    recorder.add(stack_obs(cur), np.zeros(B, bool))
+    for _ in range(num_steps):
+        action, metrics = policy(stack_obs(cur))
+        action = np.asarray(action).reshape(B, -1)
+        done = np.zeros(B, bool)
+        for b, env in enumerate(envs):
+            cur[b], _, d, _ = env.step(action[b])
+            done[b] = bool(d)
+        per_env = metrics if metrics and all(k in metrics and np.size(metrics[k]) == B for k in METRIC_KEYS) else None
+        recorder.add(stack_obs(cur), done, per_env)
+        again = np.flatnonzero(done)
+        if len(again):
+            for b in again:
+                cur[b] = envs[b].reset()
+            recorder.add(stack_obs([cur[b] for b in again]), np.zeros(len(again), bool), envs=again)
+    recorder.flush()
+    return dict(steps=B * num_steps, episodes=recorder.episodes - episodes0, files=recorder.files[files0:])

@@ -17,6 +17,14 @@
 // the PRE-tanh draw x - with z = (x - mean) / std = eps, the noise itself, no cancellation - and for kind 1 carries TanhTransform's
 // log|det J| = 2 (log 2 - x - softplus(-2 x)) per dimension.  It is NOT recovered from the action through atanh, as the generator's
 // log_prob(action) does: near saturation tanh(x) rounds to +-1 and the clamped atanh loses the draw.
+// dm_policy_draw_mode: the two draw kernels are templates over the draw mode; MODE 0 is the text above and what dm_policy_draw
+// launches, so mode 0 IS dm_policy_draw.
+//   MODE 1 (the distribution's mode; no noise is read)  kind 0: idx = the lowest k with x_k == max (a wave min over the lanes' own
+//     lowest hit) in place of the CDF walk; kinds 1, 2: eps = 0 through the same expressions - the mode of the BASE Normal pushed
+//     through the transform, tanh(5 tanh(m / 5)) / tanh(m), not the best-of-N-samples mode some Dreamer code uses.
+//   MODE 2 (sample, then action noise of size amount > 0; amount == 0 is launched as MODE 0)  kind 0: the drawn idx is replaced by
+//     min(A - 1, (int)floorf(n2[r][1] * A)) where n2[r][0] < amount, and log_prob is the policy's at the executed index; kinds 1, 2:
+//     action = clamp(a + amount n2, -1, 1), log_prob and entropy those of the policy's own draw a.
 #include "common.h"
 
 namespace {
@@ -40,12 +48,13 @@ __device__ __forceinline__ void pd_cont_params(int kind, float m, float s, float
   }
 }
 
-// rowstat: [0, rows) exp(log_prob), [rows, 2 rows) entropy
+// rowstat: [0, rows) exp(log_prob), [rows, 2 rows) entropy.  u2, amount: MODE 2 only
+template <int MODE>
 __global__ void __launch_bounds__(PD_THREADS) policy_draw_onehot_kernel(int rows, int A, const float* __restrict__ logits, int ldp,
-                                                                        const float* __restrict__ u, float* __restrict__ action,
-                                                                        int lda, int32_t* __restrict__ act_idx,
-                                                                        float* __restrict__ log_prob, float* __restrict__ entropy,
-                                                                        float* __restrict__ rowstat) {
+                                                                        const float* __restrict__ u, const float* __restrict__ u2,
+                                                                        float amount, float* __restrict__ action, int lda,
+                                                                        int32_t* __restrict__ act_idx, float* __restrict__ log_prob,
+                                                                        float* __restrict__ entropy, float* __restrict__ rowstat) {
   const int row = blockIdx.x * PD_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows) return;      // whole waves leave: the shuffles below see all 64 lanes
   const float* x = logits + (size_t)row * ldp;
@@ -64,22 +73,37 @@ __global__ void __launch_bounds__(PD_THREADS) policy_draw_onehot_kernel(int rows
     const int k = base + lane, n = A - base < 64 ? A - base : 64;
     const float d = k < A ? x[k] - mx : 0.f;
     const float p = k < A ? expf(d) / sum : 0.f;
-    for (int j = 0; j < n; ++j) total_p += __shfl(p, j, 64);
+    if (MODE != 1)
+      for (int j = 0; j < n; ++j) total_p += __shfl(p, j, 64);
     if (p > 0.f) ent -= p * (d - lsum);
   }
   ent = dm_wave_sum(ent);
-  const float target = u[row] * total_p;
-  float cdf = 0.f;
   int idx = 0;
-  for (int base = 0; base < A; base += 64) {
-    const int k = base + lane, n = A - base < 64 ? A - base : 64;
-    const float p = k < A ? expf(x[k] - mx) / sum : 0.f;
-    for (int j = 0; j < n; ++j) {
-      cdf += __shfl(p, j, 64);
-      idx += (cdf <= target) ? 1 : 0;
+  if (MODE == 1) {      // the lowest class that holds the maximum: each lane's own lowest hit, then the wave's
+    idx = A - 1;        // (a row of NaNs has no hit)
+    for (int k = lane; k < A; k += 64)
+      if (x[k] == mx) { idx = k; break; }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) idx = min(idx, __shfl_xor(idx, off, 64));
+  } else {
+    const float target = u[row] * total_p;
+    float cdf = 0.f;
+    for (int base = 0; base < A; base += 64) {
+      const int k = base + lane, n = A - base < 64 ? A - base : 64;
+      const float p = k < A ? expf(x[k] - mx) / sum : 0.f;
+      for (int j = 0; j < n; ++j) {
+        cdf += __shfl(p, j, 64);
+        idx += (cdf <= target) ? 1 : 0;
+      }
+    }
+    if (idx > A - 1) idx = A - 1;
+    if (MODE == 2) {      // row-uniform: every lane reads the same two numbers
+      if (u2[(size_t)row * 2] < amount) {
+        idx = (int)floorf(u2[(size_t)row * 2 + 1] * (float)A);
+        idx = idx > A - 1 ? A - 1 : (idx < 0 ? 0 : idx);
+      }
     }
   }
-  if (idx > A - 1) idx = A - 1;
   float* o = action + (size_t)row * lda;
   for (int k = lane; k < A; k += 64) o[k] = (k == idx) ? 1.f : 0.f;
   if (lane == 0) {
@@ -92,8 +116,10 @@ __global__ void __launch_bounds__(PD_THREADS) policy_draw_onehot_kernel(int rows
   }
 }
 
+template <int MODE>
 __global__ void __launch_bounds__(PD_THREADS) policy_draw_continuous_kernel(int kind, int rows, int A, const float* __restrict__ params,
                                                                             int ldp, const float* __restrict__ eps,
+                                                                            const float* __restrict__ eps2, float amount,
                                                                             float* __restrict__ action, int lda,
                                                                             int32_t* __restrict__ act_idx, float* __restrict__ log_prob,
                                                                             float* __restrict__ entropy, float* __restrict__ rowstat) {
@@ -105,9 +131,11 @@ __global__ void __launch_bounds__(PD_THREADS) policy_draw_continuous_kernel(int 
   for (int a = lane; a < A; a += 64) {
     float mean, std;
     pd_cont_params(kind, pr[a], pr[A + a], &mean, &std);
-    const float e = eps[(size_t)row * A + a];
+    const float e = MODE == 1 ? 0.f : eps[(size_t)row * A + a];
     const float x = mean + std * e;
-    action[(size_t)row * lda + a] = kind == 1 ? tanhf(x) : x;
+    float act = kind == 1 ? tanhf(x) : x;
+    if (MODE == 2) act = fminf(fmaxf(act + amount * eps2[(size_t)row * A + a], -1.f), 1.f);
+    action[(size_t)row * lda + a] = act;
     const float ls = logf(std);
     lp += -0.5f * e * e - ls - LOG_SQRT_2PI;
     if (kind == 1) lp -= 2.f * (0.6931471805599453f - x - pd_softplus(-2.f * x));
@@ -151,11 +179,29 @@ __global__ void __launch_bounds__(PD_THREADS) policy_stats_kernel(int rows, cons
 
 extern "C" size_t dm_policy_draw_ws_floats(int rows) { return rows < 1 ? 0 : (size_t)2 * rows; }
 
-extern "C" int dm_policy_draw(int kind, int rows, int A, const float* params, int ldp, const float* noise, const float* value,
-                              float* action, int lda, int32_t* act_idx, float* log_prob, float* entropy, float* stats, void* ws,
-                              size_t ws_bytes, void* stream) {
-  DM_REQUIRE(params && noise && action && stats, DM_E_NULL, "policy_draw: null pointer");      // value, act_idx, log_prob, entropy may be NULL
+namespace {
+
+template <int MODE>
+void policy_draw_launch(int kind, float amount, int rows, int A, const float* params, int ldp, const float* noise, const float* noise2,
+                        float* action, int lda, int32_t* act_idx, float* log_prob, float* entropy, float* rowstat, hipStream_t st) {
+  const int blocks = dm_cdiv(rows, PD_WAVES);
+  if (kind == 0)
+    hipLaunchKernelGGL(policy_draw_onehot_kernel<MODE>, dim3(blocks), dim3(PD_THREADS), 0, st, rows, A, params, ldp, noise, noise2,
+                       amount, action, lda, act_idx, log_prob, entropy, rowstat);
+  else
+    hipLaunchKernelGGL(policy_draw_continuous_kernel<MODE>, dim3(blocks), dim3(PD_THREADS), 0, st, kind, rows, A, params, ldp, noise,
+                       noise2, amount, action, lda, act_idx, log_prob, entropy, rowstat);
+}
+
+// dm_policy_draw is mode 0 of this: its checks, in its order, come first
+int policy_draw_impl(int kind, int mode, float amount, int rows, int A, const float* params, int ldp, const float* noise,
+                     const float* noise2, const float* value, float* action, int lda, int32_t* act_idx, float* log_prob,
+                     float* entropy, float* stats, void* ws, size_t ws_bytes, void* stream) {
+  DM_REQUIRE(params && (noise || mode == 1) && action && stats, DM_E_NULL, "policy_draw: null pointer");      // value, act_idx, log_prob, entropy may be NULL
   DM_REQUIRE(kind >= 0 && kind <= 2, DM_E_SHAPE, "policy_draw: kind %d (0 onehot, 1 tanh_normal, 2 normal_tanh)", kind);
+  DM_REQUIRE(mode >= 0 && mode <= 2, DM_E_SHAPE, "policy_draw: mode %d (0 sample, 1 mode, 2 sample + action noise)", mode);
+  DM_REQUIRE(amount >= 0.f, DM_E_SHAPE, "policy_draw: action noise amount %g (must be >= 0)", (double)amount);      // NaN fails too
+  DM_REQUIRE(noise2 || !(mode == 2 && amount > 0.f), DM_E_NULL, "policy_draw: null noise2 with action noise %g", (double)amount);
   DM_REQUIRE(rows >= 1 && A >= 1, DM_E_SHAPE, "policy_draw: rows=%d A=%d", rows, A);
   DM_REQUIRE(A <= (1 << 29), DM_E_SHAPE, "policy_draw: A=%d", A);
   const int width = kind == 0 ? A : 2 * A;
@@ -165,15 +211,30 @@ extern "C" int dm_policy_draw(int kind, int rows, int A, const float* params, in
   DM_REQUIRE(ws, DM_E_NULL, "policy_draw: null workspace");
   DM_REQUIRE(ws_bytes >= need, DM_E_WORKSPACE, "policy_draw: workspace of %zu bytes, need %zu", ws_bytes, need);
   hipStream_t st = (hipStream_t)stream;
-  const int blocks = dm_cdiv(rows, PD_WAVES);
-  if (kind == 0)
-    hipLaunchKernelGGL(policy_draw_onehot_kernel, dim3(blocks), dim3(PD_THREADS), 0, st, rows, A, params, ldp, noise, action, lda,
-                       act_idx, log_prob, entropy, (float*)ws);
-  else
-    hipLaunchKernelGGL(policy_draw_continuous_kernel, dim3(blocks), dim3(PD_THREADS), 0, st, kind, rows, A, params, ldp, noise, action,
-                       lda, act_idx, log_prob, entropy, (float*)ws);
+  if (mode == 1)
+    policy_draw_launch<1>(kind, 0.f, rows, A, params, ldp, nullptr, nullptr, action, lda, act_idx, log_prob, entropy, (float*)ws, st);
+  else if (mode == 2 && amount > 0.f)
+    policy_draw_launch<2>(kind, amount, rows, A, params, ldp, noise, noise2, action, lda, act_idx, log_prob, entropy, (float*)ws, st);
+  else      // mode 0, and mode 2 without noise: the same launch, so the same bits
+    policy_draw_launch<0>(kind, 0.f, rows, A, params, ldp, noise, nullptr, action, lda, act_idx, log_prob, entropy, (float*)ws, st);
   DM_LAUNCH_CHECK();
   hipLaunchKernelGGL(policy_stats_kernel, dim3(1), dim3(PD_THREADS), 0, st, rows, (const float*)ws, value, stats);
   DM_LAUNCH_CHECK();
   return DM_OK;
+}
+
+}  // namespace
+
+extern "C" int dm_policy_draw(int kind, int rows, int A, const float* params, int ldp, const float* noise, const float* value,
+                              float* action, int lda, int32_t* act_idx, float* log_prob, float* entropy, float* stats, void* ws,
+                              size_t ws_bytes, void* stream) {
+  return policy_draw_impl(kind, 0, 0.f, rows, A, params, ldp, noise, nullptr, value, action, lda, act_idx, log_prob, entropy, stats, ws,
+                          ws_bytes, stream);
+}
+
+extern "C" int dm_policy_draw_mode(int kind, int mode, float amount, int rows, int A, const float* params, int ldp, const float* noise,
+                                   const float* noise2, const float* value, float* action, int lda, int32_t* act_idx, float* log_prob,
+                                   float* entropy, float* stats, void* ws, size_t ws_bytes, void* stream) {
+  return policy_draw_impl(kind, mode, amount, rows, A, params, ldp, noise, noise2, value, action, lda, act_idx, log_prob, entropy, stats,
+                          ws, ws_bytes, stream);
 }

@@ -244,6 +244,8 @@ _SIGNATURES = {
     'dm_gru_sequence_fuse_enable': (c_int, [c_int]),
     'dm_policy_draw_ws_floats': (c_size_t, [c_int]),
     'dm_policy_draw': (c_int, [c_int, c_int, c_int, _P, c_int, _P, _P, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    'dm_policy_draw_mode': (c_int, [c_int, c_int, c_float, c_int, c_int, _P, c_int, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, c_size_t,
+                                    _P]),
 }
 
 _lib = None

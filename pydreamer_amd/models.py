@@ -2186,7 +2186,7 @@ class Dreamer(nn.Module):
         return action_distr, out_state, dict(policy_value=value.mean())
 
     # ---- acting (generator.py:311-331 for B environments)
-    def act(self, obs, in_state, noise=None, return_rows=False):
+    def act(self, obs, in_state, noise=None, return_rows=False, mode='sample', action_noise=0.0):
         """inference() followed, on the device, by what the reference's NetworkPolicy does with the distribution object: the draw,
         log_prob(action).exp().mean(), entropy().mean() and policy_value - one dm_policy_draw call behind the actor and critic MLPs,
         no torch op after them and no host synchronisation.  Returns (action (1,B,A) float32, out_state, metrics): metrics =
@@ -2196,7 +2196,11 @@ class Dreamer(nn.Module):
         the one dm_sample_onehot / dm_sample_continuous give for the actor's output and u_act: the acting and the imagined policy
         are the same function of the same numbers.  tanh_normal's log-probability is taken at the pre-tanh draw, not through atanh
         of the action as the reference's log_prob(action) does (that loses the draw near saturation).
-        return_rows=True: metrics also holds log_prob, entropy, value (each (B,)) and, for the one-hot actor, act_idx ((B,) int32)."""
+        return_rows=True: metrics also holds log_prob, entropy, value (each (B,)) and, for the one-hot actor, act_idx ((B,) int32).
+        mode='mode' (evaluation): the distribution's mode instead of a draw - the lowest argmax class, or the base
+        Normal's mean through the transform; u_act is not used.  action_noise > 0 (with mode='sample' only): DreamerV2's exploration
+        noise on the drawn action through dm_policy_draw_mode's mode 2 - `noise` may carry u_expl, (B,2) uniforms for the one-hot
+        actor or (B,A) standard normals for the continuous ones; log_prob stays the policy's.  The defaults are dm_policy_draw."""
         assert 'action' in obs, 'Observation should contain previous action'
         act_shape = obs['action'].shape
         assert len(act_shape) == 3 and act_shape[0] == 1, f'Expected shape (1,B,A), got {act_shape}'
@@ -2206,6 +2210,18 @@ class Dreamer(nn.Module):
         ua_shape = (B,) if kind == 0 else (B, A)
         if u_act is not None and tuple(u_act.shape) != ua_shape:
             raise ValueError(f'actor noise has shape {tuple(u_act.shape)}, expected {ua_shape}')
+        if mode not in ('sample', 'mode'):
+            raise ValueError(f"mode is {mode!r}, expected 'sample' or 'mode'")
+        action_noise = float(action_noise)
+        if not action_noise >= 0.0:
+            raise ValueError(f'action_noise is {action_noise}, expected a number >= 0')
+        if action_noise > 0.0 and mode == 'mode':
+            raise ValueError("action_noise > 0 goes with mode='sample': the distribution's mode is taken without noise")
+        u_expl = noise.get('u_expl')
+        ue_shape = (B, 2) if kind == 0 else (B, A)
+        if u_expl is not None and tuple(u_expl.shape) != ue_shape:
+            raise ValueError(f'exploration noise has shape {tuple(u_expl.shape)}, expected {ue_shape}')
+        draw_mode = 1 if mode == 'mode' else (2 if action_noise > 0.0 else 0)
         with torch.no_grad():
             self.join_optimizers()
             features, out_state = self.wm.forward(obs, in_state, noise.get('u_post'))
@@ -2214,17 +2230,28 @@ class Dreamer(nn.Module):
             ws = self.wm.workspace(self.wm.shape(1, B, 1), dev)
             logits, _ = self.ac.actor.fwd(feat, feat.shape[1], B, ws, save_acts=False)
             value, _ = self.ac.critic.fwd(feat, feat.shape[1], B, ws, save_acts=False)
-            if u_act is None:
-                u_act = torch.rand(ua_shape, device=dev) if kind == 0 else torch.randn(ua_shape, device=dev)
-            u_act = u_act.float().contiguous()
+            if draw_mode == 1:
+                u_act = None
+            else:
+                if u_act is None:
+                    u_act = torch.rand(ua_shape, device=dev) if kind == 0 else torch.randn(ua_shape, device=dev)
+                u_act = u_act.float().contiguous()
+            if draw_mode == 2:
+                if u_expl is None:
+                    u_expl = torch.rand(ue_shape, device=dev) if kind == 0 else torch.randn(ue_shape, device=dev)
+                u_expl = u_expl.float().contiguous()
             action = torch.empty(1, B, A, device=dev)
             stats = torch.empty(4, device=dev)
             dws = torch.empty(int(H.lib().dm_policy_draw_ws_floats(B)), device=dev)
             rows = torch.empty(2, B, device=dev) if return_rows else None
             act_idx = torch.empty(B, dtype=torch.int32, device=dev) if return_rows and kind == 0 else None
-            H.call('dm_policy_draw', kind, B, A, H.fptr(logits), logits.shape[1], H.fptr(u_act), H.fptr(value), H.fptr(action), A,
-                   H.ptr(act_idx), H.fptr(rows), None if rows is None else H.fptr(rows[1]), H.fptr(stats), H.fptr(dws),
-                   dws.numel() * 4, H.stream())
+            tail = (H.fptr(value), H.fptr(action), A, H.ptr(act_idx), H.fptr(rows), None if rows is None else H.fptr(rows[1]),
+                    H.fptr(stats), H.fptr(dws), dws.numel() * 4, H.stream())
+            if draw_mode == 0:
+                H.call('dm_policy_draw', kind, B, A, H.fptr(logits), logits.shape[1], H.fptr(u_act), *tail)
+            else:
+                H.call('dm_policy_draw_mode', kind, draw_mode, action_noise, B, A, H.fptr(logits), logits.shape[1], H.fptr(u_act),
+                       H.fptr(u_expl) if draw_mode == 2 else None, *tail)
         metrics = dict(policy_value=stats[0], action_prob=stats[1], policy_entropy=stats[2])
         if return_rows:
             metrics.update(log_prob=rows[0], entropy=rows[1], value=value.view(B))

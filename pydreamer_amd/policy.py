@@ -30,10 +30,18 @@ class NetworkPolicy:
     """generator.py:311-331.  `preprocess`: any callable from the environment's observation dict to numpy (1, B, ...) fields
     (StepPreprocessor above; an object with the reference's `.apply(obs, expandTB=True)` is taken too).  __call__ returns
     (action ndarray, {policy_value, action_prob, policy_entropy} as Python floats); the action is (A,) for batch_size == 1 as in
-    the reference, (B, A) otherwise.  The recurrent state is carried on the device between calls."""
+    the reference, (B, A) otherwise.  The recurrent state is carried on the device between calls.
+    mode, action_noise: Dreamer.act's ('mode' for evaluation; action_noise > 0 for DreamerV2's exploration noise).  per_env=True:
+    the three metrics are (B,) float32 arrays, one number per environment - the critic's value, exp(log_prob) and the entropy of
+    act(..., return_rows=True) - in the same single copy as the action; what an EpisodeRecorder (collect.py) stores per step."""
 
-    def __init__(self, model, preprocess, batch_size=1, device=None):
+    def __init__(self, model, preprocess, batch_size=1, device=None, mode='sample', action_noise=0.0, per_env=False):
         self.model, self.preprocess, self.batch_size = model, preprocess, int(batch_size)
+        if mode not in ('sample', 'mode'):
+            raise ValueError(f"mode is {mode!r}, expected 'sample' or 'mode'")
+        if not float(action_noise) >= 0.0 or (float(action_noise) > 0.0 and mode == 'mode'):
+            raise ValueError(f'action_noise is {action_noise} with mode {mode!r}: expected >= 0, and 0 with mode=\'mode\'')
+        self.mode, self.action_noise, self.per_env = mode, float(action_noise), bool(per_env)
         if device is None:
             device = next(model.parameters()).device
         self.device = torch.device(device)
@@ -68,11 +76,43 @@ class NetworkPolicy:
         B = obs_model['action'].shape[1]
         if B != self.batch_size:
             raise ValueError(f'the preprocessed observation holds {B} environments, this policy was built for {self.batch_size}')
-        action, self.state, metrics = self.model.act(obs_model, self.state)
-        # the step's single device-to-host wait: the action and the three scalars in one buffer
-        host = torch.cat([action.reshape(-1)] + [metrics[k].reshape(1) for k in METRIC_KEYS]).cpu().numpy()
+        kw = {}
+        if self.mode != 'sample' or self.action_noise > 0.0:      # the defaults are the call as it always was
+            kw.update(mode=self.mode, action_noise=self.action_noise)
+        if self.per_env:
+            kw.update(return_rows=True)
+        action, self.state, metrics = self.model.act(obs_model, self.state, **kw)
+        # the step's single device-to-host wait: the action and the three scalars (per_env: three rows) in one buffer
+        if self.per_env:
+            tail = [metrics['value'].reshape(B), metrics['log_prob'].reshape(B).exp(), metrics['entropy'].reshape(B)]
+        else:
+            tail = [metrics[k].reshape(1) for k in METRIC_KEYS]
+        host = torch.cat([action.reshape(-1)] + tail).cpu().numpy()
         A = action.shape[-1]
         act = host[:B * A].reshape(B, A)
         if B == 1:
             act = act[0]      # (1,1,A) => A
+        if self.per_env:
+            return act.copy(), {k: host[B * A + i * B:B * A + (i + 1) * B].copy() for i, k in enumerate(METRIC_KEYS)}
         return act.copy(), {k: float(host[B * A + i]) for i, k in enumerate(METRIC_KEYS)}
+
+
+class RandomPolicy:
+    """generator.py:303-308, the prefill policy, for batch_size environments: uniform one-hot actions, or with continuous=True
+    uniform actions in [-1, 1); no metrics.  The action is (A,) for batch_size == 1, (B, A) otherwise, float32; the same seed gives
+    the same actions."""
+
+    def __init__(self, action_dim, batch_size=1, seed=None, continuous=False):
+        self.action_dim, self.batch_size, self.continuous = int(action_dim), int(batch_size), bool(continuous)
+        if self.action_dim < 1 or self.batch_size < 1:
+            raise ValueError(f'action_dim={action_dim} batch_size={batch_size}')
+        self.rng = np.random.RandomState(seed)
+
+    def __call__(self, obs):
+        B, A = self.batch_size, self.action_dim
+        if self.continuous:
+            act = self.rng.uniform(-1.0, 1.0, (B, A)).astype(np.float32)
+        else:
+            act = np.zeros((B, A), np.float32)
+            act[np.arange(B), self.rng.randint(0, A, B)] = 1.0
+        return (act[0] if B == 1 else act), {}
