@@ -97,7 +97,8 @@ int dm_version(void);                 /* ABI version, currently 16 (v2: LayerNor
                                               dm_cat_image_loss_mix of the dense categorical image path; dm_convt_kskip_enable;
                                               dm_kl_staged_enable; dm_dec_l4_fwd_shared_enable; dm_policy_draw /
                                               dm_policy_draw_ws_floats of the acting path; dm_policy_draw_mode of the
-                                              collection loop */
+                                              collection loop; dm_metric_accum / dm_batch_stats / dm_masked_mean /
+                                              dm_export_image_u8 of the trainer loop's device-side logging */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
 size_t dm_workspace_bytes(const dm_shape* shp);   /* scratch needed by any call below for this shape */
@@ -685,6 +686,33 @@ int dm_replay_gather(int T, int B, int nfields, const dm_replay_field* fields /*
                      const void* const* src, void* stream);
 /* y = a*x + b*y */
 int dm_axpby(int64_t n, float a, const float* x, float b, float* y, void* stream);
+
+/* ---- the trainer loop's device-side logging (csrc/logging.hip; pydreamer_amd/train.py) ----
+ * One launch each, nothing waits; no float atomics; reductions accumulate in fp64 in a fixed order (thread-strided partials, then
+ * a fixed LDS tree) and round to fp32 once: the same inputs give the same bits.  Arguments are checked on the host first. */
+/* Folds one step's scalars into running accumulators (train.py:204-214, 346-347, 387-389 without the .item() calls).  vals: n
+ * floats (the model's metric buffer, or any device floats), n <= 256; rules: n device bytes; sum, maxv: n doubles; count: n int64.
+ *   rule 0  the slot is left alone              rule 1  counted iff not NaN (inf is counted)
+ *   rule 2  counted iff finite, and the max over the counted values is tracked
+ *   rule 3  always counted                      rule 4  the max only (a NaN stays, as in numpy's max)
+ * counted: sum += (double)v, count += 1 - in call order, so sum is what a Python float sum of the same values gives, exactly.
+ * A max slot starts at -inf (the caller fills it).  A rule byte above 4 is treated as 0; the Python wrapper refuses it. */
+int dm_metric_accum(int n, const float* vals, const uint8_t* rules, double* sum, double* maxv, int64_t* count, void* stream);
+/* out4 = [mean reward, mean reset, mean terminal, max reward] over n = T*B elements (train.py:211-214).  reset: bool bytes,
+ * counted in integers - its mean is fl32(count) / fl32(n); terminal may be NULL (gives 0); a NaN reward gives NaN in the mean
+ * and in the max, as torch.max propagates it.  n <= 2^24. */
+int dm_batch_stats(int n, const float* reward, const uint8_t* reset, const float* terminal, float* out4, void* stream);
+/* out[0] = the mean of x[t][b] (row-major, leading dimension ldx) over t < min(take_rows, T) and the columns with col_keep[b] != 0
+ * (col_keep NULL: all).  skip_nan = 1 leaves NaN elements out - nanmean(logprobs[:5] * mask / mask), train.py:365-372 -, skip_nan
+ * = 0 is the plain IEEE mean - (loss_map.mean(0) * reset).sum() / reset.sum(), train.py:346.  The empty set gives NaN.  One
+ * deliberate difference from the reference with skip_nan = 0: a non-finite value in a column that is NOT kept does not reach the
+ * result here; there it poisons it through NaN * 0. */
+int dm_masked_mean(int T, int B, const float* x, int ldx, int take_rows, const uint8_t* col_keep, int skip_nan, float* out,
+                   void* stream);
+/* A logged float image tensor (T,B,C,H,W) -> the npz layout (min(take_b,B), T, H, W, C) in uint8 (train.py:427, 447, 452, 462 in
+ * one pass): fl32(fl32(x + 0.5f) * 255.0f) without contraction, clamped to [0, 255], truncated toward zero.  NaN gives 0 (numpy's
+ * own cast of NaN to uint8 is undefined).  C is 1 or 3 and H == W, as the reference asserts. */
+int dm_export_image_u8(int T, int B, int take_b, int C, int H, int W, const float* src, uint8_t* dst, void* stream);
 
 #ifdef __cplusplus
 }

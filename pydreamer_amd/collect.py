@@ -3,11 +3,13 @@ and what happened becomes the episode files SequentialReplay / ReplayFeed / Devi
 
   * `EpisodeRecorder`  - the per-environment row lists of the reference's CollectWrapper (wrappers.py:75-93), the three policy
     columns of generator.py:140-149 and the npz writer of generator.py:218-253, for B environments at once;
-  * `collect`          - reset, stack, one policy call per step, step, record, reset what is done.
+  * `collect`          - reset, stack, one policy call per step, step, record, reset what is done;
+  * `Collector`        - the same loop for a trainer that alternates collecting and training: the current observations and the
+    recorder's open episodes live across run() calls.
 
 Host code only: the device work of a step is the policy's (policy.NetworkPolicy: one Dreamer.act call, one device-to-host copy).
 Not here, and not needed by the readers: gym adapters and wrappers, mlflow logging, checkpoint polling, rate limiting
-(generator.py:103-121), the train / eval repository split and episode chunking (generator.py:237-240)."""
+(generator.py:103-121; train.run turns it into a schedule) and the train / eval repository split."""
 import numpy as np
 
 from .policy import METRIC_KEYS
@@ -41,11 +43,14 @@ class EpisodeRecorder:
     up; when their steps (rows - 1 each, generator.py:222) reach steps_per_npz they are concatenated and written as ONE file: a
     (T,H,W,C) `image` as `image_t` (H,W,C,T), an integer class image as it is (generator.py:246-252).  Episode numbers go on from
     repository.count_steps(); episodes are numbered in the order they close, the lower environment index first within a step.
-    flush() writes what is queued.  An episode is always written whole: the reference cuts a queue of 2 steps_per_npz steps or
-    more into chunks (generator.py:237-240, chunk_episode_data), this recorder does not."""
+    flush() writes what is queued.  chunk=False (the default) always writes the queue whole, as ONE file.  chunk=True follows
+    generator.py:237-240: a queue of 2 steps_per_npz steps or more is cut as chunk_episode_data (tools.py:269-278) cuts it - with
+    n = rows - 1 into n // steps_per_npz pieces, piece i the rows up to n (i + 1) // pieces + 1 - and written as one file per
+    piece, the piece's number in the file name; a shorter queue is written as with chunk=False."""
 
-    def __init__(self, repository, num_envs, steps_per_npz=1000):
+    def __init__(self, repository, num_envs, steps_per_npz=1000, chunk=False):
         self.repository, self.num_envs, self.steps_per_npz = repository, int(num_envs), int(steps_per_npz)
+        self.chunk = bool(chunk)
         if self.num_envs < 1:
             raise ValueError(f'num_envs={num_envs}')
         self.episodes = int(repository.count_steps()[2])      # the number the next closed episode gets
@@ -104,18 +109,33 @@ class EpisodeRecorder:
         self.episodes += 1
 
     def flush(self):
-        """Writes the queued episodes as one file; returns its path (None with an empty queue)."""
+        """Writes the queued episodes as one file - with chunk=True and 2 steps_per_npz steps or more queued, as several; returns the
+        path of the (last) file written (None with an empty queue)."""
         if not self.queue:
             return None
         datas, steps = self.queue, self.queued_steps
         self.queue, self.queued_steps = [], 0
         data = {k: np.concatenate([d[k] for d in datas], axis=0) for k in datas[0]}
-        if 'image' in data and data['image'].ndim == 4:      # THWC => HWCT for better compression; a class image stays
-            data['image_t'] = data.pop('image').transpose(1, 2, 3, 0)
-        path = self.repository.save_data(data, self.episodes - len(datas), self.episodes - 1)
+        if self.chunk and steps >= 2 * self.steps_per_npz:
+            pieces = list(enumerate(chunk_episode_data(data, self.steps_per_npz)))
+        else:
+            pieces = [(None, data)]
+        for seq, piece in pieces:
+            if 'image' in piece and piece['image'].ndim == 4:      # THWC => HWCT for better compression; a class image stays
+                piece['image_t'] = piece.pop('image').transpose(1, 2, 3, 0)
+            path = self.repository.save_data(piece, self.episodes - len(datas), self.episodes - 1, seq)
+            self.files.append(path)
         self.steps_saved += steps
-        self.files.append(path)
         return path
+
+
+def chunk_episode_data(data, min_length):
+    """The cut rule of tools.py:269-278: with steps = rows - 1 (the first reset row is free: 2000 steps become 1001 + 1000 rows) the
+    rows go into steps // min_length consecutive pieces of min_length ... 2 min_length - 1 steps each.  Returns dicts of views."""
+    steps = len(data['reward']) - 1
+    pieces = steps // min_length
+    bounds = [0] + [steps * (i + 1) // pieces + 1 for i in range(pieces)]
+    return [{k: v[a:z] for k, v in data.items()} for a, z in zip(bounds, bounds[1:])]
 
 
 def collect(envs, policy, recorder, num_steps):
@@ -151,3 +171,54 @@ def collect(envs, policy, recorder, num_steps):
             recorder.add(stack_obs([cur[b] for b in again]), np.zeros(len(again), bool), envs=again)
     recorder.flush()
     return dict(steps=B * num_steps, episodes=recorder.episodes - episodes0, files=recorder.files[files0:])
+
+
+class Collector:
+    """collect() for a loop that alternates collecting and training: run(num_steps) drives the environments for num_steps steps of
+    all of them and can be called again - the current observations and the recorder's open episodes are kept, so an episode that
+    spans two calls is written whole.  The environments are reset once, by the first run().  Files appear when the recorder's
+    steps_per_npz is reached, on flush() (the closed episodes queued so far) and on close() (the same; episodes still open are
+    not written).  Wherever no episode is open between two calls, run(k) twice records what collect() records in 2 k steps."""
+
+    def __init__(self, envs, policy, recorder):
+        if len(envs) != recorder.num_envs:
+            raise ValueError(f'{len(envs)} environments, the recorder was built for {recorder.num_envs}')
+        self.envs, self.policy, self.recorder = list(envs), policy, recorder
+        self.cur = None
+        self.steps = 0
+
+    def run(self, num_steps):
+        """Returns dict(steps, episodes, files) of this call: transitions taken, episodes closed, files written."""
+        envs, recorder, B = self.envs, self.recorder, len(self.envs)
+        episodes0, files0 = recorder.episodes, len(recorder.files)
+        if self.cur is None:
+            self.cur = [env.reset() for env in envs]
+            recorder.add(stack_obs(self.cur), np.zeros(B, bool))
+        cur = self.cur
+        for _ in range(int(num_steps)):
+            action, metrics = self.policy(stack_obs(cur))
+            action = np.asarray(action).reshape(B, -1)
+            done = np.zeros(B, bool)
+            for b, env in enumerate(envs):
+                cur[b], _, d, _ = env.step(action[b])
+                done[b] = bool(d)
+            per_env = metrics if metrics and all(k in metrics and np.size(metrics[k]) == B for k in METRIC_KEYS) else None
+            recorder.add(stack_obs(cur), done, per_env)
+            again = np.flatnonzero(done)
+            if len(again):
+                for b in again:
+                    cur[b] = envs[b].reset()
+                recorder.add(stack_obs([cur[b] for b in again]), np.zeros(len(again), bool), envs=again)
+        self.steps += B * int(num_steps)
+        return dict(steps=B * int(num_steps), episodes=recorder.episodes - episodes0, files=recorder.files[files0:])
+
+    def flush(self):
+        return self.recorder.flush()
+
+    def close(self):
+        """Writes the queued episodes; the open ones are dropped, and the next run() resets the environments."""
+        path = self.recorder.flush()
+        self.recorder.rows = [[] for _ in range(self.recorder.num_envs)]
+        self.recorder.mets = [[] for _ in range(self.recorder.num_envs)]
+        self.cur = None
+        return path

@@ -29,6 +29,12 @@ SECTIONS = {
         actor_dist='onehot',
         # aux critic
         aux_critic=False, aux_critic_weight=1.0, gamma_aux=0.99, lambda_gae_aux=0.95, target_interval_aux=1000,
+        # the trainer loop (train.py; defaults.yaml:3-16, 34-35, 59-65, 113-118)
+        n_steps=100_000_000, n_env_steps=1_000_000_000, offline_data_dir=None, offline_prefill_dir=None, offline_test_dir=None,
+        offline_eval_dir=None, log_interval=100, logbatch_interval=1000, save_interval=500, eval_interval=2000,
+        allow_mid_reset=True, buffer_size=10_000_000, buffer_size_offline=0, test_batches=61, test_batch_size=10,
+        test_save_size=1, eval_batches=61, eval_samples=1, eval_batch_size=32, eval_save_size=1,
+        generator_prefill_steps=50_000, limit_step_ratio=0, env_action_repeat=1,
     ),
     'atari': dict(action_dim=18, clip_rewards='tanh', deter_dim=1024, kl_weight=0.1, gamma=0.99, entropy=0.001),
     'dmc': dict(action_dim=12, entropy=1.0e-4, actor_grad='dynamics', actor_dist='tanh_normal', clip_rewards='tanh'),
