@@ -6,7 +6,10 @@ def __getattr__(name):      # `from pydreamer_amd import NetworkPolicy` without 
     if name in ('NetworkPolicy', 'RandomPolicy', 'StepPreprocessor'):
         from . import policy
         return getattr(policy, name)
-    if name == 'EpisodeRecorder':      # (the loop itself is pydreamer_amd.collect.collect: the name is the submodule's)
-        from .collect import EpisodeRecorder
-        return EpisodeRecorder
+    if name in ('EpisodeRecorder', 'EpisodeStats'):      # (the loop itself is pydreamer_amd.collect.collect: the name is the submodule's)
+        from . import collect
+        return getattr(collect, name)
+    if name in ('wrap_env', 'wrap_envs'):
+        from . import envs
+        return getattr(envs, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -35,6 +35,8 @@ SECTIONS = {
         allow_mid_reset=True, buffer_size=10_000_000, buffer_size_offline=0, test_batches=61, test_batch_size=10,
         test_save_size=1, eval_batches=61, eval_samples=1, eval_batch_size=32, eval_save_size=1,
         generator_prefill_steps=50_000, limit_step_ratio=0, env_action_repeat=1,
+        # the environment wrappers (envs.wrap_envs; defaults.yaml:119-120)
+        env_time_limit=0, env_no_terminal=False,
     ),
     'atari': dict(action_dim=18, clip_rewards='tanh', deter_dim=1024, kl_weight=0.1, gamma=0.99, entropy=0.001),
     'dmc': dict(action_dim=12, entropy=1.0e-4, actor_grad='dynamics', actor_dist='tanh_normal', clip_rewards='tanh'),

@@ -395,7 +395,8 @@ def _feed(conf, repository, batch_size, device, has_goals, **replay_kw):
 
 
 def run(conf, train_repository, eval_repository=None, test_repository=None, envs=None, policy_kwargs=None, logdir=None, logger=None,
-        env_steps_per_grad_step=None, on_step=None, seed=0, steps_per_npz=1000):
+        env_steps_per_grad_step=None, on_step=None, seed=0, steps_per_npz=1000, agent_log_every=10, eval_envs=None,
+        eval_episodes=None, eval_policy_kwargs=None, split_fraction=0.0):
     """train.py:24-303 in one process.  Data: DeviceReplay(SequentialReplay(train_repository, ...)) with the reference's reader
     arguments; model: Dreamer, or WorldModelProbe for conf.model = 'gru_probe'; logdir/checkpoints/latest.pt is resumed if
     present.  Per step: training_step, prefetch of the next batch, zero_grad, backward, grad_clip, step, then two accumulate
@@ -409,8 +410,18 @@ def run(conf, train_repository, eval_repository=None, test_repository=None, envs
     reach grad steps x ratio - env_steps_per_grad_step, or conf.limit_step_ratio when > 0: the reference's rate limit
     (generator.py:118) as a schedule; the recorder writes a file once steps_per_npz steps of closed episodes are queued, and after
     every collection round.
+    Agent metrics (online, agent_log_every > 0): the training recorder feeds a collect.EpisodeStats('agent') through its
+    on_episode hook; after every collection round, prefill included, logger(stats.pop(), steps) once agent_log_every returns are
+    held - a logger call of its own, every key agent/..., host numbers only: no device read, no accumulator call.
+    Evaluation episodes (eval_envs; needs eval_repository): at every eval_interval step, before the two evaluate() calls, a second
+    Collector with its own NetworkPolicy(model, ..., batch_size=len(eval_envs), per_env=True, **eval_policy_kwargs) runs
+    run_episodes(eval_episodes or len(eval_envs)) into eval_repository and is closed (open episodes are dropped, the next round
+    resets the environments); one agent_eval/... entry over the round's episodes is logged, and evaluate('eval') reads what was
+    just written.  The default policy samples, as the reference's evaluation generators do; dict(mode='mode') is greedy.  This
+    draws from the device's random stream, which is why it is opt-in.
+    split_fraction > 0: the training recorder writes that fraction of its files to test_repository (generator.py:244).
     on_step(step, model, obs, tensors): a hook behind the optimizer step (tests); None costs nothing.  Returns the step count."""
-    from .collect import Collector, EpisodeRecorder
+    from .collect import Collector, EpisodeRecorder, EpisodeStats
     from .policy import NetworkPolicy, RandomPolicy, StepPreprocessor
     model_name = getattr(conf, 'model', 'dreamer')
     if model_name not in ('dreamer', 'gru_probe'):
@@ -421,6 +432,12 @@ def run(conf, train_repository, eval_repository=None, test_repository=None, envs
         ratio = env_steps_per_grad_step if env_steps_per_grad_step else (conf.limit_step_ratio if conf.limit_step_ratio > 0 else None)
         if not ratio:
             raise ValueError('online training needs env_steps_per_grad_step, or conf.limit_step_ratio > 0')
+    if eval_envs is not None and eval_repository is None:
+        raise ValueError('eval_envs needs an eval_repository to write the evaluation episodes to')
+    if split_fraction > 0 and test_repository is None:
+        raise ValueError(f'split_fraction={split_fraction} needs a test_repository')
+    if split_fraction > 0 and not online:
+        raise ValueError(f'split_fraction={split_fraction} without envs: nothing is recorded offline')
     if logdir is None:
         raise ValueError('run() needs a logdir: checkpoints, logged batches and the default logger write there')
     device = torch.device(conf.device)
@@ -434,17 +451,40 @@ def run(conf, train_repository, eval_repository=None, test_repository=None, envs
     has_goals = 'goals' in getattr(conf, 'probe_model', 'none')
     image_cat = conf.image_channels if conf.image_categorical else None
 
+    def attach_stats(prefix, log_every, col):
+        """An EpisodeStats fed by the on_episode hook of the collector's recorder, with the counters of both."""
+        stats, rec = EpisodeStats(prefix, action_repeat=conf.env_action_repeat, log_every=log_every), col.recorder
+        rec.on_episode = lambda data: stats.add_episode(data, col.steps, rec.steps_saved, rec.episodes + 1, col.seconds())
+        return stats
+
+    def log_agent():
+        if stats is not None and stats.ready():
+            logger(stats.pop(), steps)
+
+    prep = StepPreprocessor(conf.action_dim, clip_rewards=conf.clip_rewards, image_key=conf.image_key,
+                            image_categorical=image_cat, batched=True)
+    eval_collector = None
+    if eval_envs is not None:
+        eval_collector = Collector(eval_envs, NetworkPolicy(model, prep, batch_size=len(eval_envs), device=device, per_env=True,
+                                                            **(eval_policy_kwargs or {})),
+                                   EpisodeRecorder(eval_repository, len(eval_envs), steps_per_npz=steps_per_npz))
+        eval_stats = attach_stats('agent_eval', 0, eval_collector)
+
     # prefill
-    collector = None
+    collector, stats = None, None
     if online:
         B_env = len(envs)
-        recorder = EpisodeRecorder(train_repository, B_env, steps_per_npz=steps_per_npz)
-        prep = StepPreprocessor(conf.action_dim, clip_rewards=conf.clip_rewards, image_key=conf.image_key,
-                                image_categorical=image_cat, batched=True)
+        split = {}
+        if split_fraction > 0:
+            split = dict(repository2=test_repository, split_fraction=split_fraction, rng=np.random.RandomState(seed))
+        recorder = EpisodeRecorder(train_repository, B_env, steps_per_npz=steps_per_npz, **split)
         collector = Collector(envs, RandomPolicy(conf.action_dim, B_env, seed=seed, continuous=conf.actor_dist != 'onehot'), recorder)
+        if agent_log_every:
+            stats = attach_stats('agent', agent_log_every, collector)
         while train_repository.count_steps()[1] < conf.generator_prefill_steps:
             collector.run(max(1, -(-(conf.generator_prefill_steps - train_repository.count_steps()[1]) // B_env)))
             collector.flush()
+            log_agent()
         collector.policy = NetworkPolicy(model, prep, batch_size=B_env, device=device, per_env=True, **(policy_kwargs or {}))
         recorded0 = recorder.steps_saved + recorder.queued_steps
         if train_repository.count_steps()[1] * conf.env_action_repeat >= conf.n_env_steps:
@@ -510,6 +550,12 @@ def run(conf, train_repository, eval_repository=None, test_repository=None, envs
 
             # (the reference returns at n_steps before it evaluates; here a run whose last step is an evaluation step evaluates)
             if conf.eval_interval and steps % conf.eval_interval == 0:
+                if eval_collector is not None:
+                    eval_collector.run_episodes(eval_episodes or len(eval_envs))
+                    eval_collector.close()
+                    agent_eval = eval_stats.pop()
+                    if agent_eval:
+                        logger(agent_eval, steps)
                 _evaluate_both(conf, model, steps, test_repository, eval_repository, device, has_goals, logdir, logger, seed)
             if steps >= conf.n_steps:
                 break
@@ -518,6 +564,7 @@ def run(conf, train_repository, eval_repository=None, test_repository=None, envs
                 while (collector.recorder.steps_saved + collector.recorder.queued_steps - recorded0) < grad_steps * ratio:
                     collector.run(1)
                 collector.flush()
+                log_agent()
     finally:
         data.close()
         if collector is not None:
