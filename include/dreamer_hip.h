@@ -98,7 +98,8 @@ int dm_version(void);                 /* ABI version, currently 16 (v2: LayerNor
                                               dm_kl_staged_enable; dm_dec_l4_fwd_shared_enable; dm_policy_draw /
                                               dm_policy_draw_ws_floats of the acting path; dm_policy_draw_mode of the
                                               collection loop; dm_metric_accum / dm_batch_stats / dm_masked_mean /
-                                              dm_export_image_u8 of the trainer loop's device-side logging */
+                                              dm_export_image_u8 of the trainer loop's device-side logging;
+                                              dm_head_loss_catsup of the categorical reward decoder */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
 size_t dm_workspace_bytes(const dm_shape* shp);   /* scratch needed by any call below for this shape */
@@ -328,6 +329,22 @@ int dm_head_loss(int kind, int rows, const float* out, const float* target, floa
  * out / target / dout / mean_out are (rows,V); loss[r] = 0.5 * sum_v (mu-y)^2 + V * loss_const; dout = scale * (mu-y). */
 int dm_head_loss_normal_nd(int rows, int V, const float* out, const float* target, float scale, float loss_const,
                            float* loss, float* dout, float* mean_out, void* stream);
+
+/* the same for a DenseCategoricalSupportDecoder (csrc/cat_support.hip; decoders.py:322-362 over CategoricalSupport,
+ * common.py:77-86: reward_decoder_categorical): a categorical distribution over K fixed support values.
+ * logits (rows, K) with leading dimension ld >= K; support (K) on the device; target (rows / I) - row r reads target r / I as
+ * dm_cat_image_loss does, rows % I == 0.  With b = argmin_k (t - support[k])^2 - the reference's own fp32 arithmetic
+ * (d = t - support[k], d * d, strict '<' scanning k upwards: bit for bit torch.square(t[:, None] - support).argmin(-1)):
+ *   loss[r] = logsumexp_k x - x[b];  dlogits[r][k] = scale * (softmax_k - [k == b]), dense, leading dimension K;
+ *   mean_out[r] = sum_k softmax_k * support[k];  bin[r / I] = b, int32 (rows / I).
+ * Every output pointer is optional.  target == NULL is the mean-only form (the imagined rows, dreamer.py:212, where only
+ * `.mean` is read): loss, dlogits and bin must then be NULL too; its mean_out has the bits of the full form's.
+ * fp32 arithmetic with the maximum subtracted, whatever the precision of the products around it; one launch; no float atomics
+ * (the same inputs give the same bits).  Checked on the host before anything is launched: K outside 2 .. 32, rows < 0, I < 1,
+ * rows % I != 0 or ld < K -> DM_E_SHAPE; NULL logits or support, or a NULL target beside a non-NULL loss, dlogits or bin ->
+ * DM_E_NULL; rows == 0 -> DM_OK with nothing launched. */
+int dm_head_loss_catsup(int rows, int I, int K, const float* logits, int ld, const float* support, const float* target, float scale,
+                        float* loss, float* dlogits, float* mean_out, int32_t* bin, void* stream);
 
 /* Per-cell categorical losses over a (C, H, W) logit block (csrc/cat_image.hip): the map probe's CatImageDecoder
  * (decoders.py:183-254, probes.py:32-86).  A logit row is class-major as nn.Unflatten(-1, (C,H,W)) lays it out: class c of

@@ -164,6 +164,7 @@ _SIGNATURES = {
                                 POINTER(dm_mlp_grads), _P, c_int, c_int, _P, c_size_t, _P]),
     'dm_head_loss': (c_int, [c_int, c_int, _P, _P, c_float, c_float, _P, _P, _P, _P]),
     'dm_head_loss_normal_nd': (c_int, [c_int, c_int, _P, _P, c_float, c_float, _P, _P, _P, _P]),
+    'dm_head_loss_catsup': (c_int, [c_int, c_int, c_int, _P, c_int, _P, _P, c_float, _P, _P, _P, _P, _P]),
     'dm_cat_target_index': (c_int, [c_int, c_int, c_int, _P, _P, _P]),
     'dm_cat_image_loss': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P]),
     'dm_cat_image_pred': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P, _P]),

@@ -20,12 +20,15 @@ convolution), vecobs_size > 0 beside the image (an MLP encoder whose
 DenseNormalDecoder with out_dim = vecobs_size), or vecobs_size > 0 with NO image at all - image_encoder and image_decoder both
 empty (None or ''), the `vectorenv` section; the gate is imageless_gate(), DESIGN 4.12: the vecobs MLP's output is the RSSM's
 embedding, the loss has no image term, obs needs no `image`, probe_model must be 'none', reward_input is ignored as in the
-reference; everything in the RSSM, the heads and the actor-critic works as beside an image).
+reference; everything in the RSSM, the heads and the actor-critic works as beside an image), reward_decoder_categorical = a list
+of 2..32 reward values (DenseCategoricalSupportDecoder in place of the Normal reward head; it combines with all of
+the above).
 """
 import contextlib
 import ctypes
 import math
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -351,6 +354,58 @@ class DenseBernoulliDecoder(_Params):
         self.model = MLP(in_dim, 1, MLP_HIDDEN, hidden_layers, layer_norm)
 
 
+CATSUP_MAX = 32           # dm_head_loss_catsup: at most 32 support values (a row group is at most half a wave)
+
+
+def reward_support(conf):
+    """The support of the categorical reward decoder, or None for the Normal head (decoders.py:34-41):
+    clip_rewards_np(conf.reward_decoder_categorical, conf.clip_rewards) - the listed values are untransformed rewards, tanh /
+    log1p is applied to the list (functions.py:153-160) - as float64, which the decoder rounds to fp32.  ValueError for fewer than
+    two values or a non-finite one (log1p of a value <= -1: the reference would train on NaN); NotImplementedError for more than
+    CATSUP_MAX values."""
+    raw = conf.reward_decoder_categorical
+    if raw is None or (isinstance(raw, (list, tuple)) and len(raw) == 0):
+        return None
+    if not isinstance(raw, (list, tuple)):
+        raise ValueError(f'reward_decoder_categorical={raw!r}: a list of reward values is expected')
+    x = np.asarray(raw, dtype=np.float64)
+    if x.ndim != 1 or x.size < 2:
+        raise ValueError(f'reward_decoder_categorical={raw!r}: at least 2 support values are needed')
+    if x.size > CATSUP_MAX:
+        raise NotImplementedError(f'reward_decoder_categorical with {x.size} support values: the HIP path is built for at most '
+                                  f'{CATSUP_MAX} (dm_head_loss_catsup)')
+    clip = conf.clip_rewards
+    with np.errstate(all='ignore'):
+        if clip == 'tanh':
+            x = np.tanh(x)
+        elif clip == 'log1p':
+            x = np.log1p(x)
+        elif clip:
+            raise ValueError(f'clip_rewards={clip!r}')
+    if not np.isfinite(x.astype(np.float32)).all():
+        raise ValueError(f'reward_decoder_categorical={raw!r} with clip_rewards={clip!r} gives the support {x.tolist()}: every '
+                         'support value must be finite')
+    return x
+
+
+class DenseCategoricalSupportDecoder(_Params):
+    """decoders.py:322-362: a categorical distribution over fixed support values.  `_support` is a frozen parameter as in the
+    reference: it stands in state_dict() in front of model.model.* and in the world-model optimizer's parameter list, where it
+    never receives a gradient.  Loss, decoded mean and the target's bin are dm_head_loss_catsup (csrc/cat_support.hip).
+    Not built on the `meta` device: every other parameter of the model is re-initialised or loaded after to_empty(), but
+    `_support` carries VALUES fixed at construction that no initialiser restores - a model materialised from `meta` would train
+    against whatever the allocator left there.  Construct on a real device (CPU, then .to(device))."""
+
+    def __init__(self, in_dim, support, hidden_layers, layer_norm=True):
+        super().__init__()
+        self.model = MLP(in_dim, len(support), MLP_HIDDEN, hidden_layers, layer_norm)
+        self.support = np.array(support).astype(float)
+        self._support = nn.Parameter(torch.tensor(self.support).to(torch.float), requires_grad=False)
+        if self._support.is_meta:
+            raise NotImplementedError('reward_decoder_categorical on the meta device is not built: `_support` holds values fixed '
+                                      'at construction, which a meta tensor drops; construct the model on a real device')
+
+
 class MultiDecoder(_Params):
     """decoders.py:10-108."""
 
@@ -358,9 +413,10 @@ class MultiDecoder(_Params):
         super().__init__()
         dense = dense_image_gate(conf)
         imageless = not dense and imageless_gate(conf)
-        if (conf.image_decoder != 'cnn' and not dense and not imageless) or conf.reward_decoder_categorical:
-            raise NotImplementedError('only image_decoder=cnn (or the dense categorical image path, dense_image_gate) with Normal '
-                                      'reward decoder is built in the HIP path')
+        if conf.image_decoder != 'cnn' and not dense and not imageless:
+            raise NotImplementedError(f'image_decoder={conf.image_decoder!r}: only image_decoder=cnn, the dense categorical image '
+                                      'path (dense_image_gate) and the image-less path (imageless_gate) are built in the HIP path')
+        support = reward_support(conf)
         self.image_weight, self.reward_weight, self.terminal_weight = conf.image_weight, conf.reward_weight, conf.terminal_weight
         if dense:      # decoders.py:23-28
             self.image = CatImageDecoder(features_dim, (conf.image_channels, conf.image_size, conf.image_size),
@@ -369,7 +425,11 @@ class MultiDecoder(_Params):
             self.image = None
         else:
             self.image = ConvDecoder(in_dim=features_dim, out_channels=conf.image_channels, cnn_depth=conf.cnn_depth)
-        self.reward = DenseNormalDecoder(features_dim, conf.reward_decoder_layers, conf.layer_norm)
+        if support is not None:      # decoders.py:34-39
+            self.reward = DenseCategoricalSupportDecoder(features_dim, support, conf.reward_decoder_layers, conf.layer_norm)
+        else:
+            self.reward = DenseNormalDecoder(features_dim, conf.reward_decoder_layers, conf.layer_norm)
+        self.reward_bins = 0 if support is None else len(support)      # K of dm_head_loss_catsup, 0 for the Normal head
         self.terminal = DenseBernoulliDecoder(features_dim, conf.terminal_decoder_layers, conf.layer_norm)
         self.vecobs_weight = conf.vecobs_weight
         if conf.vecobs_size:      # decoders.py:45-48
@@ -1363,7 +1423,7 @@ class WorldModel(_Params):
             H.call('dm_conv_decoder_mse_fwd', ctypes.byref(shp), H.fptr(feat), F_, H.ptr(image), ctypes.byref(dec_p),
                    H.fptr(dec_acts), H.fptr(loss_image), None, H.ptr(ws), ws.numel(), H.stream())
 
-        reward_t = obs['reward'].float().contiguous()
+        reward_t = reward_tb = obs['reward'].float().contiguous()
         terminal_t = obs['terminal'].float().contiguous()
         if I > 1:                                  # targets expanded over I (decoders.py:270,305: insert_dim)
             reward_t = reward_t.repeat_interleave(I, dim=1).contiguous()
@@ -1371,14 +1431,20 @@ class WorldModel(_Params):
         sp = 0 if c.stoch_discrete == 0 else c.stoch_dim * c.stoch_discrete      # the one-hot latent columns of a feature row
         mu, r_acts = dec.reward.model.fwd(feat, F_, N, ws, sparse_cols=sp)
         tl, t_acts = dec.terminal.model.fwd(feat, F_, N, ws, sparse_cols=sp)
-        loss_reward, dmu, reward_rec = (torch.empty(N, device=dev) for _ in range(3))
+        K = dec.reward_bins      # > 0: DenseCategoricalSupportDecoder, `mu` holds (N, K) logits and `dmu` their gradient
+        loss_reward, reward_rec = (torch.empty(N, device=dev) for _ in range(2))
+        dmu = torch.empty((N, K) if K else N, device=dev)
         loss_terminal, dtl, terminal_rec = (torch.empty(N, device=dev) for _ in range(3))
         # -Normal(mu, std).log_prob(y) * std^2 = 0.5 (mu-y)^2 + std^2 (log std + log sqrt(2 pi))   (decoders.py:296-304)
         loss_const = REWARD_STD ** 2 * (math.log(REWARD_STD) + math.log(math.sqrt(2 * math.pi)))
         # gw: the data-parallel shard weight B_r/B (dist.attach), folded into every gradient scale; loss values are unaffected
         gw = float(getattr(self, 'grad_weight', 1.0))
-        H.call('dm_head_loss', 0, N, H.fptr(mu), H.fptr(reward_t), gw * dec.reward_weight / NE, loss_const, H.fptr(loss_reward),
-               H.fptr(dmu), H.fptr(reward_rec), H.stream())
+        if K:      # decoders.py:340-362; the target is the (T,B) reward itself: row r reads target r / I
+            H.call('dm_head_loss_catsup', N, I, K, H.fptr(mu), K, H.fptr(dec.reward._support), H.fptr(reward_tb),
+                   gw * dec.reward_weight / NE, H.fptr(loss_reward), H.fptr(dmu), H.fptr(reward_rec), None, H.stream())
+        else:
+            H.call('dm_head_loss', 0, N, H.fptr(mu), H.fptr(reward_t), gw * dec.reward_weight / NE, loss_const, H.fptr(loss_reward),
+                   H.fptr(dmu), H.fptr(reward_rec), H.stream())
         H.call('dm_head_loss', 1, N, H.fptr(tl), H.fptr(terminal_t), gw * dec.terminal_weight / NE, 0.0, H.fptr(loss_terminal),
                H.fptr(dtl), H.fptr(terminal_rec), H.stream())
 
@@ -1541,8 +1607,9 @@ class WorldModel(_Params):
         dfeat = torch.zeros(N, F_, device=dev)
         # dense heads (decoders.py:73-83)
         if iw is not None and not pk.get('iw_applied'):
-            for dout in (pk['dmu'], pk['dtl']):
-                H.call('dm_scale_rows', N, 1, H.fptr(dout), 1, H.fptr(iw), 1.0, H.stream())
+            for dout in (pk['dmu'], pk['dtl']):      # (N,), or the (N, K) logit gradient of the categorical reward head
+                n = dout.numel() // N
+                H.call('dm_scale_rows', N, n, H.fptr(dout), n, H.fptr(iw), 1.0, H.stream())
             if pk.get('dmu_v') is not None:
                 H.call('dm_scale_rows', N, c.vecobs_size, H.fptr(pk['dmu_v']), c.vecobs_size, H.fptr(iw), 1.0, H.stream())
             pk['iw_applied'] = True
@@ -1714,11 +1781,18 @@ class WorldModel(_Params):
                     H.call('dm_reduce_i', NE, I, 1, H.fptr(lv_i), 1, H.fptr(lv), None, H.stream())
                     H.call('dm_reduce_i', NE, I, V, H.fptr(vp_i), 0, H.fptr(vp), None, H.stream())
             reward_t, terminal_t = obs['reward'].float().contiguous(), obs['terminal'].float().contiguous()
+            reward_tb = reward_t
             if I > 1:                              # targets expanded over I (decoders.py:270,305: insert_dim)
                 reward_t = reward_t.repeat_interleave(I, dim=1).contiguous()
                 terminal_t = terminal_t.repeat_interleave(I, dim=1).contiguous()
-            H.call('dm_head_loss', 0, N, H.fptr(mu), H.fptr(reward_t), 0.0, loss_const, H.fptr(lr),
-                   H.fptr(scratch), H.fptr(rp), H.stream())
+            K, rbin = dec.reward_bins, None
+            if K:      # the same call as the training path with scale 0; `rbin` (T,B): the target's bin, not per IWAE sample
+                rbin = torch.empty(T, B, dtype=torch.int32, device=dev)
+                H.call('dm_head_loss_catsup', N, I, K, H.fptr(mu), K, H.fptr(dec.reward._support), H.fptr(reward_tb), 0.0,
+                       H.fptr(lr), None, H.fptr(rp), H.ptr(rbin), H.stream())
+            else:
+                H.call('dm_head_loss', 0, N, H.fptr(mu), H.fptr(reward_t), 0.0, loss_const, H.fptr(lr),
+                       H.fptr(scratch), H.fptr(rp), H.stream())
             H.call('dm_head_loss', 1, N, H.fptr(tl), H.fptr(terminal_t), 0.0, 0.0, H.fptr(lt),
                    H.fptr(scratch), H.fptr(tp), H.stream())
             if I > 1:                              # TBI => TB
@@ -1744,9 +1818,14 @@ class WorldModel(_Params):
                 metrics.update(logprob_vecobs=lv.mean())
             nan = torch.full((), float('nan'), device=dev)
             nanmean = lambda x: torch.nansum(x) / (~torch.isnan(x)).sum()     # functions.py:149-150
-            for sig in (-1, 1):
-                lp = torch.where(torch.sign(obs['reward'].float()) == sig, tb(lr), nan)
-                metrics[f'logprob_reward{sig}'], tensors[f'logprob_reward{sig}'] = nanmean(lp), lp
+            if K:      # decoders.py:86-94: one entry per support bucket, indexed by bucket; a bucket nobody hit is 0 / 0 = NaN
+                for i in range(K):
+                    lp = torch.where(rbin == i, tb(lr), nan)
+                    metrics[f'logprob_reward{i}'], tensors[f'logprob_reward{i}'] = nanmean(lp), lp
+            else:
+                for sig in (-1, 1):
+                    lp = torch.where(torch.sign(obs['reward'].float()) == sig, tb(lr), nan)
+                    metrics[f'logprob_reward{sig}'], tensors[f'logprob_reward{sig}'] = nanmean(lp), lp
             lp = torch.where(obs['terminal'].float() > 0, tb(lt), nan)
             metrics['logprob_terminal1'], tensors['logprob_terminal1'] = nanmean(lp), lp
         return metrics, tensors, idx
@@ -2315,7 +2394,8 @@ class Dreamer(nn.Module):
                H.fptr(a_acts), H.fptr(a_logits), H.ptr(ws), ws.numel(), H.stream())
         f2 = feats.view(rows, F_)
         Zc = c.stoch_dim * c.stoch_discrete            # the sampled one-hot latent columns of a feature row
-        mu, tl = torch.empty(rows, 1, device=dev), torch.empty(rows, 1, device=dev)
+        Kr = self.wm.decoder.reward_bins      # categorical reward head: `mu` holds (rows, K) logits, decoded behind the windows
+        mu, tl = torch.empty(rows, Kr or 1, device=dev), torch.empty(rows, 1, device=dev)
         values = self.ac.value_buffers(rows, dev) if _pack is not None else None
 
         def heads(a, b, wsx):
@@ -2337,6 +2417,10 @@ class Dreamer(nn.Module):
             heads(r_split, rows, ws)
         term = torch.empty(rows, device=dev)
         H.call('dm_head_loss', 1, rows, H.fptr(tl), None, 0.0, 0.0, None, None, H.fptr(term), H.stream())
+        if Kr:      # dreamer.py:212: only `.mean` of the decoded distribution is ever read - the mean-only form, one launch over all rows
+            logits, mu = mu, torch.empty(rows, device=dev)
+            H.call('dm_head_loss_catsup', rows, 1, Kr, H.fptr(logits), Kr, H.fptr(self.wm.decoder.reward._support), None, 0.0,
+                   None, None, H.fptr(mu), None, H.stream())
         if _pack is not None:
             _pack.update(act_idx=act_idx, ws=ws, actor_acts=a_acts, actor_logits=a_logits, values=values)
         return feats, actions, _Mean(mu.view(Hh + 1, M)), _Mean(term.view(Hh + 1, M))

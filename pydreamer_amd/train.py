@@ -271,7 +271,9 @@ def load_checkpoint(path, model, optimizers=(), map_location=None):
 
 
 # ------------------------------------------------------------------------------------------------ evaluation
-_EVAL_EXTRA = 96      # slots for the scalars of an evaluation batch: the step's metrics, then the *_open means
+# slots for the scalars of an evaluation batch: the step's metrics, then the *_open means.  A categorical reward decoder adds one
+# logprob_reward{i} and one logprob_reward{i}_open per support value, up to 2 x 32 names on top of the ~35 of a Normal head
+_EVAL_EXTRA = 160
 
 
 def _to_device(batch, device):
