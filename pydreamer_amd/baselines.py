@@ -8,10 +8,10 @@ categorical image.  As everywhere in this package the modules only own parameter
 C-ABI of libdreamer_hip.so: dm_conv_encoder_fwd(_planes), one dm_gemm_f32 for the squeeze (written straight into the leading 32
 columns of the GRU's input rows), dm_gru_sequence_fwd (csrc/gru_seq.hip), the probe heads of models.py unchanged,
 and in loss.backward() - on the caller's stream - the heads' backward WITH their input gradient, dm_gru_sequence_bwd, the squeeze
-backward and dm_conv_encoder_bwd(_planes), all into the one flat gradient buffer of the optimizer.  On the dense branch the two
-encoder calls are replaced by the entry points WorldModel uses for it: dm_dense_image_rows (from the float one-hot (T,B,C,S,S) or
-the integer class map (T,B,S,S): same bits), MLP.fwd, dm_elu_rows_fwd into `embed`; backward dm_elu_rows_bwd in place on dembed,
-then dm_mlp_head_bwd without an input gradient.  No entry point is new.
+backward and dm_conv_encoder_bwd(_planes), all into the one flat gradient buffer of the optimizer.  The encoder is run by the methods
+WorldModel runs it by - MultiEncoder.ingest / encode / backward - so on the dense branch the two encoder calls become
+dm_dense_image_rows (from the float one-hot (T,B,C,S,S) or the integer class map (T,B,S,S): same bits), MLP.fwd, dm_elu_rows_fwd
+into `embed`; backward dm_elu_rows_bwd in place on dembed, then dm_mlp_head_bwd without an input gradient.  No entry point is new.
 
 Not built (NotImplementedError at construction): model in {vae, gru_vae, transformer_vae}; probe_gradients=False (the reference
 then returns the Python float 0.0 as its first loss, which train.py:187 cannot backpropagate); probe_model='none';
@@ -161,15 +161,8 @@ class WorldModelProbe(nn.Module):
         if self.dense:      # the encoder MLP may be deeper than the four layers dm_workspace_bytes sizes the heads for
             deep = max(4, self.wm.encoder.encoder_image.hidden_layers)
             need = max(need, 4 * int(H.lib().dm_mlp_ws_floats(T * B, M.MLP_HIDDEN, deep)))
-        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
+        self._ws = M._grow_ws(self._ws, need, device)
         return self._ws
-
-    def _enc_struct(self, gof=None):
-        convs = self.wm.encoder.encoder_image.convs()
-        if gof is None:
-            return H.conv_struct([m.weight for m in convs], [m.bias for m in convs])
-        return H.conv_struct([gof[id(m.weight)] for m in convs], [gof[id(m.bias)] for m in convs], cls=H.dm_conv_grads)
 
     # ---- the step
     def training_step(self, obs, in_state, iwae_samples=1, imag_horizon=None, do_open_loop=False, do_image_pred=False,
@@ -195,63 +188,17 @@ class WorldModelProbe(nn.Module):
         In = SQUEEZE_DIM + A_
         train = torch.is_grad_enabled()
         shp = self._shape(T, B)
-        u8 = image.dtype == torch.uint8 and not self.dense
-        if self.dense:
-            if not image.is_floating_point() and image.dim() == 5:
-                raise ValueError(f'the dense image path takes a float one-hot (T,B,C,S,S) image or an integer class map (T,B,S,S), '
-                                 f'not a {image.dtype} frame of shape {tuple(image.shape)}')
-            image = image.float().contiguous() if image.is_floating_point() else image.to(torch.int32).contiguous()
-        elif u8:
-            image = image.contiguous()
-            shp.flags |= H.DM_FLAG_IMAGE_U8
-        else:
-            image = image.float().contiguous()
-        planes = wm.encoder.reward_input
-        want = dict(image=(T, B, c.image_size, c.image_size, c.image_channels) if u8 else
-                    (T, B, c.image_channels, c.image_size, c.image_size), action_next=(T, B, A_), reset=(T, B))
-        if self.dense and not image.is_floating_point():
-            want['image'] = (T, B, c.image_size, c.image_size)
-        got = dict(image=tuple(image.shape), action_next=tuple(obs['action_next'].shape), reset=tuple(obs['reset'].shape))
-        for k in ('reward', 'terminal'):
-            if planes:
-                if k not in obs:
-                    raise ValueError(f"reward_input: obs['{k}'] is an input of the encoder (encoders.py:52-59)")
-                want[k], got[k] = (T, B), tuple(obs[k].shape)
         h0 = in_state.float().contiguous()
-        want['in_state'], got['in_state'] = (1, B, D_), tuple(h0.shape)
-        bad = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
-        if bad:
-            raise ValueError('training_step input shapes (got, expected): ' + ', '.join(f'{k}: {v[0]} != {v[1]}' for k, v in bad.items()))
+        want = dict(action_next=(T, B, A_), reset=(T, B), in_state=(1, B, D_))
+        got = dict(action_next=tuple(obs['action_next'].shape), reset=tuple(obs['reset'].shape), in_state=tuple(h0.shape))
+        image, _, plane_r, plane_t, _ = wm.encoder.ingest(obs, T, B, shp, want, got)
         lib = H.lib()
         mbuf = torch.zeros(M.METRIC_BUF_FLOATS, device=dev)
         self.metric_buffer = mbuf
+        ws = self._workspace(shp, T, B, dev)
+        embed, enc_st = wm.encoder.encode(image, plane_r, plane_t, None, shp, ws)      # (in the caller's grad mode: it decides what is saved)
         with torch.no_grad():
-            ws = self._workspace(shp, T, B, dev)
             reset0 = obs['reset'][0].to(torch.uint8).contiguous()          # baselines.py:339-341: the batch start only
-            embed = torch.empty(N, E, device=dev)
-            plane_r = plane_t = enc_x = None
-            if planes:
-                plane_r = obs['reward'].float().contiguous().view(N)
-                plane_t = obs['terminal'].float().contiguous().view(N)
-            if self.dense:
-                # encoders.py:50-61,121-125: rows [image | reward plane | terminal plane] -> MLP -> ELU (WorldModel._dense_encode)
-                enc = wm.encoder.encoder_image
-                enc_x = torch.empty(N, enc.in_dim, device=dev)
-                onehot = image.is_floating_point()
-                H.call('dm_dense_image_rows', N, c.image_channels, c.image_size ** 2, H.fptr(image) if onehot else None,
-                       None if onehot else H.ptr(image), H.fptr(plane_r), H.fptr(plane_t), H.fptr(enc_x), enc.in_dim, H.stream())
-                pre, enc_acts = enc.fwd(enc_x, enc.in_dim, N, ws, save_acts=train)
-                H.call('dm_elu_rows_fwd', N, E, H.fptr(pre), E, H.fptr(embed), E, H.stream())
-                del pre
-            else:
-                enc_p = self._enc_struct()
-                enc_acts = torch.empty(int(lib.dm_conv_encoder_acts_floats(ctypes.byref(shp))), device=dev)
-                if planes:
-                    H.call('dm_conv_encoder_fwd_planes', ctypes.byref(shp), H.ptr(image), ctypes.byref(enc_p), H.fptr(plane_r),
-                           H.fptr(plane_t), H.fptr(enc_acts), H.fptr(embed), E, H.ptr(ws), ws.numel(), H.stream())
-                else:
-                    H.call('dm_conv_encoder_fwd', ctypes.byref(shp), H.ptr(image), ctypes.byref(enc_p), H.fptr(enc_acts), H.fptr(embed),
-                           H.ptr(ws), ws.numel(), H.stream())
             # the GRU's input rows [squeeze(embed) | action_next] (baselines.py:346-348): the squeeze product writes the
             # leading 32 columns through its leading dimension
             x = torch.empty(N, In, device=dev)
@@ -290,8 +237,7 @@ class WorldModelProbe(nn.Module):
                 loss = l_ if loss is None else loss + l_
         if not train:
             return (loss,), out_state, metrics, tensors, {}
-        pk = dict(loss=loss, heads=heads, T=T, B=B, shp=shp, image=image, enc_x=enc_x, plane_r=plane_r, plane_t=plane_t, enc_acts=enc_acts,
-                  embed=embed, x=x, gru_acts=gru_acts, Hs=Hs, ws=ws)
+        pk = dict(loss=loss, heads=heads, T=T, B=B, shp=shp, x=x, gru_acts=gru_acts, Hs=Hs, ws=ws, **enc_st)
         self._last_pack = pk
         loss_probe = _GruProbeLoss.apply(self, pk, *self.parameters())
         return (loss_probe,), out_state, metrics, tensors, {}
@@ -309,12 +255,8 @@ class WorldModelProbe(nn.Module):
         ldd = max(hp['mlp'].in_dim for hp in pk['heads'])
         dH = torch.empty(N, ldd, device=dev)
         for i, hp in enumerate(pk['heads']):
-            mlp = hp['mlp']
-            assert i == 0 or mlp.in_dim == D_
-            st, gs = mlp.struct(), mlp.grad_struct(gof)
-            H.call('dm_mlp_head_bwd', hp['rows'], mlp.in_dim, mlp.hidden_dim, mlp.hidden_layers, mlp.out_dim, H.fptr(hp['x']), hp['ldx'],
-                   ctypes.byref(st), H.fptr(hp['acts']), H.fptr(hp['dout']), ctypes.byref(gs), H.fptr(dH), ldd, 1 if i else 0,
-                   H.ptr(hp['ws']), hp['ws'].numel(), H.stream())
+            assert i == 0 or hp['mlp'].in_dim == D_
+            hp['mlp'].bwd_into(gof, hp['x'], hp['ldx'], hp['rows'], hp['acts'], hp['dout'], hp['ws'], dx=dH, lddx=ldd, dx_accum=i > 0)
             for k in ('acts', 'dout', 'x'):
                 hp.pop(k, None)
         rnn = wm.rnn
@@ -331,23 +273,6 @@ class WorldModelProbe(nn.Module):
         dembed = torch.empty(N, E, device=dev)
         H.call('dm_gemm_f32', 0, 1, N, E, SQUEEZE_DIM, H.fptr(dx), In, H.fptr(sq.weight), E, H.fptr(dembed), E, None, None, 0, 0,
                H.ptr(ws), ws.numel(), H.stream())
-        if self.dense:      # through the trailing ELU (derivative from embed = ELU(pre), in place), then the MLP; no input gradient
-            enc = wm.encoder.encoder_image
-            H.call('dm_elu_rows_bwd', N, E, H.fptr(pk['embed']), E, H.fptr(dembed), E, H.fptr(dembed), E, H.stream())
-            st, gs = enc.struct(), enc.grad_struct(gof)
-            H.call('dm_mlp_head_bwd', N, enc.in_dim, enc.hidden_dim, enc.hidden_layers, enc.out_dim, H.fptr(pk['enc_x']), enc.in_dim,
-                   ctypes.byref(st), H.fptr(pk['enc_acts']), H.fptr(dembed), ctypes.byref(gs), None, 0, 0, H.ptr(ws), ws.numel(),
-                   H.stream())
-            for k in ('gru_acts', 'enc_acts', 'enc_x', 'embed', 'x', 'Hs'):
-                pk.pop(k, None)
-            return
-        enc_p, enc_g = self._enc_struct(), self._enc_struct(gof)
-        if pk['plane_r'] is not None:
-            H.call('dm_conv_encoder_bwd_planes', ctypes.byref(pk['shp']), H.ptr(pk['image']), ctypes.byref(enc_p), H.fptr(pk['plane_r']),
-                   H.fptr(pk['plane_t']), H.fptr(pk['enc_acts']), H.fptr(dembed), E, ctypes.byref(enc_g), H.ptr(ws), ws.numel(),
-                   H.stream())
-        else:
-            H.call('dm_conv_encoder_bwd', ctypes.byref(pk['shp']), H.ptr(pk['image']), ctypes.byref(enc_p), H.fptr(pk['enc_acts']),
-                   H.fptr(dembed), ctypes.byref(enc_g), H.ptr(ws), ws.numel(), H.stream())
-        for k in ('gru_acts', 'enc_acts', 'embed', 'x', 'Hs'):
+        wm.encoder.backward(dembed, pk, gof, ws)
+        for k in ('gru_acts', 'enc_acts', 'enc_x', 'embed', 'x', 'Hs'):
             pk.pop(k, None)

@@ -38,6 +38,8 @@ from .optim import FusedAdamW
 MLP_HIDDEN = 400          # a2c.py:16, decoders.py:259,289
 ACTOR_KINDS = {'onehot': 0, 'tanh_normal': 1, 'normal_tanh': 2}   # dm_shape.flags bits 0-1
 REWARD_STD = 0.3989422804  # decoders.py:289
+# -Normal(mu, std).log_prob(y) * std^2 = 0.5 (mu-y)^2 + NORMAL_LOSS_CONST per output (decoders.py:296-304), std = REWARD_STD
+NORMAL_LOSS_CONST = REWARD_STD ** 2 * (math.log(REWARD_STD) + math.log(math.sqrt(2 * math.pi)))
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -180,12 +182,17 @@ class MLP(_Params):
         ARE the optimizer's `.grad` slots (freshly zeroed), so autograd has nothing left to accumulate."""
         plist = self.param_list()
         flat, out, direct = _flat_views(plist, x2d.device, getattr(self, '_fused', None), scratch)
-        grads = {id(p): v for p, v in zip(plist, out)}
-        st, gs = self.struct(), self.grad_struct(grads)
-        H.call('dm_mlp_head_bwd', rows, self.in_dim, self.hidden_dim, self.hidden_layers, self.out_dim, H.fptr(x2d), ldx,
-               ctypes.byref(st), H.fptr(acts), H.fptr(dout), ctypes.byref(gs), H.fptr(dx) if dx is not None else None, lddx,
-               1 if dx_accum else 0, H.ptr(ws), ws.numel(), H.stream())
+        self.bwd_into({id(p): v for p, v in zip(plist, out)}, x2d, ldx, rows, acts, dout, ws, dx, lddx, dx_accum)
         return out, flat, direct
+
+    def bwd_into(self, gof, x2d, ldx, rows, acts, dout, ws, dx=None, lddx=0, dx_accum=False):
+        """The backward pass with every parameter gradient written to gof[id(parameter)] (views of a caller's flat buffer that
+        may hold other modules' gradients too).  dx: the input gradient (leading dim lddx), overwritten or, with dx_accum,
+        added to; None: not computed."""
+        st, gs = self.struct(), self.grad_struct(gof)
+        H.call('dm_mlp_head_bwd', rows, self.in_dim, self.hidden_dim, self.hidden_layers, self.out_dim, H.fptr(x2d), ldx,
+               ctypes.byref(st), H.fptr(acts), H.fptr(dout), ctypes.byref(gs), H.fptr(dx), lddx, 1 if dx_accum else 0, H.ptr(ws),
+               ws.numel(), H.stream())
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -269,7 +276,7 @@ def imageless_gate(conf):
 class DenseEncoder(MLP):
     """encoders.py:99-125: model = Sequential[Flatten, (Linear, LayerNorm | NoNorm, ELU) x L, Linear, ELU] - the Linears sit at
     1, 4, ..., 3L + 1, one behind the indices of `MLP`.  The marshalling, forward and backward are MLP's; the trailing ELU is
-    dm_elu_rows_fwd / _bwd (WorldModel._dense_encode)."""
+    dm_elu_rows_fwd / _bwd (MultiEncoder.dense_encode / MultiEncoder.backward)."""
     _base = 1
 
     def __init__(self, in_dim, hidden_layers, layer_norm=True):
@@ -284,23 +291,54 @@ class CatImageDecoder(MLP):
         C, S1, S2 = (int(x) for x in out_shape)
         super().__init__(in_dim, C * S1 * S2, MLP_HIDDEN, hidden_layers, layer_norm)
         self.out_shape, self.min_prob = (C, S1, S2), float(min_prob or 0)
+
+    def target(self, image, NE):
+        """The (NE, cells) class index of the image the loss is taken against (_cat_target_index)."""
+        C, S1, S2 = self.out_shape
+        return _cat_target_index(image, NE, C, S1 * S2)
+
+    def loss(self, logits, target, N, loss, dlogits):
+        """CatImageDecoder.loss (decoders.py:219-236) per row; min_prob = 0 is the map probe's kernel, bit for bit."""
+        C, cells = self.out_shape[0], self.out_shape[1] * self.out_shape[2]
+        if self.min_prob == 0:
+            H.call('dm_cat_image_loss', N, 1, C, cells, H.fptr(logits), C * cells, H.ptr(target), H.fptr(loss), H.fptr(dlogits),
+                   H.stream())
+        else:
+            H.call('dm_cat_image_loss_mix', N, 1, C, cells, H.fptr(logits), C * cells, H.ptr(target), self.min_prob, H.fptr(loss),
+                   H.fptr(dlogits), H.stream())
+
+    def logp(self, logits, target, NE):
+        """The decoded image (decoders.py:247-251 with I = 1): per-cell normalised log-probabilities (NE, C, cells)."""
+        C, cells = self.out_shape[0], self.out_shape[1] * self.out_shape[2]
+        logp, acc = torch.empty(NE, C, cells, device=logits.device), torch.empty(NE, device=logits.device)
+        H.call('dm_cat_image_pred', NE, 1, C, cells, H.fptr(logits), C * cells, H.ptr(target), None, H.fptr(logp), H.fptr(acc), None,
+               H.stream())
+        return logp
+
+
 REWARD_INPUT_DEPTHS = (8, 16, 32, 48, 64)     # the depths of the direct layer-1 kernels (csrc/conv_direct.hip dm_enc_l1_direct_ok)
 
 
 class MultiEncoder(_Params):
     """encoders.py:10-69 (image encoder, with or without the reward / terminal planes of reward_input; the vecobs MLP beside it,
-    or alone on the image-less path)."""
+    or alone on the image-less path).  Owns the parameters and runs the encoder for WorldModel and the gru_probe baseline:
+    ingest() normalises what it reads of `obs`, encode() writes the (T*B, out_dim) embedding, backward() its gradients."""
 
     def __init__(self, conf):
         super().__init__()
         self.reward_input = bool(conf.reward_input)
-        if dense_image_gate(conf):      # encoders.py:23-27: the flattened (C [+ 2], S, S) block through a DenseEncoder
+        self.vecobs_size = int(conf.vecobs_size or 0)
+        self.dense = dense_image_gate(conf)
+        self.imageless = not self.dense and imageless_gate(conf)
+        if not self.imageless:          # (image-less: image_size and image_channels are not read)
+            self.image_channels, self.image_size = conf.image_channels, conf.image_size
+        if self.dense:      # encoders.py:23-27: the flattened (C [+ 2], S, S) block through a DenseEncoder
             self.encoder_image = DenseEncoder(conf.image_size ** 2 * (conf.image_channels + (2 if self.reward_input else 0)),
                                               conf.image_encoder_layers, conf.layer_norm)
             self.encoder_vecobs = None
             self.out_dim = self.encoder_image.out_dim
             return
-        if imageless_gate(conf):        # encoders.py:28-40,64-69: no image branch; reward_input is read inside it only, so it is ignored
+        if self.imageless:        # encoders.py:28-40,64-69: no image branch; reward_input is read inside it only, so it is ignored
             self.reward_input = False
             self.encoder_image = None
             self.encoder_vecobs = MLP(conf.vecobs_size, VECOBS_EMBED, MLP_HIDDEN, 2, conf.layer_norm)
@@ -317,6 +355,132 @@ class MultiEncoder(_Params):
         # encoders.py:33-36,64-68: the vecobs embedding is concatenated behind the image embedding
         self.encoder_vecobs = MLP(conf.vecobs_size, VECOBS_EMBED, MLP_HIDDEN, 2, conf.layer_norm) if conf.vecobs_size else None
         self.out_dim = self.encoder_image.out_dim + (VECOBS_EMBED if conf.vecobs_size else 0)
+
+    # ---- the step: ingest -> encode -> backward
+    def ingest(self, obs, T, B, shp, want, got):
+        """What the encoder reads of `obs`, normalised for the kernels: (image or None, u8, plane_r, plane_t, vecobs rows).
+        want / got: the caller's own entries of the step's shape check; the encoder adds its entries and runs the check before it
+        reshapes anything.  u8: the replay's native (T,B,H,W,C) uint8 frames are
+        consumed AS THEY ARE - x/255-0.5 and HWC->CHW (preprocessing.py:21-29) happen inside the first conv's patch loader and
+        inside the MSE kernel (dm_shape.flags bit DM_FLAG_IMAGE_U8, set on `shp` here); no float image is ever written (SURVEY
+        8(f) N1).  Dense: the reference's float one-hot (T,B,C,S,S) (preprocessing.py:108-109) or an integer class map (T,B,S,S),
+        same bits.  Image-less: no frame ingest, no obs['image']."""
+        image, u8, NE = None, False, T * B
+        if not self.imageless:
+            image = obs['image']
+            C, S = self.image_channels, self.image_size
+            u8 = image.dtype == torch.uint8 and not self.dense
+            want['image'] = (T, B, S, S, C) if u8 else (T, B, C, S, S)
+            if self.dense:
+                if not image.is_floating_point() and image.dim() == 5:
+                    raise ValueError(f'the dense image path takes a float one-hot (T,B,C,S,S) image or an integer class map (T,B,S,S), '
+                                     f'not a {image.dtype} frame of shape {tuple(image.shape)}')
+                image = image.float().contiguous() if image.is_floating_point() else image.to(torch.int32).contiguous()
+                if not image.is_floating_point():
+                    want['image'] = (T, B, S, S)
+            elif u8:
+                if image.dim() != 5 or tuple(image.shape[2:]) != (S, S, C):
+                    raise ValueError(f'uint8 image must be (T,B,{S},{S},{C}), got {tuple(image.shape)}')
+                image = image.contiguous()
+                shp.flags |= H.DM_FLAG_IMAGE_U8
+            else:
+                image = image.float().contiguous()
+            got['image'] = tuple(image.shape)
+        plane_r = plane_t = vecobs = None
+        if self.reward_input:      # encoders.py:52-59: per-frame constants, (T,B) -> (NE,); never expanded to image planes
+            for k in ('reward', 'terminal'):
+                if k not in obs:
+                    raise ValueError(f"reward_input: obs['{k}'] is an input of the encoder (encoders.py:52-59)")
+                want[k], got[k] = (T, B), tuple(obs[k].shape)
+        V = self.vecobs_size
+        if V:
+            if 'vecobs' not in obs:
+                raise ValueError(f"vecobs_size={V}: obs['vecobs'] is an input of the encoder (encoders.py:64-66)")
+            want['vecobs'], got['vecobs'] = (T, B, V), tuple(obs['vecobs'].shape)
+        _check_shapes(want, got)
+        if self.reward_input:
+            plane_r = obs['reward'].float().contiguous().view(NE)
+            plane_t = obs['terminal'].float().contiguous().view(NE)
+        if V:
+            vecobs = obs['vecobs'].float().contiguous().view(NE, V)
+        return image, u8, plane_r, plane_t, vecobs
+
+    def dense_encode(self, image, plane_r, plane_t, embed, NE, ws, save):
+        """encoders.py:50-61,121-125: rows [image | reward plane | terminal plane] -> MLP -> ELU, written into `embed`.
+        `image`: float one-hot (T,B,C,S,S), copied as it is, or an int32 class map (T,B,S,S).  Returns (rows, activations)."""
+        enc = self.encoder_image
+        onehot = image.is_floating_point()
+        x = torch.empty(NE, enc.in_dim, device=embed.device)
+        H.call('dm_dense_image_rows', NE, self.image_channels, self.image_size ** 2, H.fptr(image) if onehot else None,
+               None if onehot else H.ptr(image), H.fptr(plane_r), H.fptr(plane_t), H.fptr(x), enc.in_dim, H.stream())
+        pre, acts = enc.fwd(x, enc.in_dim, NE, ws, save_acts=save)
+        H.call('dm_elu_rows_fwd', NE, enc.out_dim, H.fptr(pre), enc.out_dim, H.fptr(embed), embed.shape[1], H.stream())
+        return x, acts
+
+    def conv_structs(self, gof=None):
+        """The convolution stack's parameters, or with gof their gradient slots, as the library takes them."""
+        convs = self.encoder_image.convs()
+        if gof is None:
+            return H.conv_struct([m.weight for m in convs], [m.bias for m in convs])
+        return H.conv_struct([gof[id(m.weight)] for m in convs], [gof[id(m.bias)] for m in convs], cls=H.dm_conv_grads)
+
+    def encode(self, image, plane_r, plane_t, vecobs, shp_e, ws, forward_only=False):
+        """The (T*B, E) embedding of the ingested observation and what backward() needs of this pass, under the pack's names:
+        returns (embed, dict(image, plane_r, plane_t, vecobs, shp_e, embed, enc_x, enc_acts, ev_acts))."""
+        NE, E = shp_e.T * shp_e.B, self.out_dim
+        enc, V = self.encoder_image, self.vecobs_size
+        enc_x = enc_acts = ev_acts = None
+        if self.imageless:
+            # encoders.py:64-69 with encoder_image = None: the vecobs MLP's (T*B, 256) output IS the RSSM's embed, no copy pass
+            embed, ev_acts = self.encoder_vecobs.fwd(vecobs, V, NE, ws, save_acts=not forward_only and torch.is_grad_enabled())
+        elif self.dense:
+            embed = torch.empty(NE, E, device=image.device)
+            enc_x, enc_acts = self.dense_encode(image, plane_r, plane_t, embed, NE, ws,
+                                                save=not forward_only and torch.is_grad_enabled())
+        else:
+            enc_p = self.conv_structs()
+            enc_acts = torch.empty(int(H.lib().dm_conv_encoder_acts_floats(ctypes.byref(shp_e))), device=image.device)
+            embed = torch.empty(NE, E, device=image.device)
+            if self.reward_input or V:
+                # the image embedding is written as the leading E - 256 columns of the (NE, E) buffer (leading dimension E), the
+                # vecobs embedding behind it: one buffer for the RSSM, no copy pass over the image embedding
+                shp_c = H.dm_shape.from_buffer_copy(shp_e)
+                shp_c.E = enc.out_dim                   # the convolution stack's own width
+                H.call('dm_conv_encoder_fwd_planes', ctypes.byref(shp_c), H.ptr(image), ctypes.byref(enc_p), H.fptr(plane_r),
+                       H.fptr(plane_t), H.fptr(enc_acts), H.fptr(embed), E, H.ptr(ws), ws.numel(), H.stream())
+                if V:
+                    ev, ev_acts = self.encoder_vecobs.fwd(vecobs, V, NE, ws, save_acts=not forward_only)
+                    embed[:, enc.out_dim:].copy_(ev)
+            else:
+                H.call('dm_conv_encoder_fwd', ctypes.byref(shp_e), H.ptr(image), ctypes.byref(enc_p), H.fptr(enc_acts),
+                       H.fptr(embed), H.ptr(ws), ws.numel(), H.stream())
+        return embed, dict(image=image, plane_r=plane_r, plane_t=plane_t, vecobs=vecobs, shp_e=shp_e, embed=embed, enc_x=enc_x,
+                           enc_acts=enc_acts, ev_acts=ev_acts)
+
+    def backward(self, dembed, pk, gof, ws):
+        """dembed (T*B, E) -> every encoder parameter's gradient into gof[id(parameter)]; pk: what encode() returned (or a pack
+        that holds it).  dembed is consumed (the dense path's ELU derivative is applied in place).  No input gradient."""
+        enc, ev, shp_e = self.encoder_image, self.encoder_vecobs, pk['shp_e']
+        NE, E = shp_e.T * shp_e.B, self.out_dim
+        if self.dense:      # through the trailing ELU (derivative from embed = ELU(pre), in place), then the MLP
+            H.call('dm_elu_rows_bwd', NE, E, H.fptr(pk['embed']), E, H.fptr(dembed), E, H.fptr(dembed), E, H.stream())
+            enc.bwd_into(gof, pk['enc_x'], enc.in_dim, NE, pk['enc_acts'], dembed, ws)
+            return
+        if self.imageless:      # the whole (T*B, 256) dembed is the vecobs MLP's output gradient
+            ev.bwd_into(gof, pk['vecobs'], ev.in_dim, NE, pk['ev_acts'], dembed, ws)
+            return
+        enc_p, enc_g = self.conv_structs(), self.conv_structs(gof)
+        if ev is not None:      # the vecobs encoder: its output gradient is the trailing 256 columns of dembed
+            ev.bwd_into(gof, pk['vecobs'], ev.in_dim, NE, pk['ev_acts'], dembed[:, enc.out_dim:].contiguous(), ws)
+        if self.reward_input or ev is not None:
+            shp_c = H.dm_shape.from_buffer_copy(shp_e)
+            shp_c.E = enc.out_dim
+            H.call('dm_conv_encoder_bwd_planes', ctypes.byref(shp_c), H.ptr(pk['image']), ctypes.byref(enc_p),
+                   H.fptr(pk['plane_r']), H.fptr(pk['plane_t']), H.fptr(pk['enc_acts']), H.fptr(dembed), E, ctypes.byref(enc_g),
+                   H.ptr(ws), ws.numel(), H.stream())
+        else:
+            H.call('dm_conv_encoder_bwd', ctypes.byref(shp_e), H.ptr(pk['image']), ctypes.byref(enc_p),
+                   H.fptr(pk['enc_acts']), H.fptr(dembed), ctypes.byref(enc_g), H.ptr(ws), ws.numel(), H.stream())
 
 
 class ConvDecoder(_Params):
@@ -407,12 +571,14 @@ class DenseCategoricalSupportDecoder(_Params):
 
 
 class MultiDecoder(_Params):
-    """decoders.py:10-108."""
+    """decoders.py:10-108.  Owns the heads' parameters and runs the image term (convolution, dense categorical or none) for
+    WorldModel and Dreamer's log dream; the reward / terminal / vecobs heads are run by WorldModel."""
 
     def __init__(self, features_dim, conf):
         super().__init__()
-        dense = dense_image_gate(conf)
-        imageless = not dense and imageless_gate(conf)
+        dense = self.dense = dense_image_gate(conf)
+        imageless = self.imageless = not dense and imageless_gate(conf)
+        self.features_dim = features_dim
         if conf.image_decoder != 'cnn' and not dense and not imageless:
             raise NotImplementedError(f'image_decoder={conf.image_decoder!r}: only image_decoder=cnn, the dense categorical image '
                                       'path (dense_image_gate) and the image-less path (imageless_gate) are built in the HIP path')
@@ -425,6 +591,8 @@ class MultiDecoder(_Params):
             self.image = None
         else:
             self.image = ConvDecoder(in_dim=features_dim, out_channels=conf.image_channels, cnn_depth=conf.cnn_depth)
+        if not imageless:
+            self.image_shape = (conf.image_channels, conf.image_size, conf.image_size)
         if support is not None:      # decoders.py:34-39
             self.reward = DenseCategoricalSupportDecoder(features_dim, support, conf.reward_decoder_layers, conf.layer_norm)
         else:
@@ -436,6 +604,100 @@ class MultiDecoder(_Params):
             self.vecobs = DenseNormalDecoder(features_dim, 4, conf.layer_norm, out_dim=conf.vecobs_size)
         else:
             self.vecobs = None
+
+    # ---- the image term: training forward (image_buffers, image_loss), backward (image_heads, image_bwd), evaluation (decode)
+    def _conv_fwd(self, shp, feat, image, ws, acts, loss, pred):
+        """ConvDecoder on shp's T*B*I feature rows: `loss` (rows,) = the MSE term against `image` and / or `pred` (rows, C, H, W),
+        either may be None; `acts`: the activation buffer (dm_conv_decoder_acts_floats), which also keeps the NHWC prediction."""
+        dl = self.image.layers()
+        dec_p = H.conv_struct([m.weight for m in dl], [m.bias for m in dl])
+        H.call('dm_conv_decoder_mse_fwd', ctypes.byref(shp), H.fptr(feat), self.features_dim, H.ptr(image), ctypes.byref(dec_p),
+               H.fptr(acts), H.fptr(loss), H.fptr(pred), H.ptr(ws), ws.numel(), H.stream())
+
+    def _conv_acts(self, shp, device):
+        return torch.empty(int(H.lib().dm_conv_decoder_acts_floats(ctypes.byref(shp))), device=device)
+
+    def image_buffers(self, shp, N, device):
+        """(dec_acts, loss_image) of a training forward, either may be None.  Apart from image_loss() because they outlive the
+        forward's tail: the caller allocates them on ITS stream, whichever stream the tail then runs on."""
+        if self.imageless:
+            return None, None
+        return None if self.dense else self._conv_acts(shp, device), torch.empty(N, device=device)
+
+    def image_loss(self, shp, feat, image, ws, acts, loss, gw):
+        """Writes loss_image (one value per feature row) into `loss` and returns the pack entries of this pass: dec_acts, and on
+        the dense path target, dec_logits and dlogits = d loss_model / d logits (gw: the data-parallel shard weight)."""
+        if self.imageless:      # decoders.py:29-30: no image term
+            return dict(dec_acts=None)
+        if not self.dense:
+            self._conv_fwd(shp, feat, image, ws, acts, loss, None)
+            return dict(dec_acts=acts)
+        # CatImageDecoder.training_step (decoders.py:238-254): MLP -> per-cell cross-entropy, I = 1
+        dec, N, NE = self.image, feat.shape[0], shp.T * shp.B
+        train = torch.is_grad_enabled()
+        target = dec.target(image, NE)
+        logits, acts = dec.fwd(feat, self.features_dim, N, ws, save_acts=train)
+        dlogits = torch.empty_like(logits) if train else None
+        dec.loss(logits, target, N, loss, dlogits)
+        if train:      # d loss_model / d loss_image[r] = image_weight / (T*B), times the data-parallel shard weight
+            scale = torch.full((1,), gw * self.image_weight / NE, device=feat.device)
+            H.call('dm_scale_inplace', H.fptr(dlogits), dlogits.numel(), H.fptr(scale), H.stream())
+        return dict(target=target, dec_acts=acts, dec_logits=logits, dlogits=dlogits)
+
+    def image_heads(self, pk):
+        """Dense path: the image decoder is one more dense head of the backward's head loop (its dx accumulates into dfeat)."""
+        return [(self.image, pk['dec_acts'], pk['dlogits'])] if self.dense else []
+
+    def image_bwd(self, pk, gof, dfeat, scale, iw, ws):
+        """Convolution path: the MSE term's gradient (scale = d loss_model / d loss_image row, iw = the IWAE importance weights
+        or None) through the decoder into gof and, accumulated, into dfeat."""
+        if self.dense or self.imageless:
+            return
+        dl, F_ = self.image.layers(), self.features_dim
+        dec_p = H.conv_struct([m.weight for m in dl], [m.bias for m in dl])
+        dec_g = H.conv_struct([gof[id(m.weight)] for m in dl], [gof[id(m.bias)] for m in dl], cls=H.dm_conv_grads)
+        H.call('dm_conv_decoder_mse_bwd_rows', ctypes.byref(pk['shp']), H.fptr(pk['feat']), F_, H.ptr(pk['image']), ctypes.byref(dec_p),
+               H.fptr(pk['dec_acts']), scale, H.fptr(iw), ctypes.byref(dec_g), H.fptr(dfeat), F_, H.ptr(ws), ws.numel(), H.stream())
+
+    def decode(self, shp, feat, image, ws, target=None, loss=False, raw=False):
+        """Evaluation form, no gradients: decodes shp's T*B*I feature rows.  Returns (loss rows (N,) or None, prediction (N, C, H,
+        W)); (None, None) without an image decoder.  `image` / `target`: what the loss is taken against (the convolution kernel
+        takes the image argument also when no loss is asked for; the dense path's normalised log-probabilities need `target`).
+        raw (dense only): the logits as they are (decoder.image.forward) instead of normalised log-probabilities."""
+        if self.imageless:
+            return None, None
+        N, dev = feat.shape[0], feat.device
+        li = torch.empty(N, device=dev) if loss else None
+        if self.dense:
+            logits, _ = self.image.fwd(feat, self.features_dim, N, ws, save_acts=False)
+            if loss:
+                self.image.loss(logits, target, N, li, None)
+            pred = logits if raw else self.image.logp(logits, target, N)
+        else:
+            acts = self._conv_acts(shp, dev)
+            pred = torch.empty(N, *self.image_shape, device=dev)
+            self._conv_fwd(shp, feat, image, ws, acts, li, pred)
+        return li, pred.view(N, *self.image_shape)
+
+    def image_rec_thunk(self, pk):
+        """image_rec (T,B,C,H,W) of a training forward, computed when somebody reads it (LazyTensors).  The thunk holds the
+        decoder's logits / activations alive until the tensors dict is dropped."""
+        T, B, I = pk['T'], pk['B'], pk['I']
+        Cc, S, _ = self.image_shape
+        if self.dense:
+            def thunk(logits=pk['dec_logits'], target=pk['target']):
+                with torch.no_grad():
+                    return self.image.logp(logits, target, T * B).view(T, B, Cc, S, S)
+            return thunk
+        N, hw = T * B * I, S * S
+        pred_off = int(H.lib().dm_conv_decoder_pred_offset(ctypes.byref(pk['shp'])))
+
+        def thunk(acts=pk['dec_acts']):
+            with torch.no_grad():
+                pred = acts[pred_off:pred_off + N * hw * Cc].view(N, hw, Cc)                       # NHWC
+                rec = pred.transpose(1, 2).contiguous().view(T, B, I, Cc, S, S)                    # -> (T,B,I,C,H,W)
+                return rec[:, :, 0] if I == 1 else rec.mean(2)       # decoded.mean(dim=2), decoders.py:171 (logging only)
+        return thunk
 
 
 class NormGRUCellP(_Params):
@@ -560,8 +822,7 @@ class MapProbeHead(_Params):
     def _workspace(self, rows, device):
         d = self.decoder
         need = 4 * int(H.lib().dm_mlp_ws_floats(rows, d.hidden_dim, d.hidden_layers))
-        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
+        self._ws = _grow_ws(self._ws, need, device)
         return self._ws
 
     def training_step(self, features, obs, mbuf=None, _defer=False):
@@ -582,17 +843,11 @@ class MapProbeHead(_Params):
         seen = obs.get('map_seen_mask')
         if seen is not None:
             want['map_seen_mask'], got['map_seen_mask'] = (T, B, S, S), tuple(seen.shape)
-        bad = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
-        if bad:
-            raise ValueError('training_step input shapes (got, expected): ' + ', '.join(f'{k}: {v[0]} != {v[1]}' for k, v in bad.items()))
+        _check_shapes(want, got)
         train = torch.is_grad_enabled()
         with torch.no_grad():
             # target.argmax(dim=-3) (decoders.py:221); an integer class map is taken as it is
-            if onehot:
-                target = torch.empty(NE, cells, dtype=torch.int32, device=dev)
-                H.call('dm_cat_target_index', NE, C, cells, H.fptr(m.float().contiguous()), H.ptr(target), H.stream())
-            else:
-                target = m.to(torch.int32).contiguous().view(NE, cells)
+            target = _cat_target_index(m, NE, C, cells)
             # torch.cat((features, insert_dim(map_coord, 2, I)), -1) (probes.py:54-55)
             feat2d = features.reshape(N, F_)
             x = torch.empty(N, F_ + 4, device=dev)
@@ -671,8 +926,7 @@ class GoalsProbe(_Params):
 
     def _workspace(self, rows, device):
         need = 4 * int(H.lib().dm_mlp_ws_floats(rows, MLP_HIDDEN, 4))
-        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
+        self._ws = _grow_ws(self._ws, need, device)
         return self._ws
 
     def training_step(self, features, obs, mbuf=None, _defer=False):
@@ -692,12 +946,8 @@ class GoalsProbe(_Params):
         visage = obs.get('goals_visage')
         if visage is not None:
             want['goals_visage'], got['goals_visage'] = (T, B, G), tuple(visage.shape)
-        bad = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
-        if bad:
-            raise ValueError('training_step input shapes (got, expected): ' + ', '.join(f'{k}: {v[0]} != {v[1]}' for k, v in bad.items()))
+        _check_shapes(want, got)
         train = torch.is_grad_enabled()
-        # -Normal(mu, std).log_prob(y) * std^2 summed over the outputs (decoders.py:296-304), the reward head's constant per output
-        loss_const = REWARD_STD ** 2 * (math.log(REWARD_STD) + math.log(math.sqrt(2 * math.pi)))
         with torch.no_grad():
             feat2d = features.reshape(N, F_).contiguous()
             ws = self._workspace(N, dev)
@@ -714,7 +964,7 @@ class GoalsProbe(_Params):
                 loss_tbi, mean_i = torch.empty(N, device=dev), torch.empty(N, V, device=dev)
                 dmu = torch.empty(N, V, device=dev) if train else None
                 # d loss_probe / d loss_tb = 1 / (T*B); with I > 1 the importance weights come in below
-                H.call('dm_head_loss_normal_nd', N, V, H.fptr(mu), H.fptr(rows_t), gw / NE if I == 1 else 1.0, loss_const,
+                H.call('dm_head_loss_normal_nd', N, V, H.fptr(mu), H.fptr(rows_t), gw / NE if I == 1 else 1.0, NORMAL_LOSS_CONST,
                        H.fptr(loss_tbi), H.fptr(dmu), H.fptr(mean_i), H.stream())
                 if I == 1:
                     loss_tb, pred = loss_tbi, mean_i
@@ -830,6 +1080,30 @@ def _flat_views(plist, device, fused=None, scratch=False):
         views.append(flat[off:off + p.numel()].view(p.shape))
         off += p.numel()
     return flat, views, False
+
+
+def _check_shapes(want, got):
+    """The C side sizes every access from the geometry alone: refuse what the caller handed over in another shape."""
+    bad = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
+    if bad:
+        raise ValueError('training_step input shapes (got, expected): ' + ', '.join(f'{k}: {v[0]} != {v[1]}' for k, v in bad.items()))
+
+
+def _grow_ws(buf, need, device):
+    """`buf` when it holds `need` bytes on `device`, else a new workspace of that size."""
+    if buf is None or buf.numel() < need or buf.device != device:
+        buf = torch.empty(need, dtype=torch.uint8, device=device)
+    return buf
+
+
+def _cat_target_index(x, NE, C, cells):
+    """The (NE, cells) int32 class index of a categorical target: target.argmax(dim=-3) (decoders.py:221) of a float one-hot
+    (..., C, S, S); an integer class map (..., S, S) is taken as it is."""
+    if not x.is_floating_point():
+        return x.to(torch.int32).contiguous().view(NE, cells)
+    target = torch.empty(NE, cells, dtype=torch.int32, device=x.device)
+    H.call('dm_cat_target_index', NE, C, cells, H.fptr(x.float().contiguous()), H.ptr(target), H.stream())
+    return target
 
 
 def _multi_sum(items, device, out=None):
@@ -1140,52 +1414,8 @@ class WorldModel(_Params):
         if self.dense:      # the image MLPs may be deeper than the four layers dm_workspace_bytes sizes the heads for
             deep = max(4, self.encoder.encoder_image.hidden_layers, self.decoder.image.hidden_layers)
             need = max(need, 4 * int(H.lib().dm_mlp_ws_floats(shp.T * shp.B * max(shp.I, 1), MLP_HIDDEN, deep)))
-        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
+        self._ws = _grow_ws(self._ws, need, device)
         return self._ws
-
-    # ---- the dense categorical image path: DenseEncoder / CatImageDecoder beside the convolution stacks
-    def _dense_encode(self, image, plane_r, plane_t, embed, NE, ws, save):
-        """encoders.py:50-61,121-125: rows [image | reward plane | terminal plane] -> MLP -> ELU, written into `embed`.
-        `image`: float one-hot (T,B,C,S,S), copied as it is, or an int32 class map (T,B,S,S).  Returns (rows, activations)."""
-        c, enc = self.conf, self.encoder.encoder_image
-        onehot = image.is_floating_point()
-        x = torch.empty(NE, enc.in_dim, device=embed.device)
-        H.call('dm_dense_image_rows', NE, c.image_channels, c.image_size ** 2, H.fptr(image) if onehot else None,
-               None if onehot else H.ptr(image), H.fptr(plane_r), H.fptr(plane_t), H.fptr(x), enc.in_dim, H.stream())
-        pre, acts = enc.fwd(x, enc.in_dim, NE, ws, save_acts=save)
-        H.call('dm_elu_rows_fwd', NE, enc.out_dim, H.fptr(pre), enc.out_dim, H.fptr(embed), embed.shape[1], H.stream())
-        return x, acts
-
-    def _dense_target(self, image, NE):
-        """target.argmax(dim=-3) (decoders.py:221) of a float image; an integer class map is taken as it is."""
-        c = self.conf
-        cells = c.image_size ** 2
-        if not image.is_floating_point():
-            return image.view(NE, cells)
-        target = torch.empty(NE, cells, dtype=torch.int32, device=image.device)
-        H.call('dm_cat_target_index', NE, c.image_channels, cells, H.fptr(image), H.ptr(target), H.stream())
-        return target
-
-    def _dense_loss(self, logits, target, N, loss, dlogits):
-        """CatImageDecoder.loss (decoders.py:219-236) per row; min_prob = 0 is the map probe's kernel, bit for bit."""
-        c, dec = self.conf, self.decoder.image
-        C, cells = c.image_channels, c.image_size ** 2
-        if dec.min_prob == 0:
-            H.call('dm_cat_image_loss', N, 1, C, cells, H.fptr(logits), C * cells, H.ptr(target), H.fptr(loss), H.fptr(dlogits),
-                   H.stream())
-        else:
-            H.call('dm_cat_image_loss_mix', N, 1, C, cells, H.fptr(logits), C * cells, H.ptr(target), dec.min_prob, H.fptr(loss),
-                   H.fptr(dlogits), H.stream())
-
-    def _dense_logp(self, logits, target, NE):
-        """The decoded image (decoders.py:247-251 with I = 1): per-cell normalised log-probabilities (NE, C, cells)."""
-        c = self.conf
-        C, cells = c.image_channels, c.image_size ** 2
-        logp, acc = torch.empty(NE, C, cells, device=logits.device), torch.empty(NE, device=logits.device)
-        H.call('dm_cat_image_pred', NE, 1, C, cells, H.fptr(logits), C * cells, H.ptr(target), None, H.fptr(logp), H.fptr(acc), None,
-               H.stream())
-        return logp
 
     def forward(self, obs, in_state, u_post=None):
         """dreamer.py:289-295: features and out_state only (used by Dreamer.inference)."""
@@ -1202,16 +1432,13 @@ class WorldModel(_Params):
         (T,B,1: encoder), `shp_r` (T, B*I, 1: the RSSM calls take the expanded batch as their batch)."""
         c = self.conf
         action = obs['action']
-        if self.imageless:      # no frame ingest, no obs['image'] (DESIGN 4.12): the step's device is the action's
-            image = None
-            _require_cuda(action, "obs['action']")
-        else:
-            image = obs['image']
-            _require_cuda(image, "obs['image']")
+        # the step's device is the image's; image-less (DESIGN 4.12) the action's
+        src = 'action' if self.imageless else 'image'
+        _require_cuda(obs[src], f"obs['{src}']")
         T, B = action.shape[:2]
         I = int(iwae)
-        BI, NE = B * I, T * B
-        N, dev = T * B * I, action.device if self.imageless else image.device
+        BI = B * I
+        N, dev = T * B * I, obs[src].device
         D_, F_, E = c.deter_dim, self.features_dim, self.encoder.out_dim
         gauss = not c.stoch_discrete         # Gaussian latents: z is stoch_dim wide, its parameters (mean | raw std) twice that
         Z, ZP = c.stoch_dim * (c.stoch_discrete or 1), c.stoch_dim * (c.stoch_discrete or 2)
@@ -1220,59 +1447,23 @@ class WorldModel(_Params):
         shp = self.shape(T, B, imag_horizon)
         shp.I = I
         ws = self.workspace(shp, dev)
-        u8 = not self.imageless and image.dtype == torch.uint8 and not self.dense
-        if self.imageless:
-            pass
-        elif self.dense:
-            # the reference's float one-hot (T,B,C,S,S) (preprocessing.py:108-109) or an integer class map (T,B,S,S): same bits
-            if not image.is_floating_point() and image.dim() == 5:
-                raise ValueError(f'the dense image path takes a float one-hot (T,B,C,S,S) image or an integer class map (T,B,S,S), '
-                                 f'not a {image.dtype} frame of shape {tuple(image.shape)}')
-            image = image.float().contiguous() if image.is_floating_point() else image.to(torch.int32).contiguous()
-        elif u8:
-            # the replay's native frames (T,B,H,W,C) uint8 are consumed AS THEY ARE: x/255-0.5 and HWC->CHW
-            # (preprocessing.py:21-29) happen inside the first conv's patch loader and inside the MSE kernel
-            # (dm_shape.flags bit DM_FLAG_IMAGE_U8); no float image is ever written
-            if image.dim() != 5 or tuple(image.shape[2:]) != (c.image_size, c.image_size, c.image_channels):
-                raise ValueError(f'uint8 image must be (T,B,{c.image_size},{c.image_size},{c.image_channels}), got {tuple(image.shape)}')
-            image = image.contiguous()
-            shp.flags |= H.DM_FLAG_IMAGE_U8
-        else:
-            image = image.float().contiguous()
         action = action.float().contiguous()
         reset = obs['reset'].to(torch.uint8).contiguous()
         h0, z0 = (x.float().contiguous() for x in in_state)
-        # the C side sizes every access from dm_shape alone: check what the caller handed over before packing pointers
-        want = dict(image=(T, B, c.image_size, c.image_size, c.image_channels) if u8 else
-                    (T, B, c.image_channels, c.image_size, c.image_size), action=(T, B, c.action_dim), reset=(T, B))
-        if self.dense and not image.is_floating_point():
-            want['image'] = (T, B, c.image_size, c.image_size)
+        # the C side sizes every access from dm_shape alone: check what the caller handed over before packing pointers (this
+        # model's own entries; the encoder adds what it reads and runs the check)
+        want = dict(action=(T, B, c.action_dim), reset=(T, B))
         got = dict(action=tuple(action.shape), reset=tuple(reset.shape))
-        if self.imageless:
-            del want['image']
-        else:
-            got['image'] = tuple(image.shape)
-        planes = self.encoder.reward_input
         for k in ('reward', 'terminal'):
-            if planes and k not in obs:
-                raise ValueError(f"reward_input: obs['{k}'] is an input of the encoder (encoders.py:52-59)")
-            if not forward_only or k in obs:
-                if k in obs:
-                    want[k], got[k] = (T, B), tuple(obs[k].shape)
-        V = c.vecobs_size
-        if V:
-            if 'vecobs' not in obs:
-                raise ValueError(f"vecobs_size={V}: obs['vecobs'] is an input of the encoder (encoders.py:64-66)")
-            want['vecobs'], got['vecobs'] = (T, B, V), tuple(obs['vecobs'].shape)
+            if k in obs:
+                want[k], got[k] = (T, B), tuple(obs[k].shape)
         want['in_state[0]'], got['in_state[0]'] = (BI, D_), tuple(h0.shape)
         want['in_state[1]'], got['in_state[1]'] = (BI, Z), tuple(z0.shape)
         if u_post is not None:
             want['u_post numel'], got['u_post numel'] = T * BI * c.stoch_dim, u_post.numel()
         if forced_idx is not None:
             want['forced_idx'], got['forced_idx'] = (T, BI, c.stoch_dim), tuple(forced_idx.shape)
-        bad = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
-        if bad:
-            raise ValueError('training_step input shapes (got, expected): ' + ', '.join(f'{k}: {v[0]} != {v[1]}' for k, v in bad.items()))
+        image, _, plane_r, plane_t, vecobs = self.encoder.ingest(obs, T, B, shp, want, got)
         # Every buffer of the step is its own allocation: nothing is shared between steps, so a backward() on an older
         # step's losses is always valid.  Uniforms for the categorical inverse-CDF rule; standard-normal eps of
         # Normal.rsample for Gaussian latents.
@@ -1288,13 +1479,6 @@ class WorldModel(_Params):
             shp_r = H.dm_shape.from_buffer_copy(shp)
             shp_r.B, shp_r.I = BI, 1
 
-        enc = self.encoder.encoder_image
-        enc_p = enc_acts = None
-        conv = not self.dense and not self.imageless
-        if conv:
-            enc_p = H.conv_struct([m.weight for m in enc.convs()], [m.bias for m in enc.convs()])
-            enc_acts = torch.empty(int(lib.dm_conv_encoder_acts_floats(ctypes.byref(shp_e))), device=dev)
-        embed = None if self.imageless else torch.empty(NE, E, device=dev)      # image-less: the vecobs MLP's own output buffer
         cell = self.core.cell
         rssm_p = H.rssm_struct(cell.ordered())
         if open_loop:
@@ -1316,16 +1500,9 @@ class WorldModel(_Params):
         fidx = forced_idx.to(torch.int32).contiguous() if forced_idx is not None else None
         u_ptr = H.fptr(u_post) if u_post is not None else None
         dec = self.decoder
-        dec_p = dec_acts = loss_image = None
-        if conv:
-            dl = dec.image.layers()
-            dec_p = H.conv_struct([m.weight for m in dl], [m.bias for m in dl])
+        dec_acts = loss_image = None
         if not forward_only:
-            if conv:
-                dec_acts = torch.empty(int(lib.dm_conv_decoder_acts_floats(ctypes.byref(shp))), device=dev)
-            if not self.imageless:
-                loss_image = torch.empty(N, device=dev)
-            image_rec = None          # materialised lazily from the decoder's saved prediction (see LazyTensors)
+            dec_acts, loss_image = dec.image_buffers(shp, N, dev)
 
         # rssm.py:35-41: (T,B,X) -> (T,B*I,X), pure data movement (I = 1: the caller's tensors as they are)
         A_ = c.action_dim
@@ -1336,32 +1513,7 @@ class WorldModel(_Params):
             reset_x.view(T, B, I).copy_(reset.view(T, B, 1).expand(T, B, I))
         else:
             action_x, reset_x = action, reset
-        plane_r = plane_t = vecobs = ev_acts = None
-        if planes:      # encoders.py:52-59: per-frame constants, (T,B) -> (N,); never expanded to image planes
-            plane_r = obs['reward'].float().contiguous().view(NE)
-            plane_t = obs['terminal'].float().contiguous().view(NE)
-        enc_x = None
-        if self.imageless:
-            # encoders.py:64-69 with encoder_image = None: the vecobs MLP's (T*B, 256) output IS the RSSM's embed, no copy pass
-            vecobs = obs['vecobs'].float().contiguous().view(NE, V)
-            embed, ev_acts = self.encoder.encoder_vecobs.fwd(vecobs, V, NE, ws, save_acts=not forward_only and torch.is_grad_enabled())
-        elif self.dense:
-            enc_x, enc_acts = self._dense_encode(image, plane_r, plane_t, embed, NE, ws,
-                                                 save=not forward_only and torch.is_grad_enabled())
-        elif planes or V:
-            # the image embedding is written as the leading E - 256 columns of the (NE, E) buffer (leading dimension E), the
-            # vecobs embedding behind it: one buffer for the RSSM, no copy pass over the image embedding
-            shp_c = H.dm_shape.from_buffer_copy(shp_e)
-            shp_c.E = enc.out_dim                   # the convolution stack's own width
-            H.call('dm_conv_encoder_fwd_planes', ctypes.byref(shp_c), H.ptr(image), ctypes.byref(enc_p), H.fptr(plane_r),
-                   H.fptr(plane_t), H.fptr(enc_acts), H.fptr(embed), E, H.ptr(ws), ws.numel(), H.stream())
-            if V:
-                vecobs = obs['vecobs'].float().contiguous().view(NE, V)
-                ev, ev_acts = self.encoder.encoder_vecobs.fwd(vecobs, V, NE, ws, save_acts=not forward_only)
-                embed[:, enc.out_dim:].copy_(ev)
-        else:
-            H.call('dm_conv_encoder_fwd', ctypes.byref(shp_e), H.ptr(image), ctypes.byref(enc_p), H.fptr(enc_acts),
-                   H.fptr(embed), H.ptr(ws), ws.numel(), H.stream())
+        embed, enc_st = self.encoder.encode(image, plane_r, plane_t, vecobs, shp_e, ws, forward_only)
         embed_x = embed
         if I > 1:
             embed_x = torch.empty(N, E, device=dev)
@@ -1373,9 +1525,8 @@ class WorldModel(_Params):
 
         last = feat[(T - 1) * BI:]
         out_state = (last[:, :D_].clone(), last[:, D_:].clone())                  # detached by construction (rssm.py:77)
-        pk = dict(shp=shp, shp_e=shp_e, shp_r=shp_r, T=T, B=B, I=I, feat=feat, post=post, prior=prior, idx=idx,
-                  out_state=out_state, embed=embed, embed_x=embed_x, action_x=action_x, reset_x=reset_x,
-                  plane_r=plane_r, plane_t=plane_t, vecobs=vecobs, ev_acts=ev_acts, enc_x=enc_x)
+        pk = dict(shp=shp, shp_r=shp_r, T=T, B=B, I=I, feat=feat, post=post, prior=prior, idx=idx,
+                  out_state=out_state, embed_x=embed_x, action_x=action_x, reset_x=reset_x, **enc_st)
         if forward_only:
             return pk
         # The tail of the world-model forward - decoder + MSE, reward / terminal heads, KL, the loss sums (dreamer.py:311-365) -
@@ -1386,20 +1537,15 @@ class WorldModel(_Params):
         # (test_world_model_tail_on_side_stream_is_bit_identical).
         use_tail = tail is not None
         if use_tail:
-            need = ws.numel()
-            if tail.ws_wm is None or tail.ws_wm.numel() < need:
-                tail.ws_wm = torch.empty(need, dtype=torch.uint8, device=dev)
-            ws = tail.ws_wm
+            ws = tail.ws_wm = _grow_ws(tail.ws_wm, ws.numel(), dev)
             tail.ev_fork.record(torch.cuda.current_stream())
             tail.s_wm.wait_event(tail.ev_fork)
             pk['tail'] = tail
         with (torch.cuda.stream(tail.s_wm) if use_tail else contextlib.nullcontext()):
-            return self._forward_tail(pk, obs, c, dec, dec_p, dec_acts, loss_image, ws, mbuf, image, action, reset, enc_acts,
-                                      rssm_acts)
+            return self._forward_tail(pk, obs, c, dec, dec_acts, loss_image, ws, mbuf, action, reset, rssm_acts)
 
-    def _forward_tail(self, pk, obs, c, dec, dec_p, dec_acts, loss_image, ws, mbuf, image, action, reset, enc_acts, rssm_acts):
+    def _forward_tail(self, pk, obs, c, dec, dec_acts, loss_image, ws, mbuf, action, reset, rssm_acts):
         shp, T, B, I, feat, post, prior, idx = (pk[k] for k in ('shp', 'T', 'B', 'I', 'feat', 'post', 'prior', 'idx'))
-        lib = H.lib()
         N, NE, dev = T * B * I, T * B, feat.device
         D_, F_ = c.deter_dim, self.features_dim
         gauss = not c.stoch_discrete
@@ -1407,21 +1553,7 @@ class WorldModel(_Params):
         # image-less (decoders.py:29-30,59-64): no image term.  `none` stands in the image's place in the one-launch sums below: an
         # item of zero elements sums to an exact 0.0, so metric slot 1 stays zero and is never named
         none = torch.empty(0, device=dev) if self.imageless else None
-        if self.imageless:
-            pass
-        elif self.dense:      # CatImageDecoder.training_step (decoders.py:238-254): MLP -> per-cell cross-entropy, I = 1
-            train = torch.is_grad_enabled()
-            target = pk['target'] = self._dense_target(image, NE)
-            logits, dec_acts = dec.image.fwd(feat, F_, N, ws, save_acts=train)
-            dlogits = torch.empty_like(logits) if train else None
-            self._dense_loss(logits, target, N, loss_image, dlogits)
-            if train:      # d loss_model / d loss_image[r] = image_weight / (T*B), times the data-parallel shard weight
-                scale = torch.full((1,), float(getattr(self, 'grad_weight', 1.0)) * dec.image_weight / NE, device=dev)
-                H.call('dm_scale_inplace', H.fptr(dlogits), dlogits.numel(), H.fptr(scale), H.stream())
-            pk.update(dec_logits=logits, dlogits=dlogits)
-        else:
-            H.call('dm_conv_decoder_mse_fwd', ctypes.byref(shp), H.fptr(feat), F_, H.ptr(image), ctypes.byref(dec_p),
-                   H.fptr(dec_acts), H.fptr(loss_image), None, H.ptr(ws), ws.numel(), H.stream())
+        pk.update(dec.image_loss(shp, feat, pk['image'], ws, dec_acts, loss_image, float(getattr(self, 'grad_weight', 1.0))))
 
         reward_t = reward_tb = obs['reward'].float().contiguous()
         terminal_t = obs['terminal'].float().contiguous()
@@ -1435,15 +1567,13 @@ class WorldModel(_Params):
         loss_reward, reward_rec = (torch.empty(N, device=dev) for _ in range(2))
         dmu = torch.empty((N, K) if K else N, device=dev)
         loss_terminal, dtl, terminal_rec = (torch.empty(N, device=dev) for _ in range(3))
-        # -Normal(mu, std).log_prob(y) * std^2 = 0.5 (mu-y)^2 + std^2 (log std + log sqrt(2 pi))   (decoders.py:296-304)
-        loss_const = REWARD_STD ** 2 * (math.log(REWARD_STD) + math.log(math.sqrt(2 * math.pi)))
         # gw: the data-parallel shard weight B_r/B (dist.attach), folded into every gradient scale; loss values are unaffected
         gw = float(getattr(self, 'grad_weight', 1.0))
         if K:      # decoders.py:340-362; the target is the (T,B) reward itself: row r reads target r / I
             H.call('dm_head_loss_catsup', N, I, K, H.fptr(mu), K, H.fptr(dec.reward._support), H.fptr(reward_tb),
                    gw * dec.reward_weight / NE, H.fptr(loss_reward), H.fptr(dmu), H.fptr(reward_rec), None, H.stream())
         else:
-            H.call('dm_head_loss', 0, N, H.fptr(mu), H.fptr(reward_t), gw * dec.reward_weight / NE, loss_const, H.fptr(loss_reward),
+            H.call('dm_head_loss', 0, N, H.fptr(mu), H.fptr(reward_t), gw * dec.reward_weight / NE, NORMAL_LOSS_CONST, H.fptr(loss_reward),
                    H.fptr(dmu), H.fptr(reward_rec), H.stream())
         H.call('dm_head_loss', 1, N, H.fptr(tl), H.fptr(terminal_t), gw * dec.terminal_weight / NE, 0.0, H.fptr(loss_terminal),
                H.fptr(dtl), H.fptr(terminal_rec), H.stream())
@@ -1457,7 +1587,7 @@ class WorldModel(_Params):
             mu_v, v_acts = dec.vecobs.model.fwd(feat, F_, N, ws, sparse_cols=sp)
             loss_vecobs = torch.empty(N, device=dev)
             dmu_v, vecobs_rec = torch.empty(N, V, device=dev), torch.empty(N, V, device=dev)
-            H.call('dm_head_loss_normal_nd', N, V, H.fptr(mu_v), H.fptr(vec_t), gw * dec.vecobs_weight / NE, loss_const,
+            H.call('dm_head_loss_normal_nd', N, V, H.fptr(mu_v), H.fptr(vec_t), gw * dec.vecobs_weight / NE, NORMAL_LOSS_CONST,
                    H.fptr(loss_vecobs), H.fptr(dmu_v), H.fptr(vecobs_rec), H.stream())
 
         # KL + entropies (dreamer.py:326-343,369-379)
@@ -1554,9 +1684,8 @@ class WorldModel(_Params):
                 H.call('dm_reduce_i', NE, I, V, H.fptr(vecobs_rec), 0, H.fptr(t_vr), None, H.stream())
                 _multi_sum([(t_lv, 1.0 / NE)], dev, out=mbuf[15:16])
 
-        pk.update(loss=loss, image=image, action=action, reset=reset, enc_acts=enc_acts, rssm_acts=rssm_acts,
-                  dec_acts=dec_acts, r_acts=r_acts, t_acts=t_acts, dmu=dmu, dtl=dtl, ws=ws, mbuf=mbuf, iw=iw, aux=aux,
-                  v_acts=v_acts, dmu_v=dmu_v)
+        pk.update(loss=loss, action=action, reset=reset, rssm_acts=rssm_acts, r_acts=r_acts, t_acts=t_acts, dmu=dmu, dtl=dtl, ws=ws,
+                  mbuf=mbuf, iw=iw, aux=aux, v_acts=v_acts, dmu_v=dmu_v)
         pk['tensors'] = LazyTensors(loss_kl=t_kl, entropy_prior=t_ep, entropy_post=t_eq,
                                     loss_image=t_li, image_rec=None,
                                     loss_reward=t_lr, reward_rec=t_rr,
@@ -1566,20 +1695,7 @@ class WorldModel(_Params):
         if self.imageless:      # decoders.py:59-64: there is no loss_image metric and no loss_image / image_rec tensor
             del pk['metrics']['loss_image'], pk['tensors']['loss_image'], pk['tensors']['image_rec']
         else:
-            Cc, hw = c.image_channels, c.image_size * c.image_size
-            if self.dense:
-                def image_rec_thunk(logits=pk['dec_logits'], target=pk['target']):      # holds the logits alive until the dict is dropped
-                    with torch.no_grad():
-                        return self._dense_logp(logits, target, NE).view(T, B, Cc, c.image_size, c.image_size)
-            else:
-                pred_off = int(lib.dm_conv_decoder_pred_offset(ctypes.byref(shp)))
-
-                def image_rec_thunk(acts=dec_acts):       # holds the decoder activations alive until the dict is dropped
-                    with torch.no_grad():
-                        pred = acts[pred_off:pred_off + N * hw * Cc].view(N, hw, Cc)                       # NHWC
-                        rec = pred.transpose(1, 2).contiguous().view(T, B, I, Cc, c.image_size, c.image_size)   # -> (T,B,I,C,H,W)
-                        return rec[:, :, 0] if I == 1 else rec.mean(2)       # decoded.mean(dim=2), decoders.py:171 (logging only)
-            pk['tensors'].lazy('image_rec', image_rec_thunk)
+            pk['tensors'].lazy('image_rec', dec.image_rec_thunk(pk))
         if V:
             pk['metrics'].update(loss_vecobs=mbuf[15])
             pk['tensors'].update(loss_vecobs=t_lv, vecobs_rec=t_vr)
@@ -1618,18 +1734,9 @@ class WorldModel(_Params):
             heads.append((dec.vecobs.model, pk['v_acts'], pk['dmu_v']))
         if pk.get('aux') is not None:          # the auxiliary critic trains on the world model's own features (not detached)
             heads.append((self.ac_aux.critic, pk['aux']['acts'], pk['aux']['dvalue']))
-        if self.dense:                         # the image decoder is one more dense head: its dx accumulates into dfeat
-            heads.append((dec.image, pk['dec_acts'], pk['dlogits']))
+        heads += dec.image_heads(pk)
         for head, acts, dout in heads:
-            st, gs = head.struct(), head.grad_struct(gof)
-            H.call('dm_mlp_head_bwd', N, F_, head.hidden_dim, head.hidden_layers, head.out_dim, H.fptr(feat), F_, ctypes.byref(st),
-                   H.fptr(acts), H.fptr(dout), ctypes.byref(gs), H.fptr(dfeat), F_, 1, H.ptr(ws), ws.numel(), H.stream())
-        # image decoder
-        conv = not self.dense and not self.imageless
-        if conv:
-            dl = dec.image.layers()
-            dec_p = H.conv_struct([m.weight for m in dl], [m.bias for m in dl])
-            dec_g = H.conv_struct([gof[id(m.weight)] for m in dl], [gof[id(m.bias)] for m in dl], cls=H.dm_conv_grads)
+            head.bwd_into(gof, feat, F_, N, acts, dout, ws, dx=dfeat, lddx=F_, dx_accum=True)
         # Parameter gradients are leaves: nothing waits for them before the gradient clip, while the DATA gradients are the
         # chain decoder -> BPTT -> encoder.  Armed, the library enqueues the decoder's and the RSSM's parameter gradients on its
         # low-priority side stream, where they run beside the BPTT loop (a 50-row latency chain that leaves most CUs idle); they
@@ -1639,20 +1746,16 @@ class WorldModel(_Params):
         #  round 6 measured it over a one-rank RCCL group: off costs +0.9 ... +1.2 ms at 25 / 50 columns, on costs nothing beside the
         #  all-reduce - profiles/r06_force_dp.txt run K: it stays on there.)
         # (off on the dense and the image-less paths: no decoder call to hide the weight gradients behind, not measured there)
-        side = defer_wgrad and _WGRAD_SIDE and B * I >= 16 and not torch.cuda.is_current_stream_capturing() and conv
+        side = defer_wgrad and _WGRAD_SIDE and B * I >= 16 and not torch.cuda.is_current_stream_capturing() and \
+            not self.dense and not self.imageless
         ws_dec = ws_enc = ws
         if side:
             need = H.workspace_bytes(shp)
-            if self._ws_dec is None or self._ws_dec.numel() < need or self._ws_dec.device != dev:
-                self._ws_dec = torch.empty(need, dtype=torch.uint8, device=dev)
-                self._ws_enc = torch.empty(need, dtype=torch.uint8, device=dev)
-            ws_dec, ws_enc = self._ws_dec, self._ws_enc       # decoder / BPTT (`ws`) / encoder: one workspace each until the join
+            ws_dec = self._ws_dec = _grow_ws(self._ws_dec, need, dev)
+            ws_enc = self._ws_enc = _grow_ws(self._ws_enc, need, dev)      # decoder / BPTT (`ws`) / encoder: one each until the join
             H.call('dm_wgrad_side_arm', 1)
         try:
-            if conv:
-                H.call('dm_conv_decoder_mse_bwd_rows', ctypes.byref(shp), H.fptr(feat), F_, H.ptr(pk['image']), ctypes.byref(dec_p),
-                       H.fptr(pk['dec_acts']), gw * dec.image_weight / NE, H.fptr(iw), ctypes.byref(dec_g), H.fptr(dfeat), F_,
-                       H.ptr(ws_dec), ws_dec.numel(), H.stream())
+            dec.image_bwd(pk, gof, dfeat, gw * dec.image_weight / NE, iw, ws_dec)      # (convolution path; dense: a head above)
             # KL (dreamer.py:334-343)
             dpost = torch.empty(N, Z, device=dev)
             dprior = torch.empty(N, Z, device=dev)
@@ -1684,41 +1787,7 @@ class WorldModel(_Params):
                 dsum = torch.empty(NE, E, device=dev)
                 H.call('dm_reduce_i', NE, I, E, H.fptr(dembed), 2, H.fptr(dsum), None, H.stream())
                 dembed = dsum
-            # encoder
-            enc = self.encoder.encoder_image
-            if self.dense:      # through the trailing ELU (derivative from embed = ELU(pre), in place), then the MLP; no input gradient
-                H.call('dm_elu_rows_bwd', NE, E, H.fptr(pk['embed']), E, H.fptr(dembed), E, H.fptr(dembed), E, H.stream())
-                st, gs = enc.struct(), enc.grad_struct(gof)
-                H.call('dm_mlp_head_bwd', NE, enc.in_dim, enc.hidden_dim, enc.hidden_layers, enc.out_dim, H.fptr(pk['enc_x']),
-                       enc.in_dim, ctypes.byref(st), H.fptr(pk['enc_acts']), H.fptr(dembed), ctypes.byref(gs), None, 0, 0,
-                       H.ptr(ws_enc), ws_enc.numel(), H.stream())
-                return views, flat, direct
-            if self.imageless:      # the whole (T*B, 256) dembed is the vecobs MLP's output gradient; no input gradient
-                ev = self.encoder.encoder_vecobs
-                st, gs = ev.struct(), ev.grad_struct(gof)
-                H.call('dm_mlp_head_bwd', NE, ev.in_dim, ev.hidden_dim, ev.hidden_layers, ev.out_dim, H.fptr(pk['vecobs']), ev.in_dim,
-                       ctypes.byref(st), H.fptr(pk['ev_acts']), H.fptr(dembed), ctypes.byref(gs), None, 0, 0, H.ptr(ws_enc),
-                       ws_enc.numel(), H.stream())
-                return views, flat, direct
-            enc_p = H.conv_struct([m.weight for m in enc.convs()], [m.bias for m in enc.convs()])
-            enc_g = H.conv_struct([gof[id(m.weight)] for m in enc.convs()], [gof[id(m.bias)] for m in enc.convs()],
-                                  cls=H.dm_conv_grads)
-            if pk.get('vecobs') is not None:      # the vecobs encoder: its output gradient is the trailing 256 columns of dembed
-                ev = self.encoder.encoder_vecobs
-                d_ev = dembed[:, enc.out_dim:].contiguous()
-                st, gs = ev.struct(), ev.grad_struct(gof)
-                H.call('dm_mlp_head_bwd', NE, ev.in_dim, ev.hidden_dim, ev.hidden_layers, ev.out_dim, H.fptr(pk['vecobs']), ev.in_dim,
-                       ctypes.byref(st), H.fptr(pk['ev_acts']), H.fptr(d_ev), ctypes.byref(gs), None, 0, 0, H.ptr(ws_enc),
-                       ws_enc.numel(), H.stream())
-            if pk.get('plane_r') is not None or pk.get('vecobs') is not None:
-                shp_c = H.dm_shape.from_buffer_copy(pk['shp_e'])
-                shp_c.E = enc.out_dim
-                H.call('dm_conv_encoder_bwd_planes', ctypes.byref(shp_c), H.ptr(pk['image']), ctypes.byref(enc_p),
-                       H.fptr(pk['plane_r']), H.fptr(pk['plane_t']), H.fptr(pk['enc_acts']), H.fptr(dembed), E, ctypes.byref(enc_g),
-                       H.ptr(ws_enc), ws_enc.numel(), H.stream())
-            else:
-                H.call('dm_conv_encoder_bwd', ctypes.byref(pk['shp_e']), H.ptr(pk['image']), ctypes.byref(enc_p),
-                       H.fptr(pk['enc_acts']), H.fptr(dembed), ctypes.byref(enc_g), H.ptr(ws_enc), ws_enc.numel(), H.stream())
+            self.encoder.backward(dembed, pk, gof, ws_enc)
         except BaseException:
             if side:
                 H.lib().dm_wgrad_side_join(H.stream())      # disarm this thread; the error propagates
@@ -1739,7 +1808,6 @@ class WorldModel(_Params):
         NE, N, dev = T * B, T * B * I, feat.device
         D_, S, C, F_ = c.deter_dim, c.stoch_dim, c.stoch_discrete, self.features_dim
         ws = self.workspace(shp, dev)
-        lib = H.lib()
         with torch.no_grad():
             if u_pred is None:
                 u_pred = (torch.rand if C else torch.randn)(N, S, device=dev)
@@ -1748,32 +1816,20 @@ class WorldModel(_Params):
             idx = torch.empty(N, S, dtype=torch.int32, device=dev)
             H.call('dm_sample_onehot', N, S, C, H.fptr(pk['prior']), S * (C or 2), H.fptr(u_pred), None,
                    ctypes.c_void_p(fp.data_ptr() + 4 * D_), F_, H.ptr(idx), H.stream())
-            li = image_pred = None
-            if not self.imageless:
-                li = torch.empty(N, device=dev)
-            if self.imageless:      # decoders.py:59-64: no logprob_image, no image_pred
-                pass
-            elif self.dense:      # loss and normalised log-probabilities of the decoder on the prior-sample features (I = 1)
-                logits, _ = dec.image.fwd(fp, F_, N, ws, save_acts=False)
-                self._dense_loss(logits, pk['target'], N, li, None)
-                image_pred = self._dense_logp(logits, pk['target'], NE).view(T, B, I, c.image_channels, c.image_size, c.image_size)
-            else:
-                dl = dec.image.layers()
-                dec_p = H.conv_struct([m.weight for m in dl], [m.bias for m in dl])
-                acts = torch.empty(int(lib.dm_conv_decoder_acts_floats(ctypes.byref(shp))), device=dev)
-                image_pred = torch.empty(T, B, I, c.image_channels, c.image_size, c.image_size, device=dev)
-                H.call('dm_conv_decoder_mse_fwd', ctypes.byref(shp), H.fptr(fp), F_, H.ptr(pk['image']), ctypes.byref(dec_p),
-                       H.fptr(acts), H.fptr(li), H.fptr(image_pred), H.ptr(ws), ws.numel(), H.stream())
+            # loss and prediction (dense: normalised log-probabilities) of the image decoder on the prior-sample features;
+            # image-less (decoders.py:59-64): no logprob_image, no image_pred - both None
+            li, image_pred = dec.decode(shp, fp, pk['image'], ws, target=pk.get('target'), loss=True)
+            if image_pred is not None:
+                image_pred = image_pred.view(T, B, I, *image_pred.shape[1:])
             mu, _ = dec.reward.model.fwd(fp, F_, N, ws, save_acts=False)
             tl, _ = dec.terminal.model.fwd(fp, F_, N, ws, save_acts=False)
             lr, lt, rp, tp, scratch = (torch.empty(N, device=dev) for _ in range(5))
-            loss_const = REWARD_STD ** 2 * (math.log(REWARD_STD) + math.log(math.sqrt(2 * math.pi)))
             V = c.vecobs_size
             if V:
                 vec_t = pk['vecobs'].repeat_interleave(I, dim=0).contiguous() if I > 1 else pk['vecobs']
                 mu_v, _ = dec.vecobs.model.fwd(fp, F_, N, ws, save_acts=False)
                 lv, vp = torch.empty(N, device=dev), torch.empty(N, V, device=dev)
-                H.call('dm_head_loss_normal_nd', N, V, H.fptr(mu_v), H.fptr(vec_t), 0.0, loss_const, H.fptr(lv), None, H.fptr(vp),
+                H.call('dm_head_loss_normal_nd', N, V, H.fptr(mu_v), H.fptr(vec_t), 0.0, NORMAL_LOSS_CONST, H.fptr(lv), None, H.fptr(vp),
                        H.stream())
                 if I > 1:
                     lv_i, vp_i = lv, vp
@@ -1791,7 +1847,7 @@ class WorldModel(_Params):
                 H.call('dm_head_loss_catsup', N, I, K, H.fptr(mu), K, H.fptr(dec.reward._support), H.fptr(reward_tb), 0.0,
                        H.fptr(lr), None, H.fptr(rp), H.ptr(rbin), H.stream())
             else:
-                H.call('dm_head_loss', 0, N, H.fptr(mu), H.fptr(reward_t), 0.0, loss_const, H.fptr(lr),
+                H.call('dm_head_loss', 0, N, H.fptr(mu), H.fptr(reward_t), 0.0, NORMAL_LOSS_CONST, H.fptr(lr),
                        H.fptr(scratch), H.fptr(rp), H.stream())
             H.call('dm_head_loss', 1, N, H.fptr(tl), H.fptr(terminal_t), 0.0, 0.0, H.fptr(lt),
                    H.fptr(scratch), H.fptr(tp), H.stream())
@@ -1800,13 +1856,13 @@ class WorldModel(_Params):
                 for j, (x, mode) in enumerate(((li, 1), (lr, 1), (lt, 1), (rp, 0), (tp, 0))):
                     if x is not None:
                         H.call('dm_reduce_i', NE, I, 1, H.fptr(x), mode, H.fptr(red[j]), None, H.stream())
-                li, lr, lt, rp, tp = (None if self.imageless and j == 0 else red[j] for j in range(5))
+                li, lr, lt, rp, tp = (None if li is None and j == 0 else red[j] for j in range(5))
                 if image_pred is not None:
                     image_pred = image_pred.mean(2)                           # decoded.mean(dim=2), decoders.py:171
             elif image_pred is not None:
                 image_pred = image_pred[:, :, 0]
             tb = lambda x: x.view(T, B)
-            if self.imageless:
+            if li is None:
                 tensors = dict(logprob_reward=tb(lr), logprob_terminal=tb(lt), reward_pred=tb(rp), terminal_pred=tb(tp))
                 metrics = dict(logprob_reward=lr.mean(), logprob_terminal=lt.mean())
             else:
@@ -1915,11 +1971,7 @@ class _ProbeLoss(torch.autograd.Function):
         flat, views, direct = _flat_views(plist, grad_loss.device, getattr(owner, '_fused', None))
         gof = {id(p): v for p, v in zip(plist, views)}
         for hp in pk['heads']:
-            mlp = hp['mlp']
-            st, gs = mlp.struct(), mlp.grad_struct(gof)
-            H.call('dm_mlp_head_bwd', hp['rows'], mlp.in_dim, mlp.hidden_dim, mlp.hidden_layers, mlp.out_dim, H.fptr(hp['x']), hp['ldx'],
-                   ctypes.byref(st), H.fptr(hp['acts']), H.fptr(hp['dout']), ctypes.byref(gs), None, 0, 0, H.ptr(hp['ws']),
-                   hp['ws'].numel(), H.stream())
+            hp['mlp'].bwd_into(gof, hp['x'], hp['ldx'], hp['rows'], hp['acts'], hp['dout'], hp['ws'])
             for k in ('acts', 'dout', 'x'):
                 hp.pop(k, None)
         pk['consumed'] = True
@@ -2489,9 +2541,7 @@ class Dreamer(nn.Module):
                 if getattr(owner, '_fused', None) is not None:          # an OLDER step's losses - may come before the
                     gens[id(owner)] = owner._fused.claim_scratch()      # launcher thread has touched the buffers
             # world-model backward: on its own stream and workspace, concurrent with everything below
-            need = pk['ws'].numel()
-            if ov.ws_wm is None or ov.ws_wm.numel() < need:
-                ov.ws_wm = torch.empty(need, dtype=torch.uint8, device=dev)
+            ov.ws_wm = _grow_ws(ov.ws_wm, pk['ws'].numel(), dev)
             # (with the forward's tail already on s_wm the backward simply follows it in stream order)
             ov.ev_wm_fwd.record(ov.s_wm if pk.get('tail') is not None else torch.cuda.current_stream())
             pk['pre'] = ov.submit(ov.s_wm, ov.ev_wm_fwd, lambda: self.wm._backward(
@@ -2508,8 +2558,7 @@ class Dreamer(nn.Module):
         dpk = {}
         if ov is not None:
             need = 4 * int(H.lib().dm_mlp_ws_floats((imag_horizon + 1) * T * B * I, MLP_HIDDEN, 4))
-            if ov.ws_ac is None or ov.ws_ac.numel() < need:
-                ov.ws_ac = torch.empty(need, dtype=torch.uint8, device=pk['feat'].device)
+            ov.ws_ac = _grow_ws(ov.ws_ac, need, pk['feat'].device)
         self._await_ac_optimizers()      # (pipelined mode: the previous step's actor / critic AdamW ran on the actor-critic stream)
         self.ac.begin_step()             # the target-network refresh comes before the first use of critic_target (a2c.py:76-79)
         features_dream, actions_dream, rewards_dream, terminals_dream = \
@@ -2546,18 +2595,10 @@ class Dreamer(nn.Module):
                 f2, a2, r2, t2 = self._dream_from_features(
                     pk['feat'][:B * I:I].contiguous(), T - 1,
                     noise.get('u_act_log') if kind == 0 else noise.get('eps_act_log'), noise.get('u_prior_log'), _pack=dpk2)
-                shp, dev = pk['shp_e'], pk['feat'].device          # (T,B,1): the log dream has one row per (step, column)
-                ws = self.wm.workspace(shp, dev)
-                if self.wm.dense:      # decoder.image.forward (dreamer.py:171): the raw logits, not normalised
-                    image_dream, _ = self.wm.decoder.image.fwd(f2.view(T * B, -1), self.wm.features_dim, T * B, ws, save_acts=False)
-                    image_dream = image_dream.view(T, B, self.conf.image_channels, self.conf.image_size, self.conf.image_size)
-                else:
-                    dl = self.wm.decoder.image.layers()
-                    dec_p = H.conv_struct([m.weight for m in dl], [m.bias for m in dl])
-                    acts = torch.empty(int(H.lib().dm_conv_decoder_acts_floats(ctypes.byref(shp))), device=dev)
-                    image_dream = torch.empty(T, B, self.conf.image_channels, self.conf.image_size, self.conf.image_size, device=dev)
-                    H.call('dm_conv_decoder_mse_fwd', ctypes.byref(shp), H.fptr(f2), self.wm.features_dim, H.ptr(pk['image']),
-                           ctypes.byref(dec_p), H.fptr(acts), None, H.fptr(image_dream), H.ptr(ws), ws.numel(), H.stream())
+                shp = pk['shp_e']          # (T,B,1): the log dream has one row per (step, column)
+                ws = self.wm.workspace(shp, pk['feat'].device)
+                # decoder.image.forward (dreamer.py:171); on the dense path the raw logits, not normalised
+                _, image_dream = self.wm.decoder.decode(shp, f2.view(T * B, -1), pk['image'], ws, raw=True)
                 _, _, t_ac2 = self.ac.training_step(f2, a2, r2.mean, t2.mean, log_only=True, act_idx=dpk2['act_idx'],
                                                     ws=dpk2['ws'], actor_acts=dpk2['actor_acts'],
                                                     actor_logits=dpk2['actor_logits'], values=dpk2['values'])

@@ -259,7 +259,7 @@ def _struct(hip, shape_rows, wm, conf):
 
 @pytest.mark.parametrize('rows,reward_input,layers', [(15, True, 3), (15, False, 1), (16384, False, 2), (16384, True, 2)])
 def test_encoder_against_fp64(hip, rows, reward_input, layers):
-    """WorldModel._dense_encode (dm_dense_image_rows -> MLP -> dm_elu_rows_fwd into an embed buffer with a leading dimension of 256
+    """MultiEncoder.dense_encode (dm_dense_image_rows -> MLP -> dm_elu_rows_fwd into an embed buffer with a leading dimension of 256
     + 8) and its backward (dm_elu_rows_bwd in place, dm_mlp_head_bwd without an input gradient) against fp64 autograd: in_dim 196
     (no planes: a multiple of 4, the row-panel layer at 16 384 rows) and 294 (planes: the generic product)."""
     import ctypes
@@ -274,8 +274,8 @@ def test_encoder_against_fp64(hip, rows, reward_input, layers):
     pr, pt = (reward.to(DEV), terminal.to(DEV)) if reward_input else (None, None)
     ws = _struct(hip, rows, wm, conf)
     embed, embed_i = _nan(rows, 264), _nan(rows, 264)
-    x, acts = wm._dense_encode(onehot.to(DEV), pr, pt, embed, rows, ws, save=True)
-    wm._dense_encode(cls.to(DEV), pr, pt, embed_i, rows, ws, save=False)
+    x, acts = wm.encoder.dense_encode(onehot.to(DEV), pr, pt, embed, rows, ws, save=True)
+    wm.encoder.dense_encode(cls.to(DEV), pr, pt, embed_i, rows, ws, save=False)
     torch.cuda.synchronize()
     assert torch.equal(embed[:, :256], embed_i[:, :256]), 'the class map and its one-hot form give different bits'
     assert torch.isnan(embed[:, 256:]).all(), 'embed padding written'
@@ -311,8 +311,8 @@ def test_encoder_against_fp64(hip, rows, reward_input, layers):
 
 @pytest.mark.parametrize('rows,min_prob', [(15, 0.0), (15, 0.05), (16384, 0.0), (16384, 0.05)])
 def test_decoder_head_against_fp64(hip, rows, min_prob):
-    """The image decoder as WorldModel runs it - MLP.fwd on the feature rows, WorldModel._dense_loss, the scaled output gradient
-    through dm_mlp_head_bwd with the input gradient ACCUMULATED into a pre-filled buffer, WorldModel._dense_logp - against fp64
+    """The image decoder as WorldModel runs it - MLP.fwd on the feature rows, CatImageDecoder.loss, the scaled output gradient
+    through dm_mlp_head_bwd with the input gradient ACCUMULATED into a pre-filled buffer, CatImageDecoder.logp - against fp64
     autograd of CatImageDecoder.training_step (decoders.py:219-254)."""
     import ctypes
     conf, wm = _wm(min_prob=min_prob, seed=rows)
@@ -326,8 +326,8 @@ def test_decoder_head_against_fp64(hip, rows, min_prob):
     fd, tg = feat.to(DEV), target.to(DEV)
     logits, acts = dec.fwd(fd, F_, rows, ws, save_acts=True)
     loss, dlogits = _nan(rows), _nan(rows, C * cells)
-    wm._dense_loss(logits, tg, rows, loss, dlogits)
-    logp = wm._dense_logp(logits, tg, rows)
+    dec.loss(logits, tg, rows, loss, dlogits)
+    logp = dec.logp(logits, tg, rows)
     scale = 1.0 / rows
     hip.call('dm_scale_inplace', hip.fptr(dlogits), dlogits.numel(), hip.fptr(torch.full((1,), scale, device=DEV)), hip.stream())
     params = list(dec.parameters())
