@@ -2,7 +2,8 @@
 
 Mirrors the reference module tree so `state_dict()` keys, shapes and optimizer grouping are identical
 (reference: pydreamer/models/{dreamer,rssm,rnn,a2c,encoders,decoders,common,probes}.py), but no module here has a
-torch `forward`: the nn.Modules only own `nn.Parameter`s.  `Dreamer.training_step()` packs raw device pointers and
+torch `forward`: the nn.Modules own `nn.Parameter`s, and MultiEncoder / MultiDecoder and the decoder classes the methods that run
+their kernels (each dense decoder's loss call is its own `loss`).  `Dreamer.training_step()` packs raw device pointers and
 calls the C-ABI of libdreamer_hip.so (pydreamer_amd/hip.py) through three `torch.autograd.Function`s — world
 model, actor, critic — so each of the 4 returned losses supports an independent `.backward()` exactly like the
 reference (train.py:184-187).  There is no CPU path: tensors must live on a gfx950 device.
@@ -501,21 +502,65 @@ class ConvDecoder(_Params):
         return [self.model[i] for i in (0, 2, 4, 6, 8)]
 
 
-class DenseNormalDecoder(_Params):
-    """decoders.py:287-319."""
+def _reduce_i(x, NE, I, mode, iw=None):
+    """TBI => TB (decoders.py:170-171,277-278,312-313) of x's NE * I rows -> (NE, ...).  mode 1: -logavgexp_i(-x) of a loss (`iw`
+    (NE * I,) receives the importance weights softmax_i(-x)); mode 0: the mean over I of a prediction; mode 2: the sum."""
+    out = x.new_empty(NE, *x.shape[1:])
+    H.call('dm_reduce_i', NE, I, out.numel() // NE, H.fptr(x), mode, H.fptr(out), H.fptr(iw), H.stream())
+    return out
 
-    def __init__(self, in_dim, hidden_layers, layer_norm=True, out_dim=1):
+
+class _DenseDecoder(_Params):
+    """A dense decoder: `model` is the MLP, loss() the one kernel call behind its output `out` (N rows).
+    loss(out, target, scale, grad, I, bins) -> (loss (N,), dout, mean, bin): dout = scale * d loss / d out, only with grad - the
+    caller folds every factor of ITS loss into `scale`, none is computed here; `mean` the decoded mean per row; `bin` None but
+    for the categorical head.  target=None is the mean-only form.
+    buckets(target, bin) yields the (suffix, mask) pairs of the logprob_<name><suffix> splits (decoders.py:86-105)."""
+
+    target_rows = True      # loss() takes one target per row (the (T,B) target expanded over I), not the (T,B) target itself
+
+
+class DenseNormalDecoder(_DenseDecoder):
+    """decoders.py:287-319.  nd: an Independent Normal over the out_dim outputs (dm_head_loss_normal_nd, at every width - the
+    vecobs and goals heads) instead of the scalar head (dm_head_loss kind 0 - the reward head); the owner decides at
+    construction."""
+
+    def __init__(self, in_dim, hidden_layers, layer_norm=True, out_dim=1, nd=False):
         super().__init__()
         self.model = MLP(in_dim, out_dim, MLP_HIDDEN, hidden_layers, layer_norm)
         self.std = REWARD_STD
+        self.nd = nd
+
+    def loss(self, out, target=None, scale=0.0, grad=False, I=1, bins=False):
+        (N, V), shape = out.shape, out.shape if self.nd else out.shape[:1]
+        if target is None:      # the mean of a Normal is the MLP's output: nothing to launch
+            return None, None, out.view(shape), None
+        loss, dout, mean = out.new_empty(N), out.new_empty(shape) if grad else None, out.new_empty(shape)
+        # (nd, decoders.py:295-304: the scalar head's std and constant per output)
+        H.call(*(('dm_head_loss_normal_nd', N, V) if self.nd else ('dm_head_loss', 0, N)), H.fptr(out), H.fptr(target), scale,
+               NORMAL_LOSS_CONST, H.fptr(loss), H.fptr(dout), H.fptr(mean), H.stream())
+        return loss, dout, mean, None
+
+    def buckets(self, target, bin):      # decoders.py:95-98: by the sign of the reward (the scalar head only)
+        for sig in (() if self.nd else (-1, 1)):
+            yield sig, torch.sign(target.float()) == sig
 
 
-class DenseBernoulliDecoder(_Params):
+class DenseBernoulliDecoder(_DenseDecoder):
     """decoders.py:257-284."""
 
     def __init__(self, in_dim, hidden_layers, layer_norm=True):
         super().__init__()
         self.model = MLP(in_dim, 1, MLP_HIDDEN, hidden_layers, layer_norm)
+
+    def loss(self, out, target=None, scale=0.0, grad=False, I=1, bins=False):
+        N = out.shape[0]
+        loss, dout, mean = (out.new_empty(N) if want else None for want in (target is not None, grad, True))
+        H.call('dm_head_loss', 1, N, H.fptr(out), H.fptr(target), scale, 0.0, H.fptr(loss), H.fptr(dout), H.fptr(mean), H.stream())
+        return loss, dout, mean, None
+
+    def buckets(self, target, bin):      # decoders.py:101-105
+        yield 1, target.float() > 0
 
 
 CATSUP_MAX = 32           # dm_head_loss_catsup: at most 32 support values (a row group is at most half a wave)
@@ -552,7 +597,7 @@ def reward_support(conf):
     return x
 
 
-class DenseCategoricalSupportDecoder(_Params):
+class DenseCategoricalSupportDecoder(_DenseDecoder):
     """decoders.py:322-362: a categorical distribution over fixed support values.  `_support` is a frozen parameter as in the
     reference: it stands in state_dict() in front of model.model.* and in the world-model optimizer's parameter list, where it
     never receives a gradient.  Loss, decoded mean and the target's bin are dm_head_loss_catsup (csrc/cat_support.hip).
@@ -569,10 +614,27 @@ class DenseCategoricalSupportDecoder(_Params):
             raise NotImplementedError('reward_decoder_categorical on the meta device is not built: `_support` holds values fixed '
                                       'at construction, which a meta tensor drops; construct the model on a real device')
 
+    target_rows = False      # the target is the (T,B) reward itself: row r reads target r / I (decoders.py:340-362)
+
+    def loss(self, out, target=None, scale=0.0, grad=False, I=1, bins=False):
+        """`out`: (N, K) logits.  bins: `bin` (N / I,) int32, the support index of each target (not per IWAE sample)."""
+        N, K = out.shape
+        loss, dout, mean = (out.new_empty(shape) if want else None
+                            for shape, want in ((N, target is not None), ((N, K), grad), (N, True)))
+        bin = torch.empty(N // I, dtype=torch.int32, device=out.device) if bins else None
+        H.call('dm_head_loss_catsup', N, I, K, H.fptr(out), K, H.fptr(self._support), H.fptr(target), scale, H.fptr(loss),
+               H.fptr(dout), H.fptr(mean), H.ptr(bin), H.stream())
+        return loss, dout, mean, bin
+
+    def buckets(self, target, bin):      # decoders.py:86-94: one entry per support value; one nobody hit is 0 / 0 = NaN
+        for i in range(self.model.out_dim):
+            yield i, bin == i
+
 
 class MultiDecoder(_Params):
-    """decoders.py:10-108.  Owns the heads' parameters and runs the image term (convolution, dense categorical or none) for
-    WorldModel and Dreamer's log dream; the reward / terminal / vecobs heads are run by WorldModel."""
+    """decoders.py:10-108.  Owns the heads' parameters and runs them for WorldModel and Dreamer: the image term (convolution,
+    dense categorical or none) and the dense heads reward / terminal / vecobs - training forward (heads_loss), evaluation on
+    prior-sample features (predict), the dream's windowed forward and mean decode (dream_buffers / dream_fwd / dream_means)."""
 
     def __init__(self, features_dim, conf):
         super().__init__()
@@ -597,13 +659,95 @@ class MultiDecoder(_Params):
             self.reward = DenseCategoricalSupportDecoder(features_dim, support, conf.reward_decoder_layers, conf.layer_norm)
         else:
             self.reward = DenseNormalDecoder(features_dim, conf.reward_decoder_layers, conf.layer_norm)
-        self.reward_bins = 0 if support is None else len(support)      # K of dm_head_loss_catsup, 0 for the Normal head
+        self.reward_bins = 0 if support is None else len(support)      # the number of support values, 0 for the Normal head
         self.terminal = DenseBernoulliDecoder(features_dim, conf.terminal_decoder_layers, conf.layer_norm)
         self.vecobs_weight = conf.vecobs_weight
         if conf.vecobs_size:      # decoders.py:45-48
-            self.vecobs = DenseNormalDecoder(features_dim, 4, conf.layer_norm, out_dim=conf.vecobs_size)
+            self.vecobs = DenseNormalDecoder(features_dim, 4, conf.layer_norm, out_dim=conf.vecobs_size, nd=True)
         else:
             self.vecobs = None
+        self.sparse_cols = conf.stoch_dim * conf.stoch_discrete      # the one-hot latent columns of a feature row (0: Gaussian)
+
+    # ---- the dense heads: training forward (heads_loss), evaluation (predict), the dream (dream_buffers, dream_fwd, dream_means)
+    def heads(self):
+        """(name, decoder, weight in loss_model) in the order of the loss terms and of the backward's head list: reward and
+        terminal, which every model has and whose schedules pair them ([:2]), then each further head ([2:])."""
+        hs = [('reward', self.reward, self.reward_weight), ('terminal', self.terminal, self.terminal_weight)]
+        return hs + [('vecobs', self.vecobs, self.vecobs_weight)] if self.vecobs is not None else hs
+
+    @staticmethod
+    def _targets(names, obs, pk):
+        """name -> (the (T,B) target, its expansion over I: insert_dim, decoders.py:270,305); I = 1: the same tensor twice."""
+        y = {n: pk['vecobs'] if n == 'vecobs' else obs[n].float().contiguous() for n in names}
+        return {n: (t, t if pk['I'] == 1 else t.repeat_interleave(pk['I'], dim=int(n != 'vecobs')).contiguous()) for n, t in y.items()}
+
+    def heads_loss(self, pk, obs, ws, gw):
+        """Training forward of the dense heads on pk's T*B*I feature rows (decoders.py:57-83).  Returns name -> (loss (N,), rec (N,
+        ...), target rows), per IWAE sample, and the backward's entries [(mlp, acts, dout)] in heads() order, dout = gw * weight /
+        (T*B) * d loss / d out."""
+        feat, NE, hs, res, bwd = pk['feat'], pk['T'] * pk['B'], self.heads(), {}, []
+        N = feat.shape[0]
+        for group in (hs[:2], hs[2:]):      # reward and terminal run side by side, each further head behind them
+            y = self._targets([n for n, _, _ in group], obs, pk)
+            outs = [head.model.fwd(feat, self.features_dim, N, ws, sparse_cols=self.sparse_cols) for _, head, _ in group]
+            for (n, head, weight), (out, acts) in zip(group, outs):
+                loss, dout, rec, _ = head.loss(out, y[n][head.target_rows], gw * weight / NE, grad=True, I=pk['I'])
+                res[n] = (loss, rec, y[n][1])
+                bwd.append((head.model, acts, dout))
+        return res, bwd
+
+    def predict(self, pk, feat, obs, ws):
+        """The evaluation form (decoders.py:50-108 with extra_metrics), no gradients: every decoder on `feat`, pk's T*B*I rows with
+        the latent part replaced (do_image_pred).  Returns (metrics, tensors): logprob_<name> and <name>_pred per decoder, reduced
+        TBI => TB, and the NaN-masked splits logprob_<name><bucket> of each decoder's buckets() as (T,B) torch expressions."""
+        T, B, I, shp = pk['T'], pk['B'], pk['I'], pk['shp']
+        NE, N, F_ = T * B, T * B * I, self.features_dim
+        tb = lambda x: x.view(T, B, *x.shape[1:])
+        red = (lambda x, mode: x) if I == 1 else (lambda x, mode: _reduce_i(x, NE, I, mode))
+        # loss and prediction (dense: normalised log-probabilities) of the image decoder; image-less: both None
+        li, image_pred = self.decode(shp, feat, pk['image'], ws, target=pk.get('target'), loss=True)
+        hs, lp, pred, bins = self.heads(), {}, {}, {}
+        outs = [head.model.fwd(feat, F_, N, ws, save_acts=False)[0] for _, head, _ in hs[:2]]
+        for n, head, _ in hs[2:]:
+            y = self._targets([n], obs, pk)[n]
+            l, _, p, _ = head.loss(head.model.fwd(feat, F_, N, ws, save_acts=False)[0], y[head.target_rows], I=I)
+            lp[n], pred[n] = red(l, 1), red(p, 0)
+        y = self._targets([n for n, _, _ in hs[:2]], obs, pk)
+        per_sample = [head.loss(out, y[n][head.target_rows], I=I, bins=True) for (n, head, _), out in zip(hs[:2], outs)]
+        if li is not None:
+            lp['image'] = red(li, 1)
+        for mode, into, k in ((1, lp, 0), (0, pred, 2)):      # -logavgexp over I for the losses, then the means of the predictions
+            for (n, _, _), r in zip(hs[:2], per_sample):
+                into[n], bins[n] = red(r[k], mode), r[3]
+        if image_pred is not None:      # decoded.mean(dim=2), decoders.py:171
+            image_pred = image_pred.view(NE, I, *image_pred.shape[1:])
+            pred['image'] = image_pred.mean(1) if I > 1 else image_pred[:, 0]
+        metrics, tensors = {}, {}
+        for group in ([n for n in ('image', 'reward', 'terminal') if n in lp], *([n] for n, _, _ in hs[2:])):
+            tensors.update({f'logprob_{n}': tb(lp[n]) for n in group})
+            tensors.update({f'{n}_pred': tb(pred[n]) for n in group})
+            metrics.update({f'logprob_{n}': lp[n].mean() for n in group})
+        nan = torch.full((), float('nan'), device=feat.device)
+        nanmean = lambda x: torch.nansum(x) / (~torch.isnan(x)).sum()     # functions.py:149-150
+        for n, head, _ in hs:
+            for s, mask in head.buckets(obs.get(n), bins.get(n)):
+                x = torch.where(mask.view(T, B), tb(lp[n]), nan)
+                metrics[f'logprob_{n}{s}'], tensors[f'logprob_{n}{s}'] = nanmean(x), x
+        return metrics, tensors
+
+    def dream_buffers(self, rows, device):
+        """The reward and terminal heads' outputs over all `rows` imagined states, filled window by window (dream_fwd)."""
+        return [torch.empty(rows, head.model.out_dim, device=device) for _, head, _ in self.heads()[:2]]
+
+    def dream_fwd(self, feat, row0, n, ws, bufs):
+        """Rows [row0, row0 + n) of the reward and terminal heads (dreamer.py:212-213); nobody differentiates them."""
+        for (_, head, _), out in zip(self.heads()[:2], bufs):
+            head.model.fwd(feat, self.features_dim, n, ws, save_acts=False, sparse_cols=self.sparse_cols, window=(out.shape[0], row0),
+                           out=out)
+
+    def dream_means(self, bufs):
+        """(terminal, reward) means (rows,) behind the windows: only `.mean` of either distribution is read (dreamer.py:212-213)."""
+        return self.terminal.loss(bufs[1])[2], self.reward.loss(bufs[0])[2]
 
     # ---- the image term: training forward (image_buffers, image_loss), backward (image_heads, image_bwd), evaluation (decode)
     def _conv_fwd(self, shp, feat, image, ws, acts, loss, pred):
@@ -866,8 +1010,8 @@ class MapProbeHead(_Params):
                 if train:      # d loss_probe / d loss_tb = 1 / (T*B)
                     H.call('dm_scale_inplace', H.fptr(dlogits), N * ld, H.fptr(torch.full((1,), gw / NE, device=dev)), H.stream())
             else:              # loss_tb = -logavgexp_i(-loss_tbi) (decoders.py:245); its importance weights scale the row gradients
-                loss_tb, iw = torch.empty(NE, device=dev), torch.empty(N, device=dev)
-                H.call('dm_reduce_i', NE, I, 1, H.fptr(loss_tbi), 1, H.fptr(loss_tb), H.fptr(iw), H.stream())
+                iw = torch.empty(N, device=dev)
+                loss_tb = _reduce_i(loss_tbi, NE, I, 1, iw=iw)
                 if train:
                     H.call('dm_scale_rows', N, ld, H.fptr(dlogits), ld, H.fptr(iw), gw / NE, H.stream())
             map_rec = torch.empty(T, B, C, S, S, device=dev)
@@ -907,7 +1051,7 @@ class GoalsProbe(_Params):
     (out_dim 2) and `goals_direction` (out_dim 2 * goals_size), each with hidden_layers=4 and layer_norm=True whatever
     conf.layer_norm says (probes.py:94-95).  Keys probe_model.decoders.{goal_direction,goals_direction}.model.model.{0,1,3,...};
     torch's default Linear init, as for the map probe.  Forward and backward of the heads are MLP.fwd / dm_mlp_head_bwd, the
-    Normal loss dm_head_loss_normal_nd, the IWAE reduction dm_reduce_i / dm_scale_rows; mse_goals, var_goals and the six
+    Normal loss DenseNormalDecoder.loss (nd), the IWAE reduction _reduce_i / dm_scale_rows; mse_goals, var_goals and the six
     mse_goal_age* come from one dm_goals_stats call (csrc/goals.hip) that writes them into the step's metric buffer."""
 
     def __init__(self, state_dim, conf):
@@ -917,8 +1061,8 @@ class GoalsProbe(_Params):
             raise NotImplementedError(f"probe_model={getattr(conf, 'probe_model', 'goals')!r} needs goals_size >= 1 "
                                       f'(got goals_size={self.goals_size}): a zero-width goals decoder is not built in the HIP path')
         self.decoders = _Decoders()
-        self.decoders.add_module('goal_direction', DenseNormalDecoder(state_dim, 4, True, out_dim=2))
-        self.decoders.add_module('goals_direction', DenseNormalDecoder(state_dim, 4, True, out_dim=2 * self.goals_size))
+        self.decoders.add_module('goal_direction', DenseNormalDecoder(state_dim, 4, True, out_dim=2, nd=True))
+        self.decoders.add_module('goals_direction', DenseNormalDecoder(state_dim, 4, True, out_dim=2 * self.goals_size, nd=True))
         self._ws = None
 
     def heads(self):
@@ -956,22 +1100,16 @@ class GoalsProbe(_Params):
                 mbuf = torch.zeros(METRIC_BUF_FLOATS, device=dev)
             s0 = GOALS_METRIC_SLOTS['loss_goal_direction']
             packs, metrics, tensors, means, targets = [], {}, {}, [], {}
-            for n, (key, mlp) in enumerate(zip(GOAL_KEYS, self.heads())):
-                V = mlp.out_dim
+            for n, (key, head) in enumerate(self.decoders.named_children()):      # GOAL_KEYS, in that order
+                mlp, V = head.model, head.model.out_dim
                 target = targets[key] = obs[key].float().contiguous().view(NE, V)
                 rows_t = target.repeat_interleave(I, dim=0).contiguous() if I > 1 else target      # insert_dim(target, 2, I), decoders.py:309
                 mu, acts = mlp.fwd(feat2d, F_, N, ws, save_acts=train)
-                loss_tbi, mean_i = torch.empty(N, device=dev), torch.empty(N, V, device=dev)
-                dmu = torch.empty(N, V, device=dev) if train else None
                 # d loss_probe / d loss_tb = 1 / (T*B); with I > 1 the importance weights come in below
-                H.call('dm_head_loss_normal_nd', N, V, H.fptr(mu), H.fptr(rows_t), gw / NE if I == 1 else 1.0, NORMAL_LOSS_CONST,
-                       H.fptr(loss_tbi), H.fptr(dmu), H.fptr(mean_i), H.stream())
-                if I == 1:
-                    loss_tb, pred = loss_tbi, mean_i
-                else:          # loss_tb = -logavgexp_i(-loss_tbi), decoded.mean.mean(dim=2) (decoders.py:313-314)
-                    loss_tb, iw, pred = torch.empty(NE, device=dev), torch.empty(N, device=dev), torch.empty(NE, V, device=dev)
-                    H.call('dm_reduce_i', NE, I, 1, H.fptr(loss_tbi), 1, H.fptr(loss_tb), H.fptr(iw), H.stream())
-                    H.call('dm_reduce_i', NE, I, V, H.fptr(mean_i), 0, H.fptr(pred), None, H.stream())
+                loss_tb, dmu, pred, _ = head.loss(mu, rows_t, gw / NE if I == 1 else 1.0, grad=train)
+                if I > 1:          # loss_tb = -logavgexp_i(-loss_tbi), decoded.mean.mean(dim=2) (decoders.py:313-314)
+                    iw = torch.empty(N, device=dev)
+                    loss_tb, pred = _reduce_i(loss_tb, NE, I, 1, iw=iw), _reduce_i(pred, NE, I, 0)
                     if train:
                         H.call('dm_scale_rows', N, V, H.fptr(dmu), V, H.fptr(iw), gw / NE, H.stream())
                 means.append((loss_tb, 1.0 / NE))
@@ -1350,7 +1488,7 @@ class _WMStep(torch.autograd.Function):
             torch.cuda.current_stream().wait_stream(ov.s_wm)
         else:
             grads, flat, direct = wm._backward(pk, pk['ws'])
-        for k in ('enc_acts', 'rssm_acts', 'dec_acts', 'r_acts', 't_acts', 'aux', 'v_acts', 'ev_acts', 'enc_x', 'dlogits'):
+        for k in ('enc_acts', 'rssm_acts', 'dec_acts', 'heads', 'aux', 'ev_acts', 'enc_x', 'dlogits'):
             pk.pop(k, None)                               # only now: the side stream may have been reading them
         pk['consumed'] = True
         return (None, None) + _finish_backward(wm, grads, flat, direct, grad_loss)
@@ -1547,49 +1685,11 @@ class WorldModel(_Params):
     def _forward_tail(self, pk, obs, c, dec, dec_acts, loss_image, ws, mbuf, action, reset, rssm_acts):
         shp, T, B, I, feat, post, prior, idx = (pk[k] for k in ('shp', 'T', 'B', 'I', 'feat', 'post', 'prior', 'idx'))
         N, NE, dev = T * B * I, T * B, feat.device
-        D_, F_ = c.deter_dim, self.features_dim
-        gauss = not c.stoch_discrete
-        Z = c.stoch_dim * (c.stoch_discrete or 1)
-        # image-less (decoders.py:29-30,59-64): no image term.  `none` stands in the image's place in the one-launch sums below: an
-        # item of zero elements sums to an exact 0.0, so metric slot 1 stays zero and is never named
-        none = torch.empty(0, device=dev) if self.imageless else None
-        pk.update(dec.image_loss(shp, feat, pk['image'], ws, dec_acts, loss_image, float(getattr(self, 'grad_weight', 1.0))))
-
-        reward_t = reward_tb = obs['reward'].float().contiguous()
-        terminal_t = obs['terminal'].float().contiguous()
-        if I > 1:                                  # targets expanded over I (decoders.py:270,305: insert_dim)
-            reward_t = reward_t.repeat_interleave(I, dim=1).contiguous()
-            terminal_t = terminal_t.repeat_interleave(I, dim=1).contiguous()
-        sp = 0 if c.stoch_discrete == 0 else c.stoch_dim * c.stoch_discrete      # the one-hot latent columns of a feature row
-        mu, r_acts = dec.reward.model.fwd(feat, F_, N, ws, sparse_cols=sp)
-        tl, t_acts = dec.terminal.model.fwd(feat, F_, N, ws, sparse_cols=sp)
-        K = dec.reward_bins      # > 0: DenseCategoricalSupportDecoder, `mu` holds (N, K) logits and `dmu` their gradient
-        loss_reward, reward_rec = (torch.empty(N, device=dev) for _ in range(2))
-        dmu = torch.empty((N, K) if K else N, device=dev)
-        loss_terminal, dtl, terminal_rec = (torch.empty(N, device=dev) for _ in range(3))
+        D_, F_, gauss = c.deter_dim, self.features_dim, not c.stoch_discrete
         # gw: the data-parallel shard weight B_r/B (dist.attach), folded into every gradient scale; loss values are unaffected
         gw = float(getattr(self, 'grad_weight', 1.0))
-        if K:      # decoders.py:340-362; the target is the (T,B) reward itself: row r reads target r / I
-            H.call('dm_head_loss_catsup', N, I, K, H.fptr(mu), K, H.fptr(dec.reward._support), H.fptr(reward_tb),
-                   gw * dec.reward_weight / NE, H.fptr(loss_reward), H.fptr(dmu), H.fptr(reward_rec), None, H.stream())
-        else:
-            H.call('dm_head_loss', 0, N, H.fptr(mu), H.fptr(reward_t), gw * dec.reward_weight / NE, NORMAL_LOSS_CONST, H.fptr(loss_reward),
-                   H.fptr(dmu), H.fptr(reward_rec), H.stream())
-        H.call('dm_head_loss', 1, N, H.fptr(tl), H.fptr(terminal_t), gw * dec.terminal_weight / NE, 0.0, H.fptr(loss_terminal),
-               H.fptr(dtl), H.fptr(terminal_rec), H.stream())
-
-        V = c.vecobs_size
-        loss_vecobs = dmu_v = vecobs_rec = v_acts = None
-        if V:      # decoders.py:66-71: Independent Normal over the V outputs, the reward head's std and constant per output
-            vec_t = pk['vecobs']
-            if I > 1:
-                vec_t = vec_t.repeat_interleave(I, dim=0).contiguous()
-            mu_v, v_acts = dec.vecobs.model.fwd(feat, F_, N, ws, sparse_cols=sp)
-            loss_vecobs = torch.empty(N, device=dev)
-            dmu_v, vecobs_rec = torch.empty(N, V, device=dev), torch.empty(N, V, device=dev)
-            H.call('dm_head_loss_normal_nd', N, V, H.fptr(mu_v), H.fptr(vec_t), gw * dec.vecobs_weight / NE, NORMAL_LOSS_CONST,
-                   H.fptr(loss_vecobs), H.fptr(dmu_v), H.fptr(vecobs_rec), H.stream())
-
+        pk.update(dec.image_loss(shp, feat, pk['image'], ws, dec_acts, loss_image, gw))
+        heads, pk['heads'] = dec.heads_loss(pk, obs, ws, gw)      # name -> (loss, rec, target) per row; the backward's entries
         # KL + entropies (dreamer.py:326-343,369-379)
         kl, ent_post, ent_prior = (torch.empty(N, device=dev) for _ in range(3))
         H.call('dm_kl_balance_fwd', N, c.stoch_dim, c.stoch_discrete, H.fptr(post), H.fptr(prior), H.fptr(kl),
@@ -1597,10 +1697,7 @@ class WorldModel(_Params):
 
         if mbuf is None:
             mbuf = torch.zeros(METRIC_BUF_FLOATS, device=dev)
-        loss = mbuf[6]
-        w = (ctypes.c_float * 4)(self.kl_weight, dec.image_weight, dec.reward_weight, dec.terminal_weight)
-        iw = None
-        aux = None
+        loss, iw, aux = mbuf[6], None, None
         if self.ac_aux is not None and T >= 2:
             # Auxiliary critic (dreamer.py:347-358): ActorCritic.training_step on the REAL trajectory - features (T,B,F) as
             # the "dream", the batch's own actions / rewards / terminals; only loss_critic is kept.  Its actor forward and
@@ -1612,10 +1709,10 @@ class WorldModel(_Params):
                 ac.update_critic_target()
             ac.train_steps += 1
             rows = (T - 1) * B
-            value_t, _ = ac.critic_target.fwd(feat, F_, N, ws, save_acts=False, sparse_cols=0 if gauss else Z)
-            value, aux_acts = ac.critic.fwd(feat, F_, N, ws, sparse_cols=0 if gauss else Z)
+            value_t, _ = ac.critic_target.fwd(feat, F_, N, ws, save_acts=False, sparse_cols=dec.sparse_cols)
+            value, aux_acts = ac.critic.fwd(feat, F_, N, ws, sparse_cols=dec.sparse_cols)
             adv, agae, vtgt, wgt = (torch.empty(T - 1, B, device=dev) for _ in range(4))
-            H.call('dm_gae_losses', T - 1, B, ac.gamma, ac.lambda_, H.fptr(reward_t), H.fptr(terminal_t), H.fptr(value_t),
+            H.call('dm_gae_losses', T - 1, B, ac.gamma, ac.lambda_, H.fptr(heads['reward'][2]), H.fptr(heads['terminal'][2]), H.fptr(value_t),
                    H.fptr(adv), H.fptr(agae), H.fptr(vtgt), H.fptr(wgt), H.stream())
             lc = torch.empty(rows, device=dev)
             dvalue = torch.zeros(N, device=dev)                      # value[-1] gets no gradient
@@ -1623,82 +1720,66 @@ class WorldModel(_Params):
                    H.fptr(dvalue), H.stream())
             _multi_sum([(lc, 1.0 / rows), (value.view(T, B)[:-1], 1.0 / rows)], dev, out=mbuf[24:26])
             aux = dict(acts=aux_acts, dvalue=dvalue, value=value, lc=lc, rows=rows)
-        if I == 1:
-            means = _multi_sum([(kl, 1.0 / N), (none if self.imageless else loss_image, 1.0 / N), (loss_reward, 1.0 / N),
-                                (loss_terminal, 1.0 / N), (ent_prior, 1.0 / N), (ent_post, 1.0 / N)], dev, out=mbuf[0:6])
-            terms = [(kl, 1.0 / N), (loss_image, 1.0 / N), (loss_reward, 1.0 / N), (loss_terminal, 1.0 / N)]
-            wts = [self.kl_weight, dec.image_weight, dec.reward_weight, dec.terminal_weight]
-            if self.imageless:      # four terms: kl, reward, terminal and (below) vecobs
-                del terms[1], wts[1]
-            if V:      # loss_reconstr += vecobs_weight * loss_vecobs (decoders.py:68): one more term of loss_model
-                _multi_sum([(loss_vecobs, 1.0 / N)], dev, out=mbuf[15:16])
-                terms, wts = terms + [(loss_vecobs, 1.0 / N)], wts + [dec.vecobs_weight]
-                H.call('dm_combine', len(wts), H.fptr(_multi_sum(terms, dev)), (ctypes.c_float * len(wts))(*wts),
-                       ctypes.c_void_p(mbuf.data_ptr() + 24), H.stream())
-            else:
-                H.call('dm_combine', 4, H.fptr(means), w, ctypes.c_void_p(mbuf.data_ptr() + 24), H.stream())   # dreamer.py:362-365
-            if aux is not None:       # loss = loss_model.mean() + aux_critic_weight * loss_critic_aux (dreamer.py:365) -> slot 7
-                terms, wts = terms + [(aux['lc'], 1.0 / aux['rows'])], wts + [self.aux_critic_weight]
-                H.call('dm_combine', len(wts), H.fptr(_multi_sum(terms, dev)), (ctypes.c_float * len(wts))(*wts),
-                       ctypes.c_void_p(mbuf.data_ptr() + 28), H.stream())
-                loss = mbuf[7]
-            tb = lambda x: None if x is None else x.view(T, B)
-            t_kl, t_ep, t_eq, t_li, t_lr, t_lt, t_rr, t_tr = (tb(x) for x in (kl, ent_prior, ent_post, loss_image, loss_reward,
-                                                                              loss_terminal, reward_rec, terminal_rec))
-            if V:
-                t_lv, t_vr = tb(loss_vecobs), vecobs_rec.view(T, B, V)
-        else:
+        # loss_model = mean_tb of the weighted terms [kl, image (none on the image-less path), *heads] (dreamer.py:362-365)
+        names = list(heads)
+        img = [] if loss_image is None else [(loss_image, dec.image_weight)]
+        xs = [kl] + [x for x, _ in img] + [heads[n][0] for n in names]
+        wts = [self.kl_weight] + [w for _, w in img] + [w for _, _, w in dec.heads()]
+        red = lambda x, mode: x
+        if I > 1:
             # IWAE: sampled KL (dreamer.py:340-343); loss_model = mean_tb -logavgexp_i(-loss_tbi) (dreamer.py:362-365);
             # the logged tensors are -logavgexp_i(-x) of the per-sample losses (decoders.py:170,277,312), means over I for the
             # entropies and the reconstructions (dreamer.py:371-372, decoders.py:171,278,313)
-            kl_s = torch.empty(N, device=dev)
+            xs[0] = torch.empty(N, device=dev)
             if gauss:      # Normal log-densities of the reparameterised sample z = feat[:, D:] (rssm.py:202-203)
                 H.call('dm_kl_sampled_gauss_fwd', N, c.stoch_dim, H.fptr(post), H.fptr(prior),
-                       ctypes.c_void_p(feat.data_ptr() + 4 * D_), F_, H.fptr(kl_s), H.stream())
+                       ctypes.c_void_p(feat.data_ptr() + 4 * D_), F_, H.fptr(xs[0]), H.stream())
             else:
-                H.call('dm_kl_sampled_fwd', N, c.stoch_dim, c.stoch_discrete, H.fptr(post), H.fptr(prior), H.ptr(idx), H.fptr(kl_s),
+                H.call('dm_kl_sampled_fwd', N, c.stoch_dim, c.stoch_discrete, H.fptr(post), H.fptr(prior), H.ptr(idx), H.fptr(xs[0]),
                        H.stream())
             l_tbi = torch.empty(N, device=dev)
-            rows_l, rows_w = [kl_s, loss_image, loss_reward, loss_terminal], list(w)
-            if self.imageless:
-                del rows_l[1], rows_w[1]
-            if V:
-                rows_l, rows_w = rows_l + [loss_vecobs], rows_w + [dec.vecobs_weight]
-            ptrs = (ctypes.c_void_p * len(rows_l))(*[x.data_ptr() for x in rows_l])
-            H.call('dm_combine_rows', len(rows_l), N, ptrs, (ctypes.c_float * len(rows_w))(*rows_w), H.fptr(l_tbi), H.stream())
+            ptrs = (ctypes.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
+            H.call('dm_combine_rows', len(xs), N, ptrs, (ctypes.c_float * len(wts))(*wts), H.fptr(l_tbi), H.stream())
             iw = torch.empty(N, device=dev)                   # importance weights softmax_i(-loss_tbi) = d loss_tb / d loss_tbi
-            red = torch.empty(9, NE, device=dev)
-            H.call('dm_reduce_i', NE, I, 1, H.fptr(l_tbi), 1, H.fptr(red[0]), H.fptr(iw), H.stream())
-            for j, (x, mode) in enumerate(((kl, 1), (loss_image, 1), (loss_reward, 1), (loss_terminal, 1), (ent_prior, 0),
-                                           (ent_post, 0), (reward_rec, 0), (terminal_rec, 0))):
-                if x is not None:      # (image-less: row 2 of `red` is never written nor read)
-                    H.call('dm_reduce_i', NE, I, 1, H.fptr(x), mode, H.fptr(red[j + 1]), None, H.stream())
-            _multi_sum([(red[1], 1.0 / NE), (none if self.imageless else red[2], 1.0 / NE), (red[3], 1.0 / NE), (red[4], 1.0 / NE),
-                        (red[5], 1.0 / NE), (red[6], 1.0 / NE), (red[0], 1.0 / NE)], dev, out=mbuf[0:7])
-            means = mbuf[0:6]
-            tb = lambda x: x.view(T, B)
-            t_kl, t_li, t_lr, t_lt, t_ep, t_eq, t_rr, t_tr = (tb(red[j]) for j in range(1, 9))
-            if V:      # -logavgexp over I for the loss, the mean over I for the reconstruction (decoders.py:312-313)
-                t_lv, t_vr = torch.empty(T, B, device=dev), torch.empty(T, B, V, device=dev)
-                H.call('dm_reduce_i', NE, I, 1, H.fptr(loss_vecobs), 1, H.fptr(t_lv), None, H.stream())
-                H.call('dm_reduce_i', NE, I, V, H.fptr(vecobs_rec), 0, H.fptr(t_vr), None, H.stream())
-                _multi_sum([(t_lv, 1.0 / NE)], dev, out=mbuf[15:16])
+            l_tb = _reduce_i(l_tbi, NE, I, 1, iw=iw)
+            red = lambda x, mode: _reduce_i(x, NE, I, mode)
+        # Per (t,b), and the means in the metric buffer: slots 0-5 and under IWAE loss_model in slot 6 are one launch (image-less, an
+        # item of zero elements leaves an exact 0.0 in slot 1); every further head has a slot of its own
+        t_kl = red(kl, 1)
+        t_li = None if loss_image is None else red(loss_image, 1)
+        t_loss = {n: red(heads[n][0], 1) for n in names[:2]}
+        t_ep, t_eq = red(ent_prior, 0), red(ent_post, 0)
+        t_rec = {n: red(heads[n][1], 0) for n in names[:2]}
+        items = [t_kl, torch.empty(0, device=dev) if t_li is None else t_li, *t_loss.values(), t_ep, t_eq] + ([l_tb] if I > 1 else [])
+        _multi_sum([(x, 1.0 / NE) for x in items], dev, out=mbuf[0:len(items)])
+        for n in names[2:]:
+            t_loss[n], t_rec[n] = red(heads[n][0], 1), red(heads[n][1], 0)
+            s = METRIC_SLOTS[f'loss_{n}']
+            _multi_sum([(t_loss[n], 1.0 / NE)], dev, out=mbuf[s:s + 1])
+        if I == 1:
+            def combine(sums, w, slot):
+                H.call('dm_combine', len(w), H.fptr(sums), (ctypes.c_float * len(w))(*w), ctypes.c_void_p(mbuf.data_ptr() + 4 * slot),
+                       H.stream())
+            terms = [(x, 1.0 / N) for x in xs]
+            # (kl, image, reward, terminal and nothing else: their means stand in slots 0-3 already)
+            combine(mbuf[0:4] if img and not names[2:] else _multi_sum(terms, dev), wts, 6)
+            if aux is not None:       # loss = loss_model.mean() + aux_critic_weight * loss_critic_aux (dreamer.py:365) -> slot 7
+                combine(_multi_sum(terms + [(aux['lc'], 1.0 / aux['rows'])], dev), wts + [self.aux_critic_weight], 7)
+                loss = mbuf[7]
 
-        pk.update(loss=loss, action=action, reset=reset, rssm_acts=rssm_acts, r_acts=r_acts, t_acts=t_acts, dmu=dmu, dtl=dtl, ws=ws,
-                  mbuf=mbuf, iw=iw, aux=aux, v_acts=v_acts, dmu_v=dmu_v)
-        pk['tensors'] = LazyTensors(loss_kl=t_kl, entropy_prior=t_ep, entropy_post=t_eq,
-                                    loss_image=t_li, image_rec=None,
-                                    loss_reward=t_lr, reward_rec=t_rr,
-                                    loss_terminal=t_lt, terminal_rec=t_tr)
-        pk['metrics'] = dict(loss_model=mbuf[6], loss_kl=means[0], entropy_prior=means[4], entropy_post=means[5],
-                             loss_image=means[1], loss_reward=means[2], loss_terminal=means[3])
-        if self.imageless:      # decoders.py:59-64: there is no loss_image metric and no loss_image / image_rec tensor
-            del pk['metrics']['loss_image'], pk['tensors']['loss_image'], pk['tensors']['image_rec']
-        else:
+        pk.update(loss=loss, action=action, reset=reset, rssm_acts=rssm_acts, ws=ws, mbuf=mbuf, iw=iw, aux=aux)
+        tb = lambda x: x.view(T, B, *x.shape[1:])
+        tensors = dict(loss_kl=tb(t_kl), entropy_prior=tb(t_ep), entropy_post=tb(t_eq))
+        metrics = dict(loss_model=mbuf[6], loss_kl=mbuf[0], entropy_prior=mbuf[4], entropy_post=mbuf[5])
+        if t_li is not None:      # (decoders.py:59-64: image-less there is no loss_image metric and no loss_image / image_rec tensor)
+            tensors.update(loss_image=tb(t_li), image_rec=None)
+            metrics.update(loss_image=mbuf[1])
+        for n in names:
+            tensors.update({f'loss_{n}': tb(t_loss[n]), f'{n}_rec': tb(t_rec[n])})
+            metrics[f'loss_{n}'] = mbuf[METRIC_SLOTS[f'loss_{n}']]
+        pk['tensors'], pk['metrics'] = LazyTensors(tensors), metrics
+        if t_li is not None:
             pk['tensors'].lazy('image_rec', dec.image_rec_thunk(pk))
-        if V:
-            pk['metrics'].update(loss_vecobs=mbuf[15])
-            pk['tensors'].update(loss_vecobs=t_lv, vecobs_rec=t_vr)
         if aux is not None:
             pk['metrics'].update(loss_critic_aux=mbuf[24], policy_value_aux=mbuf[25])
             pk['tensors']['policy_value_aux'] = aux['value'].view(T, B)
@@ -1723,15 +1804,11 @@ class WorldModel(_Params):
         dfeat = torch.zeros(N, F_, device=dev)
         # dense heads (decoders.py:73-83)
         if iw is not None and not pk.get('iw_applied'):
-            for dout in (pk['dmu'], pk['dtl']):      # (N,), or the (N, K) logit gradient of the categorical reward head
+            for _, _, dout in pk['heads']:      # (N,) or (N, n): one importance weight per row
                 n = dout.numel() // N
                 H.call('dm_scale_rows', N, n, H.fptr(dout), n, H.fptr(iw), 1.0, H.stream())
-            if pk.get('dmu_v') is not None:
-                H.call('dm_scale_rows', N, c.vecobs_size, H.fptr(pk['dmu_v']), c.vecobs_size, H.fptr(iw), 1.0, H.stream())
             pk['iw_applied'] = True
-        heads = [(dec.reward.model, pk['r_acts'], pk['dmu']), (dec.terminal.model, pk['t_acts'], pk['dtl'])]
-        if pk.get('dmu_v') is not None:
-            heads.append((dec.vecobs.model, pk['v_acts'], pk['dmu_v']))
+        heads = list(pk['heads'])      # reward, terminal, vecobs (MultiDecoder.heads_loss)
         if pk.get('aux') is not None:          # the auxiliary critic trains on the world model's own features (not detached)
             heads.append((self.ac_aux.critic, pk['aux']['acts'], pk['aux']['dvalue']))
         heads += dec.image_heads(pk)
@@ -1784,9 +1861,7 @@ class WorldModel(_Params):
                    H.fptr(dfeat), H.fptr(dpost), H.fptr(dprior), ctypes.byref(rssm_g), H.fptr(dembed), H.ptr(ws), ws.numel(),
                    H.stream())
             if I > 1:                  # the I samples of a (t,b) share one embedding row: their gradients add up
-                dsum = torch.empty(NE, E, device=dev)
-                H.call('dm_reduce_i', NE, I, E, H.fptr(dembed), 2, H.fptr(dsum), None, H.stream())
-                dembed = dsum
+                dembed = _reduce_i(dembed, NE, I, 2)
             self.encoder.backward(dembed, pk, gof, ws_enc)
         except BaseException:
             if side:
@@ -1799,13 +1874,10 @@ class WorldModel(_Params):
     def _image_pred(self, pk, obs, u_pred):
         """do_image_pred (dreamer.py:381-394): decode from a PRIOR sample instead of the posterior sample and report the
         reconstruction losses as logprob_* / *_pred (decoders.py:50-108 with extra_metrics).  Logging variant, no grads.
-        iwae_samples = I > 1 (the call shape of evaluate(), train.py:353-359,380-385): one prior sample per (t,b,i) row; the
-        decoders reduce TBI => TB by -logavgexp(-loss) for the losses and a mean for the predictions
-        (decoders.py:170-171,277-278,312-313).  The NaN-masked sign / terminal splits (decoders.py:94-105) are (T,B) torch
-        expressions."""
+        iwae_samples = I > 1 (the call shape of evaluate(), train.py:353-359,380-385): one prior sample per (t,b,i) row, which
+        MultiDecoder.predict decodes and reduces TBI => TB."""
         c, dec = self.conf, self.decoder
-        T, B, I, feat, shp = pk['T'], pk['B'], pk.get('I', 1), pk['feat'], pk['shp']
-        NE, N, dev = T * B, T * B * I, feat.device
+        feat, shp, N, dev = pk['feat'], pk['shp'], pk['feat'].shape[0], pk['feat'].device
         D_, S, C, F_ = c.deter_dim, c.stoch_dim, c.stoch_discrete, self.features_dim
         ws = self.workspace(shp, dev)
         with torch.no_grad():
@@ -1816,74 +1888,7 @@ class WorldModel(_Params):
             idx = torch.empty(N, S, dtype=torch.int32, device=dev)
             H.call('dm_sample_onehot', N, S, C, H.fptr(pk['prior']), S * (C or 2), H.fptr(u_pred), None,
                    ctypes.c_void_p(fp.data_ptr() + 4 * D_), F_, H.ptr(idx), H.stream())
-            # loss and prediction (dense: normalised log-probabilities) of the image decoder on the prior-sample features;
-            # image-less (decoders.py:59-64): no logprob_image, no image_pred - both None
-            li, image_pred = dec.decode(shp, fp, pk['image'], ws, target=pk.get('target'), loss=True)
-            if image_pred is not None:
-                image_pred = image_pred.view(T, B, I, *image_pred.shape[1:])
-            mu, _ = dec.reward.model.fwd(fp, F_, N, ws, save_acts=False)
-            tl, _ = dec.terminal.model.fwd(fp, F_, N, ws, save_acts=False)
-            lr, lt, rp, tp, scratch = (torch.empty(N, device=dev) for _ in range(5))
-            V = c.vecobs_size
-            if V:
-                vec_t = pk['vecobs'].repeat_interleave(I, dim=0).contiguous() if I > 1 else pk['vecobs']
-                mu_v, _ = dec.vecobs.model.fwd(fp, F_, N, ws, save_acts=False)
-                lv, vp = torch.empty(N, device=dev), torch.empty(N, V, device=dev)
-                H.call('dm_head_loss_normal_nd', N, V, H.fptr(mu_v), H.fptr(vec_t), 0.0, NORMAL_LOSS_CONST, H.fptr(lv), None, H.fptr(vp),
-                       H.stream())
-                if I > 1:
-                    lv_i, vp_i = lv, vp
-                    lv, vp = torch.empty(NE, device=dev), torch.empty(NE, V, device=dev)
-                    H.call('dm_reduce_i', NE, I, 1, H.fptr(lv_i), 1, H.fptr(lv), None, H.stream())
-                    H.call('dm_reduce_i', NE, I, V, H.fptr(vp_i), 0, H.fptr(vp), None, H.stream())
-            reward_t, terminal_t = obs['reward'].float().contiguous(), obs['terminal'].float().contiguous()
-            reward_tb = reward_t
-            if I > 1:                              # targets expanded over I (decoders.py:270,305: insert_dim)
-                reward_t = reward_t.repeat_interleave(I, dim=1).contiguous()
-                terminal_t = terminal_t.repeat_interleave(I, dim=1).contiguous()
-            K, rbin = dec.reward_bins, None
-            if K:      # the same call as the training path with scale 0; `rbin` (T,B): the target's bin, not per IWAE sample
-                rbin = torch.empty(T, B, dtype=torch.int32, device=dev)
-                H.call('dm_head_loss_catsup', N, I, K, H.fptr(mu), K, H.fptr(dec.reward._support), H.fptr(reward_tb), 0.0,
-                       H.fptr(lr), None, H.fptr(rp), H.ptr(rbin), H.stream())
-            else:
-                H.call('dm_head_loss', 0, N, H.fptr(mu), H.fptr(reward_t), 0.0, NORMAL_LOSS_CONST, H.fptr(lr),
-                       H.fptr(scratch), H.fptr(rp), H.stream())
-            H.call('dm_head_loss', 1, N, H.fptr(tl), H.fptr(terminal_t), 0.0, 0.0, H.fptr(lt),
-                   H.fptr(scratch), H.fptr(tp), H.stream())
-            if I > 1:                              # TBI => TB
-                red = torch.empty(5, NE, device=dev)
-                for j, (x, mode) in enumerate(((li, 1), (lr, 1), (lt, 1), (rp, 0), (tp, 0))):
-                    if x is not None:
-                        H.call('dm_reduce_i', NE, I, 1, H.fptr(x), mode, H.fptr(red[j]), None, H.stream())
-                li, lr, lt, rp, tp = (None if li is None and j == 0 else red[j] for j in range(5))
-                if image_pred is not None:
-                    image_pred = image_pred.mean(2)                           # decoded.mean(dim=2), decoders.py:171
-            elif image_pred is not None:
-                image_pred = image_pred[:, :, 0]
-            tb = lambda x: x.view(T, B)
-            if li is None:
-                tensors = dict(logprob_reward=tb(lr), logprob_terminal=tb(lt), reward_pred=tb(rp), terminal_pred=tb(tp))
-                metrics = dict(logprob_reward=lr.mean(), logprob_terminal=lt.mean())
-            else:
-                tensors = dict(logprob_image=tb(li), logprob_reward=tb(lr), logprob_terminal=tb(lt),
-                               image_pred=image_pred, reward_pred=tb(rp), terminal_pred=tb(tp))
-                metrics = dict(logprob_image=li.mean(), logprob_reward=lr.mean(), logprob_terminal=lt.mean())
-            if V:
-                tensors.update(logprob_vecobs=tb(lv), vecobs_pred=vp.view(T, B, V))
-                metrics.update(logprob_vecobs=lv.mean())
-            nan = torch.full((), float('nan'), device=dev)
-            nanmean = lambda x: torch.nansum(x) / (~torch.isnan(x)).sum()     # functions.py:149-150
-            if K:      # decoders.py:86-94: one entry per support bucket, indexed by bucket; a bucket nobody hit is 0 / 0 = NaN
-                for i in range(K):
-                    lp = torch.where(rbin == i, tb(lr), nan)
-                    metrics[f'logprob_reward{i}'], tensors[f'logprob_reward{i}'] = nanmean(lp), lp
-            else:
-                for sig in (-1, 1):
-                    lp = torch.where(torch.sign(obs['reward'].float()) == sig, tb(lr), nan)
-                    metrics[f'logprob_reward{sig}'], tensors[f'logprob_reward{sig}'] = nanmean(lp), lp
-            lp = torch.where(obs['terminal'].float() > 0, tb(lt), nan)
-            metrics['logprob_terminal1'], tensors['logprob_terminal1'] = nanmean(lp), lp
+            metrics, tensors = dec.predict(pk, fp, obs, ws)
         return metrics, tensors, idx
 
     def training_step(self, obs, in_state, iwae_samples=1, do_open_loop=False, do_image_pred=False, forward_only=False,
@@ -2445,16 +2450,14 @@ class Dreamer(nn.Module):
                H.fptr(u_act), H.fptr(u_prior), H.fptr(feats), H.fptr(actions), H.ptr(act_idx),
                H.fptr(a_acts), H.fptr(a_logits), H.ptr(ws), ws.numel(), H.stream())
         f2 = feats.view(rows, F_)
-        Zc = c.stoch_dim * c.stoch_discrete            # the sampled one-hot latent columns of a feature row
-        Kr = self.wm.decoder.reward_bins      # categorical reward head: `mu` holds (rows, K) logits, decoded behind the windows
-        mu, tl = torch.empty(rows, Kr or 1, device=dev), torch.empty(rows, 1, device=dev)
+        dec = self.wm.decoder
+        outs = dec.dream_buffers(rows, dev)
         values = self.ac.value_buffers(rows, dev) if _pack is not None else None
 
         def heads(a, b, wsx):
             if b <= a:
                 return
-            self.wm.decoder.reward.model.fwd(f2, F_, b - a, wsx, save_acts=False, sparse_cols=Zc, window=(rows, a), out=mu)
-            self.wm.decoder.terminal.model.fwd(f2, F_, b - a, wsx, save_acts=False, sparse_cols=Zc, window=(rows, a), out=tl)
+            dec.dream_fwd(f2, a, b - a, wsx, outs)
             if values is not None:
                 self.ac.forward_values(f2, F_, rows, a, b - a, wsx, values)
         if use_early:
@@ -2467,12 +2470,7 @@ class Dreamer(nn.Module):
         else:
             heads(0, r_split, ws)
             heads(r_split, rows, ws)
-        term = torch.empty(rows, device=dev)
-        H.call('dm_head_loss', 1, rows, H.fptr(tl), None, 0.0, 0.0, None, None, H.fptr(term), H.stream())
-        if Kr:      # dreamer.py:212: only `.mean` of the decoded distribution is ever read - the mean-only form, one launch over all rows
-            logits, mu = mu, torch.empty(rows, device=dev)
-            H.call('dm_head_loss_catsup', rows, 1, Kr, H.fptr(logits), Kr, H.fptr(self.wm.decoder.reward._support), None, 0.0,
-                   None, None, H.fptr(mu), None, H.stream())
+        term, mu = dec.dream_means(outs)      # the mean-only form of either head, one launch over all rows behind the windows
         if _pack is not None:
             _pack.update(act_idx=act_idx, ws=ws, actor_acts=a_acts, actor_logits=a_logits, values=values)
         return feats, actions, _Mean(mu.view(Hh + 1, M)), _Mean(term.view(Hh + 1, M))
@@ -2578,9 +2576,7 @@ class Dreamer(nn.Module):
         if I == 1:
             tensors.update(policy_value=tensors_ac['value'][0].view(T, B))
         else:                        # unflatten_batch(value[0], (T,B,I)).mean(-1), dreamer.py:159
-            pv = torch.empty(T, B, device=pk['feat'].device)
-            H.call('dm_reduce_i', T * B, I, 1, H.fptr(tensors_ac['value'][0].contiguous()), 0, H.fptr(pv), None, H.stream())
-            tensors.update(policy_value=pv)
+            tensors.update(policy_value=_reduce_i(tensors_ac['value'][0].contiguous().view(-1), T * B, I, 0).view(T, B))
         # Diagnostics for tests / debugging (not part of the reference API).  The index tensors are copies; `actions`,
         # `dream_features`, `post` and `prior` are the step's own buffers.
         self.last_extras = dict(post_idx=pk['idx'].view(T, B * I, -1).clone(), act_idx=dpk['act_idx'].clone(),
