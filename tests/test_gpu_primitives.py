@@ -4,11 +4,16 @@ Tolerances are stated per test; integer outputs (sampled indices) are compared e
 uniform lies within 1e-5 of a CDF boundary (softmax is not bit-reproducible across exp implementations).
 """
 import ctypes
+import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))      # tests/gemm_pin.py
+import gemm_pin as GP                                # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -35,19 +40,39 @@ def _close(a, b, rtol, atol, what=''):
 
 
 # ------------------------------------------------------------------------------------------- GEMM
+# Every direct GEMM test below names the kernel it expects, ('loop', 'tile', split count) or GP.SKINNY, and asserts it from the
+# per-launch profiler row (tests/gemm_pin.py): which kernel answers depends on the shape alone, and a cost-model change that
+# re-routes a case must show here.  The values are what the MI355X reported.  tests/test_gpu_gemm_menu.py covers the tile
+# menu cell by cell; these tables reach the skinny kernel and the 64x64 tile, plus the few big-tile cases marked below.
+def _pin(hip, al, bl, M, N, K, expected, fn, what):
+    got = GP.pinned(hip, fn, M, N, K)
+    print(f'{what} {al}{bl} {M}x{N}x{K}: {got}')
+    assert got == GP.cell(al, bl, expected), f'{what} {al}{bl} {M}x{N}x{K}: {got} answered, the table names {expected}'
+
+
+def _ids(cases, n):
+    """test ids from the first n (integer) fields of each case: the expected kernels stay out of the id"""
+    return ['-'.join(str(x) for x in c[:n]) for c in cases]
+
+
+R64, D64 = ('regstaged', '64x64', 1), ('dma', '64x64', 1)
 GEMM_CASES = [
-    # (al, bl, M, N, K)
-    (0, 0, 50, 1000, 1024), (0, 0, 50, 1800, 600), (0, 0, 2500, 400, 1624), (0, 0, 4097, 130, 70),
-    (0, 0, 7, 1, 400), (0, 0, 33, 18, 18), (0, 0, 3000, 1536, 96),
-    (0, 1, 50, 1024, 1000), (0, 1, 2500, 1624, 400), (0, 1, 129, 67, 33), (0, 1, 40000, 400, 1),
-    (1, 1, 400, 1624, 2500), (1, 1, 48, 48, 30000), (1, 1, 1000, 18, 250), (1, 1, 65, 131, 259), (1, 1, 1, 400, 5000),
-    (1, 0, 100, 90, 80),
+    # (al, bl, M, N, K, kernel); 4097x130x70, 33x18x18, 129x67x33, 40000x400x1, 1000x18x250, 65x131x259 and 1x400x5000 have no
+    # 16-byte loads: the scalar-load 64x64 kernel
+    (0, 0, 50, 1000, 1024, GP.SKINNY), (0, 0, 50, 1800, 600, GP.SKINNY), (0, 0, 2500, 400, 1624, ('dma', '64x64', 2)),
+    (0, 0, 4097, 130, 70, R64), (0, 0, 7, 1, 400, ('regstaged', '64x64', 5)), (0, 0, 33, 18, 18, R64), (0, 0, 3000, 1536, 96, R64),
+    (0, 1, 50, 1024, 1000, GP.SKINNY), (0, 1, 2500, 1624, 400, R64), (0, 1, 129, 67, 33, R64), (0, 1, 40000, 400, 1, R64),
+    (1, 1, 400, 1624, 2500, ('dma', '64x64', 3)), (1, 1, 48, 48, 30000, ('regstaged', '64x64', 469)),
+    (1, 1, 1000, 18, 250, ('regstaged', '64x64', 4)), (1, 1, 65, 131, 259, ('regstaged', '64x64', 2)),
+    (1, 1, 1, 400, 5000, ('regstaged', '64x64', 53)),
+    (1, 0, 100, 90, 80, R64),
 ]
 
 
-@pytest.mark.parametrize('al,bl,M,N,K', GEMM_CASES)
-def test_gemm_layouts(hip, al, bl, M, N, K):
-    """C = A(m,k) B(n,k) for every operand layout, ragged sizes, split-K; asymmetric random operands.
+@pytest.mark.parametrize('al,bl,M,N,K,kernel', GEMM_CASES, ids=_ids(GEMM_CASES, 5))
+def test_gemm_layouts(hip, al, bl, M, N, K, kernel):
+    """C = A(m,k) B(n,k) for every operand layout, ragged sizes, split-K; asymmetric random operands.  The three 50-row cases
+    run the skinny kernel, every other case the 64x64 tile (16-byte-load, scalar-load, register-staged and LDS-DMA loop).
     Tolerance: fp32 fmaf-chain vs fp64 reference, 2e-6*sqrt(K)*|a||b| scale."""
     A = _rand(M, K, seed=1)
     B = _rand(N, K, seed=2)
@@ -55,15 +80,25 @@ def test_gemm_layouts(hip, al, bl, M, N, K):
     Bd = B if bl == 0 else B.t().contiguous()
     C = torch.full((M, N), float('nan'), device=DEV)
     ws = _ws()
-    hip.call('dm_gemm_f32', al, bl, M, N, K, hip.fptr(Ad), Ad.shape[1], hip.fptr(Bd), Bd.shape[1], hip.fptr(C), N,
-             None, None, 0, 0, hip.ptr(ws), ws.numel(), hip.stream())
+    _pin(hip, al, bl, M, N, K, kernel, lambda: hip.call(
+        'dm_gemm_f32', al, bl, M, N, K, hip.fptr(Ad), Ad.shape[1], hip.fptr(Bd), Bd.shape[1], hip.fptr(C), N,
+        None, None, 0, 0, hip.ptr(ws), ws.numel(), hip.stream()), 'gemm')
     ref = A.double() @ B.double().t()
+    assert bool(torch.isfinite(C).all()), 'part of C was left unwritten (NaN)'      # (_close lets a NaN pass: nan > tol is False)
     _close(C, ref, 0, 3e-6 * np.sqrt(K) * 4, f'gemm {al}{bl} {M}x{N}x{K}')
 
 
-@pytest.mark.parametrize('al,bl,M,N,K', [(0, 0, 300, 200, 160), (0, 1, 257, 96, 100), (1, 0, 132, 131, 64),
-                                          (1, 1, 96, 260, 4000), (0, 0, 2500, 400, 1624), (1, 1, 400, 400, 40000)])
-def test_gemm_bf16_operands(hip, al, bl, M, N, K):
+BF16_OPERAND_CASES = [
+    # (al, bl, M, N, K, kernel under DM_GEMM_BF16, kernel of the fp32 call that follows)
+    (0, 0, 300, 200, 160, ('bf16', '64x64', 1), R64), (0, 1, 257, 96, 100, ('bf16', '64x64', 1), R64),
+    (1, 0, 132, 131, 64, ('bf16', '64x64', 1), R64), (1, 1, 96, 260, 4000, ('bf16', '64x64', 25), ('regstaged', '64x64', 25)),
+    (0, 0, 2500, 400, 1624, ('bf16', '64x64', 2), ('dma', '64x64', 2)),
+    (1, 1, 400, 400, 40000, ('bf16', '128x64', 36), ('dma', '64x64', 26)),
+]
+
+
+@pytest.mark.parametrize('al,bl,M,N,K,kernel,kernel32', BF16_OPERAND_CASES, ids=_ids(BF16_OPERAND_CASES, 5))
+def test_gemm_bf16_operands(hip, al, bl, M, N, K, kernel, kernel32):
     """DM_GEMM_BF16 (a per-call flag): operands rounded to bf16 (RNE), fp32 accumulation.  Reference = the same product of the
     bf16-ROUNDED operands in fp64, so the only difference left is fp32 summation order: same tolerance as the fp32 test.
     Every operand layout (the row-contiguous ones are transposed into the [row][k] LDS image), ragged edges, split-K."""
@@ -73,11 +108,13 @@ def test_gemm_bf16_operands(hip, al, bl, M, N, K):
     Bd = B if bl == 0 else B.t().contiguous()
     C = torch.full((M, N), float('nan'), device=DEV)
     ws = _ws()
-    hip.call('dm_gemm_f32', al, bl, M, N, K, hip.fptr(Ad), Ad.shape[1], hip.fptr(Bd), Bd.shape[1], hip.fptr(C), N,
-             None, None, 0, hip.DM_GEMM_BF16, hip.ptr(ws), ws.numel(), hip.stream())
+    _pin(hip, al, bl, M, N, K, kernel, lambda: hip.call(
+        'dm_gemm_f32', al, bl, M, N, K, hip.fptr(Ad), Ad.shape[1], hip.fptr(Bd), Bd.shape[1], hip.fptr(C), N,
+        None, None, 0, hip.DM_GEMM_BF16, hip.ptr(ws), ws.numel(), hip.stream()), 'bf16 gemm')
     C32 = torch.empty_like(C)      # the next call, without the flag, is an fp32 product again: nothing sticks
-    hip.call('dm_gemm_f32', al, bl, M, N, K, hip.fptr(Ad), Ad.shape[1], hip.fptr(Bd), Bd.shape[1], hip.fptr(C32), N,
-             None, None, 0, 0, hip.ptr(ws), ws.numel(), hip.stream())
+    _pin(hip, al, bl, M, N, K, kernel32, lambda: hip.call(
+        'dm_gemm_f32', al, bl, M, N, K, hip.fptr(Ad), Ad.shape[1], hip.fptr(Bd), Bd.shape[1], hip.fptr(C32), N,
+        None, None, 0, 0, hip.ptr(ws), ws.numel(), hip.stream()), 'fp32 gemm after a bf16 one')
     torch.cuda.synchronize()
     _close(C32, A.double() @ B.double().t(), 0, 3e-6 * np.sqrt(K) * 4, f'fp32 gemm after a bf16 one {al}{bl} {M}x{N}x{K}')
     ref = A.bfloat16().double() @ B.bfloat16().double().t()
@@ -87,9 +124,16 @@ def test_gemm_bf16_operands(hip, al, bl, M, N, K):
     assert (C.double().cpu() - full.cpu()).abs().max() > 1e-4
 
 
-@pytest.mark.parametrize('al,bl,M,N,K', [(0, 0, 300, 200, 136), (0, 0, 2500, 1800, 1000), (0, 1, 257, 96, 72), (1, 0, 128, 333, 200),
-                                         (1, 1, 96, 768, 4999), (1, 1, 400, 1624, 2500), (0, 0, 70, 40, 8), (0, 0, 4096, 1024, 4096)])
-def test_gemm_bf16_storage(hip, al, bl, M, N, K):
+BF16_STORAGE_CASES = [
+    (0, 0, 300, 200, 136, ('bf16store', '64x64', 1)), (0, 0, 2500, 1800, 1000, ('bf16store', '64x64', 1)),
+    (0, 1, 257, 96, 72, ('bf16store', '64x64', 1)), (1, 0, 128, 333, 200, ('bf16store', '64x64', 1)),
+    (1, 1, 96, 768, 4999, ('bf16store', '64x64', 27)), (1, 1, 400, 1624, 2500, ('bf16store', '64x64', 3)),
+    (0, 0, 70, 40, 8, ('bf16store', '64x64', 1)), (0, 0, 4096, 1024, 4096, ('bf16store', '128x128', 2)),
+]
+
+
+@pytest.mark.parametrize('al,bl,M,N,K,kernel', BF16_STORAGE_CASES, ids=_ids(BF16_STORAGE_CASES, 5))
+def test_gemm_bf16_storage(hip, al, bl, M, N, K, kernel):
     """dm_gemm_bf16h: operands STORED as bf16 (64-k tiles, 16-byte chunks), fp32 accumulation; reference = fp64 product of the
     same bf16 values; the optional bf16 twin of the result is exactly RNE(C).  Ragged M / N / K, every layout pair."""
     g = torch.Generator().manual_seed(11)
@@ -99,26 +143,40 @@ def test_gemm_bf16_storage(hip, al, bl, M, N, K):
     C = torch.empty(M, N, device=DEV)
     Ch = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
     ws = torch.empty(64 << 20, dtype=torch.uint8, device=DEV)
-    hip.call('dm_gemm_bf16h', al, bl, M, N, K, hip.ptr(A), A.shape[1], hip.ptr(B), B.shape[1], hip.fptr(C), N, hip.ptr(Ch),
-             hip.fptr(bias), 0, hip.ptr(ws), ws.numel(), hip.stream())
+    _pin(hip, al, bl, M, N, K, kernel, lambda: hip.call(
+        'dm_gemm_bf16h', al, bl, M, N, K, hip.ptr(A), A.shape[1], hip.ptr(B), B.shape[1], hip.fptr(C), N, hip.ptr(Ch),
+        hip.fptr(bias), 0, hip.ptr(ws), ws.numel(), hip.stream()), 'bf16-storage gemm')
     ref = (A.double() if al == 0 else A.double().t()) @ (B.double() if bl == 0 else B.double().t()).t() + bias.double()
     _close(C, ref, 0, 3e-6 * np.sqrt(K) * 4, f'bf16-storage gemm {al}{bl} {M}x{N}x{K}')
     assert torch.equal(Ch, C.bfloat16())
 
 
+def _both(tile, splits):
+    return ('dma', tile, splits), ('regstaged', tile, splits)
+
+
 DMA_CASES = [
-    # (al, bl, M, N, K, flags): 16-byte-load shapes on every tile of the menu (64x64, 128x64, 128x128, 128x96, 96x128), ragged
-    # edges in M / N / K, split-K weight-gradient shapes, a single k-tile, fewer k-tiles than LDS stages
-    (0, 0, 2500, 1800, 1000, 0), (0, 0, 2500, 1000, 600, 2), (0, 0, 4096, 4096, 512, 0), (0, 0, 40000, 400, 400, 3),
-    (0, 0, 3000, 192, 864, 0), (0, 0, 300, 200, 160, 0), (0, 0, 70, 40, 8, 0), (0, 0, 129, 67, 36, 1), (0, 0, 5, 3, 4, 0),
-    (0, 1, 2500, 1624, 400, 0), (0, 1, 2500, 4800, 1536, 0), (0, 1, 4096, 2048, 300, 2), (0, 1, 257, 96, 100, 0), (0, 1, 131, 8, 33, 0),
-    (1, 1, 400, 1624, 2500, 0), (1, 1, 96, 1728, 42250, 0), (1, 1, 1536, 4800, 2500, 0), (1, 1, 48, 48, 30000, 0), (1, 1, 64, 132, 259, 1),
-    (1, 1, 4, 400, 5000, 0), (1, 0, 100, 92, 80, 0), (1, 0, 2048, 1024, 777 * 4, 0),
+    # (al, bl, M, N, K, flags, kernel with the LDS-DMA loop forced, kernel with it off): 16-byte-load shapes, ragged edges in
+    # M / N / K, split-K weight-gradient shapes, a single k-tile, fewer k-tiles than LDS stages.  Most run the 64x64 tile; 128x64
+    # is reached twice (layouts (0,0) and (0,1)), 128x128 and 96x128 once each at layout (1,1), 128x96 never (3000x192x864 takes
+    # 64x64 with two splits).  2500x4800x1536 takes 128x128 with the loop off and 64x64 with it on (the cost model steers a
+    # row-contiguous B off 128x128 then) and is bit-identical all the same; 131x8x33 has no 16-byte loads (scalar-load kernel
+    # both times).  tests/test_gpu_gemm_menu.py covers the menu cell by cell.
+    (0, 0, 2500, 1800, 1000, 0, *_both('64x64', 1)), (0, 0, 2500, 1000, 600, 2, *_both('64x64', 1)),
+    (0, 0, 4096, 4096, 512, 0, *_both('128x64', 1)), (0, 0, 40000, 400, 400, 3, *_both('64x64', 1)),
+    (0, 0, 3000, 192, 864, 0, *_both('64x64', 2)), (0, 0, 300, 200, 160, 0, *_both('64x64', 1)), (0, 0, 70, 40, 8, 0, *_both('64x64', 1)),
+    (0, 0, 129, 67, 36, 1, *_both('64x64', 1)), (0, 0, 5, 3, 4, 0, *_both('64x64', 1)),
+    (0, 1, 2500, 1624, 400, 0, *_both('64x64', 1)), (0, 1, 2500, 4800, 1536, 0, D64, ('regstaged', '128x128', 1)),
+    (0, 1, 4096, 2048, 300, 2, *_both('128x64', 1)), (0, 1, 257, 96, 100, 0, *_both('64x64', 1)), (0, 1, 131, 8, 33, 0, R64, R64),
+    (1, 1, 400, 1624, 2500, 0, *_both('64x64', 3)), (1, 1, 96, 1728, 42250, 0, *_both('96x128', 36)),
+    (1, 1, 1536, 4800, 2500, 0, *_both('128x128', 1)), (1, 1, 48, 48, 30000, 0, *_both('64x64', 469)),
+    (1, 1, 64, 132, 259, 1, *_both('64x64', 3)), (1, 1, 4, 400, 5000, 0, *_both('64x64', 53)), (1, 0, 100, 92, 80, 0, *_both('64x64', 1)),
+    (1, 0, 2048, 1024, 777 * 4, 0, *_both('64x64', 2)),
 ]
 
 
-@pytest.mark.parametrize('al,bl,M,N,K,flags', DMA_CASES)
-def test_gemm_dma_equals_register_staged_loop(hip, al, bl, M, N, K, flags):
+@pytest.mark.parametrize('al,bl,M,N,K,flags,kernel_dma,kernel_reg', DMA_CASES, ids=_ids(DMA_CASES, 6))
+def test_gemm_dma_equals_register_staged_loop(hip, al, bl, M, N, K, flags, kernel_dma, kernel_reg):
     """gemm_dma_kernel (LDS-DMA operand pipeline, round 5) against gemm_f32_kernel (register-staged loop) on the same call:
     same tiles, same k -> MFMA-step map, same epilogue => BIT-IDENTICAL results (torch.equal), with and without the bias /
     addend / accumulate / ELU epilogue; and both against the fp64 product."""
@@ -135,9 +193,10 @@ def test_gemm_dma_equals_register_staged_loop(hip, al, bl, M, N, K, flags):
         for on in (2, 0):      # 2: the LDS-DMA loop for every k extent (by default it serves products of >= 14 k-tiles)
             assert hip.lib().dm_gemm_dma_enable(on) == on
             C = C0.clone()
-            hip.call('dm_gemm_f32', al, bl, M, N, K, hip.fptr(Ad), Ad.shape[1], hip.fptr(Bd), Bd.shape[1], hip.fptr(C), N,
-                     hip.fptr(bias) if bias is not None else None, hip.fptr(add) if add is not None else None, N, flags,
-                     hip.ptr(ws), ws.numel(), hip.stream())
+            _pin(hip, al, bl, M, N, K, kernel_dma if on else kernel_reg, lambda: hip.call(
+                'dm_gemm_f32', al, bl, M, N, K, hip.fptr(Ad), Ad.shape[1], hip.fptr(Bd), Bd.shape[1], hip.fptr(C), N,
+                hip.fptr(bias) if bias is not None else None, hip.fptr(add) if add is not None else None, N, flags,
+                hip.ptr(ws), ws.numel(), hip.stream()), f'switch {on}')
             torch.cuda.synchronize()
             outs.append(C)
     finally:
@@ -156,7 +215,8 @@ def test_gemm_dma_equals_register_staged_loop(hip, al, bl, M, N, K, flags):
 
 
 def test_gemm_epilogue_and_strides(hip):
-    """bias + addend + accumulate + ELU, with sub-matrix leading dimensions (feature-matrix slices)."""
+    """bias + addend + accumulate + ELU, with sub-matrix leading dimensions (feature-matrix slices).  N * K = 20 000 is under the
+    skinny kernel's floor: the register-staged 64x64 tile (the skinny kernel's epilogue: test_gpu_gemm_menu.py)."""
     M, N, K, ldc, lda = 70, 200, 100, 264, 164
     Abig = _rand(M, lda, seed=3)
     A = Abig[:, 60:60 + K]                      # offset view: base aligned (60*4 bytes = 240 = 16*15)
@@ -168,8 +228,9 @@ def test_gemm_epilogue_and_strides(hip):
     ws = _ws()
     a_ptr = ctypes.c_void_p(Abig.data_ptr() + 60 * 4)
     c_ptr = ctypes.c_void_p(Cbig.data_ptr() + 64 * 4)
-    hip.call('dm_gemm_f32', 0, 0, M, N, K, a_ptr, lda, hip.fptr(B), K, c_ptr, ldc, hip.fptr(bias), hip.fptr(add), N + 8,
-             hip.DM_GEMM_ACCUM | hip.DM_GEMM_ELU, hip.ptr(ws), ws.numel(), hip.stream())
+    _pin(hip, 0, 0, M, N, K, R64, lambda: hip.call(
+        'dm_gemm_f32', 0, 0, M, N, K, a_ptr, lda, hip.fptr(B), K, c_ptr, ldc, hip.fptr(bias), hip.fptr(add), N + 8,
+        hip.DM_GEMM_ACCUM | hip.DM_GEMM_ELU, hip.ptr(ws), ws.numel(), hip.stream()), 'gemm epilogue')
     ref = F.elu(A.double() @ B.double().t() + bias.double() + add[:, :N].double() + C0[:, 64:64 + N].double())
     _close(Cbig[:, 64:64 + N], ref, 1e-5, 1e-4, 'gemm epilogue')
     # untouched columns stay untouched
@@ -182,22 +243,25 @@ def test_gemm_unaligned_k(hip):
     A, B = _rand(M, K, seed=8), _rand(N, K, seed=9)
     C = torch.empty(M, N, device=DEV)
     ws = _ws()
-    hip.call('dm_gemm_f32', 0, 0, M, N, K, hip.fptr(A), K, hip.fptr(B), K, hip.fptr(C), N, None, None, 0, 0, hip.ptr(ws),
-             ws.numel(), hip.stream())
+    _pin(hip, 0, 0, M, N, K, R64, lambda: hip.call(
+        'dm_gemm_f32', 0, 0, M, N, K, hip.fptr(A), K, hip.fptr(B), K, hip.fptr(C), N, None, None, 0, 0, hip.ptr(ws),
+        ws.numel(), hip.stream()), 'gemm K=18')
     _close(C, A.double() @ B.double().t(), 0, 2e-5, 'gemm K=18')
 
 
 def test_gemm_onehot_rows_exact(hip):
     """One-hot A rows (straight-through samples): result must equal the ordered sum of the selected weight columns
-    bit-for-bit (fmaf chain with exact zeros), SURVEY section 0.8."""
+    bit-for-bit (fmaf chain with exact zeros), SURVEY section 0.8.  50 rows: the skinny kernel (the tiled loops get one-hot
+    rows in test_gpu_gemm_menu.py)."""
     M, S, C, N = 50, 32, 32, 1000
     g = torch.Generator().manual_seed(10)
     idx = torch.randint(0, C, (M, S), generator=g)
     A = F.one_hot(idx, C).float().reshape(M, S * C).to(DEV)
     W = _rand(N, S * C, seed=11)
     out = torch.empty(M, N, device=DEV)
-    hip.call('dm_gemm_f32', 0, 0, M, N, S * C, hip.fptr(A), S * C, hip.fptr(W), S * C, hip.fptr(out), N, None, None, 0, 0,
-             None, 0, hip.stream())
+    _pin(hip, 0, 0, M, N, S * C, GP.SKINNY, lambda: hip.call(
+        'dm_gemm_f32', 0, 0, M, N, S * C, hip.fptr(A), S * C, hip.fptr(W), S * C, hip.fptr(out), N, None, None, 0, 0,
+        None, 0, hip.stream()), 'one-hot gemm')
     cols = (idx + torch.arange(S) * C).to(DEV)          # (M,S) selected columns, ascending in k
     ref = torch.zeros(M, N, device=DEV)
     for s in range(S):
