@@ -660,7 +660,8 @@ int dm_multi_tensor_norm_clip(const float* grad, int64_t n, float max_norm, floa
                               void* ws, size_t ws_bytes, void* stream);
 /* x *= coef[0] (device scalar): the in-place gradient scaling of clip_grad_norm_. */
 int dm_scale_inplace(float* x, int64_t n, const float* coef, void* stream);
-/* AdamW step with the clip coefficient read from device memory (clip_coef may be NULL = 1). */
+/* AdamW step with the clip coefficient read from device memory (clip_coef may be NULL = 1): the same bits as
+ * dm_scale_inplace(grad, n, clip_coef) followed by the NULL form. */
 int dm_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                   float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                   const float* clip_coef, void* stream);

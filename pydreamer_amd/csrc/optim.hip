@@ -81,7 +81,13 @@ __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, const
                                                     const float* __restrict__ clip_coef) {
   const float c = clip_coef ? clip_coef[0] : 1.0f;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const float gi = g[i] * c;
+    // the scaled gradient is rounded on its own, as dm_scale_inplace rounds it: left to contract, g * c - m became one fma and
+    // the pointer form differed in the last bit from scaling first (with c == 1 both give the same bits either way)
+    float gi;
+    {
+#pragma clang fp contract(off)
+      gi = g[i] * c;
+    }
     float pi = p[i] * decay;
     float mi = m[i];
     mi = mi + (gi - mi) * one_minus_b1;
