@@ -99,7 +99,8 @@ int dm_version(void);                 /* ABI version, currently 16 (v2: LayerNor
                                               dm_policy_draw_ws_floats of the acting path; dm_policy_draw_mode of the
                                               collection loop; dm_metric_accum / dm_batch_stats / dm_masked_mean /
                                               dm_export_image_u8 of the trainer loop's device-side logging;
-                                              dm_head_loss_catsup of the categorical reward decoder */
+                                              dm_head_loss_catsup of the categorical reward decoder; dm_disag_reward /
+                                              dm_ensemble_mse of Plan2Explore */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
 size_t dm_workspace_bytes(const dm_shape* shp);   /* scratch needed by any call below for this shape */
@@ -345,6 +346,29 @@ int dm_head_loss_normal_nd(int rows, int V, const float* out, const float* targe
  * DM_E_NULL; rows == 0 -> DM_OK with nothing launched. */
 int dm_head_loss_catsup(int rows, int I, int K, const float* logits, int ld, const float* support, const float* target, float scale,
                         float* loss, float* dlogits, float* mean_out, int32_t* bin, void* stream);
+
+/* Plan2Explore's disagreement ensemble (csrc/disag.hip; DreamerV2 expl.py - the reference has no counterpart): K one-step
+ * predictors of the next stochastic state.  means is K blocks of (rows, D) with leading dimension ld >= D, block k starting
+ * k * head_stride floats behind block 0; dmeans, where given, has the same layout.  fp32 arithmetic whatever the precision of
+ * the products around them; one launch each; no float atomics and every sum in a fixed order (the same inputs give the same
+ * bits); 16-byte accesses where a row's addresses allow them, else one float per lane.
+ * The intrinsic reward, the heads' population standard deviation (ddof 0, expl.py's std(0)) averaged over the columns:
+ *   reward[r] = scale * (1/D) * sum_d sqrt((1/K) * sum_k (x_k - mu)^2),  x_k = m_k[r][d] - m_0[r][d],  mu = (sum_k x_k) / K,
+ * k ascending.  The shift by head 0 keeps only the heads' spread in the sums (no cancellation against a large common
+ * value) and makes K identical heads give exactly 0.0f.  One wave per row: lane l adds its columns l, l + 64, ... in ascending
+ * order, the 64 partial sums meet in an xor butterfly.  reward is dense, rows floats.
+ * Checked on the host before anything is launched: K outside 2 .. 16, rows < 0, D < 1, ld < D or head_stride < 0 -> DM_E_SHAPE;
+ * NULL means or reward -> DM_E_NULL; rows == 0 -> DM_OK with nothing launched. */
+int dm_disag_reward(int K, int rows, int D, const float* means, int64_t head_stride, int ld, float scale, float* reward,
+                    void* stream);
+/* The heads' training loss against one target row each, -log Normal(y; m_k, 1) up to its constant:
+ *   loss[k][r] = 0.5 * sum_d (m_k[r][d] - y[r][d])^2 (dense, K * rows floats);  dmeans = scale * (m_k - y), optional.
+ * target (rows, D) with leading dimension ldt >= D: read in place out of a wider matrix (the feature rows' stochastic part).
+ * skip (rows) uint8 or NULL: a row with skip[r] != 0 gets loss 0 and a zero dmeans row, and neither its means nor its target
+ * are read.  One wave per (head, row).  Checked on the host as above, and ldt < D -> DM_E_SHAPE, NULL means, target or loss ->
+ * DM_E_NULL. */
+int dm_ensemble_mse(int K, int rows, int D, const float* means, int64_t head_stride, int ld, const float* target, int ldt,
+                    const uint8_t* skip, float scale, float* loss, float* dmeans, void* stream);
 
 /* Per-cell categorical losses over a (C, H, W) logit block (csrc/cat_image.hip): the map probe's CatImageDecoder
  * (decoders.py:183-254, probes.py:32-86).  A logit row is class-major as nn.Unflatten(-1, (C,H,W)) lays it out: class c of

@@ -37,6 +37,10 @@ SECTIONS = {
         generator_prefill_steps=50_000, limit_step_ratio=0, env_action_repeat=1,
         # the environment wrappers (envs.wrap_envs; defaults.yaml:119-120)
         env_time_limit=0, env_no_terminal=False,
+        # Plan2Explore (explore.py; DreamerV2's expl_behavior / disag_* / expl_* keys - no reference counterpart).  Inert unless
+        # expl_behavior='plan2explore'; expl_until counts collected environment steps, 0 = explore for the whole run
+        expl_behavior='greedy', disag_models=10, disag_action_cond=True, expl_intr_scale=1.0, expl_extr_scale=0.0, expl_until=0,
+        adam_lr_expl=3.0e-4,
     ),
     'atari': dict(action_dim=18, clip_rewards='tanh', deter_dim=1024, kl_weight=0.1, gamma=0.99, entropy=0.001),
     'dmc': dict(action_dim=12, entropy=1.0e-4, actor_grad='dynamics', actor_dist='tanh_normal', clip_rewards='tanh'),

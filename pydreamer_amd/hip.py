@@ -165,6 +165,8 @@ _SIGNATURES = {
     'dm_head_loss': (c_int, [c_int, c_int, _P, _P, c_float, c_float, _P, _P, _P, _P]),
     'dm_head_loss_normal_nd': (c_int, [c_int, c_int, _P, _P, c_float, c_float, _P, _P, _P, _P]),
     'dm_head_loss_catsup': (c_int, [c_int, c_int, c_int, _P, c_int, _P, _P, c_float, _P, _P, _P, _P, _P]),
+    'dm_disag_reward': (c_int, [c_int, c_int, c_int, _P, c_int64, c_int, c_float, _P, _P]),
+    'dm_ensemble_mse': (c_int, [c_int, c_int, c_int, _P, c_int64, c_int, _P, c_int, _P, c_float, _P, _P, _P]),
     'dm_cat_target_index': (c_int, [c_int, c_int, c_int, _P, _P, _P]),
     'dm_cat_image_loss': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P]),
     'dm_cat_image_pred': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P, _P]),

@@ -2322,7 +2322,7 @@ class Dreamer(nn.Module):
         return action_distr, out_state, dict(policy_value=value.mean())
 
     # ---- acting (generator.py:311-331 for B environments)
-    def act(self, obs, in_state, noise=None, return_rows=False, mode='sample', action_noise=0.0):
+    def act(self, obs, in_state, noise=None, return_rows=False, mode='sample', action_noise=0.0, ac=None):
         """inference() followed, on the device, by what the reference's NetworkPolicy does with the distribution object: the draw,
         log_prob(action).exp().mean(), entropy().mean() and policy_value - one dm_policy_draw call behind the actor and critic MLPs,
         no torch op after them and no host synchronisation.  Returns (action (1,B,A) float32, out_state, metrics): metrics =
@@ -2336,11 +2336,14 @@ class Dreamer(nn.Module):
         mode='mode' (evaluation): the distribution's mode instead of a draw - the lowest argmax class, or the base
         Normal's mean through the transform; u_act is not used.  action_noise > 0 (with mode='sample' only): DreamerV2's exploration
         noise on the drawn action through dm_policy_draw_mode's mode 2 - `noise` may carry u_expl, (B,2) uniforms for the one-hot
-        actor or (B,A) standard normals for the continuous ones; log_prob stays the policy's.  The defaults are dm_policy_draw."""
+        actor or (B,A) standard normals for the continuous ones; log_prob stays the policy's.  The defaults are dm_policy_draw.
+        ac: the actor-critic whose actor, critic and distribution kind act (explore.Plan2Explore's exploration policy) behind the
+        world model's encoder and posterior step; None: the task one."""
+        ac = self.ac if ac is None else ac
         assert 'action' in obs, 'Observation should contain previous action'
         act_shape = obs['action'].shape
         assert len(act_shape) == 3 and act_shape[0] == 1, f'Expected shape (1,B,A), got {act_shape}'
-        B, A, kind = act_shape[1], self.conf.action_dim, self.ac.dist_kind
+        B, A, kind = act_shape[1], self.conf.action_dim, ac.dist_kind
         noise = noise or {}
         u_act = noise.get('u_act')
         ua_shape = (B,) if kind == 0 else (B, A)
@@ -2364,8 +2367,8 @@ class Dreamer(nn.Module):
             feat = features.reshape(B, -1)
             dev = feat.device
             ws = self.wm.workspace(self.wm.shape(1, B, 1), dev)
-            logits, _ = self.ac.actor.fwd(feat, feat.shape[1], B, ws, save_acts=False)
-            value, _ = self.ac.critic.fwd(feat, feat.shape[1], B, ws, save_acts=False)
+            logits, _ = ac.actor.fwd(feat, feat.shape[1], B, ws, save_acts=False)
+            value, _ = ac.critic.fwd(feat, feat.shape[1], B, ws, save_acts=False)
             if draw_mode == 1:
                 u_act = None
             else:
@@ -2405,14 +2408,16 @@ class Dreamer(nn.Module):
         start = torch.cat((h, z), -1).contiguous()           # to_feature (rssm.py:83-84)
         return self._dream_from_features(start, Hh, u_act, u_prior, _pack)
 
-    def _dream_from_features(self, start, Hh, u_act=None, u_prior=None, _pack=None, early=None):
-        """start: (M,F) rows [h|z] (the world model's feature matrix is passed as is, no concat copy)."""
+    def _dream_from_features(self, start, Hh, u_act=None, u_prior=None, _pack=None, early=None, ac=None):
+        """start: (M,F) rows [h|z] (the world model's feature matrix is passed as is, no concat copy).
+        ac: the actor-critic that acts and is evaluated in the dream (explore.Plan2Explore's); None: the task one."""
         c = self.conf
+        ac = self.ac if ac is None else ac
         M, dev = start.shape[0], start.device
         F_, A, S = self.wm.features_dim, c.action_dim, c.stoch_dim
         shp = self.wm.shape(1, M, Hh)                        # T*B = M rows for workspace sizing
         ws = self.wm.workspace(shp, dev)
-        kind = self.ac.dist_kind
+        kind = ac.dist_kind
         # uniforms for the one-hot actor / the categorical latents, standard-normal noise for continuous actors / Gaussian latents
         ua_shape = (Hh, M) if kind == 0 else (Hh, M, A)
         if u_act is not None and tuple(u_act.shape) != ua_shape:
@@ -2427,18 +2432,18 @@ class Dreamer(nn.Module):
         actions = torch.empty(Hh, M, A, device=dev)
         act_idx = torch.empty(Hh, M, dtype=torch.int32, device=dev)
         cell_p = H.rssm_struct(self.wm.core.cell.ordered())
-        actor_p = self.ac.actor.struct()
+        actor_p = ac.actor.struct()
         a_acts = a_logits = None
         if _pack is not None:          # training: keep the actor activations of all H steps for the policy-gradient backward
-            a_acts = torch.empty(int(self.ac.actor.acts_floats(Hh * M)), device=dev)
-            a_logits = torch.empty(Hh * M, self.ac.actor.out_dim, device=dev)
+            a_acts = torch.empty(int(ac.actor.acts_floats(Hh * M)), device=dev)
+            a_logits = torch.empty(Hh * M, ac.actor.out_dim, device=dev)
         # The heads over the imagined states (reward, terminal: dreamer.py:212-213; critic_target, critic: a2c.py:85,113) are
         # per-row work on 40 000 rows, 4 ms behind a rollout whose last steps leave the chip half idle (profiles/r03_queues_*):
         # they run as two row windows - steps [0, split) and [split, H] - and with `early` (the training step's side streams)
         # the first window runs on the idle actor-critic stream as soon as the library reports those rows final, while the
         # rollout finishes on this one.  Same windows, same kernels either way: bit-identical to the single-stream order.
         rows = (Hh + 1) * M
-        r_split = self.ac.split_steps(Hh + 1) * M
+        r_split = ac.split_steps(Hh + 1) * M
         # (not under conf.amp: there the world-model backward chain on the other side stream is the step's critical path and the
         #  early window only takes CUs from it - measured 23.5 vs 23.2 ms; fp32: 37.1 vs 37.3 ms, 7-column shard 11.36 vs 11.50)
         use_early = (early is not None and _pack is not None and r_split < rows and _HEADS_EARLY
@@ -2452,14 +2457,14 @@ class Dreamer(nn.Module):
         f2 = feats.view(rows, F_)
         dec = self.wm.decoder
         outs = dec.dream_buffers(rows, dev)
-        values = self.ac.value_buffers(rows, dev) if _pack is not None else None
+        values = ac.value_buffers(rows, dev) if _pack is not None else None
 
         def heads(a, b, wsx):
             if b <= a:
                 return
             dec.dream_fwd(f2, a, b - a, wsx, outs)
             if values is not None:
-                self.ac.forward_values(f2, F_, rows, a, b - a, wsx, values)
+                ac.forward_values(f2, F_, rows, a, b - a, wsx, values)
         if use_early:
             early.s_ac.wait_event(early.ev_mark)
             with torch.cuda.stream(early.s_ac):

@@ -33,10 +33,12 @@ class NetworkPolicy:
     the reference, (B, A) otherwise.  The recurrent state is carried on the device between calls.
     mode, action_noise: Dreamer.act's ('mode' for evaluation; action_noise > 0 for DreamerV2's exploration noise).  per_env=True:
     the three metrics are (B,) float32 arrays, one number per environment - the critic's value, exp(log_prob) and the entropy of
-    act(..., return_rows=True) - in the same single copy as the action; what an EpisodeRecorder (collect.py) stores per step."""
+    act(..., return_rows=True) - in the same single copy as the action; what an EpisodeRecorder (collect.py) stores per step.
+    ac: the actor-critic handed to Dreamer.act (the exploration policy of explore.Plan2Explore); None: the model's own."""
 
-    def __init__(self, model, preprocess, batch_size=1, device=None, mode='sample', action_noise=0.0, per_env=False):
+    def __init__(self, model, preprocess, batch_size=1, device=None, mode='sample', action_noise=0.0, per_env=False, ac=None):
         self.model, self.preprocess, self.batch_size = model, preprocess, int(batch_size)
+        self.ac = ac      # the actor-critic that acts (Dreamer.act's `ac`: explore.Plan2Explore's); None: the model's own
         if mode not in ('sample', 'mode'):
             raise ValueError(f"mode is {mode!r}, expected 'sample' or 'mode'")
         if not float(action_noise) >= 0.0 or (float(action_noise) > 0.0 and mode == 'mode'):
@@ -81,6 +83,8 @@ class NetworkPolicy:
             kw.update(mode=self.mode, action_noise=self.action_noise)
         if self.per_env:
             kw.update(return_rows=True)
+        if self.ac is not None:
+            kw.update(ac=self.ac)
         action, self.state, metrics = self.model.act(obs_model, self.state, **kw)
         # the step's single device-to-host wait: the action and the three scalars (per_env: three rows) in one buffer
         if self.per_env:

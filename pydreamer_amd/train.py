@@ -246,12 +246,16 @@ def save_npz(data, path):
 
 
 # ------------------------------------------------------------------------------------------------ checkpoints
-def save_checkpoint(path, model, optimizers, steps):
+def save_checkpoint(path, model, optimizers, steps, explore=None, explore_optimizers=()):
     """The dict of tools.py:164-175 - epoch, model_state_dict, optimizer_{i}_state_dict - written with torch.save to a temporary
-    name and renamed into place."""
+    name and renamed into place.  explore (a Plan2Explore): explore_state_dict and explore_optimizer_{i}_state_dict beside them."""
     checkpoint = {'epoch': int(steps), 'model_state_dict': model.state_dict()}
     for i, opt in enumerate(optimizers):
         checkpoint[f'optimizer_{i}_state_dict'] = opt.state_dict()
+    if explore is not None:
+        checkpoint['explore_state_dict'] = explore.state_dict()
+        for i, opt in enumerate(explore_optimizers):
+            checkpoint[f'explore_optimizer_{i}_state_dict'] = opt.state_dict()
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     tmp = f'{path}.tmp{os.getpid()}'
     torch.save(checkpoint, tmp)
@@ -259,14 +263,20 @@ def save_checkpoint(path, model, optimizers, steps):
     return path
 
 
-def load_checkpoint(path, model, optimizers=(), map_location=None):
-    """tools.py:177-197: loads model and optimizers, returns the checkpoint's epoch; None when the file is absent."""
+def load_checkpoint(path, model, optimizers=(), map_location=None, explore=None, explore_optimizers=()):
+    """tools.py:177-197: loads model and optimizers, returns the checkpoint's epoch; None when the file is absent.  explore (a
+    Plan2Explore) and its optimizers are loaded from the explore_ keys when the file has them: a checkpoint written without
+    Plan2Explore leaves them as they are."""
     if not os.path.exists(path):
         return None
     checkpoint = torch.load(path, map_location=map_location)
     model.load_state_dict(checkpoint['model_state_dict'])
     for i, opt in enumerate(optimizers):
         opt.load_state_dict(checkpoint[f'optimizer_{i}_state_dict'])
+    if explore is not None and 'explore_state_dict' in checkpoint:
+        explore.load_state_dict(checkpoint['explore_state_dict'])
+        for i, opt in enumerate(explore_optimizers):
+            opt.load_state_dict(checkpoint[f'explore_optimizer_{i}_state_dict'])
     return checkpoint['epoch']
 
 
@@ -422,7 +432,13 @@ def run(conf, train_repository, eval_repository=None, test_repository=None, envs
     just written.  The default policy samples, as the reference's evaluation generators do; dict(mode='mode') is greedy.  This
     draws from the device's random stream, which is why it is opt-in.
     split_fraction > 0: the training recorder writes that fraction of its files to test_repository (generator.py:244).
-    on_step(step, model, obs, tensors): a hook behind the optimizer step (tests); None costs nothing.  Returns the step count."""
+    on_step(step, model, obs, tensors): a hook behind the optimizer step (tests); None costs nothing.  Returns the step count.
+    conf.expl_behavior = 'plan2explore' ('greedy' runs none of this): an explore.Plan2Explore beside the model - its
+    training_step behind the model's, its backward, clip and AdamW behind the model's optimizer step; its scalars go through a
+    second MetricAccumulator and are logged as train/expl_*; the checkpoint holds explore_state_dict and
+    explore_optimizer_{i}_state_dict.  Online, the training collector's NetworkPolicy acts with the exploration actor-critic while
+    conf.expl_until == 0 or the collector has taken fewer than expl_until environment steps (prefill included), then with the task
+    one, on the same carried state.  Evaluation always uses the task policy.  on_step may take a fifth argument, the Plan2Explore."""
     from .collect import Collector, EpisodeRecorder, EpisodeStats
     from .policy import NetworkPolicy, RandomPolicy, StepPreprocessor
     model_name = getattr(conf, 'model', 'dreamer')
@@ -440,8 +456,16 @@ def run(conf, train_repository, eval_repository=None, test_repository=None, envs
         raise ValueError(f'split_fraction={split_fraction} needs a test_repository')
     if split_fraction > 0 and not online:
         raise ValueError(f'split_fraction={split_fraction} without envs: nothing is recorded offline')
+    expl_behavior = getattr(conf, 'expl_behavior', 'greedy')
+    if expl_behavior not in ('greedy', 'plan2explore'):
+        raise ValueError(f'expl_behavior={expl_behavior!r}: the trainer loop builds greedy and plan2explore')
+    explore = expl_behavior == 'plan2explore'
+    if explore and model_name != 'dreamer':
+        raise ValueError(f"expl_behavior='plan2explore' needs model='dreamer', got {model_name!r}")
     if logdir is None:
         raise ValueError('run() needs a logdir: checkpoints, logged batches and the default logger write there')
+    if explore:      # (a greedy run never imports the module)
+        from .explore import EXPLORE_GRAD_NORMS, EXPLORE_METRIC_SLOTS, Plan2Explore, log_name
     device = torch.device(conf.device)
     torch.manual_seed(seed)
     logger = logger or JsonlLogger(logdir)
@@ -449,7 +473,12 @@ def run(conf, train_repository, eval_repository=None, test_repository=None, envs
 
     model = _build_model(conf).to(device)
     optimizers = model.init_optimizers(conf.adam_lr, conf.adam_lr_actor, conf.adam_lr_critic, conf.adam_eps)
-    steps = load_checkpoint(ckpt, model, optimizers, map_location=device) or 0
+    p2e, p2e_optimizers, ckpt_kw = None, (), {}
+    if explore:
+        p2e = Plan2Explore(conf, model).to(device)
+        p2e_optimizers = p2e.init_optimizers()
+        ckpt_kw = dict(explore=p2e, explore_optimizers=p2e_optimizers)
+    steps = load_checkpoint(ckpt, model, optimizers, map_location=device, **ckpt_kw) or 0
     has_goals = 'goals' in getattr(conf, 'probe_model', 'none')
     image_cat = conf.image_channels if conf.image_categorical else None
 
@@ -488,6 +517,8 @@ def run(conf, train_repository, eval_repository=None, test_repository=None, envs
             collector.flush()
             log_agent()
         collector.policy = NetworkPolicy(model, prep, batch_size=B_env, device=device, per_env=True, **(policy_kwargs or {}))
+        if p2e is not None:
+            collector.policy.ac = p2e.ac
         recorded0 = recorder.steps_saved + recorder.queued_steps
         if train_repository.count_steps()[1] * conf.env_action_repeat >= conf.n_env_steps:
             return steps      # a prefill-only job, or a finished one resumed
@@ -496,6 +527,10 @@ def run(conf, train_repository, eval_repository=None, test_repository=None, envs
                  buffer_size=conf.buffer_size if online else conf.buffer_size_offline, reset_interval=conf.reset_interval,
                  allow_mid_reset=conf.allow_mid_reset, seed=seed)
     acc = MetricAccumulator(default_slots(model), device)
+    acc_expl = None
+    if p2e is not None:      # the exploration step's own buffer, its own accumulator: default_slots(model) is what it always was
+        acc_expl = MetricAccumulator({log_name(k): (i, RULE_FINITE_MAX if k in EXPLORE_GRAD_NORMS else RULE_NOT_NAN)
+                                      for k, i in EXPLORE_METRIC_SLOTS.items()}, device)
     join = getattr(model, 'join_optimizers', None)
     state = None
     grad_steps, last_time, last_steps = 0, time.time(), steps
@@ -512,6 +547,8 @@ def run(conf, train_repository, eval_repository=None, test_repository=None, envs
                                                                                do_dream_tensors=will_log_batch)
             data.prefetch()
             state = new_state if conf.keep_state else None
+            if p2e is not None:      # on the weights and features the model's own step has just used
+                expl_losses, _ = p2e.training_step()
             for opt in optimizers:
                 opt.zero_grad()
             for loss in losses:
@@ -519,13 +556,23 @@ def run(conf, train_repository, eval_repository=None, test_repository=None, envs
             model.grad_clip(conf.grad_clip, conf.grad_clip_ac)
             for opt in optimizers:
                 opt.step()
+            if p2e is not None:
+                for opt in p2e_optimizers:
+                    opt.zero_grad()
+                for loss in expl_losses:
+                    loss.backward()
+                p2e.grad_clip(conf.grad_clip, conf.grad_clip_ac)
+                for opt in p2e_optimizers:
+                    opt.step()
             if on_step is not None:
-                on_step(steps, model, obs, tensors)
+                on_step(steps, model, obs, tensors, *(() if p2e is None else (p2e,)))
             # the step's scalars: folded on the device behind a stream-side wait for the pipelined gradient norms
             if join is not None:
                 join()
             acc.add(model.metric_buffer)
             acc.add_batch_stats(obs)
+            if acc_expl is not None:
+                acc_expl.add(p2e.metric_buffer)
 
             if will_log_batch:
                 save_npz(prepare_batch_npz({**obs, **tensors}), os.path.join(logdir, 'd2_wm_closed', f'{steps:07}.npz'))
@@ -539,6 +586,8 @@ def run(conf, train_repository, eval_repository=None, test_repository=None, envs
 
             if steps % conf.log_interval == 0:
                 metrics = {f'train/{k}': v for k, v in acc.read_and_reset().items()}      # the loop's only host wait
+                if acc_expl is not None:
+                    metrics.update({f'train/{k}': v for k, v in acc_expl.read_and_reset().items()})
                 if hasattr(model, 'check_device_status'):
                     model.check_device_status()
                 t = time.time()
@@ -548,7 +597,7 @@ def run(conf, train_repository, eval_repository=None, test_repository=None, envs
                 logger(metrics, steps)
 
             if steps % conf.save_interval == 0:
-                save_checkpoint(ckpt, model, optimizers, steps)
+                save_checkpoint(ckpt, model, optimizers, steps, **ckpt_kw)
 
             # (the reference returns at n_steps before it evaluates; here a run whose last step is an evaluation step evaluates)
             if conf.eval_interval and steps % conf.eval_interval == 0:
@@ -564,6 +613,8 @@ def run(conf, train_repository, eval_repository=None, test_repository=None, envs
 
             if online:
                 while (collector.recorder.steps_saved + collector.recorder.queued_steps - recorded0) < grad_steps * ratio:
+                    if p2e is not None and conf.expl_until > 0 and collector.steps >= conf.expl_until:
+                        collector.policy.ac = None      # from here on the task policy collects, on the same carried state
                     collector.run(1)
                 collector.flush()
                 log_agent()
