@@ -72,7 +72,7 @@ typedef struct dm_shape {
 #define DM_FLAG_GRU_MASK (3 << DM_FLAG_GRU_SHIFT)
 
 /* ---------------------------------------------------------------- library ---------------------- */
-int dm_version(void);                 /* ABI version, currently 16 (v2: LayerNorm-GRU slots; v3: per-call precision; v4: GRUCellStack layer slots;
+int dm_version(void);                 /* ABI version, currently 17 (v2: LayerNorm-GRU slots; v3: per-call precision; v4: GRUCellStack layer slots;
                                          v5: dm_kl_sampled_gauss_*, dm_chain_graph_*, dm_fp32_mode - additions only;
                                          v6: LayerNorm slots of GRUCellStack layers 1..3, dm_rssm_params grows to 58;
                                          v7: dm_wgrad_side_arm / _join, dm_dream_rollout_marks, dm_mlp_head_fwd_rows - additions only;
@@ -100,7 +100,8 @@ int dm_version(void);                 /* ABI version, currently 16 (v2: LayerNor
                                               collection loop; dm_metric_accum / dm_batch_stats / dm_masked_mean /
                                               dm_export_image_u8 of the trainer loop's device-side logging;
                                               dm_head_loss_catsup of the categorical reward decoder; dm_disag_reward /
-                                              dm_ensemble_mse of Plan2Explore */
+                                              dm_ensemble_mse of Plan2Explore;
+                                         v17: dm_gemm_plan_query added */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
 size_t dm_workspace_bytes(const dm_shape* shp);   /* scratch needed by any call below for this shape */
@@ -153,6 +154,16 @@ int dm_bf16_twins_enable(int on);
  * work item up, the register-staged loop (higher residency) below.  1 / 0 switches it on / off, 2 = on for every k extent (the
  * bit-identity test), -1 queries; returns the state (default 1). */
 int dm_gemm_dma_enable(int on);
+/* Which kernel would answer a plain dense product, and how it would cut the work: the shape test of the skinny kernel and the
+ * planner (tile / split-K cost model, main loop) that a launch runs, asked without a device.  mode 0 = a dm_gemm_f32 call, 1 = the
+ * same with DM_GEMM_BF16, 2 = a dm_gemm_bf16h call (has_add is ignored).  base_align: the alignment in bytes to assume for the
+ * operand base addresses (16: the 16-byte-load path, 4: the scalar-load path); ws_bytes: the split-K workspace of the call (0 =
+ * none).  The answer follows dm_gemm_dma_enable's state.
+ * out = {loop: 0 register-staged, 1 LDS-DMA, 2 bf16 operands, 3 bf16 storage, 4 skinny; tile index in dm_prof_end's order (-1
+ * for skinny); split count; k per split; column groups; 1 if both operands take 16-byte loads; dm_prof_end's kind (-1 for
+ * skinny); 0}.  Returns DM_OK, or the error the launch would return for that shape. */
+int dm_gemm_plan_query(int mode, int a_layout, int b_layout, int M, int N, int K, int lda, int ldb, int ldc, int flags,
+                       int has_add, int base_align, size_t ws_bytes, int32_t out[8]);
 /* The gather-form transposed convolutions (decoder layer 3 forward, the encoder's data gradients; csrc/conv.hip) are one product
  * over the (hs + k/2 - 1)^2 class pixels of a frame, whose patches reach into a zero border.  In fp32 mode the rows of that
  * product are enumerated (chunk of 128 frames, yy, xx, frame in chunk), so that a row tile lies inside one class pixel, and the

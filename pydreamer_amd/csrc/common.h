@@ -209,7 +209,8 @@ struct DmSample {
 bool dm_skinny_ln_ok(int M, int N, int K);
 int dm_gemm_sample_launch(const DmGemm& q, const DmSample& sm, hipStream_t stream);
 int dm_gemm_launch(const DmGemm& g, void* ws, size_t ws_bytes, hipStream_t stream);
-int dm_gemm_skinny_try(const DmGemm& g, hipStream_t stream);   // gemm_skinny.hip: 1 = handled, 0 = not applicable, <0 error
+int dm_gemm_skinny_takes(const DmGemm& g);                     // gemm_skinny.hip: 1 = the skinny kernel takes it, 0 = not applicable, <0 misuse; no launch
+int dm_gemm_skinny_try(const DmGemm& g, hipStream_t stream);   // ... and the launch: 1 = handled, 0 = not applicable, <0 error
 // two independent products; one launch when both are <= 64-row skinny products, else two ordinary launches
 int dm_gemm_pair_launch(const DmGemm& g0, const DmGemm& g1, void* ws, size_t ws_bytes, hipStream_t stream);
 
@@ -352,8 +353,9 @@ int dm_mlp_chain_fwd_launch(int rows, int in_dim, int layers, int out_dim, const
                             hipStream_t st, int k0 = 0, const float* add0 = nullptr, const DmChainSample* sample = nullptr);
 bool dm_mlp_chain_sparse_ok(int in_dim, int sparse_cols);      // the sparse-tail layer 0 applies (fp32 calls, aligned split)
 
-int dm_prof_slot_begin(int kind, double flops, double bytes, hipStream_t st);      // gemm.hip: per-launch HIP-event timing
+int dm_prof_slot_begin(int kind, double flops, double bytes, hipStream_t st);      // prof.hip: per-launch HIP-event timing
 void dm_prof_slot_end(int slot, hipStream_t st);
+void dm_prof_slot_shape(int slot, int M, int N, int K, int nsplit, int flags);     // the shape columns of a GEMM's row (slot < 0: no-op)
 extern "C" int dm_mlp_chain_min_rows(int rows);                                    // mlp_chain.hip: rows < 1 queries
 bool dm_prof_active();                                                             // the per-launch profiler is recording
 

@@ -1103,140 +1103,6 @@ __global__ void __launch_bounds__(256) gemm_splitk_reduce_kernel(const GemmKArgs
   }
 }
 
-// ---- optional per-launch timing (HIP events on the launch stream), used by bench.py for the roofline line -------
-#include <vector>
-struct GemmProf {
-  bool on = false;
-  size_t cap = 0, n = 0;
-  std::vector<hipEvent_t> ev;      // 2 per slot
-  std::vector<long long> shape;    // 5 per slot: M, N, K, split count, gather/scatter flags (bench.py --shape-table)
-  std::vector<double> flops, bytes;
-  std::vector<int> kind;
-};
-static GemmProf g_prof;
-static int prof_before(int kind, double flops, double bytes, hipStream_t st) {
-  if (!g_prof.on || g_prof.n >= g_prof.cap) return -1;
-  const int slot = (int)g_prof.n++;
-  g_prof.flops[slot] = flops;
-  g_prof.bytes[slot] = bytes;
-  g_prof.kind[slot] = kind;
-  (void)hipEventRecord(g_prof.ev[2 * slot], st);
-  return slot;
-}
-static void prof_after(int slot, hipStream_t st) {
-  if (slot >= 0) (void)hipEventRecord(g_prof.ev[2 * slot + 1], st);
-}
-// other translation units (panel.hip: kinds 20 = row-panel forward, 21 = row-panel backward; mlp_chain.hip: 22)
-bool dm_prof_active() { return g_prof.on; }
-int dm_prof_slot_begin(int kind, double flops, double bytes, hipStream_t st) { return prof_before(kind, flops, bytes, st); }
-void dm_prof_slot_end(int slot, hipStream_t st) { prof_after(slot, st); }
-extern "C" int dm_prof_begin(int max_launches) {
-  DM_REQUIRE(max_launches > 0 && max_launches <= (1 << 20), DM_E_SHAPE, "prof_begin: max_launches %d", max_launches);
-  if ((size_t)max_launches > g_prof.ev.size() / 2) {
-    const size_t have = g_prof.ev.size();
-    g_prof.ev.resize(2 * (size_t)max_launches);
-    for (size_t i = have; i < g_prof.ev.size(); ++i)
-      if (hipEventCreate(&g_prof.ev[i]) != hipSuccess) return dm_fail(DM_E_HIP, "prof_begin: hipEventCreate failed");
-  }
-  g_prof.flops.assign(max_launches, 0.0);
-  g_prof.bytes.assign(max_launches, 0.0);
-  g_prof.kind.assign(max_launches, 0);
-  g_prof.shape.assign(5 * (size_t)max_launches, 0);
-  g_prof.cap = max_launches;
-  g_prof.n = 0;
-  g_prof.on = true;
-  return DM_OK;
-}
-// Per-launch rows of the profiled region, BEFORE dm_prof_end: rows[i*8 + {0..7}] = {kind, M, N, K, split count, flags
-// (1 gathered A, 2 gathered B, 4 scatter epilogue, 8 bf16 operands), flops, milliseconds}; M = 0 for the non-GEMM kinds
-// (row panels, whole-MLP kernel).  Returns the number of rows written (<= max_rows).  Synchronises on the events.
-extern "C" int dm_prof_rows(double* rows, int max_rows) {
-  DM_REQUIRE(rows && max_rows > 0, DM_E_NULL, "prof_rows: null output");
-  int n = 0;
-  for (size_t i = 0; i < g_prof.n && n < max_rows; ++i, ++n) {
-    if (hipEventSynchronize(g_prof.ev[2 * i + 1]) != hipSuccess) return dm_fail(DM_E_HIP, "prof_rows: event sync failed");
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, g_prof.ev[2 * i], g_prof.ev[2 * i + 1]) != hipSuccess)
-      return dm_fail(DM_E_HIP, "prof_rows: hipEventElapsedTime failed");
-    double* r = rows + 8 * (size_t)n;
-    r[0] = g_prof.kind[i];
-    for (int j = 0; j < 5; ++j) r[1 + j] = (double)g_prof.shape[5 * i + j];
-    r[6] = g_prof.flops[i]; r[7] = ms;
-  }
-  return n;
-}
-// out[kind*4 + {0,1,2,3}] = {launches, flops, milliseconds, algorithmic bytes (4*(M*K + N*K + M*N))} for
-// kind = tile*4 + a_layout*2 + b_layout (tile 0: 128x128, 1: 128x64, 2: 64x64, 3: 128x96, 4: 96x128), + 24 when the launch took
-// gemm_dma_kernel; 20..22 panel / whole-MLP kernels; returns the number of recorded launches
-// (negative on error).  Synchronises on the recorded events.
-extern "C" int dm_prof_end(double* out, int nkinds) {
-  DM_REQUIRE(out && nkinds >= 44, DM_E_SHAPE, "prof_end: need room for 44 kinds");
-  g_prof.on = false;
-  for (int i = 0; i < nkinds * 4; ++i) out[i] = 0.0;
-  for (size_t i = 0; i < g_prof.n; ++i) {
-    if (hipEventSynchronize(g_prof.ev[2 * i + 1]) != hipSuccess) return dm_fail(DM_E_HIP, "prof_end: event sync failed");
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, g_prof.ev[2 * i], g_prof.ev[2 * i + 1]) != hipSuccess)
-      return dm_fail(DM_E_HIP, "prof_end: hipEventElapsedTime failed");
-    const int k = g_prof.kind[i];
-    out[k * 4 + 0] += 1.0;
-    out[k * 4 + 1] += g_prof.flops[i];
-    out[k * 4 + 2] += ms;
-    out[k * 4 + 3] += g_prof.bytes[i];
-  }
-  return (int)g_prof.n;
-}
-
-template <int BM, int BN, int WGM, int WGN>
-static int gemm_pipe_dispatch(const GemmKArgs& a, int al, int bl, int gather, dim3 grid, hipStream_t stream) {
-  if (a.c_tab) {
-    if (gather != 1 || al != 0 || bl != 0) return dm_fail(DM_E_SHAPE, "gemm: the scatter epilogue is built for a gathered A, layout (0,0), 16-byte loads");
-    hipLaunchKernelGGL((gemm_pipe_kernel<BM, BN, 0, 0, true, false, WGM, WGN, true>), grid, dim3(256), 0, stream, a);
-  } else if (gather == 1) {
-    if (al != 0 || bl != 0) return dm_fail(DM_E_SHAPE, "gemm: gathered A is built for layout (0,0) only");
-    hipLaunchKernelGGL((gemm_pipe_kernel<BM, BN, 0, 0, true, false, WGM, WGN, false>), grid, dim3(256), 0, stream, a);
-  } else if (gather == 2) {
-    if (al != 1 || bl != 1) return dm_fail(DM_E_SHAPE, "gemm: gathered B is built for layout (1,1) only");
-    hipLaunchKernelGGL((gemm_pipe_kernel<BM, BN, 1, 1, false, true, WGM, WGN, false>), grid, dim3(256), 0, stream, a);
-  } else if (al == 0 && bl == 0) hipLaunchKernelGGL((gemm_pipe_kernel<BM, BN, 0, 0, false, false, WGM, WGN, false>), grid, dim3(256), 0, stream, a);
-  else if (al == 0 && bl == 1) hipLaunchKernelGGL((gemm_pipe_kernel<BM, BN, 0, 1, false, false, WGM, WGN, false>), grid, dim3(256), 0, stream, a);
-  else if (al == 1 && bl == 0) hipLaunchKernelGGL((gemm_pipe_kernel<BM, BN, 1, 0, false, false, WGM, WGN, false>), grid, dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL((gemm_pipe_kernel<BM, BN, 1, 1, false, false, WGM, WGN, false>), grid, dim3(256), 0, stream, a);
-  return DM_OK;
-}
-static int gemm_pipe_tiles(int tc, const GemmKArgs& a, int al, int bl, int gather, dim3 grid, hipStream_t stream) {
-  if (tc == 0) return gemm_pipe_dispatch<128, 128, 2, 2>(a, al, bl, gather, grid, stream);
-  if (tc == 1) return gemm_pipe_dispatch<128, 64, 2, 2>(a, al, bl, gather, grid, stream);
-  if (tc == 3) return gemm_pipe_dispatch<128, 96, 4, 1>(a, al, bl, gather, grid, stream);
-  if (tc == 4) return gemm_pipe_dispatch<96, 128, 1, 4>(a, al, bl, gather, grid, stream);
-  return gemm_pipe_dispatch<64, 64, 2, 2>(a, al, bl, gather, grid, stream);
-}
-
-template <int BM, int BN, int WGM, int WGN>
-static int gemm_h_dispatch(const GemmKArgs& a, int al, int bl, int gather, dim3 grid, hipStream_t stream) {
-  if (a.c_tab) {
-    if (gather != 1 || al != 0 || bl != 0) return dm_fail(DM_E_SHAPE, "gemm: the scatter epilogue is built for a gathered A, layout (0,0)");
-    hipLaunchKernelGGL((gemm_h_kernel<BM, BN, 0, 0, true, false, WGM, WGN, true>), grid, dim3(256), 0, stream, a);
-  } else if (gather == 1) {
-    if (al != 0 || bl != 0) return dm_fail(DM_E_SHAPE, "gemm: gathered A is built for layout (0,0) only");
-    hipLaunchKernelGGL((gemm_h_kernel<BM, BN, 0, 0, true, false, WGM, WGN, false>), grid, dim3(256), 0, stream, a);
-  } else if (gather == 2) {
-    if (al != 1 || bl != 1) return dm_fail(DM_E_SHAPE, "gemm: gathered B is built for layout (1,1) only");
-    hipLaunchKernelGGL((gemm_h_kernel<BM, BN, 1, 1, false, true, WGM, WGN, false>), grid, dim3(256), 0, stream, a);
-  } else if (al == 0 && bl == 0) hipLaunchKernelGGL((gemm_h_kernel<BM, BN, 0, 0, false, false, WGM, WGN, false>), grid, dim3(256), 0, stream, a);
-  else if (al == 0 && bl == 1) hipLaunchKernelGGL((gemm_h_kernel<BM, BN, 0, 1, false, false, WGM, WGN, false>), grid, dim3(256), 0, stream, a);
-  else if (al == 1 && bl == 0) hipLaunchKernelGGL((gemm_h_kernel<BM, BN, 1, 0, false, false, WGM, WGN, false>), grid, dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL((gemm_h_kernel<BM, BN, 1, 1, false, false, WGM, WGN, false>), grid, dim3(256), 0, stream, a);
-  return DM_OK;
-}
-static int gemm_h_tiles(int tc, const GemmKArgs& a, int al, int bl, int gather, dim3 grid, hipStream_t stream) {
-  if (tc == 0) return gemm_h_dispatch<128, 128, 2, 2>(a, al, bl, gather, grid, stream);
-  if (tc == 1) return gemm_h_dispatch<128, 64, 2, 2>(a, al, bl, gather, grid, stream);
-  if (tc == 3) return gemm_h_dispatch<128, 96, 4, 1>(a, al, bl, gather, grid, stream);
-  if (tc == 4) return gemm_h_dispatch<96, 128, 1, 4>(a, al, bl, gather, grid, stream);
-  return gemm_h_dispatch<64, 64, 2, 2>(a, al, bl, gather, grid, stream);
-}
-
 // ---- gemm_dma_kernel launch: dynamic LDS (NS stages of (BM + BN) x 128 B), attribute set once per instantiation
 static int g_dma_enabled = 1;
 // 1 / 0: the direct-to-LDS main loop for fp32 16-byte-load products on / off (A/B and the bit-identity test), -1: query.
@@ -1260,53 +1126,77 @@ static int dma_launch(int lds_bytes, const GemmKArgs& a, dim3 grid, hipStream_t 
   DM_LAUNCH_CHECK();
   return DM_OK;
 }
-template <int BM, int BN, int WGM, int WGN>
-static int gemm_dma_dispatch(const GemmKArgs& a, int al, int bl, int gather, dim3 grid, hipStream_t stream) {
-  // stages: three where two workgroups still fit a CU's 160 KiB with them (64 x 64: 48 KiB, 128 x 64: 72 KiB), else two
-  constexpr int NS = (BM + BN) * 128 * 3 <= 72 * 1024 ? 3 : 2;
-  constexpr int LDS = NS * (BM + BN) * 128;
-  constexpr int LDS2 = 2 * (BM + BN) * 128;       // gathered operands: two stages (see the kernel's prologue comment)
+
+// ---- the four main loops as launcher types with one signature, launch<BM, BN, AL, BL, GA, GB, WGM, WGN, SC>(args, grid,
+// stream), so that the layout / gather ladder (launch_variant) and the tile ladder (launch_tile) below exist once
+template <bool VEC, int BF>
+struct RegLoop {      // gemm_f32_kernel, register-staged.  BF = 1: bf16 operands of shapes the pipelined loop cannot clamp
+  static constexpr bool has_scatter = VEC;      // the scalar-load variant has no scatter-epilogue instance
+  template <int BM, int BN, int AL, int BL, bool GA, bool GB, int WGM, int WGN, bool SC>
+  static int launch(const GemmKArgs& a, dim3 grid, hipStream_t stream) {
+    hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, AL, BL, VEC, GA, GB, WGM, WGN, BF, SC>), grid, dim3(256), 0, stream, a);
+    return DM_OK;
+  }
+};
+struct DmaLoop {      // gemm_dma_kernel: fp32 operands, 16-byte loads, LDS-DMA ring
+  static constexpr bool has_scatter = true;
+  template <int BM, int BN, int AL, int BL, bool GA, bool GB, int WGM, int WGN, bool SC>
+  static int launch(const GemmKArgs& a, dim3 grid, hipStream_t stream) {
+    // stages: three where two workgroups still fit a CU's 160 KiB with them (64 x 64: 48 KiB, 128 x 64: 72 KiB), else two;
+    // gathered / scattered operands: two stages (see the kernel's prologue comment)
+    constexpr int NS = (GA || GB || SC) ? 2 : ((BM + BN) * 128 * 3 <= 72 * 1024 ? 3 : 2);
+    return dma_launch<gemm_dma_kernel<BM, BN, AL, BL, GA, GB, WGM, WGN, SC, NS>>(NS * (BM + BN) * 128, a, grid, stream);
+  }
+};
+struct PipeLoop {     // gemm_pipe_kernel: bf16 operands held as fp32 in memory
+  static constexpr bool has_scatter = true;
+  template <int BM, int BN, int AL, int BL, bool GA, bool GB, int WGM, int WGN, bool SC>
+  static int launch(const GemmKArgs& a, dim3 grid, hipStream_t stream) {
+    hipLaunchKernelGGL((gemm_pipe_kernel<BM, BN, AL, BL, GA, GB, WGM, WGN, SC>), grid, dim3(256), 0, stream, a);
+    return DM_OK;
+  }
+};
+struct HLoop {        // gemm_h_kernel: bf16 storage
+  static constexpr bool has_scatter = true;
+  template <int BM, int BN, int AL, int BL, bool GA, bool GB, int WGM, int WGN, bool SC>
+  static int launch(const GemmKArgs& a, dim3 grid, hipStream_t stream) {
+    hipLaunchKernelGGL((gemm_h_kernel<BM, BN, AL, BL, GA, GB, WGM, WGN, SC>), grid, dim3(256), 0, stream, a);
+    return DM_OK;
+  }
+};
+
+// gather: 0 none, 1 = A gathered (NT: conv forward / conv-transpose backward-data), 2 = B gathered (TN: conv weight grads)
+template <class Loop, int BM, int BN, int WGM, int WGN>
+static int launch_variant(const GemmKArgs& a, int al, int bl, int gather, dim3 grid, hipStream_t stream) {
   if (a.c_tab) {
-    if (gather != 1 || al != 0 || bl != 0) return dm_fail(DM_E_SHAPE, "gemm: the scatter epilogue is built for a gathered A, layout (0,0), 16-byte loads");
-    return dma_launch<gemm_dma_kernel<BM, BN, 0, 0, true, false, WGM, WGN, true, 2>>(LDS2, a, grid, stream);
+    if constexpr (Loop::has_scatter) {
+      if (gather == 1 && al == 0 && bl == 0) return Loop::template launch<BM, BN, 0, 0, true, false, WGM, WGN, true>(a, grid, stream);
+    }
+    return dm_fail(DM_E_SHAPE, "gemm: the scatter epilogue is built for a gathered A, layout (0,0), 16-byte loads");
   }
   if (gather == 1) {
     if (al != 0 || bl != 0) return dm_fail(DM_E_SHAPE, "gemm: gathered A is built for layout (0,0) only");
-    return dma_launch<gemm_dma_kernel<BM, BN, 0, 0, true, false, WGM, WGN, false, 2>>(LDS2, a, grid, stream);
+    return Loop::template launch<BM, BN, 0, 0, true, false, WGM, WGN, false>(a, grid, stream);
   }
   if (gather == 2) {
     if (al != 1 || bl != 1) return dm_fail(DM_E_SHAPE, "gemm: gathered B is built for layout (1,1) only");
-    return dma_launch<gemm_dma_kernel<BM, BN, 1, 1, false, true, WGM, WGN, false, 2>>(LDS2, a, grid, stream);
+    return Loop::template launch<BM, BN, 1, 1, false, true, WGM, WGN, false>(a, grid, stream);
   }
-  if (al == 0 && bl == 0) return dma_launch<gemm_dma_kernel<BM, BN, 0, 0, false, false, WGM, WGN, false, NS>>(LDS, a, grid, stream);
-  if (al == 0 && bl == 1) return dma_launch<gemm_dma_kernel<BM, BN, 0, 1, false, false, WGM, WGN, false, NS>>(LDS, a, grid, stream);
-  if (al == 1 && bl == 0) return dma_launch<gemm_dma_kernel<BM, BN, 1, 0, false, false, WGM, WGN, false, NS>>(LDS, a, grid, stream);
-  return dma_launch<gemm_dma_kernel<BM, BN, 1, 1, false, false, WGM, WGN, false, NS>>(LDS, a, grid, stream);
+  if (al == 0 && bl == 0) return Loop::template launch<BM, BN, 0, 0, false, false, WGM, WGN, false>(a, grid, stream);
+  if (al == 0 && bl == 1) return Loop::template launch<BM, BN, 0, 1, false, false, WGM, WGN, false>(a, grid, stream);
+  if (al == 1 && bl == 0) return Loop::template launch<BM, BN, 1, 0, false, false, WGM, WGN, false>(a, grid, stream);
+  return Loop::template launch<BM, BN, 1, 1, false, false, WGM, WGN, false>(a, grid, stream);
+}
+// tile: index into the planner's candidate menu (gemm_plan), which is also the profiler's tile order
+template <class Loop>
+static int launch_tile(int tile, const GemmKArgs& a, int al, int bl, int gather, dim3 grid, hipStream_t stream) {
+  if (tile == 0) return launch_variant<Loop, 128, 128, 2, 2>(a, al, bl, gather, grid, stream);
+  if (tile == 1) return launch_variant<Loop, 128, 64, 2, 2>(a, al, bl, gather, grid, stream);
+  if (tile == 3) return launch_variant<Loop, 128, 96, 4, 1>(a, al, bl, gather, grid, stream);
+  if (tile == 4) return launch_variant<Loop, 96, 128, 1, 4>(a, al, bl, gather, grid, stream);
+  return launch_variant<Loop, 64, 64, 2, 2>(a, al, bl, gather, grid, stream);
 }
 
-// gather: 0 none, 1 = A gathered (NT: conv forward / conv-transpose backward-data), 2 = B gathered (TN: conv weight grads)
-template <int BM, int BN, bool V, int WGM = 2, int WGN = 2, int BF = 0>
-static int gemm_dispatch(const GemmKArgs& a, int al, int bl, int gather, dim3 grid, hipStream_t stream) {
-  if constexpr (V && BF == 0) {
-    if (a.use_dma) return gemm_dma_dispatch<BM, BN, WGM, WGN>(a, al, bl, gather, grid, stream);
-  }
-  if (a.c_tab) {
-    if (gather != 1 || al != 0 || bl != 0 || !V) return dm_fail(DM_E_SHAPE, "gemm: the scatter epilogue is built for a gathered A, layout (0,0), 16-byte loads");
-    hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, 0, 0, true, true, false, WGM, WGN, BF, true>), grid, dim3(256), 0, stream, a);
-  } else if (gather == 1) {
-    if (al != 0 || bl != 0) return dm_fail(DM_E_SHAPE, "gemm: gathered A is built for layout (0,0) only");
-    hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, 0, 0, V, true, false, WGM, WGN, BF>), grid, dim3(256), 0, stream, a);
-  } else if (gather == 2) {
-    if (al != 1 || bl != 1) return dm_fail(DM_E_SHAPE, "gemm: gathered B is built for layout (1,1) only");
-    hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, 1, 1, V, false, true, WGM, WGN, BF>), grid, dim3(256), 0, stream, a);
-  } else if (al == 0 && bl == 0) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, 0, 0, V, false, false, WGM, WGN, BF>), grid, dim3(256), 0, stream, a);
-  else if (al == 0 && bl == 1) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, 0, 1, V, false, false, WGM, WGN, BF>), grid, dim3(256), 0, stream, a);
-  else if (al == 1 && bl == 0) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, 1, 0, V, false, false, WGM, WGN, BF>), grid, dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, 1, 1, V, false, false, WGM, WGN, BF>), grid, dim3(256), 0, stream, a);
-  return DM_OK;
-}
-
-// operand precision of the call in progress on this host thread (common.h: DmPrecisionScope)
 // ---- bf16 twin map of the composite call in progress (common.h DmTwinScope)
 struct TwinRange { const float* base; size_t n; unsigned short* twin; bool valid; };
 static thread_local TwinRange tl_twins[48];
@@ -1347,7 +1237,6 @@ unsigned short* dm_twin_of(const float* p, bool need_valid) {
   return r->twin + (p - r->base);
 }
 
-#include <mutex>
 #include <unordered_map>
 static std::mutex g_arena_mu;
 static std::unordered_map<const void*, bool> g_arena_twins;
@@ -1367,10 +1256,10 @@ int dm_cur_precision() { return tl_precision; }
 DmPrecisionScope::DmPrecisionScope(int p) : prev(tl_precision) { tl_precision = p ? 1 : 0; }
 DmPrecisionScope::~DmPrecisionScope() { tl_precision = prev; }
 
-
-int dm_gemm_launch(const DmGemm& q, void* ws, size_t ws_bytes, hipStream_t stream) {
+// ---- dm_gemm_launch in steps: validate, skinny kernel, twins (stateful), plan (pure), kernel arguments, launch ----------------
+static int gemm_validate(const DmGemm& q) {
   DM_REQUIRE(q.M >= 0 && q.N >= 0 && q.K >= 1, DM_E_SHAPE, "gemm: bad dims M=%d N=%d K=%d (K must be >= 1)", q.M, q.N, q.K);
-  if (q.M == 0 || q.N == 0) return DM_OK;
+  if (q.M == 0 || q.N == 0) return DM_OK;      // nothing to do: the callers return before they look at the operands
   DM_REQUIRE(((q.A && q.B) || (q.A_h && q.B_h)) && q.C, DM_E_NULL, "gemm: null operand");
   DM_REQUIRE((q.A_h == nullptr) == (q.B_h == nullptr), DM_E_NULL, "gemm: bf16-storage operands come in pairs");
   DM_REQUIRE((unsigned)q.a_layout < 2 && (unsigned)q.b_layout < 2, DM_E_SHAPE, "gemm: bad layout");
@@ -1380,76 +1269,87 @@ int dm_gemm_launch(const DmGemm& q, void* ws, size_t ws_bytes, hipStream_t strea
              "gemm: gather tables must come in (major, minor) pairs");
   DM_REQUIRE(q.c_tab || q.ldc >= q.N, DM_E_SHAPE, "gemm: ldc %d < N %d", q.ldc, q.N);
   DM_REQUIRE(!q.add || q.ldadd >= q.N, DM_E_SHAPE, "gemm: ldadd %d < N %d", q.ldadd, q.N);
-
-  {   // <= 64-row products of the sequential RSSM chains: one-launch skinny kernel (gemm_skinny.hip)
-    const int sk = (q.A_h || q.C_h) ? 0 : dm_gemm_skinny_try(q, stream);
-    if (sk < 0) return sk;
-    if (sk == 1) {
-      // the skinny kernel keeps fp32 operands and writes no twin: a registered result gets its twin by a copy pass (dense
-      // results only; otherwise the twin stays invalid and consumers read the fp32 values)
-      unsigned short* t = (q.bf16 && dm_twins_on()) ? dm_twin_of(q.C, false) : nullptr;
-      if (t && q.ldc == q.N) {
-        const DmCvtSeg sg = {q.C, t, (size_t)q.M * q.N};
-        DM_TRY(dm_to_bf16_multi_launch(&sg, 1, stream));
-        dm_twin_mark(q.C);
-      }
-      return DM_OK;
-    }
-  }
+  return DM_OK;
+}
+// what only the <= 64-row skinny products have, asked of a product the skinny kernel did not take
+static int gemm_require_tiled(const DmGemm& q) {
   DM_REQUIRE(!q.ln_g && !q.lnb_x && !q.gates && !q.eg_x && !q.lnf_ps && !q.sm_logits, DM_E_SHAPE,
              "gemm: LayerNorm prologues / the gates epilogue are built for the <= 64-row skinny products only (M=%d K=%d)", q.M, q.K);
-  // bf16-storage operands: given explicitly (both or neither), or found in the call's twin map (common.h DmTwinScope) when
-  // BOTH operands have a valid twin and the shape meets the 16-byte chunk rules (8 elements along the minor axis); the
-  // result's twin is written whenever the map has storage for it.
-  const unsigned short* Ah = q.A_h;
-  const unsigned short* Bh = q.B_h;
-  unsigned short* Chh = q.C_h;
-  if (q.bf16 && dm_twins_on()) {
-    if (!Ah && !Bh) {
-      const unsigned short* ta = dm_twin_of(q.A, true);
-      const unsigned short* tb = dm_twin_of(q.B, true);
-      const bool fits = ta && tb && ((((uintptr_t)ta | (uintptr_t)tb) & 15) == 0) &&
-                        ((q.K & 7) == 0 || (q.a_layout == 1 && q.b_layout == 1)) &&
-                        (q.a_maj ? q.a_tab_vec8 != 0 : (q.lda & 7) == 0) && (q.b_maj ? q.b_tab_vec8 != 0 : (q.ldb & 7) == 0) &&
-                        (q.a_layout == 0 || ((q.M & 7) == 0 && q.M >= 8)) && (q.b_layout == 0 || ((q.N & 7) == 0 && q.N >= 8));
-      // measured on the step's convolution products (profiles/r03_bf16_storage.txt): weight gradients (both operands
-      // row-contiguous, K = pixels) gain 1.1-1.9x, k-contiguous products gain from K ~ 1000 up and lose below it (a 64-k tile
-      // halves the k-steps that amortise a tile's prologue and epilogue)
-      // ...; dense k-contiguous products (the 2 500-row imagination cell) gain from K ~ 400
-      const int min_k = (q.a_maj || q.b_maj || q.c_tab) ? DM_HSTORE_MIN_K : DM_HSTORE_MIN_K_DENSE;
-      if (fits && ((q.a_layout == 1 && q.b_layout == 1) || q.K >= min_k)) { Ah = ta; Bh = tb; }
-    }
-    if (!Chh && !q.no_twin) Chh = dm_twin_of(q.C, false);
-    if (Chh) dm_twin_mark(q.C);
+  return DM_OK;
+}
+
+// bf16-storage operands Ah / Bh meet the 16-byte chunk rules of gemm_h_kernel (8 elements along the minor axis)
+static bool hstore_fits(const DmGemm& q, const unsigned short* Ah, const unsigned short* Bh) {
+  return Ah && Bh && ((((uintptr_t)Ah | (uintptr_t)Bh) & 15) == 0) &&
+         ((q.K & 7) == 0 || (q.a_layout == 1 && q.b_layout == 1)) &&
+         (q.a_maj ? q.a_tab_vec8 != 0 : (q.lda & 7) == 0) && (q.b_maj ? q.b_tab_vec8 != 0 : (q.ldb & 7) == 0) &&
+         (q.a_layout == 0 || ((q.M & 7) == 0 && q.M >= 8)) && (q.b_layout == 0 || ((q.N & 7) == 0 && q.N >= 8));
+}
+static int gemm_require_hstore(const DmGemm& q, const unsigned short* Ah, const unsigned short* Bh) {
+  DM_REQUIRE(!(Ah && Bh) || hstore_fits(q, Ah, Bh), DM_E_SHAPE,
+             "gemm: bf16-storage operands need 16-byte aligned rows and extents in multiples of 8 (M=%d N=%d K=%d)", q.M, q.N, q.K);
+  return DM_OK;
+}
+// bf16-storage operands: given explicitly (both or neither), or found in the call's twin map (common.h DmTwinScope) when
+// BOTH operands have a valid twin and the shape meets hstore_fits; the result's twin is written whenever the map has storage
+// for it.  Stateful: marks the result's range of the twin map as valid.
+struct GemmTwins { const unsigned short* Ah; const unsigned short* Bh; unsigned short* Ch; };
+static GemmTwins gemm_resolve_twins(const DmGemm& q) {
+  GemmTwins t = {q.A_h, q.B_h, q.C_h};
+  if (!(q.bf16 && dm_twins_on())) return t;
+  if (!t.Ah && !t.Bh) {
+    const unsigned short* ta = dm_twin_of(q.A, true);
+    const unsigned short* tb = dm_twin_of(q.B, true);
+    // measured on the step's convolution products (profiles/r03_bf16_storage.txt): weight gradients (both operands
+    // row-contiguous, K = pixels) gain 1.1-1.9x, k-contiguous products gain from K ~ 1000 up and lose below it (a 64-k tile
+    // halves the k-steps that amortise a tile's prologue and epilogue)
+    // ...; dense k-contiguous products (the 2 500-row imagination cell) gain from K ~ 400
+    const int min_k = (q.a_maj || q.b_maj || q.c_tab) ? DM_HSTORE_MIN_K : DM_HSTORE_MIN_K_DENSE;
+    if (hstore_fits(q, ta, tb) && ((q.a_layout == 1 && q.b_layout == 1) || q.K >= min_k)) { t.Ah = ta; t.Bh = tb; }
   }
-  const bool hstore = Ah && Bh;
-  DM_REQUIRE(!hstore || ((((uintptr_t)Ah | (uintptr_t)Bh) & 15) == 0 && ((q.K & 7) == 0 || (q.a_layout == 1 && q.b_layout == 1)) &&
-                         (q.a_maj ? q.a_tab_vec8 != 0 : (q.lda & 7) == 0) && (q.b_maj ? q.b_tab_vec8 != 0 : (q.ldb & 7) == 0) &&
-                         (q.a_layout == 0 || ((q.M & 7) == 0 && q.M >= 8)) && (q.b_layout == 0 || ((q.N & 7) == 0 && q.N >= 8))),
-             DM_E_SHAPE, "gemm: bf16-storage operands need 16-byte aligned rows and extents in multiples of 8 (M=%d N=%d K=%d)",
-             q.M, q.N, q.K);
-  GemmKArgs a;
-  a.Ch = Chh;
-  a.A = q.A; a.B = q.B; a.C = q.C; a.bias = q.bias; a.add = q.add; a.mulref = q.mulref; a.row_zero = q.row_zero; a.partial = nullptr;
-  a.M = q.M; a.N = q.N; a.K = q.K;
-  a.lda = q.lda; a.ldb = q.ldb; a.ldc = q.ldc; a.ldadd = q.ldadd; a.ldmul = q.ldmul;
-  a.flags = q.flags;
-  a.a_maj = q.a_maj; a.a_min = q.a_min; a.b_maj = q.b_maj; a.b_min = q.b_min;
-  a.c_tab = q.c_tab; a.sc_cout = q.sc_cout; a.sc_wpitch = q.sc_wpitch; a.bias_mod = q.bias_mod;
-  DM_REQUIRE(!q.c_tab || (q.sc_cout > 0 && q.N % q.sc_cout == 0 && q.N / q.sc_cout == 4 && !q.add && !(q.flags & DM_GEMM_ACCUM)),
-             DM_E_SHAPE, "gemm: scatter epilogue needs N = 4 * sc_cout, no addend, no accumulate");
-  if (hstore) { a.A = reinterpret_cast<const float*>(Ah); a.B = reinterpret_cast<const float*>(Bh); }
+  if (!t.Ch && !q.no_twin) t.Ch = dm_twin_of(q.C, false);
+  if (t.Ch) dm_twin_mark(q.C);
+  return t;
+}
+
+// Which kernel answers a tiled product, and how it cuts the work.  Tiles in the profiler's order.
+static const int gemm_tiles[5][2] = {{128, 128}, {128, 64}, {64, 64}, {128, 96}, {96, 128}};
+enum { GEMM_LOOP_REG = 0, GEMM_LOOP_DMA = 1, GEMM_LOOP_BF16 = 2, GEMM_LOOP_H = 3, GEMM_LOOP_SKINNY = 4 };      // dm_gemm_plan_query's out[0]
+struct GemmPlan {
+  bool klist;                 // the tile loop walks q.k_list
+  int a_vec, b_vec;           // the operand takes 16-byte loads
+  int tile;                   // index into gemm_tiles
+  int nsplit, k_per_split;
+  int tiles_m, tiles_n, n_fast, n_groups;
+  int loop;                   // GEMM_LOOP_*: gemm_f32_kernel / gemm_dma_kernel / bf16 operands / gemm_h_kernel
+  bool pipe_ok;               // bf16 operands: gemm_pipe_kernel (else the BF = 1 instances of gemm_f32_kernel)
+  int kind;                   // profiling kind (prof.hip)
+};
+// tuning overrides for scripts/gemm_bench.py only (unset in production): DM_GEMM_TILE=1..5 forces a candidate of gemm_tiles,
+// DM_GEMM_SPLIT=n forces the split count
+static void gemm_forced(int* tile, int* split) {
+  static const int force_tile = getenv("DM_GEMM_TILE") ? atoi(getenv("DM_GEMM_TILE")) : 0;
+  static const int force_split = getenv("DM_GEMM_SPLIT") ? atoi(getenv("DM_GEMM_SPLIT")) : 0;
+  *tile = force_tile;
+  *split = force_split;
+}
+// A function of its arguments alone: reads q's pointers for alignment and null-ness only, makes no HIP call, touches no twin
+// map.  hstore: the product reads bf16-storage operands; has_ws / ws_bytes: the split-K workspace; dma_level:
+// dm_gemm_dma_enable's state; force_tile / force_split: gemm_forced.
+static int gemm_plan(const DmGemm& q, bool hstore, bool has_ws, size_t ws_bytes, int dma_level, int force_tile, int force_split,
+                     GemmPlan* p) {
   // k-tile lists: the fp32 tile loops of the scatter-epilogue product walk them; the bf16 loops (BK = 64) ignore them
   const bool klist = q.k_list && !hstore && !q.bf16;
   DM_REQUIRE(!klist || (q.c_tab && q.a_maj && q.k_list_rows > 0 && q.k_list_stride > 0), DM_E_SHAPE,
              "gemm: k-tile lists are built for the gathered-A scatter-epilogue product (rows %d, stride %d)", q.k_list_rows, q.k_list_stride);
-  a.k_list = klist ? q.k_list : nullptr; a.kl_rows = q.k_list_rows; a.kl_stride = q.k_list_stride;
+  p->klist = klist;
   // 16-byte load path: aligned base, rows a multiple of 4 floats apart, and the vectorised (minor) extent a multiple
   // of 4 so that no group of 4 straddles the edge.  Minor extent: K for layout 0, M (resp. N) for layout 1.
-  a.a_vec = hstore ? 1 : (((uintptr_t)q.A & 15) == 0 && (q.a_maj ? q.a_tab_vec != 0 : (q.lda & 3) == 0) &&
+  const int a_vec = hstore ? 1 : (((uintptr_t)q.A & 15) == 0 && (q.a_maj ? q.a_tab_vec != 0 : (q.lda & 3) == 0) &&
              (((q.a_layout == 0 ? q.K : q.M) & 3) == 0)) ? 1 : 0;
-  a.b_vec = hstore ? 1 : (((uintptr_t)q.B & 15) == 0 && (q.b_maj ? q.b_tab_vec != 0 : (q.ldb & 3) == 0) &&
+  const int b_vec = hstore ? 1 : (((uintptr_t)q.B & 15) == 0 && (q.b_maj ? q.b_tab_vec != 0 : (q.ldb & 3) == 0) &&
              (((q.b_layout == 0 ? q.K : q.N) & 3) == 0)) ? 1 : 0;
+  p->a_vec = a_vec; p->b_vec = b_vec;
 
   // ---- tile / split-K selection (deterministic in the shape only) ------------------------------------------------
   // Cost model in MACs per CU, fitted offline (scripts/fit_gemm_model.py) to per-tile timings of 28 step shapes on
@@ -1470,28 +1370,23 @@ int dm_gemm_launch(const DmGemm& q, void* ws, size_t ws_bytes, hipStream_t strea
   if (max_split > 512) max_split = 512;
   {
     const size_t per = (size_t)q.M * q.N * sizeof(float);
-    if (ws == nullptr || q.c_tab) max_split = 1;        // the scatter epilogue writes its result directly
+    if (!has_ws || q.c_tab) max_split = 1;        // the scatter epilogue writes its result directly
     else if ((size_t)max_split * per > ws_bytes) max_split = (int)(ws_bytes / per);
   }
   if (max_split < 1) max_split = 1;
-  static const int cand[5][2] = {{128, 128}, {128, 64}, {64, 64}, {128, 96}, {96, 128}};
   static const double keq[5] = {150.0, 60.0, 45.0, 45.0, 45.0};
   static const double rate[5] = {1.0, 0.9, 0.8, 0.75, 0.75};
   static const double resid[5] = {3.0, 4.0, 7.0, 4.0, 4.0};
   const double lat_macs = 1.0e6;
-  // tuning overrides for scripts/gemm_bench.py only (unset in production): DM_GEMM_TILE=1|2|3 forces a candidate,
-  // DM_GEMM_SPLIT=n forces the split count
-  static const int force_tile = getenv("DM_GEMM_TILE") ? atoi(getenv("DM_GEMM_TILE")) : 0;
-  static const int force_split = getenv("DM_GEMM_SPLIT") ? atoi(getenv("DM_GEMM_SPLIT")) : 0;
-  int BM = 64, BN = 64, nsplit = 1;
+  int tile = 2, nsplit = 1;
   DM_REQUIRE(!klist || q.k_list_rows % 64 == 0, DM_E_SHAPE, "gemm: k-tile lists cover a multiple of 64 rows (%d)", q.k_list_rows);
   double best_cost = -1.0;
   const int kt1 = ktiles > 0 ? ktiles : 1;
-  const bool dma_shape_pre = !hstore && !q.bf16 && a.a_vec && a.b_vec;
+  const bool dma_shape_pre = !hstore && !q.bf16 && a_vec && b_vec;
   for (int c = 0; c < 5; ++c) {
     if (force_tile && c != force_tile - 1) continue;
-    if (!(a.a_vec && a.b_vec) && c != 2) continue;        // the scalar-load variant exists for the 64x64 tile only
-    const int bm = cand[c][0], bn = cand[c][1];
+    if (!(a_vec && b_vec) && c != 2) continue;            // the scalar-load variant exists for the 64x64 tile only
+    const int bm = gemm_tiles[c][0], bn = gemm_tiles[c][1];
     if (klist && q.k_list_rows % bm != 0) continue;       // a work item reads ONE list: its rows must lie inside one list block
     const int64_t t = (int64_t)dm_cdiv(q.M, bm) * dm_cdiv(q.N, bn);
     int sp_fill = 1;
@@ -1540,42 +1435,39 @@ int dm_gemm_launch(const DmGemm& q, void* ws, size_t ws_bytes, hipStream_t strea
       // with the LDS-DMA loop (scripts/gemm_tile_sweep.py, profiles/r05_tile_sweep.txt): a row-contiguous B on the 128 x 128 tile
       // is the one combination it does not speed up (2500 x 4800 x 1536: 425 us against 342 on 128 x 64); split weight gradients
       // of the 400-wide heads run 6-14 % faster on 64 x 64 tiles (three resident workgroups per CU with the 3-stage ring)
-      if (!q.a_maj && !q.b_maj && !q.c_tab && dma_shape_pre && g_dma_enabled) {
+      if (!q.a_maj && !q.b_maj && !q.c_tab && dma_shape_pre && dma_level) {
         if (c == 0 && q.a_layout == 0 && q.b_layout == 1) cost *= 1.3;
         if (c == 2 && q.a_layout == 1 && q.b_layout == 1 && sp > 1 && t < 256 && dm_cdiv(kt1, sp) >= 14) cost *= 0.8;
       }
-      if (best_cost < 0 || cost < best_cost) { best_cost = cost; BM = bm; BN = bn; nsplit = sp; }
+      if (best_cost < 0 || cost < best_cost) { best_cost = cost; tile = c; nsplit = sp; }
     }
   }
+  const int BM = gemm_tiles[tile][0], BN = gemm_tiles[tile][1];
   // ---- which main loop (fp32 operands, 16-byte loads): gemm_dma_kernel when a work item has enough k-tiles to amortise the
   // ring's fill - below that the register-staged loop's higher residency (one LDS stage, 4-7 workgroups per CU) hides a
   // tile's prologue and epilogue better (profiles/r05_gemm_shapes_dma.txt vs _regstaged.txt with the switch at 2: K = 144 /
   // 192 / 384 products lose 8-15 %); both loops give the same bits, so the choice is free per call.  Layout 0 clamps edge
   // rows to the last row, layout 1 to the last full group of 4: >= 1 / >= 4 rows.
   constexpr int dma_min_kt = 14;
-  const bool dma_shape = !hstore && !q.bf16 && a.a_vec && a.b_vec && (q.a_layout == 0 ? q.M >= 1 : q.M >= 4) && (q.b_layout == 0 ? q.N >= 1 : q.N >= 4);
+  // the pipelined bf16-operand kernel clamps edge rows the same way, instead of masking them
+  const bool clamp_ok = a_vec && b_vec && (q.a_layout == 0 ? q.M >= 1 : q.M >= 4) && (q.b_layout == 0 ? q.N >= 1 : q.N >= 4);
+  const bool dma_shape = !hstore && !q.bf16 && clamp_ok;
   const int kt_item = klist ? (int)(q.k_list_mean + 0.5) : 0;      // a listed product: the mean tile count of a work item
-  auto dma_for = [&](int sp) { return g_dma_enabled && dma_shape && ((klist ? kt_item : dm_cdiv(kt1, sp)) >= dma_min_kt || g_dma_enabled >= 2); };
   // (A one-round 128 x 160 tile for the rollout's 2 500 x 1 800 gate products - 240 workgroups, one per CU, instead of 1 160
   // tiles of 64 x 64 = 4.53 per CU - was built and measured: 104.8 vs 106.3 us at K = 1000, 71.3 vs 68.4 at K = 600, step 33.94
   // vs 33.50 ms.  One 4-wave workgroup per CU leaves nobody to hide its barrier skew, prologue and epilogue: removed.)
-  const int tiles_m = dm_cdiv(q.M, BM), tiles_n = dm_cdiv(q.N, BN);
-  const int64_t tiles = (int64_t)tiles_m * tiles_n;
-  int k_per_split = dm_cdiv(ktiles > 0 ? ktiles : 1, nsplit) * 32;
-  nsplit = q.K > 0 ? dm_cdiv(q.K, k_per_split) : 1;
-  a.k_per_split = k_per_split;
-  a.nsplit = nsplit;
-  a.tiles_m = tiles_m;
-  a.partial = nsplit > 1 ? (float*)ws : nullptr;
-
+  p->tile = tile;
+  p->tiles_m = dm_cdiv(q.M, BM);
+  p->tiles_n = dm_cdiv(q.N, BN);
+  const int64_t tiles = (int64_t)p->tiles_m * p->tiles_n;
+  p->k_per_split = dm_cdiv(kt1, nsplit) * 32;
+  nsplit = dm_cdiv(q.K, p->k_per_split);
+  p->nsplit = nsplit;
   DM_REQUIRE(tiles * nsplit < (int64_t)1 << 30, DM_E_SHAPE, "gemm: too many work items");
-  a.n_tiles = (int)tiles;
-  a.tiles_n = tiles_n;
-  a.n_fast = tiles_n <= tiles_m ? 1 : 0;
-  a.n_items = (int)(tiles * nsplit);
+  p->n_fast = p->tiles_n <= p->tiles_m ? 1 : 0;
   {      // column groups of the fast dimension (gemm_decode): the grouping that minimises the operand rows one XCD's chunk touches
-    const int F = a.n_fast ? tiles_n : tiles_m, S = a.n_fast ? tiles_m : tiles_n;
-    const int bf = a.n_fast ? BN : BM, bs = a.n_fast ? BM : BN;
+    const int F = p->n_fast ? p->tiles_n : p->tiles_m, S = p->n_fast ? p->tiles_m : p->tiles_n;
+    const int bf = p->n_fast ? BN : BM, bs = p->n_fast ? BM : BN;
     int best_g = 1;
     if (nsplit == 1 && tiles >= 64 && !q.c_tab) {
       double best = -1.0;
@@ -1589,48 +1481,91 @@ int dm_gemm_launch(const DmGemm& q, void* ws, size_t ws_bytes, hipStream_t strea
         if (best < 0 || cost < best * 0.95) { best = cost; best_g = G; }      // (a new grouping has to win by 5 %)
       }
     }
-    a.n_groups = best_g;
+    p->n_groups = best_g;
   }
-  const int tc = (BM == 128 && BN == 128) ? 0 : (BM == 128 && BN == 64) ? 1 : (BM == 64 ? 2 : (BN == 96 ? 3 : 4));
-  dim3 grid((unsigned)a.n_items);
-  const int gather = q.a_maj ? 1 : (q.b_maj ? 2 : 0);
   DM_REQUIRE(!(q.a_maj && q.b_maj), DM_E_SHAPE, "gemm: only one gathered operand per call");
-  a.use_dma = dma_for(nsplit) ? 1 : 0;
+  const bool use_dma = dma_level && dma_shape && ((klist ? kt_item : dm_cdiv(kt1, nsplit)) >= dma_min_kt || dma_level >= 2);
+  p->pipe_ok = clamp_ok;
+  p->loop = hstore ? GEMM_LOOP_H : (q.bf16 && a_vec && b_vec) ? GEMM_LOOP_BF16 : use_dma ? GEMM_LOOP_DMA : GEMM_LOOP_REG;
   // profiling kinds: tile * 4 + layouts for the register-staged loop (0..19), 20..22 the panel / whole-MLP kernels (panel.hip,
   // mlp_chain.hip), 24 + (tile * 4 + layouts) for gemm_dma_kernel
-  const int kind = tc * 4 + q.a_layout * 2 + q.b_layout + (a.use_dma ? 24 : 0);
-  const int slot = prof_before(kind, 2.0 * q.M * q.N * (double)q.K,
-                               4.0 * ((double)q.M * q.K + (double)q.N * q.K + (double)q.M * q.N), stream);
-  if (slot >= 0) {
-    long long* sh = &g_prof.shape[5 * (size_t)slot];
-    sh[0] = q.M; sh[1] = q.N; sh[2] = q.K; sh[3] = nsplit; sh[4] = (q.a_maj ? 1 : 0) | (q.b_maj ? 2 : 0) | (q.c_tab ? 4 : 0) | (q.bf16 ? 8 : 0) |
-            (hstore ? 32 : 0);
+  p->kind = tile * 4 + q.a_layout * 2 + q.b_layout + (use_dma ? 24 : 0);
+  return DM_OK;
+}
+
+static GemmKArgs gemm_fill_args(const DmGemm& q, const GemmTwins& tw, const GemmPlan& p, void* ws) {
+  GemmKArgs a;
+  a.A = q.A; a.B = q.B; a.C = q.C; a.bias = q.bias; a.add = q.add; a.mulref = q.mulref; a.row_zero = q.row_zero;
+  if (p.loop == GEMM_LOOP_H) { a.A = reinterpret_cast<const float*>(tw.Ah); a.B = reinterpret_cast<const float*>(tw.Bh); }
+  a.Ch = tw.Ch;
+  a.M = q.M; a.N = q.N; a.K = q.K;
+  a.lda = q.lda; a.ldb = q.ldb; a.ldc = q.ldc; a.ldadd = q.ldadd; a.ldmul = q.ldmul;
+  a.flags = q.flags;
+  a.a_maj = q.a_maj; a.a_min = q.a_min; a.b_maj = q.b_maj; a.b_min = q.b_min;
+  a.c_tab = q.c_tab; a.sc_cout = q.sc_cout; a.sc_wpitch = q.sc_wpitch; a.bias_mod = q.bias_mod;
+  a.k_list = p.klist ? q.k_list : nullptr; a.kl_rows = q.k_list_rows; a.kl_stride = q.k_list_stride;
+  a.a_vec = p.a_vec; a.b_vec = p.b_vec;
+  a.k_per_split = p.k_per_split;
+  a.nsplit = p.nsplit;
+  a.partial = p.nsplit > 1 ? (float*)ws : nullptr;
+  a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n;
+  a.n_tiles = p.tiles_m * p.tiles_n;
+  a.n_items = a.n_tiles * p.nsplit;
+  a.n_fast = p.n_fast;
+  a.n_groups = p.n_groups;
+  a.use_dma = p.loop == GEMM_LOOP_DMA;
+  return a;
+}
+
+int dm_gemm_launch(const DmGemm& q, void* ws, size_t ws_bytes, hipStream_t stream) {
+  DM_TRY(gemm_validate(q));
+  if (q.M == 0 || q.N == 0) return DM_OK;
+  {   // <= 64-row products of the sequential RSSM chains: one-launch skinny kernel (gemm_skinny.hip)
+    const int sk = (q.A_h || q.C_h) ? 0 : dm_gemm_skinny_try(q, stream);
+    if (sk < 0) return sk;
+    if (sk == 1) {
+      // the skinny kernel keeps fp32 operands and writes no twin: a registered result gets its twin by a copy pass (dense
+      // results only; otherwise the twin stays invalid and consumers read the fp32 values)
+      unsigned short* t = (q.bf16 && dm_twins_on()) ? dm_twin_of(q.C, false) : nullptr;
+      if (t && q.ldc == q.N) {
+        const DmCvtSeg sg = {q.C, t, (size_t)q.M * q.N};
+        DM_TRY(dm_to_bf16_multi_launch(&sg, 1, stream));
+        dm_twin_mark(q.C);
+      }
+      return DM_OK;
+    }
   }
+  DM_TRY(gemm_require_tiled(q));
+  const GemmTwins tw = gemm_resolve_twins(q);
+  DM_TRY(gemm_require_hstore(q, tw.Ah, tw.Bh));
+  const bool hstore = tw.Ah && tw.Bh;
+  DM_REQUIRE(!q.c_tab || (q.sc_cout > 0 && q.N % q.sc_cout == 0 && q.N / q.sc_cout == 4 && !q.add && !(q.flags & DM_GEMM_ACCUM)),
+             DM_E_SHAPE, "gemm: scatter epilogue needs N = 4 * sc_cout, no addend, no accumulate");
+  int force_tile, force_split;
+  gemm_forced(&force_tile, &force_split);
+  GemmPlan p;
+  DM_TRY(gemm_plan(q, hstore, ws != nullptr, ws_bytes, g_dma_enabled, force_tile, force_split, &p));
+  const GemmKArgs a = gemm_fill_args(q, tw, p, ws);
+
+  const int slot = dm_prof_slot_begin(p.kind, 2.0 * q.M * q.N * (double)q.K,
+                                      4.0 * ((double)q.M * q.K + (double)q.N * q.K + (double)q.M * q.N), stream);
+  dm_prof_slot_shape(slot, q.M, q.N, q.K, p.nsplit,
+                     (q.a_maj ? 1 : 0) | (q.b_maj ? 2 : 0) | (q.c_tab ? 4 : 0) | (q.bf16 ? 8 : 0) | (hstore ? 32 : 0));
+  const dim3 grid((unsigned)a.n_items);
+  const int gather = q.a_maj ? 1 : (q.b_maj ? 2 : 0);
+  const int al = q.a_layout, bl = q.b_layout;
   int rc;
-  const bool vec = a.a_vec && a.b_vec;
-  // the pipelined kernel clamps edge rows instead of masking them: it needs >= 1 full row (layout 0) / >= 4 (layout 1 groups)
-  const bool pipe_ok = vec && (q.a_layout == 0 ? q.M >= 1 : q.M >= 4) && (q.b_layout == 0 ? q.N >= 1 : q.N >= 4);
-  if (hstore) rc = gemm_h_tiles(tc, a, q.a_layout, q.b_layout, gather, grid, stream);
-  else if (pipe_ok && q.bf16) rc = gemm_pipe_tiles(tc, a, q.a_layout, q.b_layout, gather, grid, stream);
-  else if (vec && q.bf16) {
-    if (tc == 0) rc = gemm_dispatch<128, 128, true, 2, 2, 1>(a, q.a_layout, q.b_layout, gather, grid, stream);
-    else if (tc == 1) rc = gemm_dispatch<128, 64, true, 2, 2, 1>(a, q.a_layout, q.b_layout, gather, grid, stream);
-    else if (tc == 3) rc = gemm_dispatch<128, 96, true, 4, 1, 1>(a, q.a_layout, q.b_layout, gather, grid, stream);
-    else if (tc == 4) rc = gemm_dispatch<96, 128, true, 1, 4, 1>(a, q.a_layout, q.b_layout, gather, grid, stream);
-    else rc = gemm_dispatch<64, 64, true, 2, 2, 1>(a, q.a_layout, q.b_layout, gather, grid, stream);
-  } else if (vec) {
-    if (tc == 0) rc = gemm_dispatch<128, 128, true>(a, q.a_layout, q.b_layout, gather, grid, stream);
-    else if (tc == 1) rc = gemm_dispatch<128, 64, true>(a, q.a_layout, q.b_layout, gather, grid, stream);
-    else if (tc == 3) rc = gemm_dispatch<128, 96, true, 4, 1>(a, q.a_layout, q.b_layout, gather, grid, stream);
-    else if (tc == 4) rc = gemm_dispatch<96, 128, true, 1, 4>(a, q.a_layout, q.b_layout, gather, grid, stream);
-    else rc = gemm_dispatch<64, 64, true>(a, q.a_layout, q.b_layout, gather, grid, stream);
-  } else {      // rare shapes (K = action_dim = 18, single-row weight gradients): scalar loads, smallest tile only
-    rc = gemm_dispatch<64, 64, false>(a, q.a_layout, q.b_layout, gather, grid, stream);
-  }
+  if (p.loop == GEMM_LOOP_H) rc = launch_tile<HLoop>(p.tile, a, al, bl, gather, grid, stream);
+  else if (p.loop == GEMM_LOOP_BF16 && p.pipe_ok) rc = launch_tile<PipeLoop>(p.tile, a, al, bl, gather, grid, stream);
+  else if (p.loop == GEMM_LOOP_BF16) rc = launch_tile<RegLoop<true, 1>>(p.tile, a, al, bl, gather, grid, stream);
+  else if (p.loop == GEMM_LOOP_DMA) rc = launch_tile<DmaLoop>(p.tile, a, al, bl, gather, grid, stream);
+  else if (p.a_vec && p.b_vec) rc = launch_tile<RegLoop<true, 0>>(p.tile, a, al, bl, gather, grid, stream);
+  else      // rare shapes (K = action_dim = 18, single-row weight gradients): scalar loads, smallest tile only
+    rc = launch_variant<RegLoop<false, 0>, 64, 64, 2, 2>(a, al, bl, gather, grid, stream);
   if (rc != DM_OK) return rc;
-  prof_after(slot, stream);
+  dm_prof_slot_end(slot, stream);
   DM_LAUNCH_CHECK();
-  if (nsplit > 1) {
+  if (p.nsplit > 1) {
     const size_t total = (size_t)q.M * q.N;
     int blocks = dm_cdiv(total, 256);
     if (blocks > 2048) blocks = 2048;
@@ -1641,6 +1576,45 @@ int dm_gemm_launch(const DmGemm& q, void* ws, size_t ws_bytes, hipStream_t strea
     DM_REQUIRE(q.M <= 64 && !q.c_tab, DM_E_SHAPE, "gemm: a fragment-major copy of C needs M <= 64 (M=%d)", q.M);
     DM_TRY(dm_frag_pack_launch(q.M, q.N, q.C, q.ldc, q.C_frag, stream));
   }
+  return DM_OK;
+}
+
+// The plan of a plain dense call, without a device: mode 0 = dm_gemm_f32, 1 = dm_gemm_f32 with DM_GEMM_BF16, 2 = dm_gemm_bf16h
+// (no addend: has_add is ignored), operand bases assumed aligned to base_align bytes, outside any twin scope.  Runs the skinny
+// predicate and the gemm_plan() of a launch.  out = {loop (GEMM_LOOP_*), tile index (-1: skinny), split count, k_per_split,
+// n_groups, both operands take 16-byte loads, profiling kind (-1: skinny), 0}.  Returns what the launch would return.
+extern "C" int dm_gemm_plan_query(int mode, int a_layout, int b_layout, int M, int N, int K, int lda, int ldb, int ldc, int flags,
+                                  int has_add, int base_align, size_t ws_bytes, int32_t out[8]) {
+  DM_REQUIRE(out, DM_E_NULL, "gemm_plan_query: null output");
+  DM_REQUIRE((unsigned)mode <= 2 && base_align >= 2 && base_align <= 4096 && (base_align & (base_align - 1)) == 0, DM_E_SHAPE,
+             "gemm_plan_query: mode %d, base_align %d", mode, base_align);
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  const uintptr_t base = ((uintptr_t)1 << 20) + (uintptr_t)base_align;      // placeholder address, never dereferenced
+  DmPrecisionScope prec(mode != 0);
+  DmGemm g;
+  g.a_layout = a_layout; g.b_layout = b_layout;
+  g.M = M; g.N = N; g.K = K;
+  g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.C = reinterpret_cast<float*>(base);
+  g.flags = flags & ~DM_GEMM_BF16;
+  if (mode == 2) {
+    g.A_h = g.B_h = reinterpret_cast<const unsigned short*>(base);
+  } else {
+    g.A = g.B = reinterpret_cast<const float*>(base);
+    if (has_add) { g.add = g.A; g.ldadd = N; }
+  }
+  DM_TRY(gemm_validate(g));
+  if (M == 0 || N == 0) return DM_OK;
+  const int sk = mode == 2 ? 0 : dm_gemm_skinny_takes(g);
+  if (sk < 0) return sk;
+  if (sk == 1) { out[0] = GEMM_LOOP_SKINNY; out[1] = -1; out[6] = -1; return DM_OK; }
+  DM_TRY(gemm_require_tiled(g));
+  DM_TRY(gemm_require_hstore(g, g.A_h, g.B_h));
+  int force_tile, force_split;
+  gemm_forced(&force_tile, &force_split);
+  GemmPlan p;
+  DM_TRY(gemm_plan(g, mode == 2, ws_bytes > 0, ws_bytes, g_dma_enabled, force_tile, force_split, &p));
+  out[0] = p.loop; out[1] = p.tile; out[2] = p.nsplit; out[3] = p.k_per_split; out[4] = p.n_groups;
+  out[5] = p.a_vec && p.b_vec; out[6] = p.kind;
   return DM_OK;
 }
 

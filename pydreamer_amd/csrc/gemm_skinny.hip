@@ -522,8 +522,9 @@ bool dm_skinny_ln_ok(int M, int N, int K) {
          (int64_t)N * K >= (int64_t)64 * 1024;
 }
 
-// Returns 1 if the launch was taken by the skinny kernel, 0 if the shape / alignment does not qualify, < 0 on error.
-int dm_gemm_skinny_try(const DmGemm& q, hipStream_t stream) {
+// The skinny kernel's shape test: 1 if it takes the product, 0 if the shape / alignment does not qualify, < 0 on misuse.
+// Launches nothing (dm_gemm_plan_query asks it without a device).
+int dm_gemm_skinny_takes(const DmGemm& q) {
   if (q.sm_logits) return dm_fail(DM_E_SHAPE, "skinny gemm: the softmax-backward epilogue exists in the pair launch only");
   const bool folded = q.eg_x || q.lnf_ps;      // folded LayerNorm backward (producer / consumer side): skinny-only epilogues
   if (folded) {
@@ -543,6 +544,13 @@ int dm_gemm_skinny_try(const DmGemm& q, hipStream_t stream) {
   if ((ln || lnb) && (q.K > SK_LN_MAXK || q.b_layout != 0 || !q.ln_b || !q.ln_g || q.M > 64)) return 0;
   if (lnb && (!q.lnb_stats || (q.lnb_ldx & 3) || ((uintptr_t)q.lnb_x & 15))) return 0;
   if (q.gates && ((!lnb && !q.lnf_ps) || q.N != q.gates->D || q.b_layout != 0)) return 0;
+  return 1;
+}
+// Returns 1 if the launch was taken by the skinny kernel, 0 if the shape / alignment does not qualify, < 0 on error.
+int dm_gemm_skinny_try(const DmGemm& q, hipStream_t stream) {
+  const int takes = dm_gemm_skinny_takes(q);
+  if (takes != 1) return takes;
+  const bool lnb = q.lnb_x != nullptr, ln = q.ln_g != nullptr && !lnb;
   SkinnyArgs a;
   skinny_fill(q, a);
   // 33..64 rows: two 32-row workgroups per strip instead of one 64-row one (half the matrix-pipe and operand work per

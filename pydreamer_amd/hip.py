@@ -219,6 +219,8 @@ _SIGNATURES = {
     'dm_rollout_fuse_act_enable': (c_int, [c_int]),
     'dm_bf16_twins_enable': (c_int, [c_int]),
     'dm_gemm_dma_enable': (c_int, [c_int]),
+    'dm_gemm_plan_query': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_size_t,
+                                   POINTER(c_int32)]),
     'dm_convt_kskip_enable': (c_int, [c_int]),
     'dm_kl_staged_enable': (c_int, [c_int]),
     'dm_dec_l4_bwd_direct_enable': (c_int, [c_int]),
@@ -256,7 +258,7 @@ _SIGNATURES = {
 }
 
 _lib = None
-DM_ABI_VERSION = 16     # include/dreamer_hip.h dm_version(): the struct layouts above (dm_rssm_params: 58 slots) belong to this one
+DM_ABI_VERSION = 17     # include/dreamer_hip.h dm_version(): the struct layouts above (dm_rssm_params: 58 slots) belong to this one
 
 
 def lib():

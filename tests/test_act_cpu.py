@@ -23,7 +23,7 @@ def test_new_symbols_and_host_side_argument_checks(hip):
     lib = hip.lib()
     for name in NEW_SYMBOLS:
         assert name in declared and hasattr(lib, name)
-    assert lib.dm_version() == hip.DM_ABI_VERSION == 16
+    assert lib.dm_version() == hip.DM_ABI_VERSION == 17
     assert lib.dm_policy_draw_ws_floats(0) == 0 and lib.dm_policy_draw_ws_floats(-3) == 0
     rows, A = 5, 6
     wsb = 4 * lib.dm_policy_draw_ws_floats(rows)

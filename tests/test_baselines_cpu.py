@@ -103,7 +103,7 @@ def test_refusals():
 def test_new_symbols_and_host_side_argument_checks(hip):
     assert set(NEW_SYMBOLS) <= set(hip.exported_symbols())
     lib = hip.lib()
-    assert lib.dm_version() == 16
+    assert lib.dm_version() == 17
     assert lib.dm_gru_sequence_fuse_enable(-1) == 1 and lib.dm_gru_sequence_fuse_enable(7) == 1      # default; a bad value changes nothing
     assert lib.dm_gru_sequence_fuse_enable(2) == 2 and lib.dm_gru_sequence_fuse_enable(1) == 1
     T, B, In, D = 3, 2, 7, 8

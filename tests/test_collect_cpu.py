@@ -304,7 +304,7 @@ def test_draw_mode_symbol_and_host_side_argument_checks(hip):
     hdr = open(os.path.join(ROOT, 'include', 'dreamer_hip.h')).read()
     assert 'dm_policy_draw_mode' in set(re.findall(r'\b(dm_[a-z0-9_]+)\s*\(', hdr))
     lib = hip.lib()
-    assert lib.dm_version() == hip.DM_ABI_VERSION == 16
+    assert lib.dm_version() == hip.DM_ABI_VERSION == 17
     rows = 5
     wsb = 4 * lib.dm_policy_draw_ws_floats(rows)
     fake = ctypes.c_void_p(1 << 20)          # never dereferenced: every call below fails its host-side checks

@@ -141,7 +141,7 @@ def test_preprocess_batch_image_categorical():
 def test_new_symbols_and_host_side_argument_checks(hip):
     assert set(NEW_SYMBOLS) <= set(hip.exported_symbols())
     lib = hip.lib()
-    assert lib.dm_version() == 16 and hip.DM_ABI_VERSION == 16
+    assert lib.dm_version() == 17 and hip.DM_ABI_VERSION == 17
     from pydreamer_amd.models import METRIC_BUF_FLOATS, METRIC_SLOTS
     assert METRIC_BUF_FLOATS == 48 and METRIC_SLOTS['loss_image'] == 1
     fake = ctypes.c_void_p(1 << 20)          # never dereferenced: every call below fails its host-side checks

@@ -30,7 +30,7 @@ def test_entries_are_exported_declared_and_bound():
     lib = hip.lib()
     for n in ENTRIES:
         assert n in declared and n in hip.exported_symbols() and hasattr(lib, n), n
-    assert lib.dm_version() == hip.DM_ABI_VERSION == 16
+    assert lib.dm_version() == hip.DM_ABI_VERSION == 17
     assert os.path.exists(os.path.join(ROOT, 'pydreamer_amd', 'csrc', 'disag.hip'))
 
 

@@ -23,7 +23,7 @@ def test_new_symbols_are_exported_declared_and_checked_on_the_host():
     for name in NEW:
         assert re.search(r'\bint ' + name + r'\(', hdr), name
         assert name in hip.exported_symbols() and hasattr(lib, name), name
-    assert lib.dm_version() == 16 and TR.METRIC_BUF_FLOATS == 48
+    assert lib.dm_version() == 17 and TR.METRIC_BUF_FLOATS == 48
     one = lambda: __import__('ctypes').c_void_p(64)      # a non-null pointer nothing dereferences: every call below fails its host check
     E = hip.DreamerHipError
     with pytest.raises(E, match='code -5'):
