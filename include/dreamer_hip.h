@@ -101,7 +101,8 @@ int dm_version(void);                 /* ABI version, currently 17 (v2: LayerNor
                                               dm_export_image_u8 of the trainer loop's device-side logging;
                                               dm_head_loss_catsup of the categorical reward decoder; dm_disag_reward /
                                               dm_ensemble_mse of Plan2Explore;
-                                         v17: dm_gemm_plan_query added */
+                                         v17: dm_gemm_plan_query added; later, still 17 (additions only): dm_cem_draw / dm_cem_update
+                                              of the latent-space planner */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
 size_t dm_workspace_bytes(const dm_shape* shp);   /* scratch needed by any call below for this shape */
@@ -673,6 +674,37 @@ int dm_policy_draw(int kind, int rows, int A, const float* params, int ldp, cons
 int dm_policy_draw_mode(int kind, int mode, float amount, int rows, int A, const float* params, int ldp, const float* noise,
                         const float* noise2, const float* value, float* action, int lda, int32_t* act_idx, float* log_prob,
                         float* entropy, float* stats, void* ws, size_t ws_bytes, void* stream);
+/* Latent-space planning by the cross-entropy method (csrc/cem.hip; PlaNet's planner - the reference has no counterpart): the
+ * candidate draw and the per-environment update between two open-loop rollouts.  B environments, J candidates each, Hp steps;
+ * M = B J rows, row m = b J + j; (Hp, M, ...) arrays are time-major, as dm_rssm_sequence_fwd reads them.  kind follows
+ * dm_shape.flags bits 0-1 (0 onehot, 1 tanh_normal, 2 normal_tanh; 1 and 2 behave the same here).
+ * dm_cem_draw, one launch:
+ *   kind 0      prop (B, Hp, A) probabilities, noise (Hp, M) uniforms in [0,1).  The index follows dm_sample_onehot's inverse-CDF
+ *               rule on the probabilities themselves: sequential fp32 cumsum in class order, idx = #{k : cdf_k <= u cdf_last}
+ *               clamped to A - 1.  actions (Hp, M, A) the one-hot rows, act_idx (Hp, M).
+ *   kinds 1, 2  prop (B, Hp, 2A) = [mean | std], noise (Hp, M, A) standard normals; action = clamp(fl(mean + fl(std eps)), -1, 1)
+ *               (product and sum rounded separately).  act_idx may be NULL and is not written.
+ * dm_cem_update, one launch, one workgroup per environment:
+ *   reward, terminal (Hp, M): the heads' means on the imagined states s_1 .. s_Hp; value (M): the critic on s_Hp, or NULL
+ *   ret (M)     sum_t gamma^(t-1) w_t r_t (+ gamma^Hp w_(Hp+1) v), w_1 = 1, w_(t+1) = w_t (1 - terminal_t), accumulated in t order in
+ *               fp32; written as computed.  For ranking a non-finite return counts as -FLT_MAX.
+ *   elite (B, K) int32: the candidates j of rank < K in rank order, rank_j = #{i : r_i > r_j or (r_i = r_j and i < j)} - an exact
+ *               comparison count, a function of the fp32 returns alone
+ *   prop_out    kind 0: (1 - floor) (alpha prop_in + (1 - alpha) freq) + floor / A with freq[t][a] the elites' integer class counts
+ *               over K; kinds 1, 2: mean_out = alpha mean_in + (1 - alpha) mean_e, std_out = max(alpha std_in + (1 - alpha) std_e,
+ *               floor) with the elite mean and population std taken in two passes, each summed in rank order.  May alias prop_in.
+ *   first_action (B, A): the t = 0 action of the rank-0 candidate
+ *   stats (B, 4): best return, mean elite return (both over the ranking values), the entropy of prop_out at t = 0 (kind 0) or
+ *               sum_a log std_out at t = 0 (kinds 1, 2), prop_out's probability of the executed class (kind 0) or 0
+ * No float atomics, fixed summation orders: the same inputs give the same bits.  Neither entry takes scratch memory, so neither
+ * returns DM_E_WORKSPACE.  Checked on the host before any launch: kind outside {0, 1, 2}, B < 1, J outside 1 .. 1024, Hp outside
+ * 1 .. 64, A outside 1 .. 64, B J above INT_MAX / 64, K outside 1 .. J, alpha outside [0, 1], floor < 0 (kind 0: or > 1), a
+ * non-finite gamma -> DM_E_SHAPE; a NULL required pointer (act_idx with kind 0 included; value is optional) -> DM_E_NULL. */
+int dm_cem_draw(int kind, int B, int J, int Hp, int A, const float* prop, const float* noise, float* actions, int32_t* act_idx,
+                void* stream);
+int dm_cem_update(int kind, int B, int J, int K, int Hp, int A, float gamma, const float* reward, const float* terminal,
+                  const float* value, const float* actions, const int32_t* act_idx, const float* prop_in, float alpha, float floor,
+                  float* prop_out, float* ret, int32_t* elite, float* first_action, float* stats, void* stream);
 /* critic loss rows (a2c.py:112-115): loss[r] = 0.5*(vt-v)^2*w ; dvalue = scale * -(vt-v)*w. */
 int dm_critic_loss(int rows, const float* value, const float* value_target, const float* weight, float scale,
                    float* loss, float* dvalue, void* stream);

@@ -6,6 +6,9 @@ def __getattr__(name):      # `from pydreamer_amd import NetworkPolicy` without 
     if name in ('NetworkPolicy', 'RandomPolicy', 'StepPreprocessor'):
         from . import policy
         return getattr(policy, name)
+    if name in ('CEMPlanner', 'PlannerPolicy'):
+        from . import planner
+        return getattr(planner, name)
     if name in ('EpisodeRecorder', 'EpisodeStats'):      # (the loop itself is pydreamer_amd.collect.collect: the name is the submodule's)
         from . import collect
         return getattr(collect, name)

@@ -41,6 +41,11 @@ SECTIONS = {
         # expl_behavior='plan2explore'; expl_until counts collected environment steps, 0 = explore for the whole run
         expl_behavior='greedy', disag_models=10, disag_action_cond=True, expl_intr_scale=1.0, expl_extr_scale=0.0, expl_until=0,
         adam_lr_expl=3.0e-4,
+        # latent-space planning (planner.py; PlaNet's CEM sizes - no reference counterpart).  Inert unless eval_behavior='plan':
+        # then the trainer's evaluation episodes act by planning instead of with the actor.  plan_floor: the uniform-mix share of
+        # a one-hot proposal, the minimum std of a continuous one; plan_value: the critic closes the planned return
+        plan_horizon=12, plan_candidates=1000, plan_elites=100, plan_iters=10, plan_alpha=0.0, plan_floor=0.01, plan_value=True,
+        eval_behavior='actor',
     ),
     'atari': dict(action_dim=18, clip_rewards='tanh', deter_dim=1024, kl_weight=0.1, gamma=0.99, entropy=0.001),
     'dmc': dict(action_dim=12, entropy=1.0e-4, actor_grad='dynamics', actor_dist='tanh_normal', clip_rewards='tanh'),

@@ -1494,6 +1494,20 @@ class _WMStep(torch.autograd.Function):
         return (None, None) + _finish_backward(wm, grads, flat, direct, grad_loss)
 
 
+def open_loop_struct(cell):
+    """rssm.py:50-53: every step is RSSMCell.forward_prior - the same trunk, then the PRIOR head on h' with no embedding term.
+    That is dm_rssm_sequence_fwd with the posterior head's parameter slots pointing at the prior head and a zero embedding (its
+    product with post_mlp_e is then an exact zero).  Forward only.  Used by WorldModel._forward(open_loop=True) and by the
+    planner's candidate rollout (planner.CEMPlanner)."""
+    po = list(cell.ordered())
+    ix = {n: i for i, n in enumerate(H.RSSM_PARAM_ORDER)}
+    for dst, src in (('post_mlp_h.weight', 'prior_mlp_h.weight'), ('post_mlp_h.bias', 'prior_mlp_h.bias'),
+                     ('post_norm.weight', 'prior_norm.weight'), ('post_norm.bias', 'prior_norm.bias'),
+                     ('post_mlp.weight', 'prior_mlp.weight'), ('post_mlp.bias', 'prior_mlp.bias')):
+        po[ix[dst]] = po[ix[src]]
+    return H.rssm_struct(po)
+
+
 class WorldModel(_Params):
     """dreamer.py:228-396."""
 
@@ -1620,16 +1634,7 @@ class WorldModel(_Params):
         cell = self.core.cell
         rssm_p = H.rssm_struct(cell.ordered())
         if open_loop:
-            # rssm.py:50-53: every step is RSSMCell.forward_prior - the same trunk, then the PRIOR head on h' with no
-            # embedding term.  That is dm_rssm_sequence_fwd with the posterior head's parameter slots pointing at the
-            # prior head and a zero embedding (its product with post_mlp_e is then an exact zero).  Forward only.
-            po = list(cell.ordered())
-            ix = {n: i for i, n in enumerate(H.RSSM_PARAM_ORDER)}
-            for dst, src in (('post_mlp_h.weight', 'prior_mlp_h.weight'), ('post_mlp_h.bias', 'prior_mlp_h.bias'),
-                             ('post_norm.weight', 'prior_norm.weight'), ('post_norm.bias', 'prior_norm.bias'),
-                             ('post_mlp.weight', 'prior_mlp.weight'), ('post_mlp.bias', 'prior_mlp.bias')):
-                po[ix[dst]] = po[ix[src]]
-            rssm_p = H.rssm_struct(po)
+            rssm_p = open_loop_struct(cell)
         rssm_acts = torch.empty(int(lib.dm_rssm_acts_floats(ctypes.byref(shp_r))), device=dev)
         feat = torch.empty(N, F_, device=dev)
         post = torch.empty(N, ZP, device=dev)

@@ -26,24 +26,13 @@ class StepPreprocessor:
                                 image_categorical=self.image_categorical)
 
 
-class NetworkPolicy:
-    """generator.py:311-331.  `preprocess`: any callable from the environment's observation dict to numpy (1, B, ...) fields
-    (StepPreprocessor above; an object with the reference's `.apply(obs, expandTB=True)` is taken too).  __call__ returns
-    (action ndarray, {policy_value, action_prob, policy_entropy} as Python floats); the action is (A,) for batch_size == 1 as in
-    the reference, (B, A) otherwise.  The recurrent state is carried on the device between calls.
-    mode, action_noise: Dreamer.act's ('mode' for evaluation; action_noise > 0 for DreamerV2's exploration noise).  per_env=True:
-    the three metrics are (B,) float32 arrays, one number per environment - the critic's value, exp(log_prob) and the entropy of
-    act(..., return_rows=True) - in the same single copy as the action; what an EpisodeRecorder (collect.py) stores per step.
-    ac: the actor-critic handed to Dreamer.act (the exploration policy of explore.Plan2Explore); None: the model's own."""
+class CarriedStatePolicy:
+    """What every policy that acts through the world model shares: the recurrent state carried on the device between calls
+    (reset_state), the step's preprocessing and upload (_ingest) and its ONE device-to-host copy (_emit).  NetworkPolicy acts with
+    an actor, planner.PlannerPolicy with the planner."""
 
-    def __init__(self, model, preprocess, batch_size=1, device=None, mode='sample', action_noise=0.0, per_env=False, ac=None):
-        self.model, self.preprocess, self.batch_size = model, preprocess, int(batch_size)
-        self.ac = ac      # the actor-critic that acts (Dreamer.act's `ac`: explore.Plan2Explore's); None: the model's own
-        if mode not in ('sample', 'mode'):
-            raise ValueError(f"mode is {mode!r}, expected 'sample' or 'mode'")
-        if not float(action_noise) >= 0.0 or (float(action_noise) > 0.0 and mode == 'mode'):
-            raise ValueError(f'action_noise is {action_noise} with mode {mode!r}: expected >= 0, and 0 with mode=\'mode\'')
-        self.mode, self.action_noise, self.per_env = mode, float(action_noise), bool(per_env)
+    def __init__(self, model, preprocess, batch_size=1, device=None, per_env=False):
+        self.model, self.preprocess, self.batch_size, self.per_env = model, preprocess, int(batch_size), bool(per_env)
         if device is None:
             device = next(model.parameters()).device
         self.device = torch.device(device)
@@ -72,25 +61,18 @@ class NetworkPolicy:
 
         self.state = pick(self.state, fresh)
 
-    def __call__(self, obs):
+    def _ingest(self, obs):
+        """The environment's observation dict -> (the model's (1, B, ...) device tensors, B)."""
         batch = self.preprocess.apply(obs, expandTB=True) if hasattr(self.preprocess, 'apply') else self.preprocess(obs)
         obs_model = {k: torch.from_numpy(np.ascontiguousarray(v)).to(self.device, non_blocking=True) for k, v in batch.items()}
         B = obs_model['action'].shape[1]
         if B != self.batch_size:
             raise ValueError(f'the preprocessed observation holds {B} environments, this policy was built for {self.batch_size}')
-        kw = {}
-        if self.mode != 'sample' or self.action_noise > 0.0:      # the defaults are the call as it always was
-            kw.update(mode=self.mode, action_noise=self.action_noise)
-        if self.per_env:
-            kw.update(return_rows=True)
-        if self.ac is not None:
-            kw.update(ac=self.ac)
-        action, self.state, metrics = self.model.act(obs_model, self.state, **kw)
-        # the step's single device-to-host wait: the action and the three scalars (per_env: three rows) in one buffer
-        if self.per_env:
-            tail = [metrics['value'].reshape(B), metrics['log_prob'].reshape(B).exp(), metrics['entropy'].reshape(B)]
-        else:
-            tail = [metrics[k].reshape(1) for k in METRIC_KEYS]
+        return obs_model, B
+
+    def _emit(self, action, tail, B):
+        """The step's single device-to-host wait: the action and `tail` - the three scalars in METRIC_KEYS order, per_env: three
+        (B,) rows - in one buffer."""
         host = torch.cat([action.reshape(-1)] + tail).cpu().numpy()
         A = action.shape[-1]
         act = host[:B * A].reshape(B, A)
@@ -99,6 +81,42 @@ class NetworkPolicy:
         if self.per_env:
             return act.copy(), {k: host[B * A + i * B:B * A + (i + 1) * B].copy() for i, k in enumerate(METRIC_KEYS)}
         return act.copy(), {k: float(host[B * A + i]) for i, k in enumerate(METRIC_KEYS)}
+
+
+class NetworkPolicy(CarriedStatePolicy):
+    """generator.py:311-331.  `preprocess`: any callable from the environment's observation dict to numpy (1, B, ...) fields
+    (StepPreprocessor above; an object with the reference's `.apply(obs, expandTB=True)` is taken too).  __call__ returns
+    (action ndarray, {policy_value, action_prob, policy_entropy} as Python floats); the action is (A,) for batch_size == 1 as in
+    the reference, (B, A) otherwise.  The recurrent state is carried on the device between calls.
+    mode, action_noise: Dreamer.act's ('mode' for evaluation; action_noise > 0 for DreamerV2's exploration noise).  per_env=True:
+    the three metrics are (B,) float32 arrays, one number per environment - the critic's value, exp(log_prob) and the entropy of
+    act(..., return_rows=True) - in the same single copy as the action; what an EpisodeRecorder (collect.py) stores per step.
+    ac: the actor-critic handed to Dreamer.act (the exploration policy of explore.Plan2Explore); None: the model's own."""
+
+    def __init__(self, model, preprocess, batch_size=1, device=None, mode='sample', action_noise=0.0, per_env=False, ac=None):
+        self.ac = ac      # the actor-critic that acts (Dreamer.act's `ac`: explore.Plan2Explore's); None: the model's own
+        if mode not in ('sample', 'mode'):
+            raise ValueError(f"mode is {mode!r}, expected 'sample' or 'mode'")
+        if not float(action_noise) >= 0.0 or (float(action_noise) > 0.0 and mode == 'mode'):
+            raise ValueError(f'action_noise is {action_noise} with mode {mode!r}: expected >= 0, and 0 with mode=\'mode\'')
+        self.mode, self.action_noise = mode, float(action_noise)
+        super().__init__(model, preprocess, batch_size, device, per_env)
+
+    def __call__(self, obs):
+        obs_model, B = self._ingest(obs)
+        kw = {}
+        if self.mode != 'sample' or self.action_noise > 0.0:      # the defaults are the call as it always was
+            kw.update(mode=self.mode, action_noise=self.action_noise)
+        if self.per_env:
+            kw.update(return_rows=True)
+        if self.ac is not None:
+            kw.update(ac=self.ac)
+        action, self.state, metrics = self.model.act(obs_model, self.state, **kw)
+        if self.per_env:
+            tail = [metrics['value'].reshape(B), metrics['log_prob'].reshape(B).exp(), metrics['entropy'].reshape(B)]
+        else:
+            tail = [metrics[k].reshape(1) for k in METRIC_KEYS]
+        return self._emit(action, tail, B)
 
 
 class RandomPolicy:

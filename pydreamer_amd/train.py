@@ -438,7 +438,9 @@ def run(conf, train_repository, eval_repository=None, test_repository=None, envs
     second MetricAccumulator and are logged as train/expl_*; the checkpoint holds explore_state_dict and
     explore_optimizer_{i}_state_dict.  Online, the training collector's NetworkPolicy acts with the exploration actor-critic while
     conf.expl_until == 0 or the collector has taken fewer than expl_until environment steps (prefill included), then with the task
-    one, on the same carried state.  Evaluation always uses the task policy.  on_step may take a fifth argument, the Plan2Explore."""
+    one, on the same carried state.  Evaluation always uses the task policy.  on_step may take a fifth argument, the Plan2Explore.
+    conf.eval_behavior = 'plan' ('actor' is the text above): the evaluation Collector acts with planner.PlannerPolicy -
+    CEM in latent space at the conf.plan_* sizes, eval_policy_kwargs going to CEMPlanner - and logs the same agent_eval/* keys."""
     from .collect import Collector, EpisodeRecorder, EpisodeStats
     from .policy import NetworkPolicy, RandomPolicy, StepPreprocessor
     model_name = getattr(conf, 'model', 'dreamer')
@@ -462,8 +464,15 @@ def run(conf, train_repository, eval_repository=None, test_repository=None, envs
     explore = expl_behavior == 'plan2explore'
     if explore and model_name != 'dreamer':
         raise ValueError(f"expl_behavior='plan2explore' needs model='dreamer', got {model_name!r}")
+    eval_behavior = getattr(conf, 'eval_behavior', 'actor')
+    if eval_behavior not in ('actor', 'plan'):
+        raise ValueError(f'eval_behavior={eval_behavior!r}: the evaluation episodes act with the actor or by planning (plan)')
+    if eval_behavior == 'plan' and model_name != 'dreamer':
+        raise ValueError(f"eval_behavior='plan' needs model='dreamer', got {model_name!r}")
     if logdir is None:
         raise ValueError('run() needs a logdir: checkpoints, logged batches and the default logger write there')
+    if eval_behavior == 'plan':      # (the default never imports the module)
+        from .planner import PlannerPolicy
     if explore:      # (a greedy run never imports the module)
         from .explore import EXPLORE_GRAD_NORMS, EXPLORE_METRIC_SLOTS, Plan2Explore, log_name
     device = torch.device(conf.device)
@@ -496,8 +505,11 @@ def run(conf, train_repository, eval_repository=None, test_repository=None, envs
                             image_categorical=image_cat, batched=True)
     eval_collector = None
     if eval_envs is not None:
-        eval_collector = Collector(eval_envs, NetworkPolicy(model, prep, batch_size=len(eval_envs), device=device, per_env=True,
-                                                            **(eval_policy_kwargs or {})),
+        # eval_behavior='plan' (DESIGN 4.19): the same episodes, columns and agent_eval/* keys with the CEM planner acting; the
+        # sizes are conf.plan_*, eval_policy_kwargs are then CEMPlanner's
+        eval_policy = PlannerPolicy if eval_behavior == 'plan' else NetworkPolicy
+        eval_collector = Collector(eval_envs, eval_policy(model, prep, batch_size=len(eval_envs), device=device, per_env=True,
+                                                          **(eval_policy_kwargs or {})),
                                    EpisodeRecorder(eval_repository, len(eval_envs), steps_per_npz=steps_per_npz))
         eval_stats = attach_stats('agent_eval', 0, eval_collector)
 
