@@ -102,7 +102,8 @@ int dm_version(void);                 /* ABI version, currently 17 (v2: LayerNor
                                               dm_head_loss_catsup of the categorical reward decoder; dm_disag_reward /
                                               dm_ensemble_mse of Plan2Explore;
                                          v17: dm_gemm_plan_query added; later, still 17 (additions only): dm_cem_draw / dm_cem_update
-                                              of the latent-space planner */
+                                              of the latent-space planner; dm_twohot_decode / dm_twohot_loss / dm_return_norm of the
+                                              two-hot critic and the percentile return normalisation */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
 size_t dm_workspace_bytes(const dm_shape* shp);   /* scratch needed by any call below for this shape */
@@ -705,6 +706,38 @@ int dm_cem_draw(int kind, int B, int J, int Hp, int A, const float* prop, const 
 int dm_cem_update(int kind, int B, int J, int K, int Hp, int A, float gamma, const float* reward, const float* terminal,
                   const float* value, const float* actions, const int32_t* act_idx, const float* prop_in, float alpha, float floor,
                   float* prop_out, float* ret, int32_t* elite, float* first_action, float* stats, void* stream);
+/* The two-hot symlog critic and the percentile return normalisation (csrc/twohot.hip; DreamerV3's critic head and advantage
+ * scaling - the reference has no counterpart).  fp32 throughout, compiled with floating-point contraction off: every product and
+ * sum below is rounded on its own, in the order written.  No float atomics, no scratch memory (none of the three returns
+ * DM_E_WORKSPACE): the same inputs give the same bits.  symlog(t) = copysign(log1pf(|t|), t), symexp(m) = copysign(expm1f(|m|), m).
+ * logits (rows, K; leading dimension ld), bins: K strictly increasing floats in symlog space (any increasing support), 2 <= K <= 256.
+ * One lane group per row: KP = the power of two >= K up to 64 lanes, E = 1, 2 or 4 elements per lane (element j = lane + e KP);
+ * a sum over j is lane-local over e ascending, then an xor-butterfly over the KP lanes.
+ * dm_twohot_decode, one launch:
+ *   m = max_j logit_j;  e_j = expf(logit_j - m);  s = sum_j e_j;  p_j = e_j / s;  mu = sum_j p_j bins_j;  value[r] = symexp(mu)
+ * dm_twohot_loss, one launch, for the rows r < rows:
+ *   x = min(max(symlog(target[r]), bins[0]), bins[K-1]);  k = min(max(#{i : bins[i] <= x} - 1, 0), K - 2)
+ *   w_hi = (x - bins[k]) / (bins[k+1] - bins[k]);  w_lo = 1 - w_hi;  lse = m + logf(s)
+ *   loss[r] = weight[r] * ((lse - w_lo logit_k) - w_hi logit_{k+1})
+ *   dlogits[r][j] = (scale * weight[r]) * (p_j - y_j),  y_k = w_lo, y_{k+1} = w_hi, 0 elsewhere      (dlogits: (rows_total, K) dense)
+ *   rows [rows, rows_total) of dlogits are written as exact zeros (a2c.py's "value[-1] gets no gradient"); value (optional): the
+ *   decoded value of the same logits, rows r < rows; dlogits may be NULL (the loss-only form; rows_total is then not used).
+ * dm_return_norm, two launches (one when n_adv == 0): the q_lo and q_hi percentiles of the n values x by linear interpolation
+ * between exact order statistics s_0 <= ... <= s_{n-1} (a radix select over the order-preserving integer image of the float in
+ * one workgroup; -0 sorts below +0):
+ *   pos = fl(q fl(n - 1));  i = floor(pos);  fr = fl(pos - i);  p = fl(s_i + fl(fr fl(s_{i+1} - s_i))),  s_n read as s_{n-1}
+ *   update != 0:  state[c] = fl(fl(decay state[c]) + fl(fl(1 - decay) p_c)) for c = 0 (lo), 1 (hi); update == 0: state is read only
+ *   scale = max(limit, fl(state[1] - state[0]));  adv[i] = fl(adv[i] / scale) for i < n_adv;  out[0..5) = [p_lo, p_hi, lo, hi, scale]
+ *   Inputs are finite by contract; a non-finite one gives an unspecified result, the walk still ends and stays inside the arrays.
+ * Checked on the host before any launch: K outside 2 .. 256, rows < 0, rows_total < rows, ld < K; n < 1, n_adv < 0, q outside
+ * 0 <= q_lo <= q_hi <= 1, decay outside [0, 1), limit <= 0 or not finite -> DM_E_SHAPE; a NULL required pointer (logits, bins, value
+ * for the decode; target, weight, loss for the loss; x, state, out, and adv with n_adv > 0) -> DM_E_NULL; rows == 0 -> DM_OK with
+ * nothing launched. */
+int dm_twohot_decode(int rows, int K, const float* logits, int ld, const float* bins, float* value, void* stream);
+int dm_twohot_loss(int rows, int rows_total, int K, const float* logits, int ld, const float* bins, const float* target,
+                   const float* weight, float scale, float* loss, float* dlogits, float* value, void* stream);
+int dm_return_norm(int n, const float* x, float q_lo, float q_hi, float decay, float limit, int update, float* state, float* out,
+                   float* adv, int n_adv, void* stream);
 /* critic loss rows (a2c.py:112-115): loss[r] = 0.5*(vt-v)^2*w ; dvalue = scale * -(vt-v)*w. */
 int dm_critic_loss(int rows, const float* value, const float* value_target, const float* weight, float scale,
                    float* loss, float* dvalue, void* stream);

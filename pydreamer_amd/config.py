@@ -27,6 +27,11 @@ SECTIONS = {
         # actor critic
         gamma=0.995, lambda_gae=0.95, entropy=0.003, target_interval=100, imag_horizon=15, actor_grad='reinforce',
         actor_dist='onehot',
+        # the two-hot symlog critic and the percentile return normalisation (DreamerV3's; no reference counterpart).
+        # Inert unless critic_dist='twohot' / return_norm='percentile': critic_bins symlog-spaced bins over +-critic_bin_range,
+        # advantages divided by max(return_norm_limit, running [lo, hi] percentile range of the imagined returns)
+        critic_dist='mse', critic_bins=255, critic_bin_range=20.0, return_norm='none', return_norm_lo=0.05, return_norm_hi=0.95,
+        return_norm_decay=0.99, return_norm_limit=1.0,
         # aux critic
         aux_critic=False, aux_critic_weight=1.0, gamma_aux=0.99, lambda_gae_aux=0.95, target_interval_aux=1000,
         # the trainer loop (train.py; defaults.yaml:3-16, 34-35, 59-65, 113-118)

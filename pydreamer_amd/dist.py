@@ -39,6 +39,10 @@ def attach(optimizers, local_batch, global_batch, group=None, model=None, force=
     it (or for a group fed by autograd, the 1-element group of probe_model='none') the buffer is multiplied before the collective."""
     if not dist.is_initialized() or (dist.get_world_size(group) == 1 and not force):
         return      # (force: a ONE-rank group still issues its collectives - bench.py --force-dp measures their cost on a 1-GPU box)
+    ac = getattr(model, 'ac', None)
+    if getattr(ac, 'return_norm', 'none') == 'percentile' and dist.get_world_size(group) > 1:
+        raise NotImplementedError("return_norm='percentile' with a data-parallel group of more than one rank: every rank would "
+                                  'normalise by the percentiles of its own shard (reducing them across ranks is not built)')
     w = float(local_batch) / float(global_batch)
     folded = set()
     if model is not None and hasattr(model, 'prepare_streams'):

@@ -254,6 +254,9 @@ _SIGNATURES = {
     'dm_cem_draw': (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     'dm_cem_update': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, _P, _P, _P, c_float, c_float, _P, _P, _P,
                               _P, _P, _P]),
+    'dm_twohot_decode': (c_int, [c_int, c_int, _P, c_int, _P, _P, _P]),
+    'dm_twohot_loss': (c_int, [c_int, c_int, c_int, _P, c_int, _P, _P, _P, c_float, _P, _P, _P, _P]),
+    'dm_return_norm': (c_int, [c_int, _P, c_float, c_float, c_float, c_float, c_int, _P, _P, _P, c_int, _P]),
     'dm_metric_accum': (c_int, [c_int, _P, _P, _P, _P, _P, _P]),
     'dm_batch_stats': (c_int, [c_int, _P, _P, _P, _P, _P]),
     'dm_masked_mean': (c_int, [c_int, c_int, _P, c_int, c_int, _P, c_int, _P, _P]),

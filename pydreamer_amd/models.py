@@ -23,7 +23,9 @@ empty (None or ''), the `vectorenv` section; the gate is imageless_gate(), DESIG
 embedding, the loss has no image term, obs needs no `image`, probe_model must be 'none', reward_input is ignored as in the
 reference; everything in the RSSM, the heads and the actor-critic works as beside an image), reward_decoder_categorical = a list
 of 2..32 reward values (DenseCategoricalSupportDecoder in place of the Normal reward head; it combines with all of
-the above).
+the above), critic_dist in {mse, twohot} (twohot: a categorical critic over critic_bins <= 256 symlog-spaced bins, read as a scalar
+through ActorCritic.value) and return_norm in {none, percentile} (the actor's advantages over the running percentile range of the
+imagined returns; not with a data-parallel group of more than one rank) - DESIGN 4.20; the task actor-critic only.
 """
 import contextlib
 import ctypes
@@ -1276,6 +1278,15 @@ METRIC_SLOTS = dict(loss_kl=0, loss_image=1, loss_reward=2, loss_terminal=3, ent
 GOALS_STAT_NAMES = ('mse_goals', 'var_goals') + tuple(f'mse_goal_age{a}' for a in (0, 5, 10, 50, 200, 1000))
 GOALS_METRIC_SLOTS = {k: 32 + i for i, k in enumerate(('loss_goal_direction', 'loss_goals_direction') + GOALS_STAT_NAMES)}
 METRIC_BUF_FLOATS = 48
+# the percentile return normalisation's three scalars (ActorCritic, return_norm='percentile'): free slots behind the goals probe's,
+# named by packed_metrics() only for a model that has the switch on, zero otherwise (dm_return_norm's out[2:5], copied on the device)
+RETURN_METRIC_SLOTS = dict(policy_return_lo=42, policy_return_hi=43, policy_return_scale=44)
+CRITIC_DISTS = ('mse', 'twohot')
+RETURN_NORMS = ('none', 'percentile')
+# the config keys Dreamer hands to its task ActorCritic under the same names (a conf without them - an older namespace - gets the
+# constructor's defaults).  The auxiliary critic and Plan2Explore's exploration ActorCritic keep the defaults
+AC_CONF_KEYS = ('critic_dist', 'critic_bins', 'critic_bin_range', 'return_norm', 'return_norm_lo', 'return_norm_hi',
+                'return_norm_decay', 'return_norm_limit')
 
 
 def _finish_backward(owner, grads, flat, direct, grad_loss):
@@ -1992,21 +2003,52 @@ class ActorCritic(_Params):
     """a2c.py:11-152."""
 
     def __init__(self, in_dim, out_actions, hidden_dim=400, hidden_layers=4, layer_norm=True, gamma=0.999, lambda_gae=0.95,
-                 entropy_weight=1e-3, target_interval=100, actor_grad='reinforce', actor_dist='onehot'):
+                 entropy_weight=1e-3, target_interval=100, actor_grad='reinforce', actor_dist='onehot', critic_dist='mse',
+                 critic_bins=255, critic_bin_range=20.0, return_norm='none', return_norm_lo=0.05, return_norm_hi=0.95,
+                 return_norm_decay=0.99, return_norm_limit=1.0):
         super().__init__()
         if actor_dist not in ACTOR_KINDS or actor_grad != 'reinforce':
             raise NotImplementedError(f'actor_dist={actor_dist!r} / actor_grad={actor_grad!r}: the HIP path builds onehot, '
                                       f'tanh_normal and normal_tanh actors with actor_grad=reinforce (actor_grad=dynamics '
                                       f'asserts in the reference itself, SURVEY 0.5)')
+        # the two-hot critic and the percentile return normalisation (DESIGN 4.20): refused before anything is allocated
+        if critic_dist not in CRITIC_DISTS:
+            raise ValueError(f'critic_dist={critic_dist!r}: one of {CRITIC_DISTS}')
+        if return_norm not in RETURN_NORMS:
+            raise ValueError(f'return_norm={return_norm!r}: one of {RETURN_NORMS}')
+        if int(critic_bins) != critic_bins or not 2 <= critic_bins <= 256:
+            raise ValueError(f'critic_bins={critic_bins}: 2 .. 256')
+        if not (math.isfinite(critic_bin_range) and critic_bin_range > 0):
+            raise ValueError(f'critic_bin_range={critic_bin_range}: a finite number > 0')
+        if not 0.0 <= return_norm_lo <= return_norm_hi <= 1.0:
+            raise ValueError(f'return_norm_lo={return_norm_lo}, return_norm_hi={return_norm_hi}: 0 <= lo <= hi <= 1')
+        if not 0.0 <= return_norm_decay < 1.0:
+            raise ValueError(f'return_norm_decay={return_norm_decay}: in [0, 1)')
+        if not (math.isfinite(return_norm_limit) and return_norm_limit > 0):
+            raise ValueError(f'return_norm_limit={return_norm_limit}: a finite number > 0')
         self.dist_kind = ACTOR_KINDS[actor_dist]
         self.in_dim, self.out_actions = in_dim, out_actions
         self.gamma, self.lambda_, self.entropy_weight = gamma, lambda_gae, entropy_weight
         self.target_interval, self.actor_grad, self.actor_dist = target_interval, actor_grad, actor_dist
+        self.critic_dist, self.critic_bins, self.critic_bin_range = critic_dist, int(critic_bins), float(critic_bin_range)
+        self.return_norm, self.return_norm_q = return_norm, (float(return_norm_lo), float(return_norm_hi))
+        self.return_norm_decay, self.return_norm_limit = float(return_norm_decay), float(return_norm_limit)
         actor_out_dim = out_actions if actor_dist == 'onehot' else 2 * out_actions      # a2c.py:35
+        critic_out_dim = self.critic_bins if critic_dist == 'twohot' else 1
         self.actor = MLP(in_dim, actor_out_dim, hidden_dim, hidden_layers, layer_norm)
-        self.critic = MLP(in_dim, 1, hidden_dim, hidden_layers, layer_norm)
-        self.critic_target = MLP(in_dim, 1, hidden_dim, hidden_layers, layer_norm)
+        self.critic = MLP(in_dim, critic_out_dim, hidden_dim, hidden_layers, layer_norm)
+        self.critic_target = MLP(in_dim, critic_out_dim, hidden_dim, hidden_layers, layer_norm)
         self.critic_target.requires_grad_(False)
+        if critic_dist == 'twohot':
+            # a fresh critic gives every bin the same logit: the decoded value of any state is the mean of the symmetric bins, ~0
+            out_layer = self.critic.model[3 * hidden_layers]
+            nn.init.zeros_(out_layer.weight)
+            nn.init.zeros_(out_layer.bias)
+            # the symlog-space support, fp32-rounded linspace; not part of state_dict (a function of two config keys)
+            self.register_buffer('bins', torch.linspace(-self.critic_bin_range, self.critic_bin_range, self.critic_bins),
+                                 persistent=False)
+        if return_norm == 'percentile':
+            self.register_buffer('return_range', torch.zeros(2))      # the running [lo, hi] percentiles of the imagined returns
         self.train_steps = 0
         self.sparse_cols = 0                  # trailing feature columns known to be one-hot samples (set by the owner)
         self.defer_target_update = False      # a caller that captures the step into a graph does the refresh + counter itself
@@ -2032,14 +2074,40 @@ class ActorCritic(_Params):
         return (J * 5) // 8 if J >= 9 else J
 
     def value_buffers(self, rows, device):
-        return dict(value_t=torch.empty(rows, 1, device=device), value=torch.empty(rows, 1, device=device),
+        bufs = dict(value_t=torch.empty(rows, 1, device=device), value=torch.empty(rows, 1, device=device),
                     c_acts=torch.empty(self.critic.acts_floats(rows), device=device))
+        if self.critic_dist == 'twohot':      # the two networks' logit rows, which the scalars above are decoded from
+            bufs.update(logits_t=torch.empty(rows, self.critic_bins, device=device),
+                        logits=torch.empty(rows, self.critic_bins, device=device))
+        return bufs
+
+    def value(self, feats, F_, rows, ws, target=False, window=None, out=None, acts=None, save_acts=False, sparse=True, logits=None):
+        """The scalar value of `rows` feature rows - the only place a critic's output becomes a scalar.  target: critic_target
+        instead of critic.  window / out / acts / save_acts: as MLP.fwd.  sparse=False: the feature rows' one-hot tail is not
+        announced to the first layer (Dreamer.inference / act never did).  Returns (value (rows, 1) - or `out` - , acts).
+        critic_dist='mse': exactly that MLP.fwd call.  'twohot': the MLP forward to K logits per row, then dm_twohot_decode
+        (symexp of the softmax-weighted mean of the bins); with a window, `logits` is the caller's full (rows_total, K) array."""
+        mlp = self.critic_target if target else self.critic
+        sp = self.sparse_cols if sparse else 0        # the one-hot latent columns at the end of a feature row (0: unknown)
+        if self.critic_dist == 'mse':
+            return mlp.fwd(feats, F_, rows, ws, acts=acts, save_acts=save_acts, sparse_cols=sp, window=window, out=out)
+        K = self.critic_bins
+        if window is not None:
+            rows_total, row0 = window
+            assert logits is not None and tuple(logits.shape) == (rows_total, K) and out is not None
+            mlp.fwd(feats, F_, rows, ws, acts=acts, save_acts=save_acts, sparse_cols=sp, window=window, out=logits)
+            lg, v = logits[row0:row0 + rows], out[row0:row0 + rows]
+        else:
+            lg, acts = mlp.fwd(feats, F_, rows, ws, acts=acts, save_acts=save_acts, sparse_cols=sp)
+            out = v = torch.empty(rows, 1, device=lg.device)
+        H.call('dm_twohot_decode', rows, K, H.fptr(lg), K, H.fptr(self.bins), H.fptr(v), H.stream())
+        return out, acts
 
     def forward_values(self, feats, F_, rows_total, row0, rows, ws, bufs):
         """critic_target and critic over rows [row0, row0 + rows) of the feature matrix (a2c.py:85,113)."""
-        sp = self.sparse_cols        # the one-hot latent columns at the end of a feature row (0: unknown)
-        self.critic_target.fwd(feats, F_, rows, ws, save_acts=False, sparse_cols=sp, window=(rows_total, row0), out=bufs['value_t'])
-        self.critic.fwd(feats, F_, rows, ws, acts=bufs['c_acts'], sparse_cols=sp, window=(rows_total, row0), out=bufs['value'])
+        w = (rows_total, row0)
+        self.value(feats, F_, rows, ws, target=True, window=w, out=bufs['value_t'], logits=bufs.get('logits_t'))
+        self.value(feats, F_, rows, ws, window=w, out=bufs['value'], acts=bufs['c_acts'], save_acts=True, logits=bufs.get('logits'))
 
     def training_step(self, features, actions, rewards, terminals, log_only=False, act_idx=None, ws=None,
                       actor_acts=None, actor_logits=None, overlap=None, mbuf=None, values=None, _begun=False):
@@ -2077,18 +2145,33 @@ class ActorCritic(_Params):
                H.fptr(adv), H.fptr(agae), H.fptr(vtgt), H.fptr(wgt), H.stream())
         rows = Hh * M
         lc = torch.empty(rows, device=dev)
-        dvalue = torch.zeros(J * M, device=dev)                      # value[-1] gets no gradient
         gw = float(getattr(self, 'grad_weight', 1.0))          # data-parallel shard weight B_r/B (dist.attach), gradients only
-        H.call('dm_critic_loss', rows, H.fptr(value), H.fptr(vtgt), H.fptr(wgt), gw / rows, H.fptr(lc), H.fptr(dvalue),
-               H.stream())
+        if self.critic_dist == 'twohot':
+            # the two-hot cross-entropy against symlog(value_target); the kernel zeroes the last M rows of the gradient itself
+            # (value[-1] gets no gradient) and the loss-only form (log_only) writes none at all
+            dvalue = None if log_only else torch.empty(J * M, self.critic_bins, device=dev)
+            H.call('dm_twohot_loss', rows, J * M, self.critic_bins, H.fptr(values['logits']), self.critic_bins, H.fptr(self.bins),
+                   H.fptr(vtgt), H.fptr(wgt), gw / rows, H.fptr(lc), H.fptr(dvalue), None, H.stream())
+        else:
+            dvalue = torch.zeros(J * M, 1, device=dev)               # value[-1] gets no gradient
+            H.call('dm_critic_loss', rows, H.fptr(value), H.fptr(vtgt), H.fptr(wgt), gw / rows, H.fptr(lc), H.fptr(dvalue),
+                   H.stream())
+        agae_a = agae            # what the actor loss is scaled by
+        if self.return_norm == 'percentile':
+            # advantages over max(limit, running percentile range of the imagined returns); the running range moves only on a
+            # training step.  No host synchronisation: the scale stays on the device
+            agae_a, rn_out = agae.clone(), torch.empty(5, device=dev)
+            H.call('dm_return_norm', rows, H.fptr(vtgt), self.return_norm_q[0], self.return_norm_q[1], self.return_norm_decay,
+                   self.return_norm_limit, int(torch.is_grad_enabled() and not log_only), H.fptr(self.return_range),
+                   H.fptr(rn_out), H.fptr(agae_a), rows, H.stream())
         la, ent = torch.empty(rows, device=dev), torch.empty(rows, device=dev)
         dlogits = torch.empty(rows, self.actor.out_dim, device=dev)
         if self.dist_kind == 0:
-            H.call('dm_actor_loss', rows, A, H.fptr(logits), H.ptr(act_idx), H.fptr(agae), H.fptr(wgt), self.entropy_weight,
+            H.call('dm_actor_loss', rows, A, H.fptr(logits), H.ptr(act_idx), H.fptr(agae_a), H.fptr(wgt), self.entropy_weight,
                    gw / rows, H.fptr(la), H.fptr(ent), H.fptr(dlogits), H.stream())
         else:
             H.call('dm_actor_loss_continuous', self.dist_kind, rows, A, H.fptr(logits), H.fptr(actions.contiguous()),
-                   H.fptr(agae), H.fptr(wgt), self.entropy_weight, gw / rows, H.fptr(la), H.fptr(ent), H.fptr(dlogits),
+                   H.fptr(agae_a), H.fptr(wgt), self.entropy_weight, gw / rows, H.fptr(la), H.fptr(ent), H.fptr(dlogits),
                    H.stream())
         value2d = value.view(J, M)
         reward1 = rewards.view(J, M)[1:]
@@ -2102,13 +2185,16 @@ class ActorCritic(_Params):
             loss_actor, loss_critic = loss_actor_v, loss_critic_v
         else:
             pa = dict(loss=loss_actor_v, x=feats, ldx=F_, rows=rows, acts=a_acts, dout=dlogits, ws=ws, overlap=overlap)
-            pc = dict(loss=loss_critic_v, x=feats, ldx=F_, rows=J * M, acts=c_acts, dout=dvalue.view(J * M, 1), ws=ws,
-                      overlap=overlap)
+            pc = dict(loss=loss_critic_v, x=feats, ldx=F_, rows=J * M, acts=c_acts, dout=dvalue, ws=ws, overlap=overlap)
             loss_actor = _HeadLoss.apply(self.actor, pa, *self.actor.param_list())
             loss_critic = _HeadLoss.apply(self.critic, pc, *self.critic.param_list())
             self._last_packs = (pa, pc)
         metrics = dict(loss_critic=loss_critic_v, loss_actor=loss_actor_v, policy_entropy=s[2], policy_value=s[3],
                        policy_value_im=s[4], policy_reward=s[5], policy_reward_std=std[0])
+        if self.return_norm == 'percentile':
+            s0 = RETURN_METRIC_SLOTS['policy_return_lo']
+            mbuf[s0:s0 + 3].copy_(rn_out[2:5])
+            metrics.update({k: mbuf[i] for k, i in RETURN_METRIC_SLOTS.items()})
         tensors = dict(value=value2d, value_target=vtgt, value_advantage=adv, value_advantage_gae=agae, value_weight=wgt)
         return (loss_actor, loss_critic), metrics, tensors
 
@@ -2138,7 +2224,8 @@ class Dreamer(nn.Module):
         self.wm = WorldModel(conf)
         self.ac = ActorCritic(in_dim=features_dim, out_actions=conf.action_dim, layer_norm=conf.layer_norm, gamma=conf.gamma,
                               lambda_gae=conf.lambda_gae, entropy_weight=conf.entropy, target_interval=conf.target_interval,
-                              actor_grad=conf.actor_grad, actor_dist=conf.actor_dist)
+                              actor_grad=conf.actor_grad, actor_dist=conf.actor_dist,
+                              **{k: getattr(conf, k) for k in AC_CONF_KEYS if hasattr(conf, k)})
         self.ac.sparse_cols = conf.stoch_dim * conf.stoch_discrete       # feature = [h | one-hot z] (rssm.py:83-84)
         # dreamer.py:43-52: the map probe sees [features | map_coord], the goals probe the bare features
         if conf.probe_model == 'map':
@@ -2295,6 +2382,8 @@ class Dreamer(nn.Module):
         slots = dict(METRIC_SLOTS)
         if isinstance(self.probe_model, (GoalsProbe, MapGoalsProbe)):
             slots.update(GOALS_METRIC_SLOTS)
+        if self.ac.return_norm == 'percentile':
+            slots.update(RETURN_METRIC_SLOTS)
         names = list(slots)
         return names, self.metric_buffer, [slots[n] for n in names]
 
@@ -2322,7 +2411,7 @@ class Dreamer(nn.Module):
         shp = self.wm.shape(1, B, 1)
         ws = self.wm.workspace(shp, feat.device)
         logits, _ = self.ac.actor.fwd(feat, feat.shape[1], B, ws, save_acts=False)
-        value, _ = self.ac.critic.fwd(feat, feat.shape[1], B, ws, save_acts=False)
+        value, _ = self.ac.value(feat, feat.shape[1], B, ws, sparse=False)
         action_distr = _torch_actor_distribution(self.ac.actor_dist, logits.view(1, B, -1))
         return action_distr, out_state, dict(policy_value=value.mean())
 
@@ -2373,7 +2462,7 @@ class Dreamer(nn.Module):
             dev = feat.device
             ws = self.wm.workspace(self.wm.shape(1, B, 1), dev)
             logits, _ = ac.actor.fwd(feat, feat.shape[1], B, ws, save_acts=False)
-            value, _ = ac.critic.fwd(feat, feat.shape[1], B, ws, save_acts=False)
+            value, _ = ac.value(feat, feat.shape[1], B, ws, sparse=False)
             if draw_mode == 1:
                 u_act = None
             else:

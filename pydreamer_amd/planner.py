@@ -155,7 +155,7 @@ class CEMPlanner:
             term, mu = dec.dream_means(outs)
             value = None
             if self.use_value:
-                value, _ = ac.critic.fwd(feats[(Hp - 1) * Mc:], F_, Mc, ws, save_acts=False, sparse_cols=ac.sparse_cols)
+                value, _ = ac.value(feats[(Hp - 1) * Mc:], F_, Mc, ws)
             H.call('dm_cem_update', kind, Bc, J, K, Hp, A, float(ac.gamma), H.fptr(mu), H.fptr(term), H.fptr(value), H.fptr(actions),
                    H.ptr(act_idx), H.fptr(prop), self.alpha, self.floor, H.fptr(prop), H.fptr(ret), H.ptr(elite), H.fptr(action),
                    H.fptr(stats), H.stream())
