@@ -103,7 +103,7 @@ int dm_version(void);                 /* ABI version, currently 17 (v2: LayerNor
                                               dm_ensemble_mse of Plan2Explore;
                                          v17: dm_gemm_plan_query added; later, still 17 (additions only): dm_cem_draw / dm_cem_update
                                               of the latent-space planner; dm_twohot_decode / dm_twohot_loss / dm_return_norm of the
-                                              two-hot critic and the percentile return normalisation */
+                                              two-hot critic and the percentile return normalisation; dm_mlp_plan_query */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
 size_t dm_workspace_bytes(const dm_shape* shp);   /* scratch needed by any call below for this shape */
@@ -303,8 +303,24 @@ typedef struct dm_mlp_grads {
   float* ln_b[DM_MAX_MLP_LAYERS];
 } dm_mlp_grads;
 size_t dm_mlp_acts_floats(int rows, int hidden, int layers);
-/* scratch floats (incl. the split-K region) dm_mlp_head_fwd / dm_mlp_head_bwd need for `rows` rows */
+/* scratch floats (incl. the split-K region) that are enough for dm_mlp_head_fwd* / dm_mlp_head_bwd over `rows` rows: an upper
+ * bound over in_dim <= 4096, both precisions, any sparse_cols, with or without `acts` (a wider input runs, without the optional
+ * pieces).  A smaller workspace is an error only below what the call must have; dm_mlp_plan_query tells. */
 size_t dm_mlp_ws_floats(int rows, int hidden, int layers);
+/* What a forward (which = 0) or backward (which = 1) call of a head would do, asked without a device: the plan every such call
+ * makes before it launches.  base_align (16 or 4): the alignment in bytes to assume for x and every weight matrix (the
+ * workspace counts as 16-byte aligned); normed: LayerNorm parameters given; precision: dm_mlp_params.precision; has_acts: an
+ * activation set is given; has_wpack / has_add0 / has_sample: the internal callers' packed weights, sparse addend and fused
+ * action sampler (the imagination rollout; 0 for the exported forwards); ws_bytes: the call's workspace.  The answer follows
+ * dm_mlp_chain_min_rows.  The backward ignores in_dim, out_dim, ldx, sparse_cols and the has_* arguments.
+ * out = {path: 0 row panels, 1 whole-MLP kernel, 2 per-layer launches; k0: the layer-0 columns multiplied densely (in_dim when
+ * there is no sparse split); sparse addend: 0 none, 1 computed by the call, 2 the caller's; 1 if the call packs the whole-MLP
+ * kernel's weights itself; 1 if it makes bf16 weight copies; 1 if the output layer rides in the last row-panel launch;
+ * need_floats - the workspace floats the plan touches - low 32 bits; its high 32 bits}.  Optional pieces are dropped, in the
+ * call as here, when ws_bytes has no room for them.  Returns DM_OK, or the error the call would return. */
+int dm_mlp_plan_query(int which, int rows, int in_dim, int hidden, int layers, int out_dim, int ldx, int sparse_cols,
+                      int base_align, int normed, int precision, int has_acts, int has_wpack, int has_add0, int has_sample,
+                      size_t ws_bytes, int32_t out[8]);
 /* acts may be NULL when no backward will follow (critic_target a2c.py:39,84; the dream's reward / terminal heads
  * dreamer.py:205-206; inference dreamer.py:92-111): activations then ping-pong through `ws` and nothing is saved.
  * For rows >= 16384 and hidden 400 each Linear -> LayerNorm -> ELU is ONE row-panel launch (csrc/panel.hip) and the output

@@ -304,25 +304,41 @@ int dm_dec_l4_wgrad_launch(int frames, int d, const float* G4, const float* x3, 
                            size_t ws_bytes, hipStream_t st);
 
 // fused MLP (mlp.hip)
-// chain_wpack (optional): fragment-major weights already packed by the caller (dm_mlp_chain_pack_launch) for the whole-MLP
-// kernel; null: packed here, per call, into the workspace
-// chain_sample (with chain_wpack, out_dim <= 32): the one-hot categorical draw of the output row (dreamer.py:198-200: the
-// rollout's action sampler) rides in the whole-MLP kernel's output stage - same rule and operation order as
-// dm_sample_onehot_launch(rows, 1, out_dim, out, ...), so the drawn indices are bit-identical to the stand-alone sampler's
 struct DmChainSample {
   const float* u;        // one uniform per row
   float* onehot;         // rows x out_dim (ldo floats per row)
   int ldo;
   int32_t* idx;          // optional
 };
-int dm_mlp_fwd_launch(int rows, int in_dim, int hidden, int layers, int out_dim, const float* x, int ldx,
-                      const dm_mlp_params* p, float* acts, int acts_total_rows, int acts_row_off, float* out, int ldout,
-                      void* ws, size_t ws_bytes, hipStream_t st, const float* chain_wpack = nullptr, int sparse_cols = 0,
-                      const float* chain_add0 = nullptr, const DmChainSample* chain_sample = nullptr);
-// chain_add0 (with chain_wpack packed for k0 = in_dim - sparse_cols): the caller already has the sparse columns' contribution
-// (the imagination rollout knows the latent's indices and gathers it, rssm.hip)
-// sparse_cols > 0: the LAST sparse_cols columns of x are mostly zero (one-hot latent groups); the row-panel path then
-// multiplies only the dense columns and adds the sparse ones' contribution as a sum of weight rows (dm_sparse_rows_launch)
+// One forward call of an MLP head.  mlp.hip plans it (which path, which optional pieces, where in the workspace) before it
+// launches anything; a combination the plan refuses is an error, not a fall-back.
+struct DmMlpFwd {
+  int rows = 0, in_dim = 0, hidden = 0, layers = 0, out_dim = 0;
+  const float* x = nullptr; int ldx = 0;
+  const dm_mlp_params* p = nullptr;
+  // optional activation set, carved (dm_mlp_acts_floats) for acts_total_rows rows, of which this call fills rows
+  // [acts_row_off, acts_row_off + rows); null (heads nobody differentiates): activations ping-pong through the workspace
+  float* acts = nullptr; int acts_total_rows = 0, acts_row_off = 0;
+  float* out = nullptr; int ldout = 0;
+  // > 0: the LAST sparse_cols columns of x are mostly zero (one-hot latent groups); where the plan allows, layer 0 multiplies
+  // only the dense columns and adds the sparse ones' contribution as a sum of weight rows (dm_sparse_rows_launch)
+  int sparse_cols = 0;
+  // whole-MLP kernel only (ignored on the other paths): fragment-major weights already packed by the caller
+  // (dm_mlp_chain_pack_launch); null: packed per call, into the workspace
+  const float* wpack = nullptr;
+  // requires wpack, packed for k0 = in_dim - sparse_cols: the caller already has the sparse columns' contribution (the
+  // imagination rollout knows the latent's indices and gathers it, rssm.hip)
+  const float* add0 = nullptr;
+  // whole-MLP kernel only, an error elsewhere (out_dim <= 32): the one-hot categorical draw of the output row
+  // (dreamer.py:198-200: the rollout's action sampler) rides in the kernel's output stage - same rule and operation order as
+  // dm_sample_onehot_launch(rows, 1, out_dim, out, ...), so the drawn indices are bit-identical to the stand-alone sampler's
+  const DmChainSample* sample = nullptr;
+};
+enum { DM_MLP_PANEL = 0, DM_MLP_CHAIN = 1, DM_MLP_PER_LAYER = 2 };
+int dm_mlp_fwd_launch(const DmMlpFwd& q, void* ws, size_t ws_bytes, hipStream_t st);
+// The path (DM_MLP_*) dm_mlp_fwd_launch takes for q given room for every optional piece, and (k0, optional) the layer-0
+// columns it multiplies densely (in_dim: all); < 0: the error the launch would return.  No launch; reads no operand.
+int dm_mlp_fwd_path(const DmMlpFwd& q, int* k0 = nullptr);
 
 // row-panel Linear + LayerNorm/ELU kernels for the 400-wide MLP heads (panel.hip)
 bool dm_panel_ok(int rows, int hidden);

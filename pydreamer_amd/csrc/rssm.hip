@@ -887,17 +887,17 @@ struct RolloutCtx : RssmDims {
         ar.off = mark; ar.ok = true;
       }
     }
-    if (dm_mlp_chain_ok(M, F, Hm, L, AO, feats, F, actor) && !dm_panel_ok(M, Hm)) {
-      float* wpk = ar.take(dm_mlp_chain_pack_floats(F, L));
-      if (ar.ok) {
-        actor_wpack = wpk;
-        if (C != 0 && pidx && dm_mlp_chain_sparse_ok(F, Z) && dm_z_embed_ok(Hm)) {
-          const size_t mark = ar.off;
-          float* wt = ar.take((size_t)F * Hm);
-          float* ad = ar.take((size_t)M * Hm);
-          if (ar.ok) { actor_w0t = wt; actor_add0 = ad; }
-          else { ar.off = mark; ar.ok = true; }
-        }
+    // the actor's call as every step issues it: mlp.hip's plan says whether it runs on the whole-MLP kernel (weights packed once
+    // for all H steps) and whether that kernel then takes the z columns' contribution from here
+    if (dm_mlp_fwd_path(actor_call(0)) == DM_MLP_CHAIN) {
+      actor_wpack = ar.take(dm_mlp_chain_pack_floats(F, L));
+      if (actor_wpack && C != 0 && pidx && dm_z_embed_ok(Hm)) {
+        const size_t mark = ar.off;
+        actor_w0t = ar.take((size_t)F * Hm);
+        actor_add0 = ar.take((size_t)M * Hm);
+        int k0 = F;
+        if (ar.ok) dm_mlp_fwd_path(actor_call(0), &k0);
+        if (k0 == F) { actor_w0t = actor_add0 = nullptr; ar.off = mark; ar.ok = true; }
       }
     }
     fuse_act = adist == 0 && actor_wpack && g_rollout_fuse_act;
@@ -907,14 +907,23 @@ struct RolloutCtx : RssmDims {
   // the sampled action's index of step i (scratch if the caller wants none; null when there is neither)
   int32_t* act_idx_of(int i) const { return act_idx ? act_idx + (size_t)i * M : aidx; }
 
+  // the actor's forward of step i, without the fused sampler
+  DmMlpFwd actor_call(int i) const {
+    const bool keep = actor_acts != nullptr;
+    DmMlpFwd q;
+    q.rows = M; q.in_dim = F; q.hidden = Hm; q.layers = L; q.out_dim = AO;
+    q.x = feats + (size_t)i * M * F; q.ldx = F; q.p = actor;
+    q.acts = keep ? actor_acts : macts; q.acts_total_rows = keep ? H * M : M; q.acts_row_off = keep ? i * M : 0;
+    q.out = keep ? actor_logits + (size_t)i * M * AO : logits_ws; q.ldout = AO;
+    q.wpack = actor_wpack; q.add0 = actor_add0; q.sparse_cols = actor_add0 ? Z : 0;
+    return q;
+  }
   // action ~ OneHotCategorical(actor(feature))                                          dreamer.py:195-200
   // with actor_acts the activations of all H steps are kept (rows i*M..) so ActorCritic's policy-gradient backward
   // reuses them instead of recomputing forward_actor(features[:-1]) (the reference's own TODO, a2c.py:119)
   int rollout_actor(int i) const {
     const float* cur = feats + (size_t)i * M * F;
     float* act = actions + (size_t)i * M * A;
-    const bool keep = actor_acts != nullptr;
-    float* logits = keep ? actor_logits + (size_t)i * M * AO : logits_ws;
     if (actor_add0) {
       if (i == 0) DM_TRY(dm_sparse_rows_launch(M, Hm, Z, cur + D, F, actor_w0t + (size_t)D * Hm, actor_add0, Hm, st));
       else DM_TRY(dm_z_embed_launch(M, Hm, S, C, pidx, nullptr, actor_w0t + (size_t)D * Hm, nullptr, nullptr, 0, nullptr, nullptr,
@@ -922,8 +931,10 @@ struct RolloutCtx : RssmDims {
     }
     int32_t* ai = act_idx_of(i);
     const DmChainSample samp = {u_act + (size_t)i * M, act, A, ai};
-    DM_TRY(dm_mlp_fwd_launch(M, F, Hm, L, AO, cur, F, actor, keep ? actor_acts : macts, keep ? H * M : M, keep ? i * M : 0, logits,
-                             AO, sk, skb, st, actor_wpack, actor_add0 ? Z : 0, actor_add0, fuse_act ? &samp : nullptr));
+    DmMlpFwd q = actor_call(i);
+    if (fuse_act) q.sample = &samp;
+    const float* logits = q.out;
+    DM_TRY(dm_mlp_fwd_launch(q, sk, skb, st));
     if (fuse_act) return DM_OK;
     if (adist == 0)
       return dm_sample_onehot_launch(M, 1, A, logits, A, u_act + (size_t)i * M, nullptr, act, A, ai, nullptr, nullptr, st);

@@ -221,6 +221,7 @@ _SIGNATURES = {
     'dm_gemm_dma_enable': (c_int, [c_int]),
     'dm_gemm_plan_query': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_size_t,
                                    POINTER(c_int32)]),
+    'dm_mlp_plan_query': (c_int, [c_int] * 15 + [c_size_t, POINTER(c_int32)]),
     'dm_convt_kskip_enable': (c_int, [c_int]),
     'dm_kl_staged_enable': (c_int, [c_int]),
     'dm_dec_l4_bwd_direct_enable': (c_int, [c_int]),

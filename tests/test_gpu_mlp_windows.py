@@ -37,6 +37,7 @@ WINDOWS = {
     520: [(0, 250, PER_LAYER), (250, 270, CHAIN)],      # below / above the 256-row threshold of the whole-MLP kernel
     600: [(100, 300, CHAIN)],                           # a middle window alone
 }
+UNALIGNED_X = {PANEL: PANEL, CHAIN: PER_LAYER, PER_LAYER: PER_LAYER}      # the kernel of such a window at ldx = in_dim + 1
 
 
 def _rel_l2(a, b):
@@ -96,10 +97,19 @@ def _path(pins):
     return PER_LAYER
 
 
-def _expected(path, pad):
-    """ldx = in_dim + 1: no row of x is 16-byte aligned.  The whole-MLP kernel hands over to the per-layer launches, the row
-    panels stay and take their scalar-load instantiation (the profiler row does not tell the two apart; the stride does)."""
-    return PER_LAYER if (pad & 3) and path == CHAIN else path
+def _expected(hip, m, rows, path, pad, sparse):
+    """The plan's answer for a window of `rows` rows at ldx = in_dim + pad (dm_mlp_plan_query: the mlp_fwd_plan a call runs;
+    tests/test_mlp_plan_cpu.py holds it to the dispatch table).  With 16-byte rows of x that is the kernel WINDOWS names.
+    ldx = in_dim + 1: no row of x is 16-byte aligned - the whole-MLP kernel hands over to the per-layer launches, the row panels
+    stay and take their scalar-load instantiation (the profiler row does not tell the two apart; the stride does)."""
+    out = (ctypes.c_int32 * 8)()
+    rc = hip.lib().dm_mlp_plan_query(0, rows, IN, HID, LAYERS, m.out_dim, IN + pad, sparse, 16, 1, m.struct().precision, 1, 0, 0, 0,
+                                     512 << 20, out)
+    assert rc == 0, hip.lib().dm_last_error()
+    want = (PANEL, CHAIN, PER_LAYER)[out[0]]
+    pinned = UNALIGNED_X[path] if pad & 3 else path
+    assert want == pinned, f'{rows} rows, ldx {IN + pad}: the plan says {want}, the table {pinned}'
+    return want
 
 
 def _ws():
@@ -173,7 +183,7 @@ def _run_windows(hip, c, rows_total, windows, pad, ws, bit_check=True):
     acts = _sentinel(m.acts_floats(rows_total))
     done = []
     for row0, rows, path in windows:
-        want = _expected(path, pad)
+        want = _expected(hip, m, rows, path, pad, sp)
         pins = GP.profiled_rows(hip, lambda: m.fwd(xs, ld, rows, ws, acts=acts, sparse_cols=sp, window=(rows_total, row0), out=out))
         got = _path(pins)
         assert got == want, f'window [{row0}, {row0 + rows}) of {rows_total}, ldx {ld}: {got} answered, {want} expected'
