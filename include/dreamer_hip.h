@@ -103,10 +103,18 @@ int dm_version(void);                 /* ABI version, currently 17 (v2: LayerNor
                                               dm_ensemble_mse of Plan2Explore;
                                          v17: dm_gemm_plan_query added; later, still 17 (additions only): dm_cem_draw / dm_cem_update
                                               of the latent-space planner; dm_twohot_decode / dm_twohot_loss / dm_return_norm of the
-                                              two-hot critic and the percentile return normalisation; dm_mlp_plan_query */
+                                              two-hot critic and the percentile return normalisation; dm_mlp_plan_query;
+                                              dm_workspace_query */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
-size_t dm_workspace_bytes(const dm_shape* shp);   /* scratch needed by any call below for this shape */
+/* Scratch that serves any call below for this shape: the maximum of the fused operators' own workspace layouts (each sized
+ * with every optional piece the shape could select), plus a slack of 4096 floats, in bytes.  Touches no device. */
+size_t dm_workspace_bytes(const dm_shape* shp);
+/* The terms of that maximum, in floats: parts[0..8) = conv encoder forward, conv encoder backward, conv decoder forward, conv
+ * decoder backward, dm_rssm_sequence_fwd, dm_rssm_sequence_bwd, dm_dream_rollout (M = T * B * I rows), the MLP heads
+ * (dm_mlp_ws_floats over (H + 1) * T * B * I rows).  A convolution part is 0 where its entry points refuse the geometry.  A
+ * call given exactly its part runs the schedule it runs on dm_workspace_bytes.  n: room in parts (>= 8). */
+int dm_workspace_query(const dm_shape* shp, size_t* parts, int n);
 /* A stream confined to the CUs whose bit is set in mask[0..words) (32 CUs per word), for CU-reservation experiments (no
  * reference counterpart: torch exposes no CU masks). */
 int dm_stream_create_cu_mask(const uint32_t* mask, int words, void** stream);

@@ -43,6 +43,10 @@ struct DmArena {
     off += n;
     return r;
   }
+  // Optional blocks of an operator's workspace layout.  fits(): every take so far was granted - always on an arena without a
+  // base, which only measures; give_back(mark): forget the takes made since `off` was `mark` (the call goes on without them).
+  bool fits() const { return ok || base == nullptr; }
+  void give_back(size_t mark) { off = mark; ok = true; }
 };
 
 // ---- weight-gradient side stream (lib.hip; include/dreamer_hip.h dm_wgrad_side_arm / _join) -------
@@ -377,6 +381,13 @@ bool dm_prof_active();                                                          
 
 // split-K partial region carved at the front of every operator workspace
 static const size_t DM_SPLITK_FLOATS = (size_t)16 * 1024 * 1024;
+// Workspace floats of each translation unit's fused operators at this shape: their layout functions run on an arena without a
+// base, every optional piece wanted that the shape alone could select (lib.hip dm_workspace_bytes / dm_workspace_query).
+// parts: conv {encoder forward, encoder backward, decoder forward, decoder backward} - 0 where the entry points refuse the
+// geometry; rssm {posterior chain, BPTT}.  Each returns the largest of its parts.  No device is touched.
+size_t dm_conv_ws_floats(const dm_shape* s, size_t parts[4] = nullptr);
+size_t dm_rssm_ws_floats(const dm_shape* s, size_t parts[2] = nullptr);
+size_t dm_rollout_ws_floats(const dm_shape* s);
 
 // bf16 operand path: round-to-nearest-even fp32 -> bf16 (bit pattern in the low 16 bits), 8-element MFMA fragments
 // (v_cvt_pk_bf16_f32: two conversions per instruction - the integer form cost ~5 VALU operations per element and made

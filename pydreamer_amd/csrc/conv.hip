@@ -515,6 +515,7 @@ struct EncGeom {
   bool valid(const dm_shape* s) const {
     return s->img == 64 && hs[3] == 2 && s->E == 8 * d * 4 && ch >= 1 && d >= 1;
   }
+  bool valid_planes(const dm_shape* s) const { return s->img == 64 && hs[3] == 2 && direct0; }      // reward_input: E is the caller's
 };
 
 struct DecGeom {
@@ -608,6 +609,16 @@ __global__ void __launch_bounds__(256) nhwc_to_chw_flat_ld_kernel(size_t n, int 
   }
 }
 
+// The forward's workspace: [split-K | the direct layer-1 kernel's transposed weights | reward_input: its per-frame bias].  On an
+// arena without a base it sizes.
+struct EncFwdWs { float *wt, *fb; };
+static size_t enc_fwd_layout(DmArena ar, const EncGeom& g, bool planes, EncFwdWs* w) {
+  ar.take(DM_SPLITK_FLOATS);
+  w->wt = ar.take(g.direct0 ? (size_t)48 * g.d : 0);
+  w->fb = ar.take(planes ? (size_t)g.N * g.d : 0);
+  return ar.off;
+}
+
 // reward / terminal (N,): non-null = reward_input, p->w[0] is (d, 5, 4, 4) and the two planes are folded into layer 1
 // (conv_direct.hip); ld: leading dimension of `embed` (the caller may keep other encoders' outputs behind the image embedding)
 static int conv_encoder_fwd_impl(const dm_shape* shp, const float* image, const dm_conv_params* p, float* acts, float* embed,
@@ -616,7 +627,7 @@ static int conv_encoder_fwd_impl(const dm_shape* shp, const float* image, const 
   EncGeom g(shp);
   const bool planes = reward != nullptr;
   if (planes) {
-    DM_REQUIRE(shp->img == 64 && g.hs[3] == 2 && g.direct0 && ld >= 32 * g.d, DM_E_SHAPE,
+    DM_REQUIRE(g.valid_planes(shp) && ld >= 32 * g.d, DM_E_SHAPE,
                "conv_encoder planes: built for 3 x 64 x 64 frames and cnn_depth in {8,16,32,48,64} (img=%d, ch=%d, depth=%d, ld=%d)",
                shp->img, shp->img_ch, shp->cnn_depth, ld);
   } else {
@@ -626,7 +637,9 @@ static int conv_encoder_fwd_impl(const dm_shape* shp, const float* image, const 
   hipStream_t st = (hipStream_t)stream;
   EncActs a;
   enc_carve(g, acts, (size_t)1 << 60, &a);
-  DM_REQUIRE(ws_bytes >= DM_SPLITK_FLOATS * sizeof(float), DM_E_WORKSPACE, "conv_encoder_fwd: workspace too small");
+  EncFwdWs w;
+  const size_t need = enc_fwd_layout(DmArena(ws, ws_bytes), g, planes, &w);
+  DM_REQUIRE(need <= ws_bytes / sizeof(float), DM_E_WORKSPACE, "conv_encoder_fwd: workspace too small (need %zu floats)", need);
   DmTwinScope tw((shp->flags & DM_FLAG_BF16) != 0);
   enc_register_twins(g, a, false, false);
   dm_twin_arena_note(acts, dm_twins_on());
@@ -642,17 +655,12 @@ static int conv_encoder_fwd_impl(const dm_shape* shp, const float* image, const 
   if (g.N == 0) return DM_OK;
   for (int l = 0; l < 4; ++l) {
     if (l == 0 && g.direct0) {      // 3 -> d channels: one direct kernel on the frame, no patch matrix (conv_direct.hip)
-      DmArena ar(ws, ws_bytes);
-      ar.take(DM_SPLITK_FLOATS);
-      float* wt = ar.take((size_t)48 * g.d);
-      float* fb = ar.take(planes ? (size_t)g.N * g.d : 0);
-      DM_REQUIRE(ar.ok, DM_E_WORKSPACE, "conv_encoder_fwd: workspace too small for the layer-1 weights");
       unsigned short* y0h = dm_twin_of(a.y[0], false);
       if (planes)
-        DM_TRY(dm_enc_l1_fwd_planes_launch(g.N, g.d, shape_u8(shp) ? 1 : 0, image, p->w[0], p->b[0], reward, terminal, wt, fb,
+        DM_TRY(dm_enc_l1_fwd_planes_launch(g.N, g.d, shape_u8(shp) ? 1 : 0, image, p->w[0], p->b[0], reward, terminal, w.wt, w.fb,
                                            a.y[0], y0h, st));
       else
-        DM_TRY(dm_enc_l1_fwd_launch(g.N, g.d, shape_u8(shp) ? 1 : 0, image, p->w[0], p->b[0], wt, a.y[0], y0h, st));
+        DM_TRY(dm_enc_l1_fwd_launch(g.N, g.d, shape_u8(shp) ? 1 : 0, image, p->w[0], p->b[0], w.wt, a.y[0], y0h, st));
       if (y0h) dm_twin_mark(a.y[0]);
       continue;
     }
@@ -701,6 +709,49 @@ extern "C" int dm_conv_encoder_fwd_planes(const dm_shape* shp, const float* imag
   return conv_encoder_fwd_impl(shp, image, p, acts, embed, ld_embed, reward, terminal, ws, ws_bytes, stream);
 }
 
+// The backward's workspace.  ga / gb: the gradient ping-pong (ga holds the largest, layer 1's output gradient); dwr: a weight
+// gradient in the repacked layout; dxcol: the explicit patch-matrix gradient of the layers that do not take the gather form,
+// and the direct layer-1 kernels' partials.  On an arena without a base it sizes.
+struct EncBwdWs {
+  float *splitk, *ga, *gb, *dwr, *dxcol, *gpad, *wcat;
+  int *t_rowoff, *t_koff, *t_klist; int2* t_ctab;
+  unsigned short *ga_h, *gb_h, *wcat_h;
+  size_t gmax, xcmax;      // floats of ga and of dxcol
+};
+static size_t enc_bwd_layout(DmArena ar, const EncGeom& g, bool tw_on, EncBwdWs* w) {
+  w->splitk = ar.take(DM_SPLITK_FLOATS);
+  const size_t gmax = w->gmax = g.rows[0] * g.cout[0];
+  w->ga = ar.take(gmax);
+  w->gb = ar.take(g.rows[1] * g.cout[1]);
+  w->dwr = ar.take((size_t)g.cout[3] * g.kdim[3]);
+  size_t xcmax = 0;
+  for (int l = 1; l < 4; ++l) if (g.rows[l] * g.kdim[l] > xcmax) xcmax = g.rows[l] * g.kdim[l];
+  w->dxcol = ar.take(w->xcmax = xcmax);
+  // gather-form data gradient (see convt_* above: the data gradient of a stride-2 convolution IS a transposed convolution)
+  size_t padmax = 0, tabmax = 0, wcmax = 0, klmax = 0;
+  for (int l = 1; l < 4; ++l)
+    if (convt_gather_ok(4, g.cout[l], g.cin[l], g.hs[l], (size_t)g.N)) {
+      const size_t hp = g.hs[l] + 2, Hc = g.hs[l] + 1;
+      if ((size_t)g.N * hp * hp * g.cout[l] > padmax) padmax = (size_t)g.N * hp * hp * g.cout[l];
+      if ((size_t)g.N * Hc * Hc > tabmax) tabmax = (size_t)g.N * Hc * Hc;
+      if ((size_t)16 * g.cin[l] * g.cout[l] > wcmax) wcmax = (size_t)16 * g.cin[l] * g.cout[l];
+      const size_t kl = convt_klist_ints((size_t)g.N * Hc * Hc, 4 * g.cout[l]);
+      if (kl > klmax) klmax = kl;
+    }
+  w->gpad = ar.take(padmax);
+  w->t_rowoff = (int*)ar.take(tabmax);
+  w->t_ctab = (int2*)ar.take(2 * tabmax);
+  w->t_koff = (int*)ar.take(wcmax ? 4 * 1024 : 0);
+  w->wcat = ar.take(wcmax);
+  w->t_klist = (int*)ar.take(klmax);      // (sized whether or not the switch is on)
+  // bf16 mode: twins of the two gradient ping-pong buffers and of the class-concatenated weights; the zero-padded gradient
+  // copy is written as bf16 only (it lives in the fp32 copy's storage)
+  w->ga_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(gmax) : 0);
+  w->gb_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(g.rows[1] * g.cout[1]) : 0);
+  w->wcat_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(wcmax) : 0);
+  return ar.off;
+}
+
 static int conv_encoder_bwd_impl(const dm_shape* shp, const float* image, const dm_conv_params* p, const float* acts,
                                  const float* dembed, int ld, const float* reward, const float* terminal, const dm_conv_grads* gr,
                                  void* ws, size_t ws_bytes, void* stream) {
@@ -708,7 +759,7 @@ static int conv_encoder_bwd_impl(const dm_shape* shp, const float* image, const 
   EncGeom g(shp);
   const bool planes = reward != nullptr;
   if (planes) {
-    DM_REQUIRE(shp->img == 64 && g.hs[3] == 2 && g.direct0 && ld >= 32 * g.d, DM_E_SHAPE,
+    DM_REQUIRE(g.valid_planes(shp) && ld >= 32 * g.d, DM_E_SHAPE,
                "conv_encoder planes: built for 3 x 64 x 64 frames and cnn_depth in {8,16,32,48,64} (img=%d, ch=%d, depth=%d, ld=%d)",
                shp->img, shp->img_ch, shp->cnn_depth, ld);
   } else {
@@ -717,45 +768,13 @@ static int conv_encoder_bwd_impl(const dm_shape* shp, const float* image, const 
   hipStream_t st = (hipStream_t)stream;
   EncActs a;
   enc_carve(g, const_cast<float*>(acts), (size_t)1 << 60, &a);
-  DmArena ar(ws, ws_bytes);
-  float* splitk = ar.take(DM_SPLITK_FLOATS);
-  const size_t gmax = g.rows[0] * g.cout[0];
-  float* ga = ar.take(gmax);
-  float* gb = ar.take(g.rows[1] * g.cout[1]);
-  float* dwr = ar.take((size_t)g.cout[3] * g.kdim[3]);
-  size_t xcmax = 0;
-  for (int l = 1; l < 4; ++l) if (g.rows[l] * g.kdim[l] > xcmax) xcmax = g.rows[l] * g.kdim[l];
-  float* dxcol = ar.take(xcmax);
-  // gather-form data gradient (see convt_* above: the data gradient of a stride-2 convolution IS a transposed convolution)
-  size_t padmax = 0, tabmax = 0, wcmax = 0;
-  for (int l = 1; l < 4; ++l)
-    if (convt_gather_ok(4, g.cout[l], g.cin[l], g.hs[l], (size_t)g.N)) {
-      const size_t hp = g.hs[l] + 2, Hc = g.hs[l] + 1;
-      if ((size_t)g.N * hp * hp * g.cout[l] > padmax) padmax = (size_t)g.N * hp * hp * g.cout[l];
-      if ((size_t)g.N * Hc * Hc > tabmax) tabmax = (size_t)g.N * Hc * Hc;
-      if ((size_t)16 * g.cin[l] * g.cout[l] > wcmax) wcmax = (size_t)16 * g.cin[l] * g.cout[l];
-    }
-  float* gpad = ar.take(padmax);
-  int* t_rowoff = (int*)ar.take(tabmax);
-  int2* t_ctab = (int2*)ar.take(2 * tabmax);
-  int* t_koff = (int*)ar.take(wcmax ? 4 * 1024 : 0);
-  float* wcat = ar.take(wcmax);
-  size_t klmax = 0;
-  for (int l = 1; l < 4; ++l)
-    if (convt_gather_ok(4, g.cout[l], g.cin[l], g.hs[l], (size_t)g.N)) {
-      const size_t kl = convt_klist_ints((size_t)g.N * (g.hs[l] + 1) * (g.hs[l] + 1), 4 * g.cout[l]);
-      if (kl > klmax) klmax = kl;
-    }
-  int* t_klist = (int*)ar.take(klmax);      // (sized whether or not the switch is on)
-  const bool kskip = g_convt_kskip && !(shp->flags & DM_FLAG_BF16);
-  // bf16 mode: twins of the two gradient ping-pong buffers and of the class-concatenated weights; the zero-padded gradient
-  // copy is written as bf16 only (it lives in the fp32 copy's storage)
   DmTwinScope tw((shp->flags & DM_FLAG_BF16) != 0);
   const bool tw_on = dm_twins_on();
-  unsigned short* ga_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(gmax) : 0);
-  unsigned short* gb_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(g.rows[1] * g.cout[1]) : 0);
-  unsigned short* wcat_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(wcmax) : 0);
-  DM_REQUIRE(ar.ok, DM_E_WORKSPACE, "conv_encoder_bwd: workspace too small (need %zu floats)", ar.off);
+  EncBwdWs w;
+  const size_t need = enc_bwd_layout(DmArena(ws, ws_bytes), g, tw_on, &w);
+  DM_REQUIRE(need <= ws_bytes / sizeof(float), DM_E_WORKSPACE, "conv_encoder_bwd: workspace too small (need %zu floats)", need);
+  const auto& [splitk, ga, gb, dwr, dxcol, gpad, wcat, t_rowoff, t_koff, t_klist, t_ctab, ga_h, gb_h, wcat_h, gmax, xcmax] = w;
+  const bool kskip = g_convt_kskip && !(shp->flags & DM_FLAG_BF16);
   const size_t skb = DM_SPLITK_FLOATS * sizeof(float);
   const bool arena_tw = dm_twin_arena_valid(acts);      // the forward that filled `acts` wrote its twins
   enc_register_twins(g, a, arena_tw, arena_tw);
@@ -911,6 +930,7 @@ struct DecActs {
   float* x[5];     // x[0] = fc output (N,32d); x[l] = NHWC activations after layer l (x[4] = prediction)
   unsigned short* xh[5];     // bf16 mode: twins of x[0..2] and wr[1..4], behind everything else (dm_conv_decoder_pred_offset holds)
   unsigned short* wrh[5];
+  size_t pred_off;           // float offset of x[4] in the arena
 };
 static inline size_t dec_x_elems(const DecGeom& g, int l) { return l == 0 ? (size_t)g.N * g.cin[1] : g.rows_b[l] * g.cout[l]; }
 static inline size_t dec_w_elems(const DecGeom& g, int l) { return (size_t)g.cin[l] * g.k[l] * g.k[l] * g.cout[l]; }
@@ -920,6 +940,7 @@ static size_t dec_carve(const DecGeom& g, float* base, size_t cap_floats, DecAct
   if (a) a->x[0] = x0;
   for (int l = 1; l <= 4; ++l) {
     float* w = ar.take((size_t)g.cin[l] * g.k[l] * g.k[l] * g.cout[l]);
+    if (a && l == 4) a->pred_off = ar.off;
     float* xx = ar.take(g.rows_b[l] * g.cout[l]);
     if (a) { a->wr[l] = w; a->x[l] = xx; }
   }
@@ -947,13 +968,50 @@ extern "C" size_t dm_conv_decoder_acts_floats(const dm_shape* shp) {
 extern "C" size_t dm_conv_decoder_pred_offset(const dm_shape* shp) {
   if (!shp) return 0;
   DecGeom g(shp);
-  size_t off = dm_align_up((size_t)g.N * g.cin[1], 64);                  // mirrors dec_carve
-  for (int l = 1; l <= 4; ++l) {
-    off += dm_align_up((size_t)g.cin[l] * g.k[l] * g.k[l] * g.cout[l], 64);
-    if (l == 4) break;
-    off += dm_align_up(g.rows_b[l] * g.cout[l], 64);
+  DecActs a;
+  dec_carve(g, nullptr, 0, &a);
+  return a.pred_off;
+}
+
+// The forward's workspace.  ycol: the column matrix of the layers that take neither the gather form nor (image layer) the
+// direct kernel; w4: that kernel's class-ordered weights; then the gather form's zero-padded input copy, gather / scatter
+// tables, class-concatenated weights and k-tile lists.  On an arena without a base it sizes.
+struct DecFwdWs {
+  float *splitk, *ycol, *w4, *xpad, *wcat;
+  int *t_rowoff, *t_koff, *t_klist; int2* t_ctab;
+  unsigned short* wcat_h;
+};
+static bool dec_fwd_direct4(const DecGeom& g) { return dm_dec_l4_direct_ok(g.ch, g.d, g.hsm[4], g.k[4]); }      // d -> 3 channels: conv_direct.hip, no column matrix
+static size_t dec_fwd_layout(DmArena ar, const DecGeom& g, bool tw_on, DecFwdWs* w) {
+  const size_t n = (size_t)g.N;
+  w->splitk = ar.take(DM_SPLITK_FLOATS);
+  const bool direct4 = dec_fwd_direct4(g);
+  size_t colmax = 0;
+  for (int l = 1; l <= (direct4 ? 3 : 4); ++l) {
+    const size_t c = n * g.hsm[l] * g.hsm[l] * g.k[l] * g.k[l] * g.cout[l];
+    if (c > colmax) colmax = c;
   }
-  return off;
+  w->ycol = ar.take(colmax);
+  w->w4 = ar.take(direct4 ? dm_dec_l4_w4_floats(g.d) : 0);
+  size_t padmax = 0, tabmax = 0, wcmax = 0, klmax = 0;
+  for (int l = 1; l <= 4; ++l)
+    if (convt_gather_ok(g.k[l], g.cin[l], g.cout[l], g.hsm[l], n)) {
+      const int ta = g.k[l] / 2, hp = g.hsm[l] + 2 * (ta - 1), Hc = g.hsm[l] + ta - 1;
+      const size_t pad = n * hp * hp * g.cin[l], tab = n * Hc * Hc, wc = (size_t)4 * g.cout[l] * ta * ta * g.cin[l];
+      const size_t kl = convt_klist_ints(tab, ta * ta * g.cin[l]);
+      if (pad > padmax) padmax = pad;
+      if (tab > tabmax) tabmax = tab;
+      if (wc > wcmax) wcmax = wc;
+      if (kl > klmax) klmax = kl;
+    }
+  w->xpad = ar.take(padmax);
+  w->t_rowoff = (int*)ar.take(tabmax);
+  w->t_ctab = (int2*)ar.take(2 * tabmax);
+  w->t_koff = (int*)ar.take(wcmax ? 9 * 1024 : 0);
+  w->wcat = ar.take(wcmax);
+  w->wcat_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(wcmax) : 0);
+  w->t_klist = (int*)ar.take(klmax);      // (sized whether or not the switch is on)
+  return ar.off;
 }
 
 extern "C" int dm_conv_decoder_mse_fwd(const dm_shape* shp, const float* feat, int ldf, const float* target,
@@ -970,6 +1028,9 @@ extern "C" int dm_conv_decoder_mse_fwd(const dm_shape* shp, const float* feat, i
   DmTwinScope tw((shp->flags & DM_FLAG_BF16) != 0);
   const bool tw_on = dm_twins_on();
   dec_register_twins(g, a, false, false);
+  DecFwdWs w;
+  const size_t need = dec_fwd_layout(DmArena(ws, ws_bytes), g, tw_on, &w);
+  DM_REQUIRE(need <= ws_bytes / sizeof(float), DM_E_WORKSPACE, "conv_decoder_fwd: workspace too small (need %zu floats)", need);
   dm_twin_arena_note(acts, tw_on);
   for (int l = 1; l <= 4; ++l)
     DM_TRY(dm_permute4_launch(p->w[l], a.wr[l], g.cin[l], g.cout[l], g.k[l], g.k[l], 0, 2, 3, 1, st));
@@ -979,42 +1040,9 @@ extern "C" int dm_conv_decoder_mse_fwd(const dm_shape* shp, const float* feat, i
     DM_TRY(dm_to_bf16_multi_launch(sg, 4, st));
   }
   if (n == 0) return DM_OK;
-  DmArena ar(ws, ws_bytes);
-  float* splitk = ar.take(DM_SPLITK_FLOATS);
-  const bool direct4 = dm_dec_l4_direct_ok(g.ch, g.d, g.hsm[4], g.k[4]);      // d -> 3 channels: conv_direct.hip, no column matrix
-  size_t colmax = 0;
-  for (int l = 1; l <= (direct4 ? 3 : 4); ++l) {
-    const size_t c = (size_t)n * g.hsm[l] * g.hsm[l] * g.k[l] * g.k[l] * g.cout[l];
-    if (c > colmax) colmax = c;
-  }
-  float* ycol = ar.take(colmax);
-  float* w4 = ar.take(direct4 ? dm_dec_l4_w4_floats(g.d) : 0);
-  // gather-form layers: zero-padded input copy, gather / scatter tables, class-concatenated weights
-  size_t padmax = 0, tabmax = 0, wcmax = 0;
-  for (int l = 1; l <= 4; ++l)
-    if (convt_gather_ok(g.k[l], g.cin[l], g.cout[l], g.hsm[l], (size_t)n)) {
-      const int ta = g.k[l] / 2, hp = g.hsm[l] + 2 * (ta - 1), Hc = g.hsm[l] + ta - 1;
-      const size_t pad = (size_t)n * hp * hp * g.cin[l], tab = (size_t)n * Hc * Hc, wc = (size_t)4 * g.cout[l] * ta * ta * g.cin[l];
-      if (pad > padmax) padmax = pad;
-      if (tab > tabmax) tabmax = tab;
-      if (wc > wcmax) wcmax = wc;
-    }
-  float* xpad = ar.take(padmax);
-  int* t_rowoff = (int*)ar.take(tabmax);
-  int2* t_ctab = (int2*)ar.take(2 * tabmax);
-  int* t_koff = (int*)ar.take(wcmax ? 9 * 1024 : 0);
-  float* wcat = ar.take(wcmax);
-  unsigned short* wcat_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(wcmax) : 0);
-  size_t klmax = 0;
-  for (int l = 1; l <= 4; ++l)
-    if (convt_gather_ok(g.k[l], g.cin[l], g.cout[l], g.hsm[l], (size_t)n)) {
-      const int ta = g.k[l] / 2, Hc = g.hsm[l] + ta - 1;
-      const size_t kl = convt_klist_ints((size_t)n * Hc * Hc, ta * ta * g.cin[l]);
-      if (kl > klmax) klmax = kl;
-    }
-  int* t_klist = (int*)ar.take(klmax);      // (sized whether or not the switch is on)
+  const auto& [splitk, ycol, w4, xpad, wcat, t_rowoff, t_koff, t_klist, t_ctab, wcat_h] = w;
+  const bool direct4 = dec_fwd_direct4(g);
   const bool kskip = g_convt_kskip && !(shp->flags & DM_FLAG_BF16);
-  DM_REQUIRE(ar.ok, DM_E_WORKSPACE, "conv_decoder_fwd: workspace too small (need %zu floats)", ar.off);
   const size_t skb = DM_SPLITK_FLOATS * sizeof(float);
   {
     DmGemm q;   // x0 = feat W^T + b
@@ -1104,6 +1132,48 @@ extern "C" int dm_conv_decoder_mse_bwd_rows(const dm_shape* shp, const float* fe
                                             void* stream) {
   return conv_decoder_mse_bwd_impl(shp, feat, ldf, target, p, acts, scale, row_scale, gr, dfeat, lddf, ws, ws_bytes, stream);
 }
+// The backward's workspace.  One gradient buffer per layer (together smaller than a ping-pong pair of the largest) and one
+// gather table pair per layer: a layer's weight / bias gradient only reads G[l], its tables and the saved activations, so those
+// launches can sit on the weight-gradient side stream (common.h, dm_wgrad_side_*) and run beside whatever follows the
+// DATA-gradient chain on `st` - the BPTT loop - instead of in front of it.  Every layer's output gradient is gathered
+// implicitly: channel counts that are not a multiple of 4 (the 3-channel image layer) are padded to 4 (co4) in the gradient
+// buffer and in a padded copy of the weights (wpad).  direct4: the image layer's backward runs as direct kernels.  On an arena
+// without a base it sizes.
+struct DecBwdWs {
+  float *splitk, *splitk_w, *Gl[5], *dwr, *wpad, *bsum, *l4_wp, *l4_part;
+  int *rowoff[5], *koff[5];      // index 1..4
+  unsigned short *Gl_h[5], *wpad_h;
+  int co4[5]; size_t gsz[5], wpadmax;
+};
+static size_t dec_bwd_layout(DmArena ar, const DecGeom& g, bool direct4, bool tw_on, DecBwdWs* w) {
+  w->splitk = ar.take(DM_SPLITK_FLOATS);
+  size_t wmax = 0;
+  w->co4[0] = 0; w->gsz[0] = (size_t)g.N * g.cin[1]; w->wpadmax = 0;
+  for (int l = 1; l <= 4; ++l) {
+    const int co = w->co4[l] = (g.cout[l] + 3) & ~3;
+    w->gsz[l] = g.rows_b[l] * co;
+    const size_t wl = (size_t)g.cin[l] * g.k[l] * g.k[l] * co;
+    if (wl > wmax) wmax = wl;
+    if (co != g.cout[l] && wl > w->wpadmax) w->wpadmax = wl;
+  }
+  for (int l = 0; l <= 4; ++l) w->Gl[l] = ar.take(w->gsz[l]);
+  w->dwr = ar.take(wmax);
+  w->wpad = ar.take(w->wpadmax);
+  w->bsum = ar.take(64);
+  w->rowoff[0] = w->koff[0] = nullptr;
+  for (int l = 1; l <= 4; ++l) {
+    w->rowoff[l] = (int*)ar.take(g.rows_s[l]);
+    w->koff[l] = (int*)ar.take((size_t)g.k[l] * g.k[l] * w->co4[l]);
+  }
+  w->splitk_w = ar.take(DM_SPLITK_FLOATS);          // the side stream's own split-K scratch
+  w->l4_wp = ar.take(direct4 ? dm_dec_l4_wp_floats(g.d) : 0);
+  w->l4_part = ar.take(direct4 ? dm_dec_l4_wgrad_part_floats(g.N, g.d) : 0);
+  // bf16 mode: twins of the gradient buffers and of the padded image-layer weights
+  for (int l = 0; l <= 4; ++l) w->Gl_h[l] = (unsigned short*)ar.take(tw_on ? dm_half_floats(w->gsz[l]) : 0);
+  w->wpad_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(w->wpadmax) : 0);
+  return ar.off;
+}
+
 static int conv_decoder_mse_bwd_impl(const dm_shape* shp, const float* feat, int ldf, const float* target,
                                      const dm_conv_params* p, const float* acts, float scale, const float* row_scale,
                                      const dm_conv_grads* gr, float* dfeat, int lddf, void* ws, size_t ws_bytes, void* stream) {
@@ -1114,51 +1184,14 @@ static int conv_decoder_mse_bwd_impl(const dm_shape* shp, const float* feat, int
   hipStream_t st = (hipStream_t)stream;
   DecActs a;
   dec_carve(g, const_cast<float*>(acts), (size_t)1 << 60, &a);
-  DmArena ar(ws, ws_bytes);
-  float* splitk = ar.take(DM_SPLITK_FLOATS);
-  // every layer's output gradient is gathered implicitly: channel counts that are not a multiple of 4 (the 3-channel image
-  // layer) are padded to 4 (co4) in the gradient buffer and in a padded copy of the weights
-  int co4[5] = {0, 0, 0, 0, 0};
-  size_t gmax = 0, wmax = 0, wpadmax = 0;
-  for (int l = 1; l <= 4; ++l) {
-    co4[l] = (g.cout[l] + 3) & ~3;
-    if (g.rows_b[l] * co4[l] > gmax) gmax = g.rows_b[l] * co4[l];
-    const size_t w = (size_t)g.cin[l] * g.k[l] * g.k[l] * co4[l];
-    if (w > wmax) wmax = w;
-    if (co4[l] != g.cout[l] && w > wpadmax) wpadmax = w;
-  }
-  if ((size_t)g.N * g.cin[1] > gmax) gmax = (size_t)g.N * g.cin[1];
-  // One gradient buffer per layer (together smaller than a ping-pong pair of the largest) and one gather table pair per layer:
-  // a layer's weight / bias gradient only reads G[l], its tables and the saved activations, so those launches can sit on
-  // the weight-gradient side stream (common.h, dm_wgrad_side_*) and run beside whatever follows the DATA-gradient chain on
-  // `st` - the BPTT loop - instead of in front of it.  Not armed: sw == st and the order below is simply "as enqueued".
-  float* Gl[5];
-  unsigned short* Gl_h[5];
-  size_t gsz[5];
-  gsz[0] = (size_t)g.N * g.cin[1];
-  for (int l = 1; l <= 4; ++l) gsz[l] = g.rows_b[l] * co4[l];
-  for (int l = 0; l <= 4; ++l) Gl[l] = ar.take(gsz[l]);
-  (void)gmax;
-  float* dwr = ar.take(wmax);
-  float* wpad = ar.take(wpadmax);
-  float* bsum = ar.take(64);
-  int* rowoff_l[5];
-  int* koff_l[5];
-  for (int l = 1; l <= 4; ++l) {
-    rowoff_l[l] = (int*)ar.take(g.rows_s[l]);
-    koff_l[l] = (int*)ar.take((size_t)g.k[l] * g.k[l] * co4[l]);
-  }
-  float* splitk_w = ar.take(DM_SPLITK_FLOATS);          // the side stream's own split-K scratch
   // image layer (d -> 3 channels): both backward products as direct kernels (conv_direct.hip) reading the padded gradient
   const bool direct4 = dm_dec_l4_bwd_direct_ok(g.ch, g.d, g.hsm[4], g.k[4]);
-  float* l4_wp = ar.take(direct4 ? dm_dec_l4_wp_floats(g.d) : 0);
-  float* l4_part = ar.take(direct4 ? dm_dec_l4_wgrad_part_floats(g.N, g.d) : 0);
-  // bf16 mode: twins of the gradient buffers and of the padded image-layer weights
   DmTwinScope tw((shp->flags & DM_FLAG_BF16) != 0);
   const bool tw_on = dm_twins_on();
-  for (int l = 0; l <= 4; ++l) Gl_h[l] = (unsigned short*)ar.take(tw_on ? dm_half_floats(gsz[l]) : 0);
-  unsigned short* wpad_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(wpadmax) : 0);
-  DM_REQUIRE(ar.ok, DM_E_WORKSPACE, "conv_decoder_bwd: workspace too small (need %zu floats)", ar.off);
+  DecBwdWs w;
+  const size_t need = dec_bwd_layout(DmArena(ws, ws_bytes), g, direct4, tw_on, &w);
+  DM_REQUIRE(need <= ws_bytes / sizeof(float), DM_E_WORKSPACE, "conv_decoder_bwd: workspace too small (need %zu floats)", need);
+  const auto& [splitk, splitk_w, Gl, dwr, wpad, bsum, l4_wp, l4_part, rowoff_l, koff_l, Gl_h, wpad_h, co4, gsz, wpadmax] = w;
   const size_t skb = DM_SPLITK_FLOATS * sizeof(float);
   const bool arena_tw = dm_twin_arena_valid(acts);      // the forward that filled `acts` wrote its twins
   dec_register_twins(g, a, arena_tw, arena_tw);
@@ -1276,4 +1309,35 @@ static int conv_decoder_mse_bwd_impl(const dm_shape* shp, const float* feat, int
   }
   DM_TRY(dm_wgrad_side_mark(sw, st));
   return DM_OK;
+}
+
+// ---------------------------------------------------------------- workspace sizing (common.h) ----
+// DM_FLAG_BF16 sizes the twins whatever dm_bf16_twins_enable says; reward_input and the direct image-layer backward are sized
+// wherever the shape admits them.
+size_t dm_conv_ws_floats(const dm_shape* s, size_t parts[4]) {
+  size_t p[4] = {0, 0, 0, 0};
+  const bool geom = s && s->T >= 0 && s->B >= 0 && s->img == 64 && s->img_ch >= 1 && s->cnn_depth >= 1;      // (else the geometry structs would wrap)
+  if (geom) {
+    const bool tw = (s->flags & DM_FLAG_BF16) != 0;
+    EncGeom e(s);
+    if (e.valid(s) || e.valid_planes(s)) {
+      EncFwdWs fw;
+      EncBwdWs bw;
+      p[0] = enc_fwd_layout(DmArena(nullptr, 0), e, e.valid_planes(s), &fw);
+      p[1] = enc_bwd_layout(DmArena(nullptr, 0), e, tw, &bw);
+    }
+    DecGeom d(s);
+    if (d.valid(s)) {
+      DecFwdWs fw;
+      DecBwdWs bw;
+      p[2] = dec_fwd_layout(DmArena(nullptr, 0), d, tw, &fw);
+      p[3] = dec_bwd_layout(DmArena(nullptr, 0), d, dec_fwd_direct4(d), tw, &bw);
+    }
+  }
+  size_t m = 0;
+  for (int i = 0; i < 4; ++i) {
+    if (parts) parts[i] = p[i];
+    if (p[i] > m) m = p[i];
+  }
+  return m;
 }

@@ -124,90 +124,21 @@ extern "C" int dm_wgrad_side_join(void* stream) {
   return DM_OK;
 }
 
-// Scratch sizing: the largest transient of any fused operator at this shape, mirroring the arena carves in
-// conv.hip / rssm.hip / mlp.hip (every carve is rounded up to 64 floats).  See DESIGN.md "HBM layout".
-static size_t pad64(size_t n) { return (n + 63) / 64 * 64; }
-
+// Scratch sizing: every fused operator carves its workspace with a layout function of its own (conv.hip, rssm.hip, mlp.hip);
+// the same functions, run on an arena without a base, say what each needs (common.h dm_*_ws_floats).  The caller's buffer
+// serves them one at a time: the largest, plus a slack of 4096 floats.  See DESIGN.md "HBM layout".
+extern "C" int dm_workspace_query(const dm_shape* s, size_t* parts, int n) {
+  DM_REQUIRE(s && parts && n >= 8, DM_E_NULL, "workspace_query: null argument, or room for fewer than 8 parts");
+  dm_conv_ws_floats(s, parts);
+  dm_rssm_ws_floats(s, parts + 4);
+  parts[6] = dm_rollout_ws_floats(s);
+  const long long rows = (long long)(s->H > 0 ? s->H + 1 : 2) * s->T * s->B * (s->I > 0 ? s->I : 1);      // the heads' rows: every imagined step of every row
+  parts[7] = dm_mlp_ws_floats((int)rows, s->mlp_hidden, s->mlp_layers);
+  return DM_OK;
+}
 extern "C" size_t dm_workspace_bytes(const dm_shape* s) {
-  if (!s) return 0;
-  const size_t N = (size_t)s->T * s->B * (s->I > 0 ? s->I : 1);
-  const size_t d = (size_t)s->cnn_depth, ch = (size_t)s->img_ch;
-  const size_t D = s->D, Hd = s->Hd, Z = (size_t)s->S * (s->C ? s->C : 2), A = s->A;    // C = 0 (Gaussian latents): parameters are 2S wide, z is S
-  const size_t Hm = s->mlp_hidden, L = s->mlp_layers, H = s->H > 0 ? s->H : 1;
-  const size_t SK = DM_SPLITK_FLOATS;
-  // encoder backward: ga (N*31*31*d) + gb (N*14*14*2d) + dwr (8d*64d) + dxcol (max patch matrix, l>=1)
-  size_t xc = N * 196 * 16 * d;
-  if (N * 36 * 32 * d > xc) xc = N * 36 * 32 * d;
-  if (N * 4 * 64 * d > xc) xc = N * 4 * 64 * d;
-  // + gather-form data gradient: zero-padded copies of the 14x14x2d / 6x6x4d gradients, tables, class-concatenated weights
-  size_t epad = N * 16 * 16 * 2 * d;
-  if (N * 8 * 8 * 4 * d > epad) epad = N * 8 * 8 * 4 * d;
-  // bf16 mode (DM_FLAG_BF16): + bf16 twins of gradient ping-pong buffers and per-call weight copies (common.h DmTwinScope)
-  const size_t tw = (s->flags & DM_FLAG_BF16) ? 1 : 0;
-  const size_t enc_bwd = SK + pad64(N * 961 * d) + pad64(N * 196 * 2 * d) + pad64(8 * d * 64 * d) + pad64(xc) + pad64(epad) +
-                         3 * pad64(N * 225) + pad64(4 * 1024) + pad64(16 * 2 * d * 4 * d) + 1024 +
-                         pad64((N * 225 / 128 + 1) * (d + 2)) +      // + k-tile lists (conv.hip CONVT_G): blocks x (K / 32 + 1), K <= 32 d
-                         tw * (pad64(N * 961 * d / 2 + 1) + pad64(N * 196 * d + 1) + pad64(8 * 2 * d * 4 * d + 1));
-  // decoder: column matrices rows_small * k*k*cout for layers 1..4
-  size_t col = N * 25 * 4 * d;
-  if (N * 25 * 25 * 2 * d > col) col = N * 25 * 25 * 2 * d;
-  if (N * 169 * 36 * d > col) col = N * 169 * 36 * d;
-  if (!dm_dec_l4_direct_ok((int)ch, (int)d, 30, 6) && N * 900 * 36 * ch > col) col = N * 900 * 36 * ch;   // layer 4 runs as a direct kernel otherwise
-  size_t gmax = N * 25 * 4 * d;
-  if (N * 169 * 2 * d > gmax) gmax = N * 169 * 2 * d;
-  if (N * 900 * d > gmax) gmax = N * 900 * d;
-  if (N * 4096 * ((ch + 3) / 4 * 4) > gmax) gmax = N * 4096 * ((ch + 3) / 4 * 4);   // image-layer gradient padded to 4 channels
-  if (N * 32 * d > gmax) gmax = N * 32 * d;
-  size_t wmax = 32 * d * 25 * 4 * d;
-  if (4 * d * 25 * 2 * d > wmax) wmax = 4 * d * 25 * 2 * d;
-  if (2 * d * 36 * d > wmax) wmax = 2 * d * 36 * d;
-  if (d * 36 * ch > wmax) wmax = d * 36 * ch;
-  // + gather-form transposed convolution (conv.hip): zero-padded input copy, tables, class-concatenated weights; bounded by the
-  //   k = 6 layers: inputs 13x13x2d -> 17x17, 30x30xd -> 34x34, class pixels 15x15 / 32x32
-  size_t gpad = N * 17 * 17 * 2 * d;
-  if (N * 34 * 34 * d > gpad) gpad = N * 34 * 34 * d;
-  const size_t gtab = N * 32 * 32;
-  const size_t dec_fwd = SK + pad64(col) + pad64(gpad) + 3 * pad64(gtab) + pad64(9 * 1024) + pad64(4 * 2 * d * 9 * 2 * d) +
-                         pad64(144 * d) + 1024 +      // + the direct layer-4 kernel's class-ordered weights
-                         pad64((N * 1024 / 128 + 1) * (18 * d / 32 + 2)) +      // + k-tile lists: K <= 18 d
-                         tw * pad64(2 * 2 * d * 9 * 2 * d + 1);
-  // decoder backward: one gradient buffer per layer, one gather-table pair per layer, two split-K scratches (the weight
-  // gradients may run on the side stream, conv.hip conv_decoder_mse_bwd_impl)
-  const size_t r4 = (size_t)((ch + 3) / 4 * 4), q4 = 4;
-  auto up4 = [&](size_t v) { return (v + q4 - 1) / q4 * q4; };
-  const size_t g_l[5] = {N * 32 * d, N * 25 * up4(4 * d), N * 169 * up4(2 * d), N * 900 * up4(d), N * 4096 * r4};
-  size_t g_sum = 0, g_tw = 0;
-  for (int l = 0; l < 5; ++l) { g_sum += pad64(g_l[l]); g_tw += pad64(g_l[l] / 2 + 1); }
-  const size_t dec_tabs = pad64(N) + pad64(N * 25) + pad64(N * 169) + pad64(N * 900) + pad64(25 * up4(4 * d)) + pad64(25 * up4(2 * d)) +
-                          pad64(36 * up4(d)) + pad64(36 * r4);
-  (void)gmax;
-  const size_t l4_direct = dm_dec_l4_direct_ok((int)ch, (int)d, 30, 6)       // (sized whether or not the switch is on)
-                               ? pad64(dm_dec_l4_wp_floats((int)d)) + pad64(dm_dec_l4_wgrad_part_floats((int)N, (int)d)) : 0;
-  const size_t dec_bwd = 2 * SK + g_sum + 2 * pad64(wmax + 36 * 4 * d) + dec_tabs + 1024 + l4_direct +
-                         tw * (g_tw + pad64((wmax + 36 * 4 * d) / 2 + 1));
-  const size_t rssm_bwd = 2 * SK + 8 * pad64(N * Hd) + 3 * pad64(N * 3 * D) + 2 * pad64(Z * Hd) + pad64(Hd * D) +
-                          pad64(3 * D * Hd) + pad64(3 * D * D) + 2 * pad64(3 * D) +   // + the transposed BPTT weights, LN-GRU dg
-                          2 * pad64((3 * D + 15) / 16 * 1024) + 2 * pad64((Hd + 15) / 16 * 1024);   // + fragment-major dgi / dgh / dpin / dza
-  // persistent posterior chain kernel (rssm_lds.hip): per-step exchange buffers (0 if the shape does not qualify)
-  const size_t Zw = (size_t)s->S * (s->C ? s->C : 1);
-  const size_t lds_fwd = SK + pad64(Zw * Hd) + 5 * pad64((Zw + 15) / 16 * 1024) +
-                         (s->C ? pad64(dm_rssm_lds_ws_floats(s->B, s->D, s->Hd, s->S, s->C, s->T)) : 0) + 1024;
-  const size_t rssm_bwd_lds = rssm_bwd + pad64(N * D) + pad64(N * Zw) + pad64(D) + pad64(Zw) + 2 * pad64((Hd + 15) / 16 * 128);      // (+ the folded launch schedule's x W products, column sums and strip sums)
-  const size_t rows = (H + 1) * N;
-  const size_t mlp_bwd = dm_mlp_ws_floats((int)rows, (int)Hm, (int)L);      // = SK + ping-pong + panel column partials
-  const size_t dream = SK + L * (2 * pad64(N * Hm) + pad64(N * 2)) + pad64(N * 2 * A) + 3 * pad64(N * Hd) + pad64(N * 2) +
-                       3 * pad64(N * 3 * D) + pad64(N * 6 * 4) + pad64(N * Z) +      // (LayerNorm-GRU statistics: 6 per stack layer)
-                       pad64(25 * 512 * (((D + Z + 31) / 32) + (L > 0 ? L - 1 : 0) * ((Hm + 31) / 32))) +   // + fragment-major actor weights
-                       pad64(Z * Hd) + pad64(A * Hd) + pad64(N * (size_t)s->S) + pad64(N) +   // + z_mlp^T, a_mlp^T and the sampled indices (z_embed)
-                       pad64((D + (size_t)s->S * (s->C ? s->C : 1)) * Hm) + pad64(N * Hm) +   // + the actor's W0^T and its sparse-tail addend
-                       tw * (pad64(3 * D * Hd / 2 + 1) + pad64(3 * D * D / 2 + 1) + pad64(Hd * D / 2 + 1) + pad64(Z * Hd / 2 + 1) +
-                             pad64(N * Hd / 2 + 1) + pad64((H + 1) * N * (D + (size_t)s->S * (s->C ? s->C : 1)) / 2 + 1));   // + bf16 twins of the cell's weights, za and the h columns of feats
-  size_t m = enc_bwd;
-  if (dec_fwd > m) m = dec_fwd;
-  if (dec_bwd > m) m = dec_bwd;
-  if (rssm_bwd_lds > m) m = rssm_bwd_lds;
-  if (lds_fwd > m) m = lds_fwd;
-  if (mlp_bwd > m) m = mlp_bwd;
-  if (dream > m) m = dream;
+  size_t parts[8], m = 0;
+  if (dm_workspace_query(s, parts, 8) != DM_OK) return 0;
+  for (size_t v : parts) m = v > m ? v : m;
   return (m + 4096) * sizeof(float);
 }

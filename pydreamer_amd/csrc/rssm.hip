@@ -220,16 +220,9 @@ static thread_local int tl_last_schedule[3] = {0, 0, 0};
 extern "C" int dm_rssm_last_schedule(int which) { return which >= 0 && which < 3 ? tl_last_schedule[which] : -1; }
 
 // ---------------------------------------------------------------- posterior T loop --------------
-struct PostCtx : RssmDims {
-  RssmActs a; GruStack gk;
-  const float* const* p; hipStream_t st; void* ws; size_t skb;      // ws: the split-K scratch at the head of the workspace
-  const uint8_t* reset; const float* u; const int32_t* forced; float *feat, *post; int32_t* idx;
-  // Fused schedule (5 launches per step instead of 8) when the <= 64-row products qualify: the two LayerNorm+ELU stages
-  // ride in the PROLOGUE of the product that consumes them (each workgroup recomputes the row statistics of its <= 64
-  // rows from L2) and the straight-through sampler rides in the EPILOGUE of the posterior-logits product (one 32-logit
-  // group per workgroup).  The post-LayerNorm activations `za` / `pin` that only the backward pass needs (weight
-  // gradients, ELU') are then produced for ALL rows by two batched launches after the loop.
-  bool fuse_ln, fuse_sample;
+// The chain's workspace: [split-K | optional blocks], each block taken if the schedule wants it (PostCtx::plan) and it fits -
+// a small workspace keeps the schedule without it, its pointers null.  On an arena without a base it sizes.
+struct PostWs {
   // z_mlp of the sampled (one-hot) latent as a gather-sum over rows of z_mlp^T (dm_z_embed_launch): every step after the
   // first takes its z from the sampler, whose indices are at hand; the first step's z comes from the caller as a dense
   // vector and keeps the product.
@@ -240,10 +233,42 @@ struct PostCtx : RssmDims {
   float *zinf, *x1f, *hinf, *hf, *x2f;
   // The fused schedule's steps after the first as ONE persistent kernel with the cell's weights stationary in
   // LDS (rssm_lds.hip): the first step runs as launches (its z is a dense vector from the caller) and leaves h, the masked
-  // inputs and the indices the kernel's first step continues from.
+  // inputs and the indices the kernel's first step continues from.  Needs wzt.
   float* psync; size_t psync_floats;
+};
+static size_t post_layout(DmArena ar, const RssmDims& d, bool want_wzt, bool want_frag, bool want_psync, PostWs* w) {
+  *w = {};
+  ar.take(DM_SPLITK_FLOATS);
+  if (want_wzt) {
+    const size_t mark = ar.off;
+    w->wzt = ar.take((size_t)d.Z * d.Hd);
+    if (!ar.fits()) { w->wzt = nullptr; want_psync = false; ar.give_back(mark); }
+  }
+  if (want_frag) {
+    w->zinf = ar.take(dm_frag_floats(d.Z)); w->x1f = ar.take(dm_frag_floats(d.Hd)); w->hinf = ar.take(dm_frag_floats(d.D));
+    w->hf = ar.take(dm_frag_floats(d.D)); w->x2f = ar.take(dm_frag_floats(d.Hd));
+    if (!ar.fits()) w->zinf = w->x1f = w->hinf = w->hf = w->x2f = nullptr;      // (not given back: nothing behind them fits either)
+  }
+  if (want_wzt && want_psync) {
+    w->psync_floats = dm_rssm_lds_ws_floats(d.B, d.D, d.Hd, d.S, d.C, d.T - 1);
+    w->psync = ar.take(w->psync_floats);
+    if (!ar.fits()) w->psync = nullptr;
+  }
+  return ar.off;
+}
 
-  // Decides the schedule and takes the optional buffers (a small workspace keeps the schedule without them); no launches.
+struct PostCtx : RssmDims, PostWs {
+  RssmActs a; GruStack gk;
+  const float* const* p; hipStream_t st; void* ws; size_t skb;      // ws: the split-K scratch at the head of the workspace
+  const uint8_t* reset; const float* u; const int32_t* forced; float *feat, *post; int32_t* idx;
+  // Fused schedule (5 launches per step instead of 8) when the <= 64-row products qualify: the two LayerNorm+ELU stages
+  // ride in the PROLOGUE of the product that consumes them (each workgroup recomputes the row statistics of its <= 64
+  // rows from L2) and the straight-through sampler rides in the EPILOGUE of the posterior-logits product (one 32-logit
+  // group per workgroup).  The post-LayerNorm activations `za` / `pin` that only the backward pass needs (weight
+  // gradients, ELU') are then produced for ALL rows by two batched launches after the loop.
+  bool fuse_ln, fuse_sample;
+
+  // Decides the schedule and takes the optional buffers (PostWs) it wants; no launches.
   int plan(size_t ws_bytes) {
     const bool stacked = gk.L > 1;      // GRUCellStack with several layers: the unfused schedule, 3 launches per layer
     const bool normed = p[DM_RSSM_IN_G] != nullptr;      // layer_norm=False: all three norms are NoNorm (null parameters)
@@ -253,25 +278,10 @@ struct PostCtx : RssmDims {
               (ZP >= 64 * 1024 / Hd);
     fuse_sample = fuse_ln && C == 32 && (Z & 31) == 0 && (F & 3) == 0 && (D & 3) == 0 &&
                   (((uintptr_t)feat | (uintptr_t)a.zin) & 15) == 0;
-    DmArena ar(ws, ws_bytes);
-    ar.take(DM_SPLITK_FLOATS);
-    if (!gauss && idx && T > 1 && dm_z_embed_ok(Hd)) {
-      const size_t mark = ar.off;
-      float* w = ar.take((size_t)Z * Hd);
-      if (ar.ok) wzt = w;
-      else { ar.off = mark; ar.ok = true; }
-    }
-    if (fuse_sample && kind == 0 && B <= 64) {
-      float* f0 = ar.take(dm_frag_floats(Z)); float* f1 = ar.take(dm_frag_floats(Hd)); float* f2 = ar.take(dm_frag_floats(D));
-      float* f3 = ar.take(dm_frag_floats(D)); float* f4 = ar.take(dm_frag_floats(Hd));
-      if (ar.ok) { zinf = f0; x1f = f1; hinf = f2; hf = f3; x2f = f4; }
-    }
-    if (normed && !stacked && !gauss && kind == 0 && wzt && idx && (F & 3) == 0 && T >= 3 && dm_rssm_lds_ok(B, D, Hd, S, C)) {
-      psync_floats = dm_rssm_lds_ws_floats(B, D, Hd, S, C, T - 1);
-      float* sy = ar.take(psync_floats);
-      if (ar.ok) psync = sy;
-      else ar.ok = true;
-    }
+    const bool want_wzt = !gauss && idx && T > 1 && dm_z_embed_ok(Hd);
+    post_layout(DmArena(ws, ws_bytes), *this, want_wzt, fuse_sample && kind == 0 && B <= 64,
+                normed && !stacked && !gauss && kind == 0 && want_wzt && idx && (F & 3) == 0 && T >= 3 && dm_rssm_lds_ok(B, D, Hd, S, C),
+                this);
     return DM_OK;
   }
 
@@ -440,21 +450,59 @@ extern "C" int dm_bptt_fold_enable(int on) {
   return was;
 }
 
-struct BpttCtx : RssmDims {
+// The backward's workspace: what every schedule needs (`must` floats), then the folded schedule's buffers and the fragment-major
+// copies, each taken if wanted (BpttCtx::plan) and it fits - a small caller workspace keeps the prologue form / the row-major
+// operands, the pointers null.  On an arena without a base it sizes.
+struct BpttWs {
+  float *sk, *sk_w;      // split-K scratch of the chain and of the parameter gradients' stream
+  float *dprin, *dx3, *dpin, *dx2, *dgi, *dgh, *dza, *dx1;
+  float *wt_post, *wt_post_h, *wt_ih, *wt_hh, *wt_z;      // W^T of the five backward-data products of a step
+  float *dgl, *lnpg, *lnpb;      // LayerNorm GRU cells: gradients w.r.t. the LayerNorm outputs; column sums for their parameters
+  // the side stream's own dx2 / dx1 (fused schedule: the LayerNorm backward of a chunk of rows is redone there instead of
+  // being shared with the chain)
+  float *dx2_w, *dx1_w;
+  size_t must;
+  // folded form: x2 W_post_h and x1 W_z for all rows, the weights' column sums, the per-strip row sums of g2 / g1
+  float *xw2, *xwz, *cs2, *csz, *eps2, *eps1;
+  // fragment-major copies (common.h dm_frag_off) of the two K = 3D operands of a step, dgi and dgh (written by the gates
+  // backward epilogue, read by the two products that follow it), and of dpin, dza (written by the product that makes them)
+  float *dgif, *dghf, *dpinf, *dzaf;
+};
+static size_t bptt_layout(DmArena ar, const RssmDims& d, bool want_fold, bool want_frag, BpttWs* w) {
+  const size_t rows = d.N, D = d.D, Hd = d.Hd, Z = d.Z, ZP = d.ZP;
+  *w = {};
+  w->sk = ar.take(DM_SPLITK_FLOATS);
+  w->dprin = ar.take(rows * Hd); w->dx3 = ar.take(rows * Hd); w->dpin = ar.take(rows * Hd); w->dx2 = ar.take(rows * Hd);
+  w->dgi = ar.take(rows * 3 * D); w->dgh = ar.take(rows * 3 * D); w->dza = ar.take(rows * Hd); w->dx1 = ar.take(rows * Hd);
+  w->wt_post = ar.take(ZP * Hd); w->wt_post_h = ar.take(Hd * D);
+  w->wt_ih = ar.take(3 * D * Hd); w->wt_hh = ar.take(3 * D * D); w->wt_z = ar.take(Hd * Z);
+  w->dgl = ar.take(d.kind ? rows * 3 * D : 0); w->lnpg = ar.take(d.kind ? 3 * D : 0); w->lnpb = ar.take(d.kind ? 3 * D : 0);
+  w->sk_w = ar.take(DM_SPLITK_FLOATS); w->dx2_w = ar.take(rows * Hd); w->dx1_w = ar.take(rows * Hd);
+  w->must = ar.off;
+  if (want_fold) {
+    const size_t mark = ar.off, nstrip = (Hd + 15) / 16;
+    w->xw2 = ar.take(rows * D); w->xwz = ar.take(rows * Z); w->cs2 = ar.take(D); w->csz = ar.take(Z);
+    w->eps2 = ar.take(nstrip * 128); w->eps1 = ar.take(nstrip * 128);
+    if (!ar.fits()) { w->xw2 = w->xwz = w->cs2 = w->csz = w->eps2 = w->eps1 = nullptr; ar.give_back(mark); }
+  }
+  if (want_frag) {
+    w->dgif = ar.take(dm_frag_floats(3 * d.D)); w->dghf = ar.take(dm_frag_floats(3 * d.D));
+    w->dpinf = ar.take(dm_frag_floats(d.Hd)); w->dzaf = ar.take(dm_frag_floats(d.Hd));
+    if (!ar.fits()) w->dgif = w->dghf = w->dpinf = w->dzaf = nullptr;
+  }
+  return ar.off;
+}
+
+struct BpttCtx : RssmDims, BpttWs {
   RssmActs a; GruStack gk;
   const float* const* p; float* const* g;
   // Parameter gradients are leaves of this pass: nothing reads them before the gradient clip.  They go to `sw` - the
   // library's weight-gradient side stream when the calling thread is armed (include/dreamer_hip.h dm_wgrad_side_arm), else
   // `st` itself - with a split-K scratch of their own.
   hipStream_t st, sw;
-  float *sk, *sk_w; size_t skb;
+  size_t skb;
   const float *embed, *action, *feat, *post; const uint8_t* reset; float *dfeat, *dpost;
-  float *dprin, *dx3, *dpin, *dx2, *dgi, *dgh, *dza, *dx1;
-  float *wt_post, *wt_post_h, *wt_ih, *wt_hh, *wt_z;      // W^T of the five backward-data products of a step
-  float *dgl, *lnpg, *lnpb;      // LayerNorm GRU cells: gradients w.r.t. the LayerNorm outputs; column sums for their parameters
-  // the side stream's own dx2 / dx1 (fused schedule: the LayerNorm backward of a chunk of rows is redone there instead of
-  // being shared with the chain), and whichever pair the side stream reads
-  float *dx2_w, *dx1_w; const float *dx2s, *dx1s;
+  const float *dx2s, *dx1s;      // whichever of dx2 / dx2_w (dx1 / dx1_w) the side stream reads
   // Fused schedule (5 launches per step instead of 8), mirror of the forward T loop: both LayerNorm+ELU BACKWARD stages
   // ride in the prologue of the <= 64-row product that consumes their result, and the GRU gates backward rides in the
   // epilogue of the product that completes dh'.  dx1 / dx2 (needed by the batched weight gradients) are then produced for
@@ -466,10 +514,7 @@ struct BpttCtx : RssmDims {
   // all rows (xw2, xwz: two batched products before the loop) and the weights' column sums (cs2, csz).
   // fold_sm (32 classes): step t-1's straight-through softmax backward rides in the epilogue of the product that completes its dz'.
   bool fold, fold_sm;
-  float *xw2, *xwz, *cs2, *csz, *eps2, *eps1; int nstrip;
-  // fragment-major copies (common.h dm_frag_off) of the two K = 3D operands of a step, dgi and dgh (written by the gates
-  // backward epilogue, read by the two products that follow it), and of dpin, dza (written by the product that makes them)
-  float *dgif, *dghf, *dpinf, *dzaf;
+  int nstrip;
   // time chunks of the batched weight gradients (single-layer cells): chunk k = steps [T*k/nchunk, T*(k+1)/nchunk); the loop
   // runs t downwards, so the LAST chunk completes first - it overwrites the gradient, the others accumulate
   int nchunk, next_chunk;
@@ -481,16 +526,6 @@ struct BpttCtx : RssmDims {
   // Carves the workspace, decides the schedule and lists the weight gradients; no launches.
   int plan(void* ws, size_t ws_bytes) {
     const bool stacked = gk.L > 1;
-    const size_t rows = N;
-    DmArena ar(ws, ws_bytes);
-    sk = ar.take(DM_SPLITK_FLOATS);
-    dprin = ar.take(rows * Hd); dx3 = ar.take(rows * Hd); dpin = ar.take(rows * Hd); dx2 = ar.take(rows * Hd);
-    dgi = ar.take(rows * 3 * D); dgh = ar.take(rows * 3 * D); dza = ar.take(rows * Hd); dx1 = ar.take(rows * Hd);
-    wt_post = ar.take((size_t)ZP * Hd); wt_post_h = ar.take((size_t)Hd * D);
-    wt_ih = ar.take((size_t)3 * D * Hd); wt_hh = ar.take((size_t)3 * D * D); wt_z = ar.take((size_t)Hd * Z);
-    dgl = ar.take(kind ? rows * 3 * D : 0); lnpg = ar.take(kind ? (size_t)3 * D : 0); lnpb = ar.take(kind ? (size_t)3 * D : 0);
-    sk_w = ar.take(DM_SPLITK_FLOATS); dx2_w = ar.take(rows * Hd); dx1_w = ar.take(rows * Hd);
-    DM_REQUIRE(ar.ok, DM_E_WORKSPACE, "rssm_sequence_bwd: workspace too small (need %zu floats)", ar.off);
     skb = DM_SPLITK_FLOATS * sizeof(float);
     // (the step's closing pair launch carries the LayerNorm backward on its second product: its first, dgh W_hh, must be on the
     // skinny kernel too - 3D x D over that kernel's 64K floor, i.e. deter_dim >= 148)
@@ -499,18 +534,10 @@ struct BpttCtx : RssmDims {
     fold = fuse_b && g_bptt_fold && B <= 64 && (int64_t)Hd * ZP >= (int64_t)64 * 1024 &&
            (int64_t)Hd * 3 * D >= (int64_t)64 * 1024 && (ZP & 3) == 0 && ((3 * D) & 3) == 0 && ZP >= 16;
     nstrip = (Hd + 15) / 16;
-    if (fold) {
-      const size_t mark = ar.off;
-      xw2 = ar.take(rows * D); xwz = ar.take(rows * Z); cs2 = ar.take((size_t)D); csz = ar.take((size_t)Z);
-      eps2 = ar.take((size_t)nstrip * 128); eps1 = ar.take((size_t)nstrip * 128);
-      if (!ar.ok) { ar.off = mark; ar.ok = true; fold = false; }       // a small caller workspace keeps the prologue form
-    }
+    bptt_layout(DmArena(ws, ws_bytes), *this, fold, fuse_b && B <= 64, this);
+    DM_REQUIRE(must <= ws_bytes / sizeof(float), DM_E_WORKSPACE, "rssm_sequence_bwd: workspace too small (need %zu floats)", must);
+    fold = fold && xw2;       // a small caller workspace keeps the prologue form
     fold_sm = fold && !gauss && C == 32 && Z == ZP;
-    if (fuse_b && B <= 64) {
-      dgif = ar.take(dm_frag_floats(3 * D)); dghf = ar.take(dm_frag_floats(3 * D));
-      dpinf = ar.take(dm_frag_floats(Hd)); dzaf = ar.take(dm_frag_floats(Hd));
-      if (!ar.ok) { dgif = nullptr; dghf = nullptr; dpinf = nullptr; dzaf = nullptr; }
-    }
     nchunk = (stacked || B < 16) ? 1 : (T >= 16 ? 4 : T >= 8 ? 2 : 1);      // (a few-column shard: the chunks' extra launches cost more than they hide)
     next_chunk = nchunk - 1;
     dx2s = fuse_b ? dx2_w : dx2;
@@ -834,71 +861,89 @@ extern "C" int dm_rollout_fuse_act_enable(int on) {
   return g_rollout_fuse_act;
 }
 
-struct RolloutCtx : RssmDims {
-  GruStack gk;
+struct RolloutDims : RssmDims {
   int M, H, Hm, L, adist, AO;      // rows, horizon; the actor MLP's width and depth, its distribution (0 onehot, 1 tanh_normal, 2 normal_tanh) and output width (a2c.py:35)
-  const float* const* p; const dm_mlp_params* actor; hipStream_t st; float* sk; size_t skb;
-  const float *u_act, *u_prior; float *feats, *actions; int32_t* act_idx; float *actor_acts, *actor_logits;
-  float *macts, *logits_ws, *ea, *x1, *za, *stats, *gi, *gh, *prior, *gsw, *gstw;
+};
+// The rollout's workspace: what every schedule needs (`must` floats; keep_acts: the caller keeps the actor's activations and
+// outputs, tw_on: the bf16 twins), then three optional blocks, each taken if wanted (RolloutCtx::plan) and it fits - the
+// product path needs none of them, their pointers stay null.  On an arena without a base it sizes.
+struct RolloutWs {
+  float *sk, *macts, *logits_ws, *ea, *x1, *za, *stats, *gi, *gh, *prior, *gsw, *gstw;
   // bf16 mode, plain single-layer GRU with LayerNorm: the cell's four 2 500-row products read bf16 twins (common.h DmTwinScope) -
   // per-call copies of their weights, za (written by the z_embed / LayerNorm kernels that produce it) and the h columns of
   // `feats` (written by the gates kernel; one range per step, so step 0's h, copied from `start`, stays on the fp32 path)
-  bool tw_on;
   unsigned short *wih_h, *whh_h, *wph_h, *wp_h, *za_h, *feats_h;
+  size_t must;
   // steps 1.. of the rollout read the z the prior sampler of the step before drew (pidx): z_mlp + in_norm + ELU become one
   // gather-sum launch over z_mlp^T (dm_z_embed_launch) instead of a (M x Hd x Z) product and a LayerNorm launch; with one-hot
   // actions a_mlp(action) is a row of a_mlp^T too (wat; aidx: scratch for the action's index if the caller wants none)
   float *wzt, *wat; int32_t *pidx, *aidx;
   // the actor's weights, fragment-major for the whole-MLP kernel: packed once for all H steps.  The actor's first layer
   // sees [h | one-hot z]: its z columns are a gathered sum of W0^T rows into actor_add0 (indices from the prior sampler;
-  // step 0's z is a dense vector: its non-zeros are found by ballot), the MFMA product runs over h only
+  // step 0's z is a dense vector: its non-zeros are found by ballot), the MFMA product runs over h only.  Needs pidx.
   float *actor_wpack, *actor_w0t, *actor_add0;
+};
+static size_t rollout_layout(DmArena ar, const RolloutDims& d, bool keep_acts, bool tw_on, bool want_z, bool want_pack,
+                             bool want_add0, RolloutWs* w) {
+  const size_t M = d.M, D = d.D, Hd = d.Hd, ZP = d.ZP, F = d.F;
+  *w = {};
+  w->sk = ar.take(DM_SPLITK_FLOATS);
+  w->macts = ar.take(keep_acts ? 0 : dm_mlp_acts_floats(d.M, d.Hm, d.L)); w->logits_ws = ar.take(keep_acts ? 0 : M * d.AO);
+  w->ea = ar.take(M * Hd); w->x1 = ar.take(M * Hd); w->za = ar.take(M * Hd); w->stats = ar.take(M * 2);
+  w->gi = ar.take(M * 3 * D); w->gh = ar.take(M * 3 * D); w->prior = ar.take(M * ZP);
+  w->gsw = ar.take(d.kind ? M * 3 * D : 0); w->gstw = ar.take(d.kind ? M * 6 * d.layers : 0);
+  w->wih_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(3 * D * Hd) : 0);
+  w->whh_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(3 * D * D) : 0);
+  w->wph_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(Hd * D) : 0);
+  w->wp_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(ZP * Hd) : 0);
+  w->za_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(M * Hd) : 0);
+  w->feats_h = (unsigned short*)ar.take(tw_on ? dm_half_floats((size_t)(d.H + 1) * M * F) : 0);
+  w->must = ar.off;
+  if (want_z) {
+    const size_t mark = ar.off;
+    w->wzt = ar.take((size_t)d.Z * Hd);
+    w->wat = ar.take((size_t)d.A * Hd);
+    w->pidx = reinterpret_cast<int32_t*>(ar.take(M * d.S));
+    w->aidx = reinterpret_cast<int32_t*>(ar.take(M));
+    want_z = ar.fits();
+    if (!want_z) { w->wzt = nullptr; w->pidx = nullptr; ar.give_back(mark); }
+    if (!want_z || d.adist != 0) { w->wat = nullptr; w->aidx = nullptr; }
+  }
+  if (want_pack) {
+    w->actor_wpack = ar.take(dm_mlp_chain_pack_floats(d.F, d.L));
+    if (ar.fits() && want_z && want_add0) {
+      const size_t mark = ar.off;
+      w->actor_w0t = ar.take(F * d.Hm);
+      w->actor_add0 = ar.take(M * d.Hm);
+      if (!ar.fits()) { w->actor_w0t = w->actor_add0 = nullptr; ar.give_back(mark); }
+    }
+  }
+  return ar.off;
+}
+
+struct RolloutCtx : RolloutDims, RolloutWs {
+  GruStack gk;
+  const float* const* p; const dm_mlp_params* actor; hipStream_t st; size_t skb;
+  const float *u_act, *u_prior; float *feats, *actions; int32_t* act_idx; float *actor_acts, *actor_logits;
+  bool tw_on;
   // one-hot actors on the whole-MLP kernel: the action draw rides in that kernel's output stage (dm_rollout_fuse_act_enable(0)
   // keeps the stand-alone sampler launch - same rule, same operation order, bit-identical draws)
   bool fuse_act;
 
-  // Carves the workspace and takes the optional buffers (the product path needs none of them); no launches.
+  // Decides the schedule and takes the workspace (RolloutWs) with the optional buffers it wants; no launches.
   int plan(void* ws, size_t ws_bytes) {
-    DmArena ar(ws, ws_bytes);
-    sk = ar.take(DM_SPLITK_FLOATS);
-    macts = ar.take(actor_acts ? 0 : dm_mlp_acts_floats(M, Hm, L)); logits_ws = ar.take(actor_acts ? 0 : (size_t)M * AO);
-    ea = ar.take((size_t)M * Hd); x1 = ar.take((size_t)M * Hd); za = ar.take((size_t)M * Hd); stats = ar.take((size_t)M * 2);
-    gi = ar.take((size_t)M * 3 * D); gh = ar.take((size_t)M * 3 * D); prior = ar.take((size_t)M * ZP);
-    gsw = ar.take(kind ? (size_t)M * 3 * D : 0); gstw = ar.take(kind ? (size_t)M * 6 * layers : 0);
     tw_on = dm_twins_on() && kind == 0 && layers == 1 && p[DM_RSSM_IN_G] && p[DM_RSSM_PRIOR_G] && (F & 7) == 0;
-    wih_h = (unsigned short*)ar.take(tw_on ? dm_half_floats((size_t)3 * D * Hd) : 0);
-    whh_h = (unsigned short*)ar.take(tw_on ? dm_half_floats((size_t)3 * D * D) : 0);
-    wph_h = (unsigned short*)ar.take(tw_on ? dm_half_floats((size_t)Hd * D) : 0);
-    wp_h = (unsigned short*)ar.take(tw_on ? dm_half_floats((size_t)ZP * Hd) : 0);
-    za_h = (unsigned short*)ar.take(tw_on ? dm_half_floats((size_t)M * Hd) : 0);
-    feats_h = (unsigned short*)ar.take(tw_on ? dm_half_floats((size_t)(H + 1) * M * F) : 0);
-    DM_REQUIRE(ar.ok, DM_E_WORKSPACE, "dream_rollout: workspace too small (need %zu floats)", ar.off);
     skb = DM_SPLITK_FLOATS * sizeof(float);
-    if (C != 0 && H > 1 && dm_z_embed_ok(Hd)) {
-      const size_t mark = ar.off;
-      float* w = ar.take((size_t)Z * Hd);
-      float* w2 = ar.take((size_t)A * Hd);
-      int32_t* ix = reinterpret_cast<int32_t*>(ar.take((size_t)M * S));
-      int32_t* ax = reinterpret_cast<int32_t*>(ar.take((size_t)M));
-      if (ar.ok) {
-        wzt = w; pidx = ix;
-        if (adist == 0) { wat = w2; aidx = ax; }
-      } else {
-        ar.off = mark; ar.ok = true;
-      }
-    }
     // the actor's call as every step issues it: mlp.hip's plan says whether it runs on the whole-MLP kernel (weights packed once
     // for all H steps) and whether that kernel then takes the z columns' contribution from here
-    if (dm_mlp_fwd_path(actor_call(0)) == DM_MLP_CHAIN) {
-      actor_wpack = ar.take(dm_mlp_chain_pack_floats(F, L));
-      if (actor_wpack && C != 0 && pidx && dm_z_embed_ok(Hm)) {
-        const size_t mark = ar.off;
-        actor_w0t = ar.take((size_t)F * Hm);
-        actor_add0 = ar.take((size_t)M * Hm);
-        int k0 = F;
-        if (ar.ok) dm_mlp_fwd_path(actor_call(0), &k0);
-        if (k0 == F) { actor_w0t = actor_add0 = nullptr; ar.off = mark; ar.ok = true; }
-      }
+    const bool chain = dm_mlp_fwd_path(actor_call(0)) == DM_MLP_CHAIN;
+    rollout_layout(DmArena(ws, ws_bytes), *this, actor_acts != nullptr, tw_on, C != 0 && H > 1 && dm_z_embed_ok(Hd), chain,
+                   C != 0 && dm_z_embed_ok(Hm), this);
+    DM_REQUIRE(must <= ws_bytes / sizeof(float), DM_E_WORKSPACE, "dream_rollout: workspace too small (need %zu floats)", must);
+    if (actor_add0) {
+      int k0 = F;
+      dm_mlp_fwd_path(actor_call(0), &k0);
+      if (k0 == F) actor_w0t = actor_add0 = nullptr;
     }
     fuse_act = adist == 0 && actor_wpack && g_rollout_fuse_act;
     return DM_OK;
@@ -1023,4 +1068,39 @@ extern "C" int dm_dream_rollout(const dm_shape* s, int M, const float* start, co
     marks.at_step(i, st, marks_eager);
   }
   return DM_OK;
+}
+
+// ---------------------------------------------------------------- workspace sizing (common.h) ----
+// The RSSM calls take an IWAE batch expanded (T, B * I, 1).  Wanted: what the shape alone admits - the caller's pointers are
+// taken as aligned and present (idx, the LayerNorm parameters), switches as on, DM_FLAG_BF16 as twins on, the persistent
+// kernel by dm_rssm_lds_ws_floats (0 where no plan exists), never by asking the device.
+static RolloutDims rollout_dims(const dm_shape* s) {
+  dm_shape e = *s;
+  e.B = s->B * (s->I > 0 ? s->I : 1); e.I = 1;
+  RolloutDims d = {};
+  rssm_dims(&e, &d);
+  d.M = d.N; d.H = s->H > 0 ? s->H : 1; d.Hm = s->mlp_hidden; d.L = s->mlp_layers; d.adist = s->flags & 3;
+  d.AO = d.adist == 0 ? d.A : 2 * d.A;
+  return d;
+}
+size_t dm_rssm_ws_floats(const dm_shape* s, size_t parts[2]) {
+  if (!s) return 0;
+  const RolloutDims d = rollout_dims(s);
+  const bool chain64 = !d.gauss && d.kind == 0 && d.layers == 1 && d.B <= 64;      // the fused schedules' <= 64-row single plain cell
+  const bool wzt = !d.gauss && d.T > 1 && dm_z_embed_ok(d.Hd);
+  PostWs pw;
+  BpttWs bw;
+  const size_t fwd = post_layout(DmArena(nullptr, 0), d, wzt, chain64 && d.C == 32, chain64 && wzt && (d.F & 3) == 0 && d.T >= 3, &pw);
+  const size_t bwd = bptt_layout(DmArena(nullptr, 0), d, chain64, chain64, &bw);
+  if (parts) { parts[0] = fwd; parts[1] = bwd; }
+  return fwd > bwd ? fwd : bwd;
+}
+// M = every row of the shape; the actor's activations in the workspace (actor_acts == NULL).  All three optional blocks are
+// wanted whatever the shape: whether the actor runs on the whole-MLP kernel depends on its pointers and a run-time switch.
+size_t dm_rollout_ws_floats(const dm_shape* s) {
+  if (!s) return 0;
+  const RolloutDims d = rollout_dims(s);
+  const bool tw = (s->flags & DM_FLAG_BF16) && d.kind == 0 && d.layers == 1 && (d.F & 7) == 0;
+  RolloutWs w;
+  return rollout_layout(DmArena(nullptr, 0), d, false, tw, true, true, true, &w);
 }

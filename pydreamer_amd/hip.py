@@ -131,6 +131,7 @@ _SIGNATURES = {
     'dm_last_error': (c_char_p, []),
     'dm_device_check': (c_int, []),
     'dm_workspace_bytes': (c_size_t, [POINTER(dm_shape)]),
+    'dm_workspace_query': (c_int, [POINTER(dm_shape), POINTER(c_size_t), c_int]),
     'dm_stream_create_cu_mask': (c_int, [_P, c_int, POINTER(c_void_p)]),
     'dm_stream_destroy': (c_int, [_P]),
     'dm_gemm_f32': (c_int, [c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, _P, _P, c_int, c_int,

@@ -214,6 +214,68 @@ def run_case(B, T, D_, Hd, S, C, conf_kw=None, lds=(None,), folds=(None,), reset
     return figures
 
 
+def run_on_own_parts(B, T, D_, Hd, S, C, expect_fwd, expect_bwd, seed=11, lds_level=2):
+    """dm_rssm_sequence_fwd (at dm_rssm_lds_enable `lds_level`) and dm_rssm_sequence_bwd twice: on dm_workspace_bytes, and each
+    on a workspace of exactly its own part of dm_workspace_query.  Both runs must report the schedule bits expect_fwd /
+    expect_bwd - asserted before any value is looked at - and then give the same bits in every output and gradient."""
+    from pydreamer_amd import config, hip as H
+    from pydreamer_amd.models import Dreamer
+    c = make_case(B, T, D_, Hd, S, C, None, resets_dense, seed)
+    oconf, N, E, Z, F_, A = c['oconf'], c['N'], c['E'], c['Z'], c['F'], c['A']
+    model = Dreamer(config.load_config('defaults', 'atari', **vars(oconf)))
+    model.load_state_dict(c['params'], strict=True)
+    model = model.to(DEV)
+    cell = model.wm.core.cell
+    shp = model.wm.shape(T, B, 1)
+    parts = (ctypes.c_size_t * 8)()
+    H.call('dm_workspace_query', ctypes.byref(shp), parts, 8)
+    sizes = {'full': (H.workspace_bytes(shp),) * 2, 'own': (4 * int(parts[4]), 4 * int(parts[5]))}
+    assert max(sizes['own']) < sizes['full'][0]
+    dev = lambda x: x.to(DEV).contiguous()
+    e_d, a_d, r_d, u_d = dev(c['embed'].view(N, E)), dev(c['action'].view(N, A)), dev(c['reset'].view(N).to(torch.uint8)), dev(c['u'].view(N, S))
+    h0_d, z0_d = dev(c['h0']), dev(c['z0'])
+    P = H.rssm_struct(cell.ordered())
+    lib = H.lib()
+    keep_lds = lib.dm_rssm_lds_enable(-1)
+    out = {}
+    try:
+        lib.dm_rssm_lds_enable(lds_level)
+        for tag, (fwd_bytes, bwd_bytes) in sizes.items():
+            ws_f = torch.empty(fwd_bytes, dtype=torch.uint8, device=DEV)
+            ws_b = torch.empty(bwd_bytes, dtype=torch.uint8, device=DEV)
+            acts = torch.empty(int(lib.dm_rssm_acts_floats(ctypes.byref(shp))), device=DEV)
+            feat, post, prior = torch.empty(N, F_, device=DEV), torch.empty(N, Z, device=DEV), torch.empty(N, Z, device=DEV)
+            idx = torch.empty(N, S, dtype=torch.int32, device=DEV)
+            H.call('dm_rssm_sequence_fwd', ctypes.byref(shp), H.fptr(e_d), H.fptr(a_d), H.ptr(r_d), H.fptr(h0_d), H.fptr(z0_d),
+                   H.fptr(u_d), None, ctypes.byref(P), H.fptr(acts), H.fptr(feat), H.fptr(post), H.fptr(prior), H.ptr(idx),
+                   H.ptr(ws_f), fwd_bytes, H.stream())
+            torch.cuda.synchronize()
+            assert lib.dm_rssm_lds_status() == 0
+            got = H.last_schedule(0)
+            print(f'SCHEDULE {tag} fwd ({fwd_bytes} bytes) {_fmt(got)}')
+            for k, v in expect_fwd.items():
+                assert got[k] == v, f'{tag} forward workspace ({fwd_bytes} bytes): schedule bit {k} is {got[k]}, expected {v} ({got})'
+            grads = [None if p_ is None else torch.zeros_like(p_) for p_ in cell.ordered()]
+            Gs = H.rssm_struct(grads, cls=H.dm_rssm_grads)
+            dembed = torch.empty(N, E, device=DEV)
+            dfeat, dpost, dprior = dev(c['Gf']), dev(c['Gp']), dev(c['Gq'])
+            H.call('dm_rssm_sequence_bwd', ctypes.byref(shp), H.fptr(e_d), H.fptr(a_d), H.ptr(r_d), ctypes.byref(P), H.fptr(acts),
+                   H.fptr(feat), H.fptr(post), H.fptr(dfeat), H.fptr(dpost), H.fptr(dprior), ctypes.byref(Gs), H.fptr(dembed),
+                   H.ptr(ws_b), bwd_bytes, H.stream())
+            torch.cuda.synchronize()
+            got = H.last_schedule(1)
+            print(f'SCHEDULE {tag} bwd ({bwd_bytes} bytes) {_fmt(got)}')
+            for k, v in expect_bwd.items():
+                assert got[k] == v, f'{tag} backward workspace ({bwd_bytes} bytes): schedule bit {k} is {got[k]}, expected {v} ({got})'
+            out[tag] = dict(feat=feat, post=post, prior=prior, idx=idx, dembed=dembed, dfeat=dfeat, dpost=dpost,
+                            **{f'grad {i}': g for i, g in enumerate(grads) if g is not None})
+    finally:
+        lib.dm_rssm_lds_enable(keep_lds)
+    assert all(bool(torch.isfinite(v).all()) for v in out['own'].values() if v.is_floating_point())
+    differ = [k for k in out['full'] if not torch.equal(out['full'][k].view(torch.int32), out['own'][k].view(torch.int32))]
+    assert not differ, f'{differ} differ between workspaces of the calls\' own parts and dm_workspace_bytes'
+
+
 def _fmt(bits):
     on = [k for k, v in bits.items() if v is True]
     return '+'.join(on + ([f"nchunk{bits['nchunk']}"] if 'nchunk' in bits else [])) or 'none'

@@ -175,19 +175,22 @@ def _shape(model, frames, I=1, flags=0):
     return shp
 
 
-def _workspace(H, shp, book):
-    nbytes = H.workspace_bytes(shp)
+def _workspace(H, shp, book, floats=None):
+    """dm_workspace_bytes of canary-fenced scratch, or exactly `floats` floats"""
+    nbytes = H.workspace_bytes(shp) if floats is None else 4 * floats
     assert nbytes % 4 == 0
     ws = Guarded('workspace', nbytes // 4, book)
     return ws, ctypes.c_void_p(ws.t.data_ptr()), nbytes
 
 
-def _run_encoder(H, model, frames, inp, u8=False):
-    """dm_conv_encoder_fwd + _bwd.  Returns the outputs in the reference's layouts (on the CPU)."""
-    shp = _shape(model, frames, flags=H.DM_FLAG_IMAGE_U8 if u8 else 0)
+def _run_encoder(H, model, frames, inp, u8=False, flags=0, bwd_floats=None, bwd_cut=0, book=None):
+    """dm_conv_encoder_fwd + _bwd.  Returns the outputs in the reference's layouts (on the CPU).  bwd_floats: the backward runs
+    on a workspace of its own of exactly that many floats, and is told it has bwd_cut bytes less; book: the caller's list of the
+    buffers."""
+    shp = _shape(model, frames, flags=flags | (H.DM_FLAG_IMAGE_U8 if u8 else 0))
     enc = model.wm.encoder.encoder_image
     E = enc.out_dim
-    book = []
+    book = [] if book is None else book
     ws, ws_p, ws_n = _workspace(H, shp, book)
     acts = Guarded('encoder acts', int(H.lib().dm_conv_encoder_acts_floats(ctypes.byref(shp))), book)
     embed = Guarded('embed', frames * E, book)
@@ -199,8 +202,10 @@ def _run_encoder(H, model, frames, inp, u8=False):
     enc_g = H.conv_struct([g.t for g in gw], [g.t for g in gb], cls=H.dm_conv_grads)
     H.call('dm_conv_encoder_fwd', ctypes.byref(shp), H.ptr(image), ctypes.byref(enc_p), H.fptr(acts.t), H.fptr(embed.t), ws_p, ws_n,
            H.stream())
+    if bwd_floats is not None:
+        ws, ws_p, ws_n = _workspace(H, shp, book, bwd_floats)
     H.call('dm_conv_encoder_bwd', ctypes.byref(shp), H.ptr(image), ctypes.byref(enc_p), H.fptr(acts.t), H.fptr(dembed),
-           ctypes.byref(enc_g), ws_p, ws_n, H.stream())
+           ctypes.byref(enc_g), ws_p, ws_n - bwd_cut, H.stream())
     _assert_canaries(book, f'encoder, {frames} frames')
     out = {'embed': embed.t.view(frames, E).cpu()}
     for i, m in enumerate(enc.convs()):
@@ -209,16 +214,18 @@ def _run_encoder(H, model, frames, inp, u8=False):
     return out
 
 
-def _run_decoder(H, model, frames, inp, u8=False, I=1, row_scale=None, side=False, dfeat_prev=None, pad_f=8, pad_df=12):
+def _run_decoder(H, model, frames, inp, u8=False, I=1, row_scale=None, side=False, dfeat_prev=None, pad_f=8, pad_df=12, flags=0,
+                 fwd_floats=None, bwd_floats=None, fwd_cut=0, bwd_cut=0, book=None):
     """dm_conv_decoder_mse_fwd + dm_conv_decoder_mse_bwd_rows.  feat is an ldf = F + pad_f slice of a NaN-filled matrix, dfeat an
     lddf = F + pad_df slice holding `dfeat_prev` (all columns).  side: the backward runs armed (dm_wgrad_side_arm ... _join) on a
-    workspace nothing else touches before the join."""
-    shp = _shape(model, frames, I=I, flags=H.DM_FLAG_IMAGE_U8 if u8 else 0)
+    workspace nothing else touches before the join.  fwd_floats / bwd_floats: that call runs on a workspace of exactly that
+    many floats, and is told it has fwd_cut / bwd_cut bytes less; book: the caller's list of the buffers."""
+    shp = _shape(model, frames, I=I, flags=flags | (H.DM_FLAG_IMAGE_U8 if u8 else 0))
     dl = model.wm.decoder.image.layers()
     F_, ch = model.wm.features_dim, model.conf.image_channels
     ldf, lddf = F_ + pad_f, F_ + pad_df
-    book = []
-    ws, ws_p, ws_n = _workspace(H, shp, book)
+    book = [] if book is None else book
+    ws, ws_p, ws_n = _workspace(H, shp, book, fwd_floats)
     acts = Guarded('decoder acts', int(H.lib().dm_conv_decoder_acts_floats(ctypes.byref(shp))), book)
     loss = Guarded('loss_image', frames, book)
     rec = Guarded('image_rec', frames * ch * 4096, book)
@@ -234,12 +241,15 @@ def _run_decoder(H, model, frames, inp, u8=False, I=1, row_scale=None, side=Fals
     dec_p = H.conv_struct([m.weight for m in dl], [m.bias for m in dl])
     dec_g = H.conv_struct([g.t for g in gw], [g.t for g in gb], cls=H.dm_conv_grads)
     H.call('dm_conv_decoder_mse_fwd', ctypes.byref(shp), H.fptr(featm), ldf, H.ptr(target), ctypes.byref(dec_p), H.fptr(acts.t),
-           H.fptr(loss.t), H.fptr(rec.t), ws_p, ws_n, H.stream())
+           H.fptr(loss.t), H.fptr(rec.t), ws_p, ws_n - fwd_cut, H.stream())
+    if bwd_floats is not None:
+        ws, ws_p, ws_n = _workspace(H, shp, book, bwd_floats)
     if side:
         H.call('dm_wgrad_side_arm', 1)
     try:
         H.call('dm_conv_decoder_mse_bwd_rows', ctypes.byref(shp), H.fptr(featm), ldf, H.ptr(target), ctypes.byref(dec_p),
-               H.fptr(acts.t), _scale(frames), H.fptr(rs), ctypes.byref(dec_g), H.fptr(dfeat.t), lddf, ws_p, ws_n, H.stream())
+               H.fptr(acts.t), _scale(frames), H.fptr(rs), ctypes.byref(dec_g), H.fptr(dfeat.t), lddf, ws_p, ws_n - bwd_cut,
+               H.stream())
     finally:
         if side:
             H.call('dm_wgrad_side_join', H.stream())
@@ -457,3 +467,40 @@ def test_dispatch_reaches_every_kernel_class(hip):
     print(f'  direct kernels: none of {sorted(replaced)} appears among the tile-kernel launches at {n} frames; with '
           f'dm_dec_l4_bwd_direct_enable(0) the image layer\'s two backward products do: '
           f'{[r for r in off if replaced["decoder image layer data / weight gradient"](r)]}')
+
+
+@pytest.mark.parametrize('bf16', [False, True], ids=['f32', 'bf16'])
+def test_each_call_on_exactly_its_own_workspace_part(hip, bf16):
+    """dm_workspace_query: the encoder backward, the decoder forward and the decoder backward each run on a canary-fenced
+    workspace of exactly their own part and give the bits they give on dm_workspace_bytes; one 256-byte granule less is refused
+    with DM_E_WORKSPACE before anything is launched (every output still holds its fill pattern).  cnn_depth 8, 3 frames."""
+    oconf, _, model = _model(8, 3)
+    frames, flags = 3, hip.DM_FLAG_BF16 if bf16 else 0
+    inp = _inputs(oconf, frames)
+    shp = _shape(model, frames, flags=flags)
+    q = (ctypes.c_size_t * 8)()
+    hip.call('dm_workspace_query', ctypes.byref(shp), q, 8)
+    enc_bwd, dec_fwd, dec_bwd = int(q[1]), int(q[2]), int(q[3])
+    print(f'parts (floats): encoder backward {enc_bwd}, decoder forward {dec_fwd}, decoder backward {dec_bwd}; '
+          f'dm_workspace_bytes {hip.workspace_bytes(shp)}')
+    assert min(enc_bwd, dec_fwd, dec_bwd) >= 16 * 1024 * 1024 and 4 * max(q) < hip.workspace_bytes(shp)
+    full = {**{'enc ' + k: v for k, v in _run_encoder(hip, model, frames, inp, flags=flags).items()},
+            **{'dec ' + k: v for k, v in _run_decoder(hip, model, frames, inp, flags=flags).items()}}
+    own = {**{'enc ' + k: v for k, v in _run_encoder(hip, model, frames, inp, flags=flags, bwd_floats=enc_bwd).items()},
+           **{'dec ' + k: v for k, v in _run_decoder(hip, model, frames, inp, flags=flags, fwd_floats=dec_fwd,
+                                                     bwd_floats=dec_bwd).items()}}
+    differ = [k for k in full if not torch.equal(full[k].view(torch.int32), own[k].view(torch.int32))]
+    assert not differ, f'{differ} differ between a workspace of the call\'s own part and dm_workspace_bytes'
+    assert all(bool(torch.isfinite(v).all()) for v in own.values())
+
+    def refused(run, untouched, **kw):
+        book = []
+        with pytest.raises(hip.DreamerHipError, match='code -2.*workspace too small'):
+            run(hip, model, frames, inp, flags=flags, book=book, **kw)
+        torch.cuda.synchronize()
+        checked = [b for b in book if b.name.startswith(untouched)]
+        assert checked and all(bool((b.raw == CANARY).all()) for b in checked), f'{kw}: something was launched'
+
+    refused(_run_encoder, 'encoder d', bwd_floats=enc_bwd, bwd_cut=256)
+    refused(_run_decoder, ('decoder acts', 'loss_image', 'image_rec'), fwd_floats=dec_fwd, fwd_cut=256)
+    refused(_run_decoder, 'decoder d', bwd_floats=dec_bwd, bwd_cut=256)

@@ -141,6 +141,20 @@ def test_workspace_fallbacks(hip, short_of, want):
     RC.check(c, ora, out, f'ws-M300 short of {short_of}')
 
 
+def test_workspace_of_exactly_the_rollout_part(hip):
+    """dm_workspace_query's rollout part as the whole workspace: every optional block of RolloutCtx::plan still fits - the case's
+    own bits - and all bars apply."""
+    import ctypes
+    c, ora = _inputs_and_oracle('ws-M300')
+    shp = RC._model(c, False).wm.shape(1, c['M'], c['H'])
+    parts = (ctypes.c_size_t * 8)()
+    hip.call('dm_workspace_query', ctypes.byref(shp), parts, 8)
+    fl = RC.plan_floats(c)
+    assert int(parts[6]) == fl['must'] + fl['wzt'] + fl['wpack'] + fl['add0'] and 4 * int(parts[6]) < hip.workspace_bytes(shp)
+    out = RC.run_case(c, RC.CASES['ws-M300']['bits'], ws_bytes=4 * int(parts[6]), label='ws-M300 on exactly the rollout part')
+    RC.check(c, ora, out, 'ws-M300 on exactly the rollout part')
+
+
 def test_workspace_short_of_the_mandatory_part(hip):
     """One granule short of what plan() must have: the workspace error, and nothing launched (every output still at its fill
     value after a device synchronise); one granule more and the call runs, with every optional block refused."""

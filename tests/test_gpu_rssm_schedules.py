@@ -151,3 +151,10 @@ def test_no_layernorm_at_the_base_width(hip):
     """layer_norm=False at the base width: every fused bit off; the step's plain products run on the skinny kernel (at the tiny
     width they are tiled)."""
     _run(16, 4, BASE, _fwd(fuse_ln=False, psync_level2=False), _bwd(fuse_b=False), conf_kw=dict(layer_norm=False), fused_bwd=False)
+
+
+def test_base_on_exactly_its_own_workspace_parts(hip):
+    """dm_workspace_query: the forward (at level 2) on exactly the chain's part and the backward on exactly the BPTT part take every
+    optional buffer they take on dm_workspace_bytes - wzt, the fragment copies, the persistent kernel's exchange buffers; the fold
+    buffers, fold_sm, the fragment copies - and give the same bits in every output and gradient."""
+    RC.run_on_own_parts(16, 4, *BASE, expect_fwd=_fwd()(2), expect_bwd=_bwd()(1, False))
