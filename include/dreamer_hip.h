@@ -104,7 +104,7 @@ int dm_version(void);                 /* ABI version, currently 17 (v2: LayerNor
                                          v17: dm_gemm_plan_query added; later, still 17 (additions only): dm_cem_draw / dm_cem_update
                                               of the latent-space planner; dm_twohot_decode / dm_twohot_loss / dm_return_norm of the
                                               two-hot critic and the percentile return normalisation; dm_mlp_plan_query;
-                                              dm_workspace_query */
+                                              dm_workspace_query; dm_conv_plan_query */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
 /* Scratch that serves any call below for this shape: the maximum of the fused operators' own workspace layouts (each sized
@@ -181,6 +181,22 @@ int dm_gemm_plan_query(int mode, int a_layout, int b_layout, int M, int N, int K
  * same bits for finite weights.  1 / 0 switches it on / off (off: rows ordered (frame, yy, xx), every k-tile), -1 queries;
  * returns the state (default 1).  bf16-mode calls are not affected. */
 int dm_convt_kskip_enable(int on);
+/* What a convolution entry point would do at a shape - the plan its launch loop carries out (csrc/conv.hip), asked without a
+ * device.  which 0 = dm_conv_encoder_fwd(_planes), 1 = dm_conv_encoder_bwd(_planes), 2 = dm_conv_decoder_mse_fwd, 3 =
+ * dm_conv_decoder_mse_bwd(_rows); planes != 0: the _planes variant with reward_input (encoder only).  The answer follows
+ * dm_convt_kskip_enable, dm_dec_l4_bwd_direct_enable and dm_bf16_twins_enable as they stand.
+ * out[l], l = 0..4 = form | bits << 8 of layer l (encoder layers 0..3, decoder layers 1..4; -1: no such layer).  Forms: 0 direct
+ * kernel (conv_direct.hip), 1 direct kernel with the reward / terminal planes, 2 explicit patch matrix, 3 implicit (gathered)
+ * patch matrix, 4 gather-form transposed convolution, 5 column matrix + col2im, 6 one input pixel (the product writes NHWC).
+ *   encoder forward: out[0] in {0, 2}, out[1..3] = 3;  encoder backward: out[0] in {0, 1, 2} is layer 0's weight gradient,
+ *   out[l] in {4, 5} the data gradient out of layer l = 1..3;  decoder forward: out[l] in {0, 4, 5, 6};  decoder backward:
+ *   out[l] in {0, 3}.
+ * Bits: 1 the gather form's padded operand and weights are stored as bf16, 2 the layer's output channels are padded to a
+ * multiple of 4 (decoder backward), 4 the data gradient is written at the padded pitch of the layer below, over a zero-filled
+ * buffer (decoder backward).  out[5] = 1 if gather-form products skip the zero border's k-tiles; out[6..7] = 0.
+ * need_floats (nullable): the workspace the call needs, in floats (at most the entry point's part of dm_workspace_query).
+ * Returns DM_OK, or DM_E_SHAPE for a geometry the entry point refuses. */
+int dm_conv_plan_query(int which, const dm_shape* shp, int planes, int32_t out[8], size_t* need_floats);
 /* The categorical KL-balance kernels behind dm_kl_balance_fwd / _bwd address one group of C logits per lane.  Where the shape
  * fits (C <= 63: two tensors of 128 groups at pitch C + 1 in 64 KB of LDS; forward also S <= 32, where a wave takes two rows) a
  * workgroup first copies its groups into LDS with coalesced 16-byte loads, and the backward writes both gradients back through

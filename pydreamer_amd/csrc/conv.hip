@@ -8,6 +8,7 @@
 // The backward passes are the same two gathers with the roles swapped (convT backward-data is a conv).
 // All kernels here are HBM-streaming; the contractions run in gemm.hip on the matrix cores.
 #include "common.h"
+#include <algorithm>
 
 // ---------------------------------------------------------------- patch gather ------------------
 // col[(i,ys,xs)][(ky,kx,cc)] = big[i, 2ys+ky, 2xs+kx, cc]      (NHWC, VEC floats of c per thread)
@@ -349,14 +350,6 @@ static int convt_tables_launch(int n, int hs, int cin, int ta, int hb, int cout,
   DM_LAUNCH_CHECK();
   return DM_OK;
 }
-// attach the lists written by convt_tables_launch to the product over those tables
-static void convt_attach_klist(DmGemm& q, const int* klist, int hs, int ta) {
-  if (!klist) return;
-  const int Hc = hs + ta - 1, nkt = dm_cdiv(q.K, 32);
-  q.k_list = klist; q.k_list_rows = CONVT_G; q.k_list_stride = nkt + 1;
-  q.k_list_mean = (double)nkt * hs * hs / ((double)Hc * Hc);      // the valid-tap share of the class grid: (ta hs)^2 of (ta Hc)^2
-  if (q.k_list_mean < 1.0) q.k_list_mean = 1.0;
-}
 // Wcat[(py,px,o)][(a,b,i)] = W[i][o][py+2a][px+2b]      (W: torch ConvTranspose2d layout (cin, cout, k, k))
 __global__ void __launch_bounds__(256) convt_repack_kernel(int cin, int cout, int k, const float* __restrict__ w,
                                                            float* __restrict__ wcat) {
@@ -404,6 +397,82 @@ static bool convt_gather_ok(int k, int cin, int cout, int hs, size_t n) {
   const int Hc = hs + k / 2 - 1;
   return (k & 1) == 0 && (cin & 3) == 0 && cout >= 16 && 10 * Hc * Hc <= 14 * hs * hs &&
          n * (size_t)(2 * (hs - 1) + k + 1) * (2 * (hs - 1) + k + 1) * cout < ((size_t)1 << 31);
+}
+// What one such layer needs beside its operands: floats of the zero-padded input copy, rows of the gather / scatter tables, floats of
+// the class-concatenated weights, ints of the k-tile lists; zeros and ok = false where the form is refused.  An operator folds its layers.
+struct ConvtScratch {
+  bool ok = false; size_t pad = 0, tab = 0, wcat = 0, klist = 0;
+  void fold(const ConvtScratch& s) {
+    ok |= s.ok; pad = std::max(pad, s.pad); tab = std::max(tab, s.tab); wcat = std::max(wcat, s.wcat); klist = std::max(klist, s.klist);
+  }
+};
+static ConvtScratch convt_gather_scratch(int k, int cin, int cout, int hs, size_t n) {
+  ConvtScratch s;
+  if (!(s.ok = convt_gather_ok(k, cin, cout, hs, n))) return s;
+  const size_t ta = k / 2, kdim = ta * ta * cin, hp = hs + 2 * (ta - 1), Hc = hs + ta - 1;
+  s.pad = n * hp * hp * cin; s.tab = n * Hc * Hc; s.wcat = (size_t)4 * cout * kdim; s.klist = convt_klist_ints(s.tab, kdim);
+  return s;
+}
+// The scratch block itself, carved the same way by every operator that has such layers.  koff_cap: ints of the k offset table
+// (it is indexed by (a, b, i): (k/2)^2 * cin of the widest layer the operator admits).  wcat_h: bf16 copy of wcat (bf16 mode).
+struct ConvtWs {
+  float *pad, *wcat; unsigned short* wcat_h;
+  int *t_rowoff, *t_koff, *t_klist; int2* t_ctab; int koff_cap;
+};
+static void convt_gather_carve(DmArena& ar, const ConvtScratch& s, int koff_cap, bool tw_on, ConvtWs* w) {
+  w->pad = ar.take(s.pad);
+  w->t_rowoff = (int*)ar.take(s.tab);
+  w->t_ctab = (int2*)ar.take(2 * s.tab);
+  w->t_koff = (int*)ar.take(w->koff_cap = s.wcat ? koff_cap : 0);
+  w->wcat = ar.take(s.wcat);
+  w->wcat_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(s.wcat) : 0);
+  w->t_klist = (int*)ar.take(s.klist);      // (sized whether or not dm_convt_kskip_enable is on)
+}
+// One layer: a (cin -> cout) ConvTranspose2d(k, stride 2) from n x hs x hs x cin (src, NHWC) to n x hb x hb x cout (dst, NHWC),
+// w in the torch layout (cin, cout, k, k).  dst = act(bias + ...) * ELU'(mulref).  hb = 2 (hs + k/2 - 1) for a transposed
+// convolution proper; the data gradient of a stride-2 convolution over an odd extent has one more row / column, cleared here.
+struct ConvtGather {
+  const char* what; int n, hs, hb, k, cin, cout;
+  const float *src, *w; float* dst;
+  const float *bias = nullptr, *mulref = nullptr; int flags = 0; bool no_twin = false;
+};
+// hpath: the padded copy and the weights are stored as bf16 (the product reads those); klist_on: chunk-major rows and k-tile lists
+static int convt_gather_launch(const ConvtGather& c, const ConvtWs& w, bool hpath, bool klist_on, float* splitk, hipStream_t st) {
+  const int ta = c.k / 2, Hc = c.hs + ta - 1, hp = c.hs + 2 * (ta - 1), kdim = ta * ta * c.cin;
+  DM_REQUIRE(kdim <= w.koff_cap, DM_E_SHAPE, "%s: gather-form K %d exceeds the offset table", c.what, kdim);
+  const size_t padn = (size_t)c.n * hp * hp * (c.cin / 4);
+  if (hpath) hipLaunchKernelGGL(convt_pad_h_kernel, dim3(grid_for(padn)), dim3(256), 0, st, c.n, c.hs, c.hs, c.cin / 4, ta - 1,
+                                (const float4*)c.src, (uint2*)w.pad);
+  else hipLaunchKernelGGL(convt_pad_kernel, dim3(grid_for(padn)), dim3(256), 0, st, c.n, c.hs, c.hs, c.cin / 4, ta - 1,
+                          (const float4*)c.src, (float4*)w.pad);
+  DM_LAUNCH_CHECK();
+  int* klist = klist_on ? w.t_klist : nullptr;
+  DM_TRY(convt_tables_launch(c.n, c.hs, c.cin, ta, c.hb, c.cout, w.t_rowoff, w.t_koff, w.t_ctab, klist, st));
+  hipLaunchKernelGGL(convt_repack_kernel, dim3(grid_for((size_t)4 * c.cout * kdim)), dim3(256), 0, st, c.cin, c.cout, c.k, c.w,
+                     w.wcat);
+  DM_LAUNCH_CHECK();
+  const DmCvtSeg sg = {w.wcat, w.wcat_h, (size_t)4 * c.cout * kdim};
+  if (hpath) DM_TRY(dm_to_bf16_multi_launch(&sg, 1, st));
+  if (2 * Hc != c.hb) {      // odd extent (31): the last row / column is reached by no window; the scatter epilogue writes the rest
+    const int E = 2 * Hc, nb = c.hb * c.hb - E * E, V = (c.cout & 3) == 0 ? 4 : 1;
+    hipLaunchKernelGGL(V == 4 ? convt_border_zero_kernel<4> : convt_border_zero_kernel<1>, dim3(grid_for((size_t)c.n * nb * (c.cout / V))),
+                       dim3(256), 0, st, c.n, c.hb, E, c.cout / V, c.dst, dm_twin_of(c.dst, false));
+    DM_LAUNCH_CHECK();
+  }
+  DmGemm q;   // big[n, 2yy+py, 2xx+px, o] = act( b[o] + patch(n,yy,xx) . Wcat[(py,px,o)] ) * ELU'(mulref)
+  q.M = c.n * Hc * Hc; q.N = 4 * c.cout; q.K = kdim;
+  q.A = w.pad; q.a_maj = w.t_rowoff; q.a_min = w.t_koff; q.a_tab_vec = 1; q.a_tab_vec8 = 1;
+  if (hpath) { q.A = nullptr; q.A_h = (const unsigned short*)w.pad; q.B_h = w.wcat_h; }
+  q.B = w.wcat; q.ldb = kdim;
+  q.C = c.dst;
+  q.c_tab = w.t_ctab; q.sc_cout = c.cout; q.sc_wpitch = c.hb * c.cout;
+  q.bias = c.bias; q.flags = c.flags; q.mulref = c.mulref; q.no_twin = c.no_twin;
+  if (klist) {      // the lists written by convt_tables_launch
+    q.k_list = klist; q.k_list_rows = CONVT_G; q.k_list_stride = dm_cdiv(kdim, 32) + 1;
+    // the valid-tap share of the class grid: (ta hs)^2 of (ta Hc)^2
+    q.k_list_mean = std::max(1.0, (double)dm_cdiv(kdim, 32) * c.hs * c.hs / ((double)Hc * Hc));
+  }
+  return dm_gemm_launch(q, splitk, DM_SPLITK_FLOATS * sizeof(float), st);
 }
 
 // ---------------------------------------------------------------- MSE (decoders.py:163-167) -----
@@ -543,6 +612,29 @@ struct DecGeom {
   }
   bool valid(const dm_shape* s) const { return hbg[4] == s->img && s->img == 64; }
 };
+static bool dec_direct4(const DecGeom& g) { return dm_dec_l4_direct_ok(g.ch, g.d, g.hsm[4], g.k[4]); }      // the shape admits the image layer's direct kernels
+
+// ---------------------------------------------------------------- plans -------------------------
+// What an entry point does at a shape.  enc_fwd_plan / enc_bwd_plan / dec_fwd_plan / dec_bwd_plan compute it from the geometry,
+// `planes`, whether bf16 twins are in use (tw_on) and the process switches - no HIP call, no pointer read; the launch loops only
+// carry out form[l], and the layouts size from the same plan (include/dreamer_hip.h dm_conv_plan_query lists the codes).
+enum { CONV_DIRECT = 0, CONV_DIRECT_PLANES = 1, CONV_PATCH = 2, CONV_IMPLICIT = 3, CONV_GATHER = 4, CONV_COLUMN = 5, CONV_ONE_PIXEL = 6 };
+enum { CONV_HPATH = 1, CONV_PADDED = 2, CONV_REPITCH = 4 };
+struct ConvPlan {
+  int form[5] = {-1, -1, -1, -1, -1}, bits[5] = {0, 0, 0, 0, 0};      // by layer: encoder 0..3, decoder 1..4
+  bool kskip = false;          // gather layers: chunk-major rows and k-tile lists (dm_convt_kskip_enable, fp32 only)
+  ConvtScratch gather;         // scratch of the gather layers, folded
+  size_t need = 0;             // workspace, floats
+  // layer l as a gather-form layer, if admitted; CONV_HPATH: its padded operand and weights are stored as bf16
+  bool take_gather(int l, bool tw_on, int k, int cin, int cout, int hs, size_t n) {
+    const ConvtScratch s = convt_gather_scratch(k, cin, cout, hs, n);
+    if (!s.ok) return false;
+    form[l] = CONV_GATHER;
+    bits[l] = tw_on && (cin & 7) == 0 && (k / 2) * (k / 2) * cin >= DM_HSTORE_MIN_K ? CONV_HPATH : 0;
+    gather.fold(s);
+    return true;
+  }
+};
 
 // ---------------------------------------------------------------- encoder -----------------------
 struct EncActs {
@@ -609,14 +701,39 @@ __global__ void __launch_bounds__(256) nhwc_to_chw_flat_ld_kernel(size_t n, int 
   }
 }
 
+// the embedding (n, 4 c) in torch's flatten order, leading dimension ld, to (to_chw = 0: from) the NHWC layer-4 tensor
+static int chw_flat_launch(size_t n, int c, const float* src, float* dst, int ld, int to_chw, hipStream_t st) {
+  if (ld == 4 * c)
+    hipLaunchKernelGGL(nhwc_to_chw_flat_kernel, dim3(grid_for(n * 4 * c)), dim3(256), 0, st, n, 4, c, src, dst, to_chw);
+  else
+    hipLaunchKernelGGL(nhwc_to_chw_flat_ld_kernel, dim3(grid_for(n * 4 * c)), dim3(256), 0, st, n, 4, c, src, dst, ld, to_chw);
+  DM_LAUNCH_CHECK();
+  return DM_OK;
+}
+// The geometry both directions accept.  planes (reward_input): E is the caller's, ld the leading dimension of the embedding.
+static int enc_validate(const dm_shape* shp, const EncGeom& g, bool planes, int ld, const char* what) {
+  DM_REQUIRE((planes ? g.valid_planes(shp) : g.valid(shp)) && ld >= 32 * g.d, DM_E_SHAPE,
+             "%s: unsupported geometry (img=%d, ch=%d, E=%d, depth=%d, ld=%d, planes=%d: built for 3 x 64 x 64 frames and cnn_depth in "
+             "{8,16,32,48,64})", what, shp->img, shp->img_ch, shp->E, shp->cnn_depth, ld, (int)planes);
+  return DM_OK;
+}
+
 // The forward's workspace: [split-K | the direct layer-1 kernel's transposed weights | reward_input: its per-frame bias].  On an
 // arena without a base it sizes.
-struct EncFwdWs { float *wt, *fb; };
-static size_t enc_fwd_layout(DmArena ar, const EncGeom& g, bool planes, EncFwdWs* w) {
-  ar.take(DM_SPLITK_FLOATS);
-  w->wt = ar.take(g.direct0 ? (size_t)48 * g.d : 0);
+struct EncFwdWs { float *splitk, *wt, *fb; };
+static size_t enc_fwd_layout(DmArena ar, const EncGeom& g, const ConvPlan& pl, bool planes, EncFwdWs* w) {
+  w->splitk = ar.take(DM_SPLITK_FLOATS);
+  w->wt = ar.take(pl.form[0] == CONV_DIRECT ? (size_t)48 * g.d : 0);
   w->fb = ar.take(planes ? (size_t)g.N * g.d : 0);
   return ar.off;
+}
+static ConvPlan enc_fwd_plan(const EncGeom& g, bool planes) {
+  ConvPlan pl;
+  pl.form[0] = g.direct0 ? CONV_DIRECT : CONV_PATCH;      // 3 -> d channels: one direct kernel on the frame / an explicit patch matrix
+  for (int l = 1; l < 4; ++l) pl.form[l] = CONV_IMPLICIT;
+  EncFwdWs w;
+  pl.need = enc_fwd_layout(DmArena(nullptr, 0), g, pl, planes, &w);
+  return pl;
 }
 
 // reward / terminal (N,): non-null = reward_input, p->w[0] is (d, 5, 4, 4) and the two planes are folded into layer 1
@@ -626,20 +743,14 @@ static int conv_encoder_fwd_impl(const dm_shape* shp, const float* image, const 
   DmPrecisionScope prec(shp->flags & DM_FLAG_BF16);
   EncGeom g(shp);
   const bool planes = reward != nullptr;
-  if (planes) {
-    DM_REQUIRE(g.valid_planes(shp) && ld >= 32 * g.d, DM_E_SHAPE,
-               "conv_encoder planes: built for 3 x 64 x 64 frames and cnn_depth in {8,16,32,48,64} (img=%d, ch=%d, depth=%d, ld=%d)",
-               shp->img, shp->img_ch, shp->cnn_depth, ld);
-  } else {
-    DM_REQUIRE(g.valid(shp) && ld >= 32 * g.d, DM_E_SHAPE, "conv_encoder: unsupported geometry (img=%d, E=%d, depth=%d, ld=%d)",
-               shp->img, shp->E, shp->cnn_depth, ld);
-  }
+  DM_TRY(enc_validate(shp, g, planes, ld, "conv_encoder_fwd"));
   hipStream_t st = (hipStream_t)stream;
   EncActs a;
   enc_carve(g, acts, (size_t)1 << 60, &a);
+  const ConvPlan pl = enc_fwd_plan(g, planes);
   EncFwdWs w;
-  const size_t need = enc_fwd_layout(DmArena(ws, ws_bytes), g, planes, &w);
-  DM_REQUIRE(need <= ws_bytes / sizeof(float), DM_E_WORKSPACE, "conv_encoder_fwd: workspace too small (need %zu floats)", need);
+  enc_fwd_layout(DmArena(ws, ws_bytes), g, pl, planes, &w);
+  DM_REQUIRE(pl.need <= ws_bytes / sizeof(float), DM_E_WORKSPACE, "conv_encoder_fwd: workspace too small (need %zu floats)", pl.need);
   DmTwinScope tw((shp->flags & DM_FLAG_BF16) != 0);
   enc_register_twins(g, a, false, false);
   dm_twin_arena_note(acts, dm_twins_on());
@@ -653,8 +764,8 @@ static int conv_encoder_fwd_impl(const dm_shape* shp, const float* image, const 
     DM_TRY(dm_to_bf16_multi_launch(sg, 3, st));
   }
   if (g.N == 0) return DM_OK;
-  for (int l = 0; l < 4; ++l) {
-    if (l == 0 && g.direct0) {      // 3 -> d channels: one direct kernel on the frame, no patch matrix (conv_direct.hip)
+  for (int l = 0; l < 4; ++l) switch (pl.form[l]) {
+    case CONV_DIRECT: {      // no patch matrix (conv_direct.hip)
       unsigned short* y0h = dm_twin_of(a.y[0], false);
       if (planes)
         DM_TRY(dm_enc_l1_fwd_planes_launch(g.N, g.d, shape_u8(shp) ? 1 : 0, image, p->w[0], p->b[0], reward, terminal, w.wt, w.fb,
@@ -662,9 +773,9 @@ static int conv_encoder_fwd_impl(const dm_shape* shp, const float* image, const 
       else
         DM_TRY(dm_enc_l1_fwd_launch(g.N, g.d, shape_u8(shp) ? 1 : 0, image, p->w[0], p->b[0], w.wt, a.y[0], y0h, st));
       if (y0h) dm_twin_mark(a.y[0]);
-      continue;
+      break;
     }
-    if (l == 0) {
+    case CONV_PATCH:
       if (shape_u8(shp)) {
         const size_t total = (size_t)g.N * g.hs[0] * g.hs[0] * g.kdim[0];
         hipLaunchKernelGGL(im2col_s2_u8hwc_kernel, dim3(grid_for(total)), dim3(256), 0, st, g.N, g.hb[0], g.hb[0], g.cin[0], 4,
@@ -673,29 +784,24 @@ static int conv_encoder_fwd_impl(const dm_shape* shp, const float* image, const 
       } else {
         DM_TRY(dm_im2col_s2_launch(g.N, g.hb[0], g.hb[0], g.cin[0], 4, image, 1, a.xcol[0], st));
       }
+      [[fallthrough]];      // the product over the patch matrix: explicit here, gathered from the layer below otherwise
+    default: {
+      DmGemm q;
+      q.a_layout = 0; q.b_layout = 0;
+      q.M = g.N * g.hs[l] * g.hs[l]; q.N = g.cout[l]; q.K = (int)g.kdim[l];
+      if (l == 0) { q.A = a.xcol[0]; q.lda = q.K; }
+      else {
+        q.A = a.y[l - 1]; q.a_maj = a.rowoff[l]; q.a_min = a.koff[l];
+        q.a_tab_vec = (g.cin[l] & 3) == 0; q.a_tab_vec8 = (g.cin[l] & 7) == 0;
+      }
+      q.B = l == 0 ? p->w[0] : a.wr[l]; q.ldb = q.K;
+      q.C = a.y[l]; q.ldc = q.N;
+      q.bias = p->b[l];
+      q.flags = DM_GEMM_ELU;
+      DM_TRY(dm_gemm_launch(q, w.splitk, DM_SPLITK_FLOATS * sizeof(float), st));
     }
-    DmGemm q;
-    q.a_layout = 0; q.b_layout = 0;
-    q.M = g.N * g.hs[l] * g.hs[l]; q.N = g.cout[l]; q.K = (int)g.kdim[l];
-    if (l == 0) { q.A = a.xcol[0]; q.lda = q.K; }
-    else {
-      q.A = a.y[l - 1]; q.a_maj = a.rowoff[l]; q.a_min = a.koff[l];
-      q.a_tab_vec = (g.cin[l] & 3) == 0; q.a_tab_vec8 = (g.cin[l] & 7) == 0;
-    }
-    q.B = l == 0 ? p->w[0] : a.wr[l]; q.ldb = q.K;
-    q.C = a.y[l]; q.ldc = q.N;
-    q.bias = p->b[l];
-    q.flags = DM_GEMM_ELU;
-    DM_TRY(dm_gemm_launch(q, ws, DM_SPLITK_FLOATS * sizeof(float), st));
   }
-  const size_t tot = (size_t)g.N * 4 * g.cout[3];
-  if (ld == 4 * g.cout[3])
-    hipLaunchKernelGGL(nhwc_to_chw_flat_kernel, dim3(grid_for(tot)), dim3(256), 0, st, (size_t)g.N, 4, g.cout[3], a.y[3], embed, 1);
-  else
-    hipLaunchKernelGGL(nhwc_to_chw_flat_ld_kernel, dim3(grid_for(tot)), dim3(256), 0, st, (size_t)g.N, 4, g.cout[3], a.y[3], embed,
-                       ld, 1);
-  DM_LAUNCH_CHECK();
-  return DM_OK;
+  return chw_flat_launch((size_t)g.N, g.cout[3], a.y[3], embed, ld, 1, st);
 }
 extern "C" int dm_conv_encoder_fwd(const dm_shape* shp, const float* image, const dm_conv_params* p, float* acts,
                                    float* embed, void* ws, size_t ws_bytes, void* stream) {
@@ -713,12 +819,11 @@ extern "C" int dm_conv_encoder_fwd_planes(const dm_shape* shp, const float* imag
 // gradient in the repacked layout; dxcol: the explicit patch-matrix gradient of the layers that do not take the gather form,
 // and the direct layer-1 kernels' partials.  On an arena without a base it sizes.
 struct EncBwdWs {
-  float *splitk, *ga, *gb, *dwr, *dxcol, *gpad, *wcat;
-  int *t_rowoff, *t_koff, *t_klist; int2* t_ctab;
-  unsigned short *ga_h, *gb_h, *wcat_h;
-  size_t gmax, xcmax;      // floats of ga and of dxcol
+  float *splitk, *ga, *gb, *dwr, *dxcol;
+  ConvtWs gather;      // the gather-form data gradients (the data gradient of a stride-2 convolution IS a transposed convolution)
+  unsigned short *ga_h, *gb_h; size_t gmax, xcmax;      // floats of ga and of dxcol
 };
-static size_t enc_bwd_layout(DmArena ar, const EncGeom& g, bool tw_on, EncBwdWs* w) {
+static size_t enc_bwd_layout(DmArena ar, const EncGeom& g, const ConvPlan& pl, bool tw_on, EncBwdWs* w) {
   w->splitk = ar.take(DM_SPLITK_FLOATS);
   const size_t gmax = w->gmax = g.rows[0] * g.cout[0];
   w->ga = ar.take(gmax);
@@ -727,29 +832,21 @@ static size_t enc_bwd_layout(DmArena ar, const EncGeom& g, bool tw_on, EncBwdWs*
   size_t xcmax = 0;
   for (int l = 1; l < 4; ++l) if (g.rows[l] * g.kdim[l] > xcmax) xcmax = g.rows[l] * g.kdim[l];
   w->dxcol = ar.take(w->xcmax = xcmax);
-  // gather-form data gradient (see convt_* above: the data gradient of a stride-2 convolution IS a transposed convolution)
-  size_t padmax = 0, tabmax = 0, wcmax = 0, klmax = 0;
-  for (int l = 1; l < 4; ++l)
-    if (convt_gather_ok(4, g.cout[l], g.cin[l], g.hs[l], (size_t)g.N)) {
-      const size_t hp = g.hs[l] + 2, Hc = g.hs[l] + 1;
-      if ((size_t)g.N * hp * hp * g.cout[l] > padmax) padmax = (size_t)g.N * hp * hp * g.cout[l];
-      if ((size_t)g.N * Hc * Hc > tabmax) tabmax = (size_t)g.N * Hc * Hc;
-      if ((size_t)16 * g.cin[l] * g.cout[l] > wcmax) wcmax = (size_t)16 * g.cin[l] * g.cout[l];
-      const size_t kl = convt_klist_ints((size_t)g.N * Hc * Hc, 4 * g.cout[l]);
-      if (kl > klmax) klmax = kl;
-    }
-  w->gpad = ar.take(padmax);
-  w->t_rowoff = (int*)ar.take(tabmax);
-  w->t_ctab = (int2*)ar.take(2 * tabmax);
-  w->t_koff = (int*)ar.take(wcmax ? 4 * 1024 : 0);
-  w->wcat = ar.take(wcmax);
-  w->t_klist = (int*)ar.take(klmax);      // (sized whether or not the switch is on)
-  // bf16 mode: twins of the two gradient ping-pong buffers and of the class-concatenated weights; the zero-padded gradient
-  // copy is written as bf16 only (it lives in the fp32 copy's storage)
+  convt_gather_carve(ar, pl.gather, 4 * 1024, tw_on, &w->gather);      // k = 4: K = 4 cout, up to 1024 output channels
+  // bf16 mode: twins of the two gradient ping-pong buffers (the padded gradient copy is written as bf16 only, in the fp32 copy's storage)
   w->ga_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(gmax) : 0);
   w->gb_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(g.rows[1] * g.cout[1]) : 0);
-  w->wcat_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(wcmax) : 0);
   return ar.off;
+}
+static ConvPlan enc_bwd_plan(const EncGeom& g, bool planes, bool tw_on) {
+  ConvPlan pl;
+  pl.kskip = g_convt_kskip && !g.twins;
+  pl.form[0] = !g.direct0 ? CONV_PATCH : planes ? CONV_DIRECT_PLANES : CONV_DIRECT;      // layer 0 has a weight gradient only
+  for (int l = 1; l < 4; ++l)      // the data gradient out of layer l: a (cout -> cin) transposed convolution from hs to hb
+    if (!pl.take_gather(l, tw_on, 4, g.cout[l], g.cin[l], g.hs[l], (size_t)g.N)) pl.form[l] = CONV_COLUMN;
+  EncBwdWs w;
+  pl.need = enc_bwd_layout(DmArena(nullptr, 0), g, pl, tw_on, &w);
+  return pl;
 }
 
 static int conv_encoder_bwd_impl(const dm_shape* shp, const float* image, const dm_conv_params* p, const float* acts,
@@ -758,23 +855,17 @@ static int conv_encoder_bwd_impl(const dm_shape* shp, const float* image, const 
   DmPrecisionScope prec(shp->flags & DM_FLAG_BF16);
   EncGeom g(shp);
   const bool planes = reward != nullptr;
-  if (planes) {
-    DM_REQUIRE(g.valid_planes(shp) && ld >= 32 * g.d, DM_E_SHAPE,
-               "conv_encoder planes: built for 3 x 64 x 64 frames and cnn_depth in {8,16,32,48,64} (img=%d, ch=%d, depth=%d, ld=%d)",
-               shp->img, shp->img_ch, shp->cnn_depth, ld);
-  } else {
-    DM_REQUIRE(g.valid(shp) && ld >= 32 * g.d, DM_E_SHAPE, "conv_encoder: unsupported geometry");
-  }
+  DM_TRY(enc_validate(shp, g, planes, ld, "conv_encoder_bwd"));
   hipStream_t st = (hipStream_t)stream;
   EncActs a;
   enc_carve(g, const_cast<float*>(acts), (size_t)1 << 60, &a);
   DmTwinScope tw((shp->flags & DM_FLAG_BF16) != 0);
   const bool tw_on = dm_twins_on();
+  const ConvPlan pl = enc_bwd_plan(g, planes, tw_on);
   EncBwdWs w;
-  const size_t need = enc_bwd_layout(DmArena(ws, ws_bytes), g, tw_on, &w);
-  DM_REQUIRE(need <= ws_bytes / sizeof(float), DM_E_WORKSPACE, "conv_encoder_bwd: workspace too small (need %zu floats)", need);
-  const auto& [splitk, ga, gb, dwr, dxcol, gpad, wcat, t_rowoff, t_koff, t_klist, t_ctab, ga_h, gb_h, wcat_h, gmax, xcmax] = w;
-  const bool kskip = g_convt_kskip && !(shp->flags & DM_FLAG_BF16);
+  enc_bwd_layout(DmArena(ws, ws_bytes), g, pl, tw_on, &w);
+  DM_REQUIRE(pl.need <= ws_bytes / sizeof(float), DM_E_WORKSPACE, "conv_encoder_bwd: workspace too small (need %zu floats)", pl.need);
+  const auto& [splitk, ga, gb, dwr, dxcol, gather, ga_h, gb_h, gmax, xcmax] = w;
   const size_t skb = DM_SPLITK_FLOATS * sizeof(float);
   const bool arena_tw = dm_twin_arena_valid(acts);      // the forward that filled `acts` wrote its twins
   enc_register_twins(g, a, arena_tw, arena_tw);
@@ -784,13 +875,7 @@ static int conv_encoder_bwd_impl(const dm_shape* shp, const float* image, const 
   // dY3 (NHWC) = permute(dembed) ; G = dY3 * ELU'(Y3)
   float* G = gb;      // layer-3 grads are small; ping-pong between ga / gb going down
   const size_t tot3 = (size_t)g.N * 4 * g.cout[3];
-  if (ld == 4 * g.cout[3])
-    hipLaunchKernelGGL(nhwc_to_chw_flat_kernel, dim3(grid_for(tot3)), dim3(256), 0, st, (size_t)g.N, 4, g.cout[3], dembed, G,
-                       0);
-  else
-    hipLaunchKernelGGL(nhwc_to_chw_flat_ld_kernel, dim3(grid_for(tot3)), dim3(256), 0, st, (size_t)g.N, 4, g.cout[3], dembed, G,
-                       ld, 0);
-  DM_LAUNCH_CHECK();
+  DM_TRY(chw_flat_launch((size_t)g.N, g.cout[3], dembed, G, ld, 0, st));
   DM_TRY(dm_mul_elu_grad_launch(tot3, G, a.y[3], G, st));
   if (tw_on) {
     const DmCvtSeg sg = {G, dm_twin_of(G, false), tot3};
@@ -799,22 +884,17 @@ static int conv_encoder_bwd_impl(const dm_shape* shp, const float* image, const 
   }
   for (int l = 3; l >= 0; --l) {
     const int rows = (int)g.rows[l], co = g.cout[l], kd = (int)g.kdim[l];
-    if (l == 0 && planes) {
+    const bool with_planes = pl.form[l] == CONV_DIRECT_PLANES;
+    if (!with_planes) DM_TRY(dm_colsum_launch(rows, co, G, co, gr->b[l], splitk, skb, st));
+    if (with_planes || pl.form[l] == CONV_DIRECT) {      // patches re-gathered from the frame inside the weight-gradient kernel (conv_direct.hip)
       // reward_input: the image channels' weight gradient as ever (into `dwr`, free by now), then ONE frame-weighted column sum
-      // over G gives the bias gradient and the two plane gradients, and the (d, 5, 4, 4) gradient is assembled (conv_direct.hip)
+      // over G gives the bias gradient and the two plane gradients, and the (d, 5, 4, 4) gradient is assembled
       DM_REQUIRE(image, DM_E_NULL, "conv_encoder_bwd: the direct layer-1 weight gradient reads the image");
-      DM_REQUIRE(dm_enc_l1_wgrad_part_floats(g.N, g.d) <= xcmax && dm_enc_l1_planes_part_floats(g.N, g.d) <= xcmax,
+      DM_REQUIRE(dm_enc_l1_wgrad_part_floats(g.N, g.d) <= xcmax && (!with_planes || dm_enc_l1_planes_part_floats(g.N, g.d) <= xcmax),
                  DM_E_WORKSPACE, "conv_encoder_bwd: partial buffer too small");
-      DM_TRY(dm_enc_l1_wgrad_launch(g.N, g.d, shape_u8(shp) ? 1 : 0, image, G, dxcol, dwr, splitk, skb, st));
-      DM_TRY(dm_enc_l1_planes_bwd_launch(g.N, g.d, G, reward, terminal, dwr, dxcol, gr->b[0], gr->w[0], st));
-      continue;
-    }
-    DM_TRY(dm_colsum_launch(rows, co, G, co, gr->b[l], splitk, skb, st));
-    if (l == 0 && g.direct0) {      // patches re-gathered from the frame inside the weight-gradient kernel (conv_direct.hip)
-      DM_REQUIRE(image, DM_E_NULL, "conv_encoder_bwd: the direct layer-1 weight gradient reads the image");
-      DM_REQUIRE(dm_enc_l1_wgrad_part_floats(g.N, g.d) <= xcmax, DM_E_WORKSPACE, "conv_encoder_bwd: partial buffer too small");
-      DM_TRY(dm_enc_l1_wgrad_launch(g.N, g.d, shape_u8(shp) ? 1 : 0, image, G, dxcol, gr->w[0], splitk, skb, st));
-      continue;
+      DM_TRY(dm_enc_l1_wgrad_launch(g.N, g.d, shape_u8(shp) ? 1 : 0, image, G, dxcol, with_planes ? dwr : gr->w[0], splitk, skb, st));
+      if (with_planes) DM_TRY(dm_enc_l1_planes_bwd_launch(g.N, g.d, G, reward, terminal, dwr, dxcol, gr->b[0], gr->w[0], st));
+      break;
     }
     DmGemm q;   // dWr[o][kidx] = sum_rows G[row][o] * Xcol[row][kidx]
     q.a_layout = 1; q.b_layout = 1;
@@ -827,53 +907,17 @@ static int conv_encoder_bwd_impl(const dm_shape* shp, const float* image, const 
     }
     q.C = (l == 0) ? gr->w[0] : dwr; q.ldc = kd;
     DM_TRY(dm_gemm_launch(q, splitk, skb, st));
-    if (l > 0 && convt_gather_ok(4, co, g.cin[l], g.hs[l], (size_t)g.N)) {
+    if (l == 0) break;
+    DM_TRY(dm_permute4_launch(dwr, gr->w[l], co, 4, 4, g.cin[l], 0, 3, 1, 2, st));
+    float* Gn = (l == 1 || G != ga) ? ga : gb;      // ping-pong; layer 0's output gradient, the largest, goes to ga
+    if (pl.form[l] == CONV_GATHER) {
       // dX[n, 2yy+py, 2xx+px, i] = ELU'(Y_{l-1}) * sum_{a,b,o} G[n, yy-a, xx-b, o] W[o][i][py+2a][px+2b]: one implicit GEMM
       // over a zero-padded copy of G, scattered straight into the NHWC gradient of layer l-1 (no dXcol, no col2im)
-      DM_TRY(dm_permute4_launch(dwr, gr->w[l], co, 4, 4, g.cin[l], 0, 3, 1, 2, st));
-      const int hs = g.hs[l], hb = g.hb[l], Hc = hs + 1, kdim4 = 4 * co, ci = g.cin[l];
-      DM_REQUIRE(kdim4 <= 4 * 1024, DM_E_SHAPE, "conv_encoder_bwd: gather-form K %d exceeds the offset table", kdim4);
-      float* Gn = (G == ga) ? gb : ga;
-      if (l == 1) Gn = ga;   // layer-0 output grads are the largest buffer
-      const size_t padn = (size_t)g.N * (hs + 2) * (hs + 2) * (co / 4);
-      const bool hpath = tw_on && (co & 7) == 0 && kdim4 >= DM_HSTORE_MIN_K;      // bf16-storage product: padded gradient + weights as bf16
-      if (hpath) hipLaunchKernelGGL(convt_pad_h_kernel, dim3(grid_for(padn)), dim3(256), 0, st, g.N, hs, hs, co / 4, 1, (const float4*)G,
-                                    (uint2*)gpad);
-      else hipLaunchKernelGGL(convt_pad_kernel, dim3(grid_for(padn)), dim3(256), 0, st, g.N, hs, hs, co / 4, 1, (const float4*)G,
-                              (float4*)gpad);
-      DM_LAUNCH_CHECK();
-      DM_TRY(convt_tables_launch(g.N, hs, co, 2, hb, ci, t_rowoff, t_koff, t_ctab, kskip ? t_klist : nullptr, st));
-      hipLaunchKernelGGL(convt_repack_kernel, dim3(grid_for((size_t)4 * ci * kdim4)), dim3(256), 0, st, co, ci, 4, p->w[l], wcat);
-      DM_LAUNCH_CHECK();
-      if (hpath) {
-        const DmCvtSeg sg = {wcat, wcat_h, (size_t)4 * ci * kdim4};
-        DM_TRY(dm_to_bf16_multi_launch(&sg, 1, st));
-      }
-      if (2 * Hc != hb) {      // odd input extent (31): the last row / column is reached by no window - its gradient is zero
-        const int E = 2 * Hc, nb = hb * hb - E * E;      // the scatter epilogue below writes everything else (convt_border_zero_kernel)
-        unsigned short* gnh = (unsigned short*)dm_twin_of(Gn, false);
-        if ((ci & 3) == 0)
-          hipLaunchKernelGGL(convt_border_zero_kernel<4>, dim3(grid_for((size_t)g.N * nb * (ci / 4))), dim3(256), 0, st, g.N, hb, E,
-                             ci / 4, Gn, gnh);
-        else
-          hipLaunchKernelGGL(convt_border_zero_kernel<1>, dim3(grid_for((size_t)g.N * nb * ci)), dim3(256), 0, st, g.N, hb, E, ci, Gn,
-                             gnh);
-        DM_LAUNCH_CHECK();
-      }
-      DmGemm d;
-      d.M = g.N * Hc * Hc; d.N = 4 * ci; d.K = kdim4;
-      d.A = gpad; d.a_maj = t_rowoff; d.a_min = t_koff; d.a_tab_vec = 1; d.a_tab_vec8 = 1;
-      if (hpath) { d.A = nullptr; d.A_h = (const unsigned short*)gpad; d.B_h = wcat_h; }
-      d.B = wcat; d.ldb = kdim4;
-      d.C = Gn;
-      d.c_tab = t_ctab; d.sc_cout = ci; d.sc_wpitch = hb * ci;
-      d.mulref = a.y[l - 1];
-      d.no_twin = l == 1;      // the layer-0 gradient is read by the direct weight-gradient kernel and the bias sum only (fp32)
-      convt_attach_klist(d, kskip ? t_klist : nullptr, hs, 2);
-      DM_TRY(dm_gemm_launch(d, splitk, skb, st));
-      G = Gn;
-    } else if (l > 0) {
-      DM_TRY(dm_permute4_launch(dwr, gr->w[l], co, 4, 4, g.cin[l], 0, 3, 1, 2, st));
+      ConvtGather c = {"conv_encoder_bwd", g.N, g.hs[l], g.hb[l], 4, co, g.cin[l], G, p->w[l], Gn};
+      c.mulref = a.y[l - 1];
+      c.no_twin = l == 1;      // the layer-0 gradient is read by the direct weight-gradient kernel and the bias sum only (fp32)
+      DM_TRY(convt_gather_launch(c, gather, pl.bits[l] & CONV_HPATH, pl.kskip, splitk, st));
+    } else {
       DmGemm d;   // dXcol[row][kidx] = sum_o G[row][o] * Wr[o][kidx]
       d.a_layout = 0; d.b_layout = 1;
       d.M = rows; d.N = kd; d.K = co;
@@ -881,11 +925,9 @@ static int conv_encoder_bwd_impl(const dm_shape* shp, const float* image, const 
       d.B = a.wr[l]; d.ldb = kd;
       d.C = dxcol; d.ldc = kd;
       DM_TRY(dm_gemm_launch(d, splitk, skb, st));
-      float* Gn = (G == ga) ? gb : ga;
-      if (l == 1) Gn = ga;   // layer-0 output grads are the largest buffer
       DM_TRY(dm_col2im_s2_launch(g.N, g.hb[l], g.hb[l], g.cin[l], 4, dxcol, nullptr, 0, a.y[l - 1], Gn, st));
-      G = Gn;
     }
+    G = Gn;
   }
   return DM_OK;
 }
@@ -974,44 +1016,28 @@ extern "C" size_t dm_conv_decoder_pred_offset(const dm_shape* shp) {
 }
 
 // The forward's workspace.  ycol: the column matrix of the layers that take neither the gather form nor (image layer) the
-// direct kernel; w4: that kernel's class-ordered weights; then the gather form's zero-padded input copy, gather / scatter
-// tables, class-concatenated weights and k-tile lists.  On an arena without a base it sizes.
-struct DecFwdWs {
-  float *splitk, *ycol, *w4, *xpad, *wcat;
-  int *t_rowoff, *t_koff, *t_klist; int2* t_ctab;
-  unsigned short* wcat_h;
-};
-static bool dec_fwd_direct4(const DecGeom& g) { return dm_dec_l4_direct_ok(g.ch, g.d, g.hsm[4], g.k[4]); }      // d -> 3 channels: conv_direct.hip, no column matrix
-static size_t dec_fwd_layout(DmArena ar, const DecGeom& g, bool tw_on, DecFwdWs* w) {
-  const size_t n = (size_t)g.N;
+// direct kernel; w4: that kernel's class-ordered weights; then the gather form's block.  On an arena without a base it sizes.
+struct DecFwdWs { float *splitk, *ycol, *w4; ConvtWs gather; };
+static size_t dec_fwd_layout(DmArena ar, const DecGeom& g, const ConvPlan& pl, bool tw_on, DecFwdWs* w) {
   w->splitk = ar.take(DM_SPLITK_FLOATS);
-  const bool direct4 = dec_fwd_direct4(g);
-  size_t colmax = 0;
-  for (int l = 1; l <= (direct4 ? 3 : 4); ++l) {
-    const size_t c = n * g.hsm[l] * g.hsm[l] * g.k[l] * g.k[l] * g.cout[l];
-    if (c > colmax) colmax = c;
-  }
-  w->ycol = ar.take(colmax);
-  w->w4 = ar.take(direct4 ? dm_dec_l4_w4_floats(g.d) : 0);
-  size_t padmax = 0, tabmax = 0, wcmax = 0, klmax = 0;
+  size_t colmax = 0;      // (sized over every layer that is not direct, whatever form it takes)
   for (int l = 1; l <= 4; ++l)
-    if (convt_gather_ok(g.k[l], g.cin[l], g.cout[l], g.hsm[l], n)) {
-      const int ta = g.k[l] / 2, hp = g.hsm[l] + 2 * (ta - 1), Hc = g.hsm[l] + ta - 1;
-      const size_t pad = n * hp * hp * g.cin[l], tab = n * Hc * Hc, wc = (size_t)4 * g.cout[l] * ta * ta * g.cin[l];
-      const size_t kl = convt_klist_ints(tab, ta * ta * g.cin[l]);
-      if (pad > padmax) padmax = pad;
-      if (tab > tabmax) tabmax = tab;
-      if (wc > wcmax) wcmax = wc;
-      if (kl > klmax) klmax = kl;
-    }
-  w->xpad = ar.take(padmax);
-  w->t_rowoff = (int*)ar.take(tabmax);
-  w->t_ctab = (int2*)ar.take(2 * tabmax);
-  w->t_koff = (int*)ar.take(wcmax ? 9 * 1024 : 0);
-  w->wcat = ar.take(wcmax);
-  w->wcat_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(wcmax) : 0);
-  w->t_klist = (int*)ar.take(klmax);      // (sized whether or not the switch is on)
+    if (pl.form[l] != CONV_DIRECT) colmax = std::max(colmax, g.rows_s[l] * g.k[l] * g.k[l] * g.cout[l]);
+  w->ycol = ar.take(colmax);
+  w->w4 = ar.take(pl.form[4] == CONV_DIRECT ? dm_dec_l4_w4_floats(g.d) : 0);
+  convt_gather_carve(ar, pl.gather, 9 * 1024, tw_on, &w->gather);      // k <= 6: K = 9 cin, up to 1024 input channels
   return ar.off;
+}
+static ConvPlan dec_fwd_plan(const DecGeom& g, bool tw_on) {
+  ConvPlan pl;
+  pl.kskip = g_convt_kskip && !g.twins;
+  for (int l = 1; l <= 4; ++l)
+    if (l == 4 && dec_direct4(g)) pl.form[l] = CONV_DIRECT;      // d -> 3 channels: conv_direct.hip, no column matrix
+    else if (!pl.take_gather(l, tw_on, g.k[l], g.cin[l], g.cout[l], g.hsm[l], (size_t)g.N))
+      pl.form[l] = g.hsm[l] == 1 ? CONV_ONE_PIXEL : CONV_COLUMN;      // a 1x1 input: no windows overlap, the column matrix IS the NHWC output
+  DecFwdWs w;
+  pl.need = dec_fwd_layout(DmArena(nullptr, 0), g, pl, tw_on, &w);
+  return pl;
 }
 
 extern "C" int dm_conv_decoder_mse_fwd(const dm_shape* shp, const float* feat, int ldf, const float* target,
@@ -1028,9 +1054,10 @@ extern "C" int dm_conv_decoder_mse_fwd(const dm_shape* shp, const float* feat, i
   DmTwinScope tw((shp->flags & DM_FLAG_BF16) != 0);
   const bool tw_on = dm_twins_on();
   dec_register_twins(g, a, false, false);
+  const ConvPlan pl = dec_fwd_plan(g, tw_on);
   DecFwdWs w;
-  const size_t need = dec_fwd_layout(DmArena(ws, ws_bytes), g, tw_on, &w);
-  DM_REQUIRE(need <= ws_bytes / sizeof(float), DM_E_WORKSPACE, "conv_decoder_fwd: workspace too small (need %zu floats)", need);
+  dec_fwd_layout(DmArena(ws, ws_bytes), g, pl, tw_on, &w);
+  DM_REQUIRE(pl.need <= ws_bytes / sizeof(float), DM_E_WORKSPACE, "conv_decoder_fwd: workspace too small (need %zu floats)", pl.need);
   dm_twin_arena_note(acts, tw_on);
   for (int l = 1; l <= 4; ++l)
     DM_TRY(dm_permute4_launch(p->w[l], a.wr[l], g.cin[l], g.cout[l], g.k[l], g.k[l], 0, 2, 3, 1, st));
@@ -1040,9 +1067,7 @@ extern "C" int dm_conv_decoder_mse_fwd(const dm_shape* shp, const float* feat, i
     DM_TRY(dm_to_bf16_multi_launch(sg, 4, st));
   }
   if (n == 0) return DM_OK;
-  const auto& [splitk, ycol, w4, xpad, wcat, t_rowoff, t_koff, t_klist, t_ctab, wcat_h] = w;
-  const bool direct4 = dec_fwd_direct4(g);
-  const bool kskip = g_convt_kskip && !(shp->flags & DM_FLAG_BF16);
+  const auto& [splitk, ycol, w4, gather] = w;
   const size_t skb = DM_SPLITK_FLOATS * sizeof(float);
   {
     DmGemm q;   // x0 = feat W^T + b
@@ -1054,59 +1079,28 @@ extern "C" int dm_conv_decoder_mse_fwd(const dm_shape* shp, const float* feat, i
     DM_TRY(dm_gemm_launch(q, splitk, skb, st));
   }
   for (int l = 1; l <= 4; ++l) {
-    const int kk = g.k[l] * g.k[l];
     const float* xin = a.x[l - 1];
-    if (l == 4 && direct4) {
+    if (pl.form[l] == CONV_DIRECT) {
       DM_TRY(dm_dec_l4_fwd_launch(n, g.d, xin, p->w[4], p->b[4], w4, a.x[4], st));
-      continue;
-    }
-    if (convt_gather_ok(g.k[l], g.cin[l], g.cout[l], g.hsm[l], (size_t)n)) {
-      const int ta = g.k[l] / 2, hs = g.hsm[l], hb = g.hbg[l], Hc = hs + ta - 1, kdim = ta * ta * g.cin[l];
-      DM_REQUIRE(kdim <= 9 * 1024, DM_E_SHAPE, "conv_decoder_fwd: gather-form K %d exceeds the offset table", kdim);
-      const size_t padn = (size_t)n * (hs + 2 * (ta - 1)) * (hs + 2 * (ta - 1)) * (g.cin[l] / 4);
-      const bool hpath = tw_on && (g.cin[l] & 7) == 0 && kdim >= DM_HSTORE_MIN_K;       // bf16-storage product: padded input + weights as bf16
-      if (hpath) hipLaunchKernelGGL(convt_pad_h_kernel, dim3(grid_for(padn)), dim3(256), 0, st, n, hs, hs, g.cin[l] / 4, ta - 1,
-                                    (const float4*)xin, (uint2*)xpad);
-      else hipLaunchKernelGGL(convt_pad_kernel, dim3(grid_for(padn)), dim3(256), 0, st, n, hs, hs, g.cin[l] / 4, ta - 1,
-                              (const float4*)xin, (float4*)xpad);
-      DM_LAUNCH_CHECK();
-      DM_TRY(convt_tables_launch(n, hs, g.cin[l], ta, hb, g.cout[l], t_rowoff, t_koff, t_ctab, kskip ? t_klist : nullptr, st));
-      hipLaunchKernelGGL(convt_repack_kernel, dim3(grid_for((size_t)4 * g.cout[l] * kdim)), dim3(256), 0, st, g.cin[l], g.cout[l],
-                         g.k[l], p->w[l], wcat);
-      DM_LAUNCH_CHECK();
-      if (hpath) {
-        const DmCvtSeg sg = {wcat, wcat_h, (size_t)4 * g.cout[l] * kdim};
-        DM_TRY(dm_to_bf16_multi_launch(&sg, 1, st));
-      }
-      DmGemm q;   // big[n, 2yy+py, 2xx+px, o] = act( b[o] + patch(n,yy,xx) . Wcat[(py,px,o)] )
-      q.M = n * Hc * Hc; q.N = 4 * g.cout[l]; q.K = kdim;
-      q.A = xpad; q.a_maj = t_rowoff; q.a_min = t_koff; q.a_tab_vec = 1; q.a_tab_vec8 = 1;
-      if (hpath) { q.A = nullptr; q.A_h = (const unsigned short*)xpad; q.B_h = wcat_h; }
-      q.B = wcat; q.ldb = kdim;
-      q.C = a.x[l];
-      q.c_tab = t_ctab; q.sc_cout = g.cout[l]; q.sc_wpitch = hb * g.cout[l];
-      q.bias = p->b[l];
-      q.flags = l < 4 ? DM_GEMM_ELU : 0;
-      convt_attach_klist(q, kskip ? t_klist : nullptr, hs, ta);
+    } else if (pl.form[l] == CONV_GATHER) {
+      ConvtGather c = {"conv_decoder_fwd", n, g.hsm[l], g.hbg[l], g.k[l], g.cin[l], g.cout[l], xin, p->w[l], a.x[l]};
+      c.bias = p->b[l];
+      c.flags = l < 4 ? DM_GEMM_ELU : 0;
+      DM_TRY(convt_gather_launch(c, gather, pl.bits[l] & CONV_HPATH, pl.kskip, splitk, st));
+    } else {
+      const bool one = pl.form[l] == CONV_ONE_PIXEL;      // bias + ELU in the epilogue, straight into x[l]
+      DmGemm q;   // Ycol[(n,ys,xs)][(ky,kx,o)] = X[(n,ys,xs)][i] * Wr[i][(ky,kx,o)]
+      q.a_layout = 0; q.b_layout = 1;
+      q.M = n * g.hsm[l] * g.hsm[l]; q.N = g.k[l] * g.k[l] * g.cout[l]; q.K = g.cin[l];
+      q.A = xin; q.lda = q.K;
+      q.B = a.wr[l]; q.ldb = q.N;
+      q.C = one ? a.x[l] : ycol; q.ldc = q.N;
+      if (one) { q.bias = p->b[l]; q.bias_mod = g.cout[l]; q.flags = l < 4 ? DM_GEMM_ELU : 0; }
       DM_TRY(dm_gemm_launch(q, splitk, skb, st));
-      continue;
+      if (!one)
+        DM_TRY(dm_col2im_s2_launch(n, g.hbg[l], g.hbg[l], g.cout[l], g.k[l], ycol, p->b[l], l < 4 ? DM_C2I_ELU : 0, nullptr,
+                                   a.x[l], st));
     }
-    DmGemm q;   // Ycol[(n,ys,xs)][(ky,kx,o)] = X[(n,ys,xs)][i] * Wr[i][(ky,kx,o)]
-    q.a_layout = 0; q.b_layout = 1;
-    q.M = n * g.hsm[l] * g.hsm[l]; q.N = kk * g.cout[l]; q.K = g.cin[l];
-    q.A = xin; q.lda = q.K;
-    q.B = a.wr[l]; q.ldb = q.N;
-    q.C = ycol; q.ldc = q.N;
-    if (g.hsm[l] == 1) {     // a 1x1 input: no windows overlap, the column matrix IS the NHWC output - bias + ELU in the epilogue
-      q.C = a.x[l];
-      q.bias = p->b[l]; q.bias_mod = g.cout[l];
-      q.flags = l < 4 ? DM_GEMM_ELU : 0;
-      DM_TRY(dm_gemm_launch(q, splitk, skb, st));
-      continue;
-    }
-    DM_TRY(dm_gemm_launch(q, splitk, skb, st));
-    DM_TRY(dm_col2im_s2_launch(n, g.hbg[l], g.hbg[l], g.cout[l], g.k[l], ycol, p->b[l], l < 4 ? DM_C2I_ELU : 0, nullptr,
-                               a.x[l], st));
   }
   if (loss_image || image_rec) {
     // targets are indexed by frame / I (I = iwae_samples, decoders.py:163-167)
@@ -1116,36 +1110,20 @@ extern "C" int dm_conv_decoder_mse_fwd(const dm_shape* shp, const float* feat, i
   }
   return DM_OK;
 }
-static int conv_decoder_mse_bwd_impl(const dm_shape* shp, const float* feat, int ldf, const float* target,
-                                     const dm_conv_params* p, const float* acts, float scale, const float* row_scale,
-                                     const dm_conv_grads* gr, float* dfeat, int lddf, void* ws, size_t ws_bytes, void* stream);
-extern "C" int dm_conv_decoder_mse_bwd(const dm_shape* shp, const float* feat, int ldf, const float* target,
-                                       const dm_conv_params* p, const float* acts, float scale, const dm_conv_grads* gr,
-                                       float* dfeat, int lddf, void* ws, size_t ws_bytes, void* stream) {
-  return conv_decoder_mse_bwd_impl(shp, feat, ldf, target, p, acts, scale, nullptr, gr, dfeat, lddf, ws, ws_bytes, stream);
-}
-// row_scale (N floats, nullable): per-frame factor on the image-loss gradient - the IWAE importance weights of
-// loss_model = -logavgexp(-loss_tbi) (dreamer.py:362-365, functions.py:97-102)
-extern "C" int dm_conv_decoder_mse_bwd_rows(const dm_shape* shp, const float* feat, int ldf, const float* target,
-                                            const dm_conv_params* p, const float* acts, float scale, const float* row_scale,
-                                            const dm_conv_grads* gr, float* dfeat, int lddf, void* ws, size_t ws_bytes,
-                                            void* stream) {
-  return conv_decoder_mse_bwd_impl(shp, feat, ldf, target, p, acts, scale, row_scale, gr, dfeat, lddf, ws, ws_bytes, stream);
-}
 // The backward's workspace.  One gradient buffer per layer (together smaller than a ping-pong pair of the largest) and one
 // gather table pair per layer: a layer's weight / bias gradient only reads G[l], its tables and the saved activations, so those
 // launches can sit on the weight-gradient side stream (common.h, dm_wgrad_side_*) and run beside whatever follows the
 // DATA-gradient chain on `st` - the BPTT loop - instead of in front of it.  Every layer's output gradient is gathered
 // implicitly: channel counts that are not a multiple of 4 (the 3-channel image layer) are padded to 4 (co4) in the gradient
-// buffer and in a padded copy of the weights (wpad).  direct4: the image layer's backward runs as direct kernels.  On an arena
-// without a base it sizes.
+// buffer and in a padded copy of the weights (wpad).  l4_*: the image layer's direct kernels.  On an arena without a base it sizes.
 struct DecBwdWs {
   float *splitk, *splitk_w, *Gl[5], *dwr, *wpad, *bsum, *l4_wp, *l4_part;
   int *rowoff[5], *koff[5];      // index 1..4
   unsigned short *Gl_h[5], *wpad_h;
   int co4[5]; size_t gsz[5], wpadmax;
 };
-static size_t dec_bwd_layout(DmArena ar, const DecGeom& g, bool direct4, bool tw_on, DecBwdWs* w) {
+static size_t dec_bwd_layout(DmArena ar, const DecGeom& g, const ConvPlan& pl, bool tw_on, DecBwdWs* w) {
+  const bool direct4 = pl.form[4] == CONV_DIRECT;
   w->splitk = ar.take(DM_SPLITK_FLOATS);
   size_t wmax = 0;
   w->co4[0] = 0; w->gsz[0] = (size_t)g.N * g.cin[1]; w->wpadmax = 0;
@@ -1173,6 +1151,27 @@ static size_t dec_bwd_layout(DmArena ar, const DecGeom& g, bool direct4, bool tw
   w->wpad_h = (unsigned short*)ar.take(tw_on ? dm_half_floats(w->wpadmax) : 0);
   return ar.off;
 }
+// sizing: the image layer's direct backward kernels wherever the shape admits them (a call also asks dm_dec_l4_bwd_direct_enable)
+static ConvPlan dec_bwd_plan(const DecGeom& g, bool tw_on, bool sizing) {
+  ConvPlan pl;
+  const bool direct4 = sizing ? dec_direct4(g) : dm_dec_l4_bwd_direct_ok(g.ch, g.d, g.hsm[4], g.k[4]);
+  for (int l = 4; l >= 1; --l) {
+    pl.form[l] = l == 4 && direct4 ? CONV_DIRECT : CONV_IMPLICIT;
+    if (g.cout[l] & 3) pl.bits[l] |= CONV_PADDED;      // the output gradient and a copy of the weights carry (cout + 3) & ~3 channels
+    // the layer below gathers its output gradient at a padded pitch (cnn_depth 6: 6 -> 8): the data gradient is written at that pitch
+    if (pl.form[l] == CONV_IMPLICIT && l >= 2 && (g.cout[l - 1] & 3)) pl.bits[l] |= CONV_REPITCH;
+  }
+  DecBwdWs w;
+  pl.need = dec_bwd_layout(DmArena(nullptr, 0), g, pl, tw_on, &w);
+  return pl;
+}
+// the bias gradient of a layer with padded channels: column sums of all co into bsum, the first cout of them to db
+static int dec_bias_grad_padded(int rows, int co, const float* G, float* bsum, int cout, float* db, float* splitk, hipStream_t sw) {
+  DM_TRY(dm_colsum_launch(rows, co, G, co, bsum, splitk, DM_SPLITK_FLOATS * sizeof(float), sw));
+  hipError_t e = hipMemcpyAsync(db, bsum, (size_t)cout * sizeof(float), hipMemcpyDeviceToDevice, sw);
+  if (e != hipSuccess) return dm_fail(DM_E_HIP, "conv_decoder_bwd: %s", hipGetErrorString(e));
+  return DM_OK;
+}
 
 static int conv_decoder_mse_bwd_impl(const dm_shape* shp, const float* feat, int ldf, const float* target,
                                      const dm_conv_params* p, const float* acts, float scale, const float* row_scale,
@@ -1184,19 +1183,18 @@ static int conv_decoder_mse_bwd_impl(const dm_shape* shp, const float* feat, int
   hipStream_t st = (hipStream_t)stream;
   DecActs a;
   dec_carve(g, const_cast<float*>(acts), (size_t)1 << 60, &a);
-  // image layer (d -> 3 channels): both backward products as direct kernels (conv_direct.hip) reading the padded gradient
-  const bool direct4 = dm_dec_l4_bwd_direct_ok(g.ch, g.d, g.hsm[4], g.k[4]);
   DmTwinScope tw((shp->flags & DM_FLAG_BF16) != 0);
   const bool tw_on = dm_twins_on();
+  const ConvPlan pl = dec_bwd_plan(g, tw_on, false);
   DecBwdWs w;
-  const size_t need = dec_bwd_layout(DmArena(ws, ws_bytes), g, direct4, tw_on, &w);
-  DM_REQUIRE(need <= ws_bytes / sizeof(float), DM_E_WORKSPACE, "conv_decoder_bwd: workspace too small (need %zu floats)", need);
+  dec_bwd_layout(DmArena(ws, ws_bytes), g, pl, tw_on, &w);
+  DM_REQUIRE(pl.need <= ws_bytes / sizeof(float), DM_E_WORKSPACE, "conv_decoder_bwd: workspace too small (need %zu floats)", pl.need);
   const auto& [splitk, splitk_w, Gl, dwr, wpad, bsum, l4_wp, l4_part, rowoff_l, koff_l, Gl_h, wpad_h, co4, gsz, wpadmax] = w;
   const size_t skb = DM_SPLITK_FLOATS * sizeof(float);
   const bool arena_tw = dm_twin_arena_valid(acts);      // the forward that filled `acts` wrote its twins
   dec_register_twins(g, a, arena_tw, arena_tw);
   for (int l = 0; l <= 4; ++l)
-    if (!(direct4 && l == 4)) dm_twin_add(Gl[l], gsz[l], Gl_h[l], false);      // (the direct kernels read the fp32 gradient)
+    if (pl.form[l] != CONV_DIRECT) dm_twin_add(Gl[l], gsz[l], Gl_h[l], false);      // (the direct kernels read the fp32 gradient)
   dm_twin_add(wpad, wpadmax, wpad_h, false);
   hipStream_t sw = dm_wgrad_side_stream(st);
 
@@ -1205,22 +1203,16 @@ static int conv_decoder_mse_bwd_impl(const dm_shape* shp, const float* feat, int
   DM_TRY(mse_launch(shape_u8(shp), g.N, g.hbg[4] * g.hbg[4], g.ch, a.x[4], (const void*)target, shp->I > 0 ? shp->I : 1, scale,
                     row_scale, nullptr, G, co4[4], nullptr, st));
   for (int l = 4; l >= 1; --l) {
-    const int kk = g.k[l] * g.k[l];
-    const int co = co4[l];
-    const bool padded = co != g.cout[l];
-    const int ncol = kk * co;
-    const int rows_s = (int)g.rows_s[l];
-    int* rowoff = rowoff_l[l];
-    int* koff = koff_l[l];
+    const int kk = g.k[l] * g.k[l], co = co4[l], ncol = kk * co, rows_s = (int)g.rows_s[l];
+    const bool padded = pl.bits[l] & CONV_PADDED;
+    int *rowoff = rowoff_l[l], *koff = koff_l[l];
     float* Gn = Gl[l - 1];
-    if (direct4 && l == 4) {
+    if (pl.form[l] == CONV_DIRECT) {
       DM_TRY(dm_wgrad_side_fork(st, sw));
       unsigned short* gnh = dm_twin_of(Gn, false);
       DM_TRY(dm_dec_l4_dgrad_launch(g.N, g.d, G, p->w[4], l4_wp, a.x[3], Gn, gnh, st));
       if (gnh) dm_twin_mark(Gn);
-      DM_TRY(dm_colsum_launch((int)g.rows_b[l], co, G, co, bsum, splitk_w, skb, sw));
-      hipError_t e = hipMemcpyAsync(gr->b[l], bsum, (size_t)g.cout[l] * sizeof(float), hipMemcpyDeviceToDevice, sw);
-      if (e != hipSuccess) return dm_fail(DM_E_HIP, "conv_decoder_bwd: %s", hipGetErrorString(e));
+      DM_TRY(dec_bias_grad_padded((int)g.rows_b[l], co, G, bsum, g.cout[l], gr->b[l], splitk_w, sw));
       DM_TRY(dm_dec_l4_wgrad_launch(g.N, g.d, G, a.x[3], l4_part, gr->w[4], splitk_w, skb, sw));
       G = Gn;
       continue;
@@ -1247,9 +1239,7 @@ static int conv_decoder_mse_bwd_impl(const dm_shape* shp, const float* feat, int
       d.a_tab_vec8 = (co & 7) == 0 || (co == 4 && (g.k[l] & 1) == 0);
       d.B = padded ? wpad : a.wr[l]; d.ldb = ncol;
       d.C = Gn; d.ldc = g.cin[l];
-      if (l - 1 >= 1 && co4[l - 1] != g.cin[l]) {
-        // the layer below gathers its output gradient with co4[l-1] channels per pixel (cnn_depth 6: 6 -> 8): write the rows
-        // at that pitch, over zeroed pad channels
+      if (pl.bits[l] & CONV_REPITCH) {      // rows at the pitch co4[l-1] of the layer below, over zeroed pad channels
         hipError_t e = hipMemsetAsync(Gn, 0, gsz[l - 1] * sizeof(float), st);
         if (e == hipSuccess && dm_twin_of(Gn, false))
           e = hipMemsetAsync(dm_twin_of(Gn, false), 0, gsz[l - 1] * sizeof(unsigned short), st);
@@ -1260,13 +1250,8 @@ static int conv_decoder_mse_bwd_impl(const dm_shape* shp, const float* feat, int
       DM_TRY(dm_gemm_launch(d, splitk, skb, st));
     }
     // ---- bias and weight gradient, on sw
-    if (padded) {
-      DM_TRY(dm_colsum_launch((int)g.rows_b[l], co, G, co, bsum, splitk_w, skb, sw));
-      hipError_t e = hipMemcpyAsync(gr->b[l], bsum, (size_t)g.cout[l] * sizeof(float), hipMemcpyDeviceToDevice, sw);
-      if (e != hipSuccess) return dm_fail(DM_E_HIP, "conv_decoder_bwd: %s", hipGetErrorString(e));
-    } else {
-      DM_TRY(dm_colsum_launch((int)g.rows_b[l], co, G, co, gr->b[l], splitk_w, skb, sw));
-    }
+    if (padded) DM_TRY(dec_bias_grad_padded((int)g.rows_b[l], co, G, bsum, g.cout[l], gr->b[l], splitk_w, sw));
+    else DM_TRY(dm_colsum_launch((int)g.rows_b[l], co, G, co, gr->b[l], splitk_w, skb, sw));
     DmGemm q;   // dWr[i][(ky,kx,o)] = sum_rows X[row][i] * dYcol[row][(ky,kx,o)]
     q.a_layout = 1; q.b_layout = 1;
     q.M = g.cin[l]; q.N = ncol; q.K = rows_s;
@@ -1310,6 +1295,19 @@ static int conv_decoder_mse_bwd_impl(const dm_shape* shp, const float* feat, int
   DM_TRY(dm_wgrad_side_mark(sw, st));
   return DM_OK;
 }
+extern "C" int dm_conv_decoder_mse_bwd(const dm_shape* shp, const float* feat, int ldf, const float* target,
+                                       const dm_conv_params* p, const float* acts, float scale, const dm_conv_grads* gr,
+                                       float* dfeat, int lddf, void* ws, size_t ws_bytes, void* stream) {
+  return conv_decoder_mse_bwd_impl(shp, feat, ldf, target, p, acts, scale, nullptr, gr, dfeat, lddf, ws, ws_bytes, stream);
+}
+// row_scale (N floats, nullable): per-frame factor on the image-loss gradient - the IWAE importance weights of
+// loss_model = -logavgexp(-loss_tbi) (dreamer.py:362-365, functions.py:97-102)
+extern "C" int dm_conv_decoder_mse_bwd_rows(const dm_shape* shp, const float* feat, int ldf, const float* target,
+                                            const dm_conv_params* p, const float* acts, float scale, const float* row_scale,
+                                            const dm_conv_grads* gr, float* dfeat, int lddf, void* ws, size_t ws_bytes,
+                                            void* stream) {
+  return conv_decoder_mse_bwd_impl(shp, feat, ldf, target, p, acts, scale, row_scale, gr, dfeat, lddf, ws, ws_bytes, stream);
+}
 
 // ---------------------------------------------------------------- workspace sizing (common.h) ----
 // DM_FLAG_BF16 sizes the twins whatever dm_bf16_twins_enable says; reward_input and the direct image-layer backward are sized
@@ -1319,25 +1317,27 @@ size_t dm_conv_ws_floats(const dm_shape* s, size_t parts[4]) {
   const bool geom = s && s->T >= 0 && s->B >= 0 && s->img == 64 && s->img_ch >= 1 && s->cnn_depth >= 1;      // (else the geometry structs would wrap)
   if (geom) {
     const bool tw = (s->flags & DM_FLAG_BF16) != 0;
-    EncGeom e(s);
-    if (e.valid(s) || e.valid_planes(s)) {
-      EncFwdWs fw;
-      EncBwdWs bw;
-      p[0] = enc_fwd_layout(DmArena(nullptr, 0), e, e.valid_planes(s), &fw);
-      p[1] = enc_bwd_layout(DmArena(nullptr, 0), e, tw, &bw);
-    }
-    DecGeom d(s);
-    if (d.valid(s)) {
-      DecFwdWs fw;
-      DecBwdWs bw;
-      p[2] = dec_fwd_layout(DmArena(nullptr, 0), d, tw, &fw);
-      p[3] = dec_bwd_layout(DmArena(nullptr, 0), d, dec_fwd_direct4(d), tw, &bw);
-    }
+    const EncGeom e(s); const DecGeom d(s);
+    if (e.valid(s) || e.valid_planes(s)) { p[0] = enc_fwd_plan(e, e.valid_planes(s)).need; p[1] = enc_bwd_plan(e, e.valid_planes(s), tw).need; }
+    if (d.valid(s)) { p[2] = dec_fwd_plan(d, tw).need; p[3] = dec_bwd_plan(d, tw, true).need; }
   }
-  size_t m = 0;
-  for (int i = 0; i < 4; ++i) {
-    if (parts) parts[i] = p[i];
-    if (p[i] > m) m = p[i];
-  }
-  return m;
+  for (int i = 0; i < 4 && parts; ++i) parts[i] = p[i];
+  return std::max(std::max(p[0], p[1]), std::max(p[2], p[3]));
+}
+
+// include/dreamer_hip.h dm_conv_plan_query: the plan a call of entry point `which` would carry out, the switches as they stand
+extern "C" int dm_conv_plan_query(int which, const dm_shape* shp, int planes, int32_t out[8], size_t* need_floats) {
+  DM_REQUIRE(shp && out, DM_E_NULL, "conv_plan_query: null pointer");
+  DM_REQUIRE((unsigned)which <= 3 && shp->T >= 0 && shp->B >= 0 && shp->img_ch >= 1 && shp->cnn_depth >= 1, DM_E_SHAPE,
+             "conv_plan_query: which %d, T=%d B=%d ch=%d depth=%d", which, shp->T, shp->B, shp->img_ch, shp->cnn_depth);
+  const bool tw_on = (shp->flags & DM_FLAG_BF16) && dm_bf16_twins_enable(-1);
+  const EncGeom e(shp); const DecGeom d(shp);
+  if (which <= 1) DM_TRY(enc_validate(shp, e, planes != 0, 32 * e.d, "conv_plan_query"));
+  else DM_REQUIRE(d.valid(shp), DM_E_SHAPE, "conv_plan_query: unsupported decoder geometry (img=%d)", shp->img);
+  const ConvPlan pl = which == 0 ? enc_fwd_plan(e, planes != 0) : which == 1 ? enc_bwd_plan(e, planes != 0, tw_on)
+                    : which == 2 ? dec_fwd_plan(d, tw_on) : dec_bwd_plan(d, tw_on, false);
+  for (int l = 0; l < 5; ++l) out[l] = pl.form[l] < 0 ? -1 : pl.form[l] | pl.bits[l] << 8;
+  out[5] = pl.kskip; out[6] = out[7] = 0;
+  if (need_floats) *need_floats = pl.need;
+  return DM_OK;
 }

@@ -224,6 +224,7 @@ _SIGNATURES = {
                                    POINTER(c_int32)]),
     'dm_mlp_plan_query': (c_int, [c_int] * 15 + [c_size_t, POINTER(c_int32)]),
     'dm_convt_kskip_enable': (c_int, [c_int]),
+    'dm_conv_plan_query': (c_int, [c_int, POINTER(dm_shape), c_int, POINTER(c_int32), POINTER(c_size_t)]),
     'dm_kl_staged_enable': (c_int, [c_int]),
     'dm_dec_l4_bwd_direct_enable': (c_int, [c_int]),
     'dm_dec_l4_fwd_shared_enable': (c_int, [c_int]),

@@ -434,7 +434,7 @@ def _conv_stack_bf16(model, T, B, twins, seed=5, flip_before_backward=False):
         H.lib().dm_bf16_twins_enable(1)
 
 
-@pytest.mark.parametrize('depth,T,B', [(8, 2, 3), (48, 2, 2), (16, 3, 5), (48, 1, 513), (48, 50, 50)])
+@pytest.mark.parametrize('depth,T,B', [(8, 2, 3), (48, 2, 2), (16, 3, 5), (48, 1, 513), (48, 50, 50), (64, 1, 3)])
 def test_conv_bf16_storage_twins_match_fp32_storage(hip, depth, T, B):
     """conf.amp convolution stack with operands STORED as bf16 (twins written by the producing kernels, gemm_h_kernel) against
     the same bf16 products fed from fp32 storage (rounded on the way into LDS): the operand values are identical (RNE of
