@@ -104,7 +104,8 @@ int dm_version(void);                 /* ABI version, currently 17 (v2: LayerNor
                                          v17: dm_gemm_plan_query added; later, still 17 (additions only): dm_cem_draw / dm_cem_update
                                               of the latent-space planner; dm_twohot_decode / dm_twohot_loss / dm_return_norm of the
                                               two-hot critic and the percentile return normalisation; dm_mlp_plan_query;
-                                              dm_workspace_query; dm_conv_plan_query */
+                                              dm_workspace_query; dm_conv_plan_query; dm_kl_free_fwd / dm_kl_free_bwd (free bits) and
+                                              dm_twohot_head_loss (the symlog two-hot reward head) */
 const char* dm_last_error(void);      /* thread-local message of the last failing call */
 int dm_device_check(void);            /* DM_OK iff the current HIP device is gfx950 */
 /* Scratch that serves any call below for this shape: the maximum of the fused operators' own workspace layouts (each sized
@@ -273,6 +274,17 @@ int dm_kl_balance_fwd(int rows, int S, int C, const float* post, const float* pr
 /* dpost = scale_post * dKL/dpost, dprior = scale_prior * dKL/dprior (overwrite). */
 int dm_kl_balance_bwd(int rows, int S, int C, const float* post, const float* prior,
                       float scale_post, float scale_prior, float* dpost, float* dprior, void* stream);
+/* Free bits per row (DreamerV3's rule; the reference has no counterpart).  The kernels, dispatch branches and dm_kl_staged_enable
+ * switch of the pair above, in this order per row r:
+ *   kl[r], ent_post[r], ent_prior[r]: the expressions of dm_kl_balance_fwd in its order (the same bits)
+ *   kl_clip[r] = fmaxf(free, kl[r]);  closed[r] = kl[r] <= free ? 1.0f : 0.0f
+ * dm_kl_free_bwd: rows with closed[r] == 0 get dm_kl_balance_bwd's values; every element of the others (S C, or 2 S for C = 0) of
+ * dpost and dprior is written +0.0f.  One launch each.  Checked on the host before the launch: a NULL post, prior, kl, kl_clip,
+ * closed, dpost or dprior -> DM_E_NULL (ent_post, ent_prior are optional); S < 1, C < 0, free negative or not finite -> DM_E_SHAPE. */
+int dm_kl_free_fwd(int rows, int S, int C, const float* post, const float* prior, float free, float* kl, float* kl_clip,
+                   float* closed, float* ent_post, float* ent_prior, void* stream);
+int dm_kl_free_bwd(int rows, int S, int C, const float* post, const float* prior, const float* closed, float scale_post,
+                   float scale_prior, float* dpost, float* dprior, void* stream);
 /* straight-through backward: dlogits (+)= softmax-jacobian(logits)^T dz per group (accumulate if accum). */
 int dm_st_softmax_bwd(int rows, int groups, int C, const float* logits, int ldl, const float* dz, int lddz,
                       float* dlogits, int lddl, int accum, void* stream);
@@ -778,6 +790,16 @@ int dm_twohot_loss(int rows, int rows_total, int K, const float* logits, int ld,
                    const float* weight, float scale, float* loss, float* dlogits, float* value, void* stream);
 int dm_return_norm(int n, const float* x, float q_lo, float q_hi, float decay, float limit, int update, float* state, float* out,
                    float* adv, int n_adv, void* stream);
+/* The head form of dm_twohot_loss (the symlog two-hot reward head): the same kernel instances, one launch.  rows = (t, b, i) rows
+ * under iwae_samples = I; row r reads target[r / I]; there is no weight array.  With m, s, p_j, mu, x, k, w_hi, w_lo as above:
+ *   lse = m + logf(s);  loss[r] = (lse - w_lo logit_k) - w_hi logit_{k+1};  dlogits[r][j] = scale * (p_j - y_j)   ((rows, K) dense)
+ *   mean[r] = symexp(mu)
+ * For I = 1 these are the bits of dm_twohot_loss with weight = 1 and rows_total = rows.  loss, dlogits and mean are each optional
+ * (at least one is given); target == NULL is the mean-only form, the bits of dm_twohot_decode, and then loss and dlogits are NULL.
+ * Checked on the host before the launch: K outside 2 .. 256, rows < 0, ld < K, I < 1, rows not a multiple of I -> DM_E_SHAPE; a
+ * NULL logits or bins, no output at all, loss or dlogits without a target -> DM_E_NULL; rows == 0 -> DM_OK, nothing launched. */
+int dm_twohot_head_loss(int rows, int I, int K, const float* logits, int ld, const float* bins, const float* target, float scale,
+                        float* loss, float* dlogits, float* mean, void* stream);
 /* critic loss rows (a2c.py:112-115): loss[r] = 0.5*(vt-v)^2*w ; dvalue = scale * -(vt-v)*w. */
 int dm_critic_loss(int rows, const float* value, const float* value_target, const float* weight, float scale,
                    float* loss, float* dvalue, void* stream);

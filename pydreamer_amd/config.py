@@ -32,6 +32,12 @@ SECTIONS = {
         # advantages divided by max(return_norm_limit, running [lo, hi] percentile range of the imagined returns)
         critic_dist='mse', critic_bins=255, critic_bin_range=20.0, return_norm='none', return_norm_lo=0.05, return_norm_hi=0.95,
         return_norm_decay=0.99, return_norm_limit=1.0,
+        # the world model's share of the same (DreamerV3's; no reference counterpart).  Inert by default.  kl_free: free
+        # bits per (t, b) row in nats - max(kl_free, KL) enters loss_model and a row with KL <= kl_free sends no gradient into the
+        # posterior or the prior; 0 = off; not with iwae_samples > 1.  reward_dist='twohot': the reward head predicts
+        # reward_twohot_bins symlog-spaced bins over +-reward_twohot_range (two-hot cross-entropy against symlog(reward), mean decoded by
+        # symexp) instead of a unit-variance Normal: its loss does not grow with the reward scale; not with reward_decoder_categorical
+        kl_free=0.0, reward_dist='normal', reward_twohot_bins=255, reward_twohot_range=20.0,
         # aux critic
         aux_critic=False, aux_critic_weight=1.0, gamma_aux=0.99, lambda_gae_aux=0.95, target_interval_aux=1000,
         # the trainer loop (train.py; defaults.yaml:3-16, 34-35, 59-65, 113-118)

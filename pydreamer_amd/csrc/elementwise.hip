@@ -1262,10 +1262,24 @@ int dm_gauss_sample_bwd_launch(int rows, int S, const float* par, int ldp, const
   DM_LAUNCH_CHECK();
   return DM_OK;
 }
+// Free bits (dm_kl_free_fwd / _bwd, DreamerV3's rule per (t, b) row): the FREE instances of the KL kernels below take the row sum
+// they already hold and store, beside it, kl_clip = fmaxf(free, kl) and closed = (kl <= free) ? 1 : 0; the backward kernels read
+// `closed` and store +0.0f over a closed row where they store the gradient over an open one.  FREE = false is the kernel as it was.
+template <bool FREE>
+__device__ __forceinline__ void kl_free_store(int row, float akl, float free, float* __restrict__ kl_clip,
+                                              float* __restrict__ closed) {
+  if (FREE) {
+    kl_clip[row] = fmaxf(free, akl);
+    closed[row] = akl <= free ? 1.0f : 0.0f;
+  }
+}
 // KL(N(m1,s1) || N(m2,s2)) summed over S, and the two entropies (0.5 log(2 pi e) + log std per dimension)
+template <bool FREE>
 __global__ void __launch_bounds__(256) gauss_kl_fwd_kernel(int rows, int S, const float* __restrict__ post,
                                                            const float* __restrict__ prior, float* __restrict__ kl,
-                                                           float* __restrict__ ent_post, float* __restrict__ ent_prior) {
+                                                           float* __restrict__ ent_post, float* __restrict__ ent_prior,
+                                                           float free, float* __restrict__ kl_clip,
+                                                           float* __restrict__ closed) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
@@ -1282,25 +1296,35 @@ __global__ void __launch_bounds__(256) gauss_kl_fwd_kernel(int rows, int S, cons
   akl = dm_wave_sum(akl); aep = dm_wave_sum(aep); aeq = dm_wave_sum(aeq);
   if (lane == 0) {
     kl[row] = akl;
+    kl_free_store<FREE>(row, akl, free, kl_clip, closed);
     if (ent_post) ent_post[row] = aep;
     if (ent_prior) ent_prior[row] = aeq;
   }
 }
+template <bool FREE>
 __global__ void __launch_bounds__(256) gauss_kl_bwd_kernel(int rows, int S, const float* __restrict__ post,
                                                            const float* __restrict__ prior, float sp, float sq,
-                                                           float* __restrict__ dpost, float* __restrict__ dprior) {
+                                                           float* __restrict__ dpost, float* __restrict__ dprior,
+                                                           const float* __restrict__ closed) {
   const int total = rows * S;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
     const int r = i / S, s = i % S;
     const size_t o = (size_t)r * 2 * S;
+    // (FREE: the four values are computed as without the gate and replaced at the store - an early exit for the closed rows
+    //  changed how the compiler contracts the expressions below, and with it the open rows' last bits)
+    const bool shut = FREE && closed[r] != 0.0f;
     const float g1 = dm_sigmoid(post[o + S + s]), g2 = dm_sigmoid(prior[o + S + s]);
     const float s1 = 2.0f * g1 + 0.1f, s2 = 2.0f * g2 + 0.1f;
     const float d = post[o + s] - prior[o + s];
     const float i22 = 1.0f / (s2 * s2);
-    dpost[o + s] = sp * d * i22;
-    dpost[o + S + s] = sp * (s1 * i22 - 1.0f / s1) * 2.0f * g1 * (1.0f - g1);
-    dprior[o + s] = -sq * d * i22;
-    dprior[o + S + s] = sq * (1.0f / s2 - (s1 * s1 + d * d) * i22 / s2) * 2.0f * g2 * (1.0f - g2);
+    const float dm1 = sp * d * i22;
+    const float ds1 = sp * (s1 * i22 - 1.0f / s1) * 2.0f * g1 * (1.0f - g1);
+    const float dm2 = -sq * d * i22;
+    const float ds2 = sq * (1.0f / s2 - (s1 * s1 + d * d) * i22 / s2) * 2.0f * g2 * (1.0f - g2);
+    dpost[o + s] = shut ? 0.0f : dm1;
+    dpost[o + S + s] = shut ? 0.0f : ds1;
+    dprior[o + s] = shut ? 0.0f : dm2;
+    dprior[o + S + s] = shut ? 0.0f : ds2;
   }
 }
 
@@ -1360,9 +1384,11 @@ __device__ __forceinline__ float dm_group_lse(const float* x, int C) {
   return mx + logf(s);
 }
 
+template <bool FREE>
 __global__ void __launch_bounds__(256) kl_fwd_kernel(int rows, int S, int C, const float* __restrict__ post,
                                                      const float* __restrict__ prior, float* __restrict__ kl,
-                                                     float* __restrict__ ent_post, float* __restrict__ ent_prior) {
+                                                     float* __restrict__ ent_post, float* __restrict__ ent_prior,
+                                                     float free, float* __restrict__ kl_clip, float* __restrict__ closed) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
@@ -1384,17 +1410,27 @@ __global__ void __launch_bounds__(256) kl_fwd_kernel(int rows, int S, int C, con
   akl = dm_wave_sum(akl); aep = dm_wave_sum(aep); aeq = dm_wave_sum(aeq);
   if (lane == 0) {
     kl[row] = akl;
+    kl_free_store<FREE>(row, akl, free, kl_clip, closed);
     if (ent_post) ent_post[row] = aep;
     if (ent_prior) ent_prior[row] = aeq;
   }
 }
 
 // dKL/dpost_k = p_k ((lp_k - lq_k) - KL_g) ; dKL/dprior_k = q_k - p_k
+template <bool FREE>
 __global__ void __launch_bounds__(256) kl_bwd_kernel(int rows, int S, int C, const float* __restrict__ post,
                                                      const float* __restrict__ prior, float sp, float sq,
-                                                     float* __restrict__ dpost, float* __restrict__ dprior) {
+                                                     float* __restrict__ dpost, float* __restrict__ dprior,
+                                                     const float* __restrict__ closed) {
   const int total = rows * S;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    if (FREE && closed[i / S] != 0.0f) {
+      for (int k = 0; k < C; ++k) {
+        dpost[(size_t)i * C + k] = 0.0f;
+        dprior[(size_t)i * C + k] = 0.0f;
+      }
+      continue;
+    }
     const float* a = post + (size_t)i * C;
     const float* b = prior + (size_t)i * C;
     const float la = dm_group_lse(a, C), lb = dm_group_lse(b, C);
@@ -1466,9 +1502,12 @@ __device__ __forceinline__ void kl_stage_out(const float* src, int nfl, int C, f
 // S <= 32.  Workgroup = 4 rows (4 S <= 128 groups), wave = 2 rows: lanes 0-31 the first, 32-63 the second, lane & 31 = group.
 // A row's 64-lane tree above is: off = 32 adds the idle upper half's zeros (v + 0.f == v: an accumulator is 0.f + gk, never
 // -0), then off = 16 .. 1 inside the lower half.  Here each half runs off = 16 .. 1 on the same values: the same tree.
+template <bool FREE>
 __global__ void __launch_bounds__(KL_G) kl_fwd_staged_kernel(int rows, int S, int C, int vec, const float* __restrict__ post,
                                                              const float* __restrict__ prior, float* __restrict__ kl,
-                                                             float* __restrict__ ent_post, float* __restrict__ ent_prior) {
+                                                             float* __restrict__ ent_post, float* __restrict__ ent_prior,
+                                                             float free, float* __restrict__ kl_clip,
+                                                             float* __restrict__ closed) {
   extern __shared__ __attribute__((aligned(16))) float kl_lds[];
   float* pa = kl_lds;
   float* pb = kl_lds + KL_G * (C + 1);
@@ -1501,6 +1540,7 @@ __global__ void __launch_bounds__(KL_G) kl_fwd_staged_kernel(int rows, int S, in
   }
   if (s == 0 && rl < nrow) {
     kl[row0 + rl] = akl;
+    kl_free_store<FREE>(row0 + rl, akl, free, kl_clip, closed);
     if (ent_post) ent_post[row0 + rl] = aep;
     if (ent_prior) ent_prior[row0 + rl] = aeq;
   }
@@ -1508,9 +1548,12 @@ __global__ void __launch_bounds__(KL_G) kl_fwd_staged_kernel(int rows, int S, in
 
 // Workgroup = groups g0 .. g0 + 127 of the flat (rows S) list, lane = group.  A lane overwrites its own group's logits in LDS
 // with the two gradients (element k is read before it is written, and by this lane only); they leave as coalesced 16-byte stores.
-__global__ void __launch_bounds__(KL_G) kl_bwd_staged_kernel(int total, int C, int vec, const float* __restrict__ post,
+// FREE: a lane whose group lies in a closed row (group / S) writes +0.0f over its C floats of both tensors instead.
+template <bool FREE>
+__global__ void __launch_bounds__(KL_G) kl_bwd_staged_kernel(int total, int S, int C, int vec, const float* __restrict__ post,
                                                              const float* __restrict__ prior, float sp, float sq,
-                                                             float* __restrict__ dpost, float* __restrict__ dprior) {
+                                                             float* __restrict__ dpost, float* __restrict__ dprior,
+                                                             const float* __restrict__ closed) {
   extern __shared__ __attribute__((aligned(16))) float kl_lds[];
   float* pa = kl_lds;
   float* pb = kl_lds + KL_G * (C + 1);
@@ -1522,17 +1565,24 @@ __global__ void __launch_bounds__(KL_G) kl_bwd_staged_kernel(int total, int C, i
   if ((int)threadIdx.x < ng) {
     float* a = pa + threadIdx.x * (C + 1);
     float* b = pb + threadIdx.x * (C + 1);
-    const float la = dm_group_lse(a, C), lb = dm_group_lse(b, C);
-    float gk = 0.f;
-    for (int k = 0; k < C; ++k) {
-      const float lp = a[k] - la, lq = b[k] - lb;
-      gk += expf(lp) * (lp - lq);
-    }
-    for (int k = 0; k < C; ++k) {
-      const float lp = a[k] - la, lq = b[k] - lb;
-      const float p = expf(lp), q = expf(lq);
-      a[k] = sp * p * ((lp - lq) - gk);
-      b[k] = sq * (q - p);
+    if (FREE && closed[(g0 + (int)threadIdx.x) / S] != 0.0f) {
+      for (int k = 0; k < C; ++k) {
+        a[k] = 0.0f;
+        b[k] = 0.0f;
+      }
+    } else {
+      const float la = dm_group_lse(a, C), lb = dm_group_lse(b, C);
+      float gk = 0.f;
+      for (int k = 0; k < C; ++k) {
+        const float lp = a[k] - la, lq = b[k] - lb;
+        gk += expf(lp) * (lp - lq);
+      }
+      for (int k = 0; k < C; ++k) {
+        const float lp = a[k] - la, lq = b[k] - lb;
+        const float p = expf(lp), q = expf(lq);
+        a[k] = sp * p * ((lp - lq) - gk);
+        b[k] = sq * (q - p);
+      }
     }
   }
   __syncthreads();
@@ -1781,45 +1831,60 @@ __global__ void __launch_bounds__(256) st_softmax_bwd_kernel(int rows, int group
   }
 }
 
-int dm_kl_fwd_launch(int rows, int S, int C, const float* post, const float* prior, float* kl, float* ep, float* eq,
-                     hipStream_t st) {
+// FREE = false: dm_kl_balance_fwd (free, kl_clip, closed unused).  FREE = true: dm_kl_free_fwd.  One dispatch for both.
+template <bool FREE>
+static int kl_fwd_dispatch(int rows, int S, int C, const float* post, const float* prior, float* kl, float* ep, float* eq,
+                           float free, float* kl_clip, float* closed, hipStream_t st) {
   if (rows <= 0) return DM_OK;
   if (C == 0) {
-    hipLaunchKernelGGL(gauss_kl_fwd_kernel, dim3(dm_cdiv(rows, 4)), dim3(256), 0, st, rows, S, post, prior, kl, ep, eq);
+    hipLaunchKernelGGL((gauss_kl_fwd_kernel<FREE>), dim3(dm_cdiv(rows, 4)), dim3(256), 0, st, rows, S, post, prior, kl, ep, eq,
+                       free, kl_clip, closed);
     DM_LAUNCH_CHECK();
     return DM_OK;
   }
   if (kl_fwd_staged_ok(S, C)) {
     const int vec = (((uintptr_t)post | (uintptr_t)prior) & 15) == 0;      // a workgroup's run starts a multiple of 16 bytes in
-    hipLaunchKernelGGL(kl_fwd_staged_kernel, dim3(dm_cdiv(rows, 4)), dim3(KL_G), (size_t)2 * KL_G * (C + 1) * sizeof(float), st,
-                       rows, S, C, vec, post, prior, kl, ep, eq);
+    hipLaunchKernelGGL((kl_fwd_staged_kernel<FREE>), dim3(dm_cdiv(rows, 4)), dim3(KL_G),
+                       (size_t)2 * KL_G * (C + 1) * sizeof(float), st, rows, S, C, vec, post, prior, kl, ep, eq, free, kl_clip,
+                       closed);
     DM_LAUNCH_CHECK();
     return DM_OK;
   }
-  hipLaunchKernelGGL(kl_fwd_kernel, dim3(dm_cdiv(rows, 4)), dim3(256), 0, st, rows, S, C, post, prior, kl, ep, eq);
+  hipLaunchKernelGGL((kl_fwd_kernel<FREE>), dim3(dm_cdiv(rows, 4)), dim3(256), 0, st, rows, S, C, post, prior, kl, ep, eq, free,
+                     kl_clip, closed);
   DM_LAUNCH_CHECK();
   return DM_OK;
 }
-int dm_kl_bwd_launch(int rows, int S, int C, const float* post, const float* prior, float sp, float sq, float* dpost,
-                     float* dprior, hipStream_t st) {
+template <bool FREE>
+static int kl_bwd_dispatch(int rows, int S, int C, const float* post, const float* prior, float sp, float sq, float* dpost,
+                           float* dprior, const float* closed, hipStream_t st) {
   if (rows <= 0) return DM_OK;
   if (C == 0) {
-    hipLaunchKernelGGL(gauss_kl_bwd_kernel, dim3(ew_blocks((size_t)rows * S)), dim3(256), 0, st, rows, S, post, prior, sp, sq,
-                       dpost, dprior);
+    hipLaunchKernelGGL((gauss_kl_bwd_kernel<FREE>), dim3(ew_blocks((size_t)rows * S)), dim3(256), 0, st, rows, S, post, prior, sp,
+                       sq, dpost, dprior, closed);
     DM_LAUNCH_CHECK();
     return DM_OK;
   }
   if (kl_staged_ok(C)) {
     const int vec = (((uintptr_t)post | (uintptr_t)prior | (uintptr_t)dpost | (uintptr_t)dprior) & 15) == 0;
-    hipLaunchKernelGGL(kl_bwd_staged_kernel, dim3(dm_cdiv(rows * S, KL_G)), dim3(KL_G), (size_t)2 * KL_G * (C + 1) * sizeof(float),
-                       st, rows * S, C, vec, post, prior, sp, sq, dpost, dprior);
+    hipLaunchKernelGGL((kl_bwd_staged_kernel<FREE>), dim3(dm_cdiv(rows * S, KL_G)), dim3(KL_G),
+                       (size_t)2 * KL_G * (C + 1) * sizeof(float), st, rows * S, S, C, vec, post, prior, sp, sq, dpost, dprior,
+                       closed);
     DM_LAUNCH_CHECK();
     return DM_OK;
   }
-  hipLaunchKernelGGL(kl_bwd_kernel, dim3(ew_blocks((size_t)rows * S)), dim3(256), 0, st, rows, S, C, post, prior, sp, sq,
-                     dpost, dprior);
+  hipLaunchKernelGGL((kl_bwd_kernel<FREE>), dim3(ew_blocks((size_t)rows * S)), dim3(256), 0, st, rows, S, C, post, prior, sp, sq,
+                     dpost, dprior, closed);
   DM_LAUNCH_CHECK();
   return DM_OK;
+}
+int dm_kl_fwd_launch(int rows, int S, int C, const float* post, const float* prior, float* kl, float* ep, float* eq,
+                     hipStream_t st) {
+  return kl_fwd_dispatch<false>(rows, S, C, post, prior, kl, ep, eq, 0.f, nullptr, nullptr, st);
+}
+int dm_kl_bwd_launch(int rows, int S, int C, const float* post, const float* prior, float sp, float sq, float* dpost,
+                     float* dprior, hipStream_t st) {
+  return kl_bwd_dispatch<false>(rows, S, C, post, prior, sp, sq, dpost, dprior, nullptr, st);
 }
 int dm_st_softmax_bwd_launch(int rows, int groups, int C, const float* logits, int ldl, const float* dz, int lddz,
                              float* dlogits, int lddl, int accum, hipStream_t st) {
@@ -1842,6 +1907,22 @@ extern "C" int dm_kl_balance_bwd(int rows, int S, int C, const float* post, cons
                                  float scale_prior, float* dpost, float* dprior, void* stream) {
   DM_REQUIRE(post && prior && dpost && dprior, DM_E_NULL, "kl_bwd: null pointer");
   return dm_kl_bwd_launch(rows, S, C, post, prior, scale_post, scale_prior, dpost, dprior, (hipStream_t)stream);
+}
+// Free bits per row: kl, ent_post, ent_prior as dm_kl_balance_fwd stores them (the same kernels' FREE instances), and
+// kl_clip[r] = fmaxf(free, kl[r]), closed[r] = kl[r] <= free ? 1 : 0 from the same row sum.  One launch.
+extern "C" int dm_kl_free_fwd(int rows, int S, int C, const float* post, const float* prior, float free, float* kl, float* kl_clip,
+                              float* closed, float* ent_post, float* ent_prior, void* stream) {
+  DM_REQUIRE(post && prior && kl && kl_clip && closed, DM_E_NULL, "kl_free_fwd: null pointer");
+  DM_REQUIRE(S >= 1 && C >= 0, DM_E_SHAPE, "kl_free_fwd: S=%d C=%d", S, C);
+  DM_REQUIRE(free >= 0.f && free <= 3.402823466e38f, DM_E_SHAPE, "kl_free_fwd: free=%g (finite, >= 0)", (double)free);
+  return kl_fwd_dispatch<true>(rows, S, C, post, prior, kl, ent_post, ent_prior, free, kl_clip, closed, (hipStream_t)stream);
+}
+// dm_kl_balance_bwd's values on the rows with closed[r] == 0, +0.0f over every element of the others.  One launch.
+extern "C" int dm_kl_free_bwd(int rows, int S, int C, const float* post, const float* prior, const float* closed, float scale_post,
+                              float scale_prior, float* dpost, float* dprior, void* stream) {
+  DM_REQUIRE(post && prior && closed && dpost && dprior, DM_E_NULL, "kl_free_bwd: null pointer");
+  DM_REQUIRE(S >= 1 && C >= 0, DM_E_SHAPE, "kl_free_bwd: S=%d C=%d", S, C);
+  return kl_bwd_dispatch<true>(rows, S, C, post, prior, scale_post, scale_prior, dpost, dprior, closed, (hipStream_t)stream);
 }
 extern "C" int dm_st_softmax_bwd(int rows, int groups, int C, const float* logits, int ldl, const float* dz, int lddz,
                                  float* dlogits, int lddl, int accum, void* stream) {

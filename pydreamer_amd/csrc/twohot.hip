@@ -17,6 +17,9 @@
 //                          Rows [rows, rows_total) of dlogits are stored as zeros by the same launch.  The lanes j >= K carry logit
 //                          -inf (probability exactly 0) and bin 0: they never win a reduction and store nothing.  A NaN target
 //                          counts no bin and lands on k = 0: every index stays inside the row.
+//                          The head form (dm_twohot_head_loss) runs the same instances with tdiv = I and weight = NULL: row r reads
+//                          target[r / I], and the weight is the constant 1.0f (fl(1 x) = x: the bits of the line above with
+//                          weight = 1); there loss may be NULL too.
 //   return_norm_select_kernel   ONE workgroup of 1024 threads.  The order statistics s_i of the n values are found by an exact
 //                          radix select over the order-preserving integer image of the float (sign bit flipped for x >= 0, all
 //                          bits for x < 0; -0 sorts below +0): four passes of 8 bits, most significant first, each a histogram
@@ -46,7 +49,7 @@ template <int KP, int E>
 __global__ void __launch_bounds__(TH_THREADS) twohot_kernel(int rows, int rows_total, int K, const float* __restrict__ logits, int ld,
                                                             const float* __restrict__ bins, const float* __restrict__ target,
                                                             const float* __restrict__ weight, float scale, float* __restrict__ loss,
-                                                            float* __restrict__ dlogits, float* __restrict__ value) {
+                                                            float* __restrict__ dlogits, float* __restrict__ value, int tdiv) {
   constexpr int RPB = TH_THREADS / KP;
   const int l = threadIdx.x & (KP - 1);
   const long long r = (long long)blockIdx.x * RPB + (threadIdx.x / KP);
@@ -92,7 +95,7 @@ __global__ void __launch_bounds__(TH_THREADS) twohot_kernel(int rows, int rows_t
     return;
   }
   const float b0 = bins[0], b1 = bins[K - 1];
-  const float xt = fminf(fmaxf(symlog(target[r]), b0), b1);
+  const float xt = fminf(fmaxf(symlog(target[tdiv > 1 ? r / tdiv : r]), b0), b1);
   int cnt = 0;
 #pragma unroll
   for (int e = 0; e < E; ++e) cnt += (l + e * KP < K && b[e] <= xt) ? 1 : 0;
@@ -101,7 +104,7 @@ __global__ void __launch_bounds__(TH_THREADS) twohot_kernel(int rows, int rows_t
   const int k = min(max(cnt - 1, 0), K - 2);
   const float bk = bins[k], bk1 = bins[k + 1];
   const float w_hi = (xt - bk) / (bk1 - bk), w_lo = 1.f - w_hi;
-  const float w = weight[r];
+  const float w = weight ? weight[r] : 1.f;
   if (dlogits) {
     const float sw = scale * w;
 #pragma unroll
@@ -110,7 +113,7 @@ __global__ void __launch_bounds__(TH_THREADS) twohot_kernel(int rows, int rows_t
       if (j < K) dlogits[(size_t)r * K + j] = sw * (p[e] - (j == k ? w_lo : (j == k + 1 ? w_hi : 0.f)));
     }
   }
-  if (l == 0) {
+  if (l == 0 && loss) {
     const float lk = logits[(size_t)r * ld + k], lk1 = logits[(size_t)r * ld + k + 1];
     const float lse = m + logf(s);
     loss[r] = w * ((lse - w_lo * lk) - w_hi * lk1);
@@ -119,15 +122,15 @@ __global__ void __launch_bounds__(TH_THREADS) twohot_kernel(int rows, int rows_t
 
 template <int KP, int E>
 void launch(int rows, int rows_total, int K, const float* logits, int ld, const float* bins, const float* target, const float* weight,
-            float scale, float* loss, float* dlogits, float* value, hipStream_t st) {
+            float scale, float* loss, float* dlogits, float* value, int tdiv, hipStream_t st) {
   const int cover = dlogits ? rows_total : rows;
   hipLaunchKernelGGL((twohot_kernel<KP, E>), dim3(dm_cdiv(cover, TH_THREADS / KP)), dim3(TH_THREADS), 0, st, rows, rows_total, K,
-                     logits, ld, bins, target, weight, scale, loss, dlogits, value);
+                     logits, ld, bins, target, weight, scale, loss, dlogits, value, tdiv);
 }
 
 void dispatch(int rows, int rows_total, int K, const float* logits, int ld, const float* bins, const float* target,
-              const float* weight, float scale, float* loss, float* dlogits, float* value, hipStream_t st) {
-#define TH_GO(KP, E) launch<KP, E>(rows, rows_total, K, logits, ld, bins, target, weight, scale, loss, dlogits, value, st)
+              const float* weight, float scale, float* loss, float* dlogits, float* value, int tdiv, hipStream_t st) {
+#define TH_GO(KP, E) launch<KP, E>(rows, rows_total, K, logits, ld, bins, target, weight, scale, loss, dlogits, value, tdiv, st)
   if (K <= 2) TH_GO(2, 1);
   else if (K <= 4) TH_GO(4, 1);
   else if (K <= 8) TH_GO(8, 1);
@@ -265,7 +268,7 @@ extern "C" int dm_twohot_decode(int rows, int K, const float* logits, int ld, co
   DM_TRY(twohot_checks("twohot_decode", rows, rows, K, logits, ld, bins));
   DM_REQUIRE(value, DM_E_NULL, "twohot_decode: null value");
   if (rows <= 0) return DM_OK;
-  dispatch(rows, rows, K, logits, ld, bins, nullptr, nullptr, 0.f, nullptr, nullptr, value, (hipStream_t)stream);
+  dispatch(rows, rows, K, logits, ld, bins, nullptr, nullptr, 0.f, nullptr, nullptr, value, 1, (hipStream_t)stream);
   DM_LAUNCH_CHECK();
   return DM_OK;
 }
@@ -275,7 +278,21 @@ extern "C" int dm_twohot_loss(int rows, int rows_total, int K, const float* logi
   DM_TRY(twohot_checks("twohot_loss", rows, rows_total, K, logits, ld, bins));
   DM_REQUIRE(target && weight && loss, DM_E_NULL, "twohot_loss: null target, weight or loss");
   if ((dlogits ? rows_total : rows) <= 0) return DM_OK;
-  dispatch(rows, rows_total, K, logits, ld, bins, target, weight, scale, loss, dlogits, value, (hipStream_t)stream);
+  dispatch(rows, rows_total, K, logits, ld, bins, target, weight, scale, loss, dlogits, value, 1, (hipStream_t)stream);
+  DM_LAUNCH_CHECK();
+  return DM_OK;
+}
+
+// The head form of dm_twohot_loss: rows = (t, b, i) rows of a decoder head under iwae_samples = I, row r against target[r / I], no
+// weight array (weight 1), every output optional, target == NULL the mean-only form (dm_twohot_decode's bits).  One launch.
+extern "C" int dm_twohot_head_loss(int rows, int I, int K, const float* logits, int ld, const float* bins, const float* target,
+                                   float scale, float* loss, float* dlogits, float* mean, void* stream) {
+  DM_TRY(twohot_checks("twohot_head_loss", rows, rows, K, logits, ld, bins));
+  DM_REQUIRE(I >= 1 && rows % I == 0, DM_E_SHAPE, "twohot_head_loss: rows=%d I=%d (I >= 1, rows a multiple of I)", rows, I);
+  DM_REQUIRE(target || (!loss && !dlogits), DM_E_NULL, "twohot_head_loss: loss or dlogits asked for without a target");
+  DM_REQUIRE(loss || dlogits || mean, DM_E_NULL, "twohot_head_loss: no output");
+  if (rows <= 0) return DM_OK;
+  dispatch(rows, rows, K, logits, ld, bins, target, nullptr, scale, loss, dlogits, mean, I, (hipStream_t)stream);
   DM_LAUNCH_CHECK();
   return DM_OK;
 }

@@ -145,6 +145,8 @@ _SIGNATURES = {
     'dm_sample_onehot': (c_int, [c_int, c_int, c_int, _P, c_int, _P, _P, _P, c_int, _P, _P]),
     'dm_kl_balance_fwd': (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     'dm_kl_balance_bwd': (c_int, [c_int, c_int, c_int, _P, _P, c_float, c_float, _P, _P, _P]),
+    'dm_kl_free_fwd': (c_int, [c_int, c_int, c_int, _P, _P, c_float, _P, _P, _P, _P, _P, _P]),
+    'dm_kl_free_bwd': (c_int, [c_int, c_int, c_int, _P, _P, _P, c_float, c_float, _P, _P, _P]),
     'dm_st_softmax_bwd': (c_int, [c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, _P]),
     'dm_mask_rows': (c_int, [c_int, c_int, _P, c_int, _P, _P, c_int, _P]),
     'dm_kl_sampled_fwd': (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P]),
@@ -260,6 +262,7 @@ _SIGNATURES = {
     'dm_twohot_decode': (c_int, [c_int, c_int, _P, c_int, _P, _P, _P]),
     'dm_twohot_loss': (c_int, [c_int, c_int, c_int, _P, c_int, _P, _P, _P, c_float, _P, _P, _P, _P]),
     'dm_return_norm': (c_int, [c_int, _P, c_float, c_float, c_float, c_float, c_int, _P, _P, _P, c_int, _P]),
+    'dm_twohot_head_loss': (c_int, [c_int, c_int, c_int, _P, c_int, _P, _P, c_float, _P, _P, _P, _P]),
     'dm_metric_accum': (c_int, [c_int, _P, _P, _P, _P, _P, _P]),
     'dm_batch_stats': (c_int, [c_int, _P, _P, _P, _P, _P]),
     'dm_masked_mean': (c_int, [c_int, c_int, _P, c_int, c_int, _P, c_int, _P, _P]),

@@ -25,7 +25,12 @@ reference; everything in the RSSM, the heads and the actor-critic works as besid
 of 2..32 reward values (DenseCategoricalSupportDecoder in place of the Normal reward head; it combines with all of
 the above), critic_dist in {mse, twohot} (twohot: a categorical critic over critic_bins <= 256 symlog-spaced bins, read as a scalar
 through ActorCritic.value) and return_norm in {none, percentile} (the actor's advantages over the running percentile range of the
-imagined returns; not with a data-parallel group of more than one rank) - DESIGN 4.20; the task actor-critic only.
+imagined returns; not with a data-parallel group of more than one rank) - DESIGN 4.20; the task actor-critic only.  The world
+model's share of the same, DESIGN 4.21: kl_free >= 0 (free bits per (t, b) row in nats: max(kl_free, KL) enters loss_model and a
+row with KL <= kl_free sends no gradient into the posterior or the prior; loss_kl stays the exact KL, loss_kl_clip and kl_free_frac
+are logged beside it; not with iwae_samples > 1) and reward_dist in {normal, twohot} (twohot: DenseTwoHotDecoder in place of the
+Normal reward head - reward_twohot_bins <= 256 symlog-spaced bins over +-reward_twohot_range, two-hot cross-entropy against
+symlog(reward), the mean decoded by symexp; not beside reward_decoder_categorical; it combines with all of the above).
 """
 import contextlib
 import ctypes
@@ -633,6 +638,70 @@ class DenseCategoricalSupportDecoder(_DenseDecoder):
             yield i, bin == i
 
 
+REWARD_DISTS = ('normal', 'twohot')
+
+
+def _check_twohot_support(bins, rng):
+    if isinstance(bins, bool) or int(bins) != bins or not 2 <= bins <= 256:
+        raise ValueError(f'reward_twohot_bins={bins}: 2 .. 256')
+    if not (math.isfinite(rng) and rng > 0):
+        raise ValueError(f'reward_twohot_range={rng}: a finite number > 0')
+
+
+def reward_twohot_conf(conf):
+    """(bins, range) of reward_dist='twohot', or None for the other reward heads.  ValueError for an unknown reward_dist, for
+    'twohot' beside a non-empty reward_decoder_categorical, for reward_twohot_bins outside 2 .. 256 and for a
+    reward_twohot_range that is not a finite number > 0 - the values are checked even while the head they belong to is off."""
+    dist = getattr(conf, 'reward_dist', 'normal')
+    bins, rng = getattr(conf, 'reward_twohot_bins', 255), getattr(conf, 'reward_twohot_range', 20.0)
+    if dist not in REWARD_DISTS:
+        raise ValueError(f'reward_dist={dist!r}: one of {REWARD_DISTS}')
+    _check_twohot_support(bins, rng)
+    if dist != 'twohot':
+        return None
+    raw = conf.reward_decoder_categorical
+    if not (raw is None or (isinstance(raw, (list, tuple)) and len(raw) == 0)):
+        raise ValueError(f"reward_dist='twohot' with reward_decoder_categorical={raw!r}: one reward head at a time")
+    return int(bins), float(rng)
+
+
+class DenseTwoHotDecoder(_DenseDecoder):
+    """A symlog two-hot reward head (DreamerV3's; the reference has no counterpart): K logits over the bins
+    linspace(-bin_range, bin_range, K) in symlog space, the two-hot cross-entropy against symlog(target) and the decoded mean
+    symexp(sum_j softmax_j bins_j) - dm_twohot_head_loss (csrc/twohot.hip), the head form of the critic's dm_twohot_loss.  The loss
+    is of order log K whatever the reward scale.  `bins` is a non-persistent buffer (a function of two config keys, as
+    ActorCritic.bins): state_dict() holds the MLP alone, K wide at its output.  zero_output() - the owner calls it behind its
+    weight initialisation - makes a fresh head predict reward 0 (equal logits over symmetric bins)."""
+
+    target_rows = False      # row r reads target r / I (the kernel's own index, as the categorical head)
+
+    def __init__(self, in_dim, bins=255, bin_range=20.0, hidden_layers=4, layer_norm=True):
+        super().__init__()
+        _check_twohot_support(bins, bin_range)
+        self.K, self.bin_range = int(bins), float(bin_range)
+        self.model = MLP(in_dim, self.K, MLP_HIDDEN, hidden_layers, layer_norm)
+        self.register_buffer('bins', torch.linspace(-self.bin_range, self.bin_range, self.K), persistent=False)
+        self.zero_output()
+
+    def zero_output(self):
+        out_layer = self.model.model[self.model._base + 3 * self.model.hidden_layers]
+        nn.init.zeros_(out_layer.weight)
+        nn.init.zeros_(out_layer.bias)
+
+    def loss(self, out, target=None, scale=0.0, grad=False, I=1, bins=False):
+        """`out`: (N, K) logits; target: the (N / I,) rewards themselves (untransformed; None: the mean-only form)."""
+        N, K = out.shape
+        loss, dout, mean = (out.new_empty(shape) if want else None
+                            for shape, want in ((N, target is not None), ((N, K), grad), (N, True)))
+        H.call('dm_twohot_head_loss', N, I, K, H.fptr(out), K, H.fptr(self.bins), H.fptr(target), scale, H.fptr(loss),
+               H.fptr(dout), H.fptr(mean), H.stream())
+        return loss, dout, mean, None
+
+    def buckets(self, target, bin):      # by the sign of the reward, as the Normal head (decoders.py:95-98)
+        for sig in (-1, 1):
+            yield sig, torch.sign(target.float()) == sig
+
+
 class MultiDecoder(_Params):
     """decoders.py:10-108.  Owns the heads' parameters and runs them for WorldModel and Dreamer: the image term (convolution,
     dense categorical or none) and the dense heads reward / terminal / vecobs - training forward (heads_loss), evaluation on
@@ -647,6 +716,7 @@ class MultiDecoder(_Params):
             raise NotImplementedError(f'image_decoder={conf.image_decoder!r}: only image_decoder=cnn, the dense categorical image '
                                       'path (dense_image_gate) and the image-less path (imageless_gate) are built in the HIP path')
         support = reward_support(conf)
+        twohot = reward_twohot_conf(conf)      # (checked before anything is allocated)
         self.image_weight, self.reward_weight, self.terminal_weight = conf.image_weight, conf.reward_weight, conf.terminal_weight
         if dense:      # decoders.py:23-28
             self.image = CatImageDecoder(features_dim, (conf.image_channels, conf.image_size, conf.image_size),
@@ -659,6 +729,8 @@ class MultiDecoder(_Params):
             self.image_shape = (conf.image_channels, conf.image_size, conf.image_size)
         if support is not None:      # decoders.py:34-39
             self.reward = DenseCategoricalSupportDecoder(features_dim, support, conf.reward_decoder_layers, conf.layer_norm)
+        elif twohot is not None:      # reward_dist='twohot' 
+            self.reward = DenseTwoHotDecoder(features_dim, twohot[0], twohot[1], conf.reward_decoder_layers, conf.layer_norm)
         else:
             self.reward = DenseNormalDecoder(features_dim, conf.reward_decoder_layers, conf.layer_norm)
         self.reward_bins = 0 if support is None else len(support)      # the number of support values, 0 for the Normal head
@@ -1281,6 +1353,10 @@ METRIC_BUF_FLOATS = 48
 # the percentile return normalisation's three scalars (ActorCritic, return_norm='percentile'): free slots behind the goals probe's,
 # named by packed_metrics() only for a model that has the switch on, zero otherwise (dm_return_norm's out[2:5], copied on the device)
 RETURN_METRIC_SLOTS = dict(policy_return_lo=42, policy_return_hi=43, policy_return_scale=44)
+# free bits' two scalars (WorldModel, kl_free > 0): the free slots behind those, named by packed_metrics() only for a model that has
+# the switch on, zero otherwise.  loss_kl_clip: the mean of max(kl_free, kl) per row, the value loss_model is combined from;
+# kl_free_frac: the fraction of closed rows (kl <= kl_free).  Slot 47 stays free
+KL_FREE_METRIC_SLOTS = dict(loss_kl_clip=45, kl_free_frac=46)
 CRITIC_DISTS = ('mse', 'twohot')
 RETURN_NORMS = ('none', 'percentile')
 # the config keys Dreamer hands to its task ActorCritic under the same names (a conf without them - an older namespace - gets the
@@ -1535,6 +1611,14 @@ class WorldModel(_Params):
         self.deter_dim, self.stoch_dim, self.stoch_discrete = conf.deter_dim, conf.stoch_dim, conf.stoch_discrete
         self.kl_weight = conf.kl_weight
         self.kl_balance = None if conf.kl_balance == 0.5 else conf.kl_balance     # dreamer.py:241
+        # free bits per (t, b) row, in nats (DreamerV3's rule; 0: off, the reference's loss): max(kl_free, kl) enters loss_model and a
+        # row with kl <= kl_free sends no gradient into post or prior (dm_kl_free_fwd / dm_kl_free_bwd)
+        self.kl_free = float(getattr(conf, 'kl_free', 0.0))
+        if not (math.isfinite(self.kl_free) and self.kl_free >= 0.0):
+            raise ValueError(f'kl_free={self.kl_free!r}: a finite number of nats >= 0')
+        if self.kl_free > 0 and conf.iwae_samples > 1:
+            raise NotImplementedError('kl_free > 0 with iwae_samples > 1: the sampled KL of the IWAE bound has no per-row exact KL '
+                                      'to clip')
         self.aux_critic_weight = conf.aux_critic_weight
         self.encoder = MultiEncoder(conf)
         features_dim = conf.deter_dim + conf.stoch_dim * (conf.stoch_discrete or 1)
@@ -1553,6 +1637,9 @@ class WorldModel(_Params):
                                       actor_dist=conf.actor_dist)
         for m in self.modules():
             init_weights_tf2(m)
+        for m in self.modules():      # (behind the initialiser above, which fills every Linear: a head that wants a zero output layer)
+            if hasattr(m, 'zero_output'):
+                m.zero_output()
         self._ws = None
         self._ws_dec = None                # own workspaces of the decoder / encoder backward while weight gradients are deferred
         self._ws_enc = None
@@ -1708,8 +1795,15 @@ class WorldModel(_Params):
         heads, pk['heads'] = dec.heads_loss(pk, obs, ws, gw)      # name -> (loss, rec, target) per row; the backward's entries
         # KL + entropies (dreamer.py:326-343,369-379)
         kl, ent_post, ent_prior = (torch.empty(N, device=dev) for _ in range(3))
-        H.call('dm_kl_balance_fwd', N, c.stoch_dim, c.stoch_discrete, H.fptr(post), H.fptr(prior), H.fptr(kl),
-               H.fptr(ent_post), H.fptr(ent_prior), H.stream())
+        free = self.kl_free > 0
+        if free:
+            kl_clip, closed = torch.empty(N, device=dev), torch.empty(N, device=dev)
+            H.call('dm_kl_free_fwd', N, c.stoch_dim, c.stoch_discrete, H.fptr(post), H.fptr(prior), self.kl_free, H.fptr(kl),
+                   H.fptr(kl_clip), H.fptr(closed), H.fptr(ent_post), H.fptr(ent_prior), H.stream())
+            pk['closed'] = closed
+        else:
+            H.call('dm_kl_balance_fwd', N, c.stoch_dim, c.stoch_discrete, H.fptr(post), H.fptr(prior), H.fptr(kl),
+                   H.fptr(ent_post), H.fptr(ent_prior), H.stream())
 
         if mbuf is None:
             mbuf = torch.zeros(METRIC_BUF_FLOATS, device=dev)
@@ -1739,7 +1833,7 @@ class WorldModel(_Params):
         # loss_model = mean_tb of the weighted terms [kl, image (none on the image-less path), *heads] (dreamer.py:362-365)
         names = list(heads)
         img = [] if loss_image is None else [(loss_image, dec.image_weight)]
-        xs = [kl] + [x for x, _ in img] + [heads[n][0] for n in names]
+        xs = [kl_clip if free else kl] + [x for x, _ in img] + [heads[n][0] for n in names]
         wts = [self.kl_weight] + [w for _, w in img] + [w for _, _, w in dec.heads()]
         red = lambda x, mode: x
         if I > 1:
@@ -1778,7 +1872,8 @@ class WorldModel(_Params):
                        H.stream())
             terms = [(x, 1.0 / N) for x in xs]
             # (kl, image, reward, terminal and nothing else: their means stand in slots 0-3 already)
-            combine(mbuf[0:4] if img and not names[2:] else _multi_sum(terms, dev), wts, 6)
+            # (free bits: slot 0 keeps the exact KL, the clipped mean is summed with the other terms)
+            combine(mbuf[0:4] if img and not names[2:] and not free else _multi_sum(terms, dev), wts, 6)
             if aux is not None:       # loss = loss_model.mean() + aux_critic_weight * loss_critic_aux (dreamer.py:365) -> slot 7
                 combine(_multi_sum(terms + [(aux['lc'], 1.0 / aux['rows'])], dev), wts + [self.aux_critic_weight], 7)
                 loss = mbuf[7]
@@ -1787,6 +1882,11 @@ class WorldModel(_Params):
         tb = lambda x: x.view(T, B, *x.shape[1:])
         tensors = dict(loss_kl=tb(t_kl), entropy_prior=tb(t_ep), entropy_post=tb(t_eq))
         metrics = dict(loss_model=mbuf[6], loss_kl=mbuf[0], entropy_prior=mbuf[4], entropy_post=mbuf[5])
+        if free:
+            s0 = KL_FREE_METRIC_SLOTS['loss_kl_clip']
+            _multi_sum([(kl_clip, 1.0 / N), (closed, 1.0 / N)], dev, out=mbuf[s0:s0 + 2])
+            tensors['loss_kl_clip'] = tb(kl_clip)
+            metrics.update({k: mbuf[i] for k, i in KL_FREE_METRIC_SLOTS.items()})
         if t_li is not None:      # (decoders.py:59-64: image-less there is no loss_image metric and no loss_image / image_rec tensor)
             tensors.update(loss_image=tb(t_li), image_rec=None)
             metrics.update(loss_image=mbuf[1])
@@ -1865,8 +1965,12 @@ class WorldModel(_Params):
                     sp = sq = gw * self.kl_weight / N
                 else:
                     sp, sq = gw * self.kl_weight * (1 - self.kl_balance) / N, gw * self.kl_weight * self.kl_balance / N
-                H.call('dm_kl_balance_bwd', N, c.stoch_dim, c.stoch_discrete, H.fptr(pk['post']), H.fptr(pk['prior']), sp, sq,
-                       H.fptr(dpost), H.fptr(dprior), H.stream())
+                if self.kl_free > 0:      # closed rows (kl <= kl_free): exact zeros; open rows: the values of the call below
+                    H.call('dm_kl_free_bwd', N, c.stoch_dim, c.stoch_discrete, H.fptr(pk['post']), H.fptr(pk['prior']),
+                           H.fptr(pk['closed']), sp, sq, H.fptr(dpost), H.fptr(dprior), H.stream())
+                else:
+                    H.call('dm_kl_balance_bwd', N, c.stoch_dim, c.stoch_discrete, H.fptr(pk['post']), H.fptr(pk['prior']), sp, sq,
+                           H.fptr(dpost), H.fptr(dprior), H.stream())
             # RSSM BPTT
             cell = self.core.cell
             rssm_p = H.rssm_struct(cell.ordered())
@@ -1913,6 +2017,8 @@ class WorldModel(_Params):
         I = int(iwae_samples)
         if self.dense and I > 1:
             raise NotImplementedError('iwae_samples > 1 is not built on the dense image path (DESIGN 4.11)')
+        if self.kl_free > 0 and I > 1:
+            raise NotImplementedError('kl_free > 0 with iwae_samples > 1: the sampled KL has no per-row exact KL to clip')
         if do_open_loop and torch.is_grad_enabled():
             raise NotImplementedError('do_open_loop is an evaluation variant: call it under torch.no_grad() like '
                                       'train.py:353-359 does (its backward is not built)')
@@ -2384,6 +2490,8 @@ class Dreamer(nn.Module):
             slots.update(GOALS_METRIC_SLOTS)
         if self.ac.return_norm == 'percentile':
             slots.update(RETURN_METRIC_SLOTS)
+        if self.wm.kl_free > 0:
+            slots.update(KL_FREE_METRIC_SLOTS)
         names = list(slots)
         return names, self.metric_buffer, [slots[n] for n in names]
 
@@ -2571,7 +2679,7 @@ class Dreamer(nn.Module):
             heads(r_split, rows, ws)
         term, mu = dec.dream_means(outs)      # the mean-only form of either head, one launch over all rows behind the windows
         if _pack is not None:
-            _pack.update(act_idx=act_idx, ws=ws, actor_acts=a_acts, actor_logits=a_logits, values=values)
+            _pack.update(act_idx=act_idx, ws=ws, actor_acts=a_acts, actor_logits=a_logits, values=values, head_outs=outs)
         return feats, actions, _Mean(mu.view(Hh + 1, M)), _Mean(term.view(Hh + 1, M))
 
     # ---- training step (dreamer.py:113-186)
@@ -2585,6 +2693,8 @@ class Dreamer(nn.Module):
         imag_horizon = int(imag_horizon or self.imag_horizon)
         if self.wm.dense and iwae_samples > 1:      # before anything is allocated or launched
             raise NotImplementedError('iwae_samples > 1 is not built on the dense image path (DESIGN 4.11)')
+        if self.wm.kl_free > 0 and iwae_samples > 1:
+            raise NotImplementedError('kl_free > 0 with iwae_samples > 1: the sampled KL has no per-row exact KL to clip')
         T, B = obs['action'].shape[:2]
         noise = noise or {}
         I = iwae_samples
@@ -2677,10 +2787,14 @@ class Dreamer(nn.Module):
         else:                        # unflatten_batch(value[0], (T,B,I)).mean(-1), dreamer.py:159
             tensors.update(policy_value=_reduce_i(tensors_ac['value'][0].contiguous().view(-1), T * B, I, 0).view(T, B))
         # Diagnostics for tests / debugging (not part of the reference API).  The index tensors are copies; `actions`,
-        # `dream_features`, `post` and `prior` are the step's own buffers.
+        # `dream_features`, `post` and `prior` are the step's own buffers.  dream_reward / dream_terminal: the two heads' decoded
+        # means over the imagined states, (H + 1, M), as the actor-critic reads them; dream_reward_out: the reward head's own output
+        # rows behind them ((H + 1) M, out_dim) - the logits of a two-hot or categorical head, the mean itself for the Normal head.
         self.last_extras = dict(post_idx=pk['idx'].view(T, B * I, -1).clone(), act_idx=dpk['act_idx'].clone(),
                                 actions=actions_dream, dream_features=features_dream, actor_logits=dpk.get('actor_logits'),
-                                ac_tensors=tensors_ac, post=pk['post'], prior=pk['prior'], pred_idx=pk.get('pred_idx'))
+                                ac_tensors=tensors_ac, post=pk['post'], prior=pk['prior'], pred_idx=pk.get('pred_idx'),
+                                dream_reward=rewards_dream.mean, dream_terminal=terminals_dream.mean,
+                                dream_reward_out=dpk['head_outs'][0])
         # Dream for a log sample (dreamer.py:163-180): T-1 imagined steps from the B first states, decoded to images
         dream_tensors = {}
         if do_dream_tensors and not self.wm.imageless:      # dreamer.py:164: skipped when there is no image decoder
@@ -2700,14 +2814,14 @@ class Dreamer(nn.Module):
                 dream_tensors = dict(action_pred=torch.cat([obs['action'][:1].float(), a2]), reward_pred=r2.mean,
                                      terminal_pred=t2.mean, image_pred=image_dream.view(T, B, *image_dream.shape[-3:]),
                                      **t_ac2)
-                self.last_extras.update(dream_log_act_idx=dpk2['act_idx'].clone())
+                self.last_extras.update(dream_log_act_idx=dpk2['act_idx'].clone(), dream_log_reward_out=dpk2['head_outs'][0])
         if pk.get('tail') is not None:      # losses, metrics and tensors of the world model were written on the world-model stream
             cur = torch.cuda.current_stream()
             cur.wait_event(pk['tail'].ev_tail)
             # ... and ALLOCATED from that stream's pool: what leaves training_step() is read on the caller's stream from here on, so the
             # caching allocator must not hand such a block to the next s_wm allocation while a caller-stream read is still queued
             # (the actor-critic outputs are guarded the same way)
-            leaving = [loss_model, pk.get('dec_acts'), pk.get('dec_logits'), pk.get('target')] + [v for v in dict.values(pk['tensors']) if torch.is_tensor(v)]
+            leaving = [loss_model, pk.get('dec_acts'), pk.get('dec_logits'), pk.get('target'), pk.get('closed')] + [v for v in dict.values(pk['tensors']) if torch.is_tensor(v)]
             for t in leaving:
                 if torch.is_tensor(t) and t.is_cuda:
                     t.record_stream(cur)

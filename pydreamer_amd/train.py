@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import hip as H
-from .models import GOALS_METRIC_SLOTS, METRIC_BUF_FLOATS, METRIC_SLOTS, RETURN_METRIC_SLOTS
+from .models import GOALS_METRIC_SLOTS, KL_FREE_METRIC_SLOTS, METRIC_BUF_FLOATS, METRIC_SLOTS, RETURN_METRIC_SLOTS
 
 RULE_IGNORE, RULE_NOT_NAN, RULE_FINITE_MAX, RULE_ALWAYS, RULE_MAX_ONLY = 0, 1, 2, 3, 4
 MAX_SLOTS = 256
@@ -118,6 +118,8 @@ def default_slots(model):
         table.update(GOALS_METRIC_SLOTS)
     if getattr(model.conf, 'return_norm', 'none') == 'percentile':
         table.update(RETURN_METRIC_SLOTS)
+    if getattr(model.conf, 'kl_free', 0.0) > 0:
+        table.update(KL_FREE_METRIC_SLOTS)
     slots = {k: (i, RULE_FINITE_MAX if k in GRAD_NORMS else RULE_NOT_NAN) for k, i in table.items()}
     slots.update(DATA_STATS)
     return slots
